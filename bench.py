@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- coord-samples/sec, forward+backward(+Adam), 4x256 complex WIRE MLP.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 and no WORLD_SIZE in the environment: this process starts N fresh rank processes itself
 (``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...``) BEFORE it
@@ -467,6 +467,42 @@ def secondary(ex):
     return out
 
 
+DUMP_CAP_BYTES = 64 << 20      # --dump-outputs: at most 64 MB in all
+
+
+def dump_outputs(tr, out_dir):
+    """--dump-outputs DIR: what the timed path computed in its last step, as DIR/<name>.npy (float32; the row indices
+    float64, exact below 2^53) -- the batch loss, the network output y of this rank's rows (of its last micro-shard)
+    and the flat grid index of each row, the all-reduced flat gradient, and the parameters and Adam moments after the
+    step (flat buffers of FusedTrainer, zero pads included).  An array larger than its share of the 64 MB cap is
+    stored as a fixed, seeded sample of its elements, with their flat positions in DIR/<name>_sample_idx.npy."""
+    import numpy as np
+    from wire_amd.parallel import shard_bounds
+    lo, hi = shard_bounds(tr.npoints, tr.world, tr.rank)
+    per = (hi - lo + tr.micro - 1) // tr.micro
+    first = (tr.micro - 1) * per                        # y holds the rows of the step's last micro-shard
+    n = hi - lo - first
+    arrays = {
+        "loss": tr.loss.float(),
+        "y": tr.y[:n * tr.O].view(n, tr.O),
+        "batch_indices": tr._hidx[first:first + n].double(),
+        "grad": tr.flat_grad,
+        "params": tr.flat,
+        "adam_exp_avg": tr.exp_avg,
+        "adam_exp_avg_sq": tr.exp_avg_sq,
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_CAP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.nbytes > share:
+            k = share // (a.itemsize + 8)
+            pick = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(out_dir, name + "_sample_idx.npy"), pick.astype(np.float64))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def rccl_probe(dev, tr, timeout_s=45.0):
     """What RCCL ITSELF reports about the job: ncclCommCount / ncclCommCuDevice of a communicator
     built from librccl's C ABI (the trainer's own when WIRE_DP_DIRECT=1, else one made here with the symmetric set-up of
@@ -528,7 +564,14 @@ def main():
     ap.add_argument("--shuffle", choices=["hashed", "randperm"], default="hashed",
                     help="hashed: per-rank slice of a position-keyed bijection (default); randperm: torch.randperm "
                          "of the whole grid on every rank, the reference's literal call")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, output rows, gradient, "
+                         "parameters, Adam moments) as DIR/<name>.npy, at most 64 MB in all (rank 0 only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.shuffle != "hashed":
+        ap.error("--dump-outputs needs --shuffle hashed (the row indices it writes are those of the hashed shuffle)")
 
     if args.overlap == "layer":
         os.environ["WIRE_DP_OVERLAP"] = "layer"
@@ -622,6 +665,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)
     rccl = None
     if tr.reducers[0].active:
         rccl = rccl_probe(dev, tr)

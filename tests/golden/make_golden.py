@@ -2,6 +2,7 @@
 """Generate golden vectors by IMPORTING THE REFERENCE (build container only).
 
     python3 tests/golden/make_golden.py            # writes tests/golden/*.npz
+    python3 tests/golden/make_golden.py adam64     # adam64_small_wire_hi.npz (reads small_wire_hi.npz)
 
 The reference (/root/reference, Annatk26/wire @ 2024_08_07) is pure Python; it
 is imported from its own files, run on CPU (torch CPU, fp32 and an fp64 twin)
@@ -302,6 +303,35 @@ def misc2():
     print("misc2: iou =", rec["iou_val"], "trainable g_omega (hid) =", rec["tr_hid_g_omega"], rec["tr_hid_g_omega64"])
 
 
+def adam64(name="small_wire_hi"):
+    """The fp64 twin of a small case's 3 Adam steps (the ``adam_losses`` / ``p3:`` of run_case): the reference's
+    model, started from the case's stored fp32 state_dict cast to fp64, same inputs, Adam + LambdaLR.  The fp32
+    trajectory itself depends on the host's CPU (thread split and vector width of torch's kernels) at the level of its
+    own round-off; this one does not."""
+    src = dict(np.load(os.path.join(OUT, name + ".npz")))
+    m = {k[5:]: src[k].item() for k in src if k.startswith("meta_")}
+    model = build(m["kind"], m["D"], m["hidden_features"], m["L"], m["O"], m["first_omega0"], m["hidden_omega0"],
+                  m["scale0"])
+    model.load_state_dict({k[2:]: torch.tensor(v) for k, v in src.items() if k.startswith("p:")})
+    model = to_double(model)
+    coords, target = torch.tensor(src["coords"]).double(), torch.tensor(src["target"]).double()
+    opt = torch.optim.Adam(lr=m["lr"], params=model.parameters())
+    sched = torch.optim.lr_scheduler.LambdaLR(opt, lambda e: 0.1 ** min(e / m["niters"], 1))
+    losses = []
+    for _ in range(3):
+        ll = ((model(coords) - target) ** 2).mean()
+        opt.zero_grad()
+        ll.backward()
+        opt.step()
+        sched.step()
+        losses.append(ll.item())
+    rec = {"adam_losses64": np.array(losses, np.float64)}
+    for k, v in sd_numpy(model).items():
+        rec["p3_64:" + k] = v
+    np.savez_compressed(os.path.join(OUT, f"adam64_{name}.npz"), **rec)
+    print(f"wrote adam64_{name}.npz: losses {losses}")
+
+
 def misc3():
     """ComplexGaborLayer2D(trainable=True) (modules/wire2d.py:21-67): gradients of omega_0 / scale_0 and of both
     Linears, hidden and first layer, fp32 and fp64."""
@@ -360,6 +390,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "misc3":
         misc3()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "adam64":
+        adam64()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "ct_pair":
         ct_pair()

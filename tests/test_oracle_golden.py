@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import FULL, SMALL, checksum, load_golden, meta, oracle_run, params_np, build_model, relmax
+from _util import FULL, SMALL, checksum, load_golden, meta, oracle_run, params_np, build_model, relmax, within_ref
 from oracle import torch_ref, wire_oracle as wo
 
 
@@ -108,11 +108,28 @@ def test_torch_ref_matches_reference():
     assert relmax(y.numpy(), rec["y"]) < 1e-5
     for i, a in enumerate(acts):
         assert relmax(a.numpy(), rec[f"act{i}"]) < 1e-5
-    losses, p3 = torch_ref.train_steps(p, torch.tensor(rec["coords"]), torch.tensor(rec["target"]),
-                                       m["L"], m["om1"], m["om"], m["sc"], m["lr"], 3, m["niters"])
-    np.testing.assert_allclose(losses, rec["adam_losses"], rtol=1e-5)
+    # 3 Adam steps.  The fp32 trajectory depends on the host's CPU (how torch splits its reductions over threads, the
+    # vector width of its kernels) at the level of the arithmetic's own round-off: the reference's fp32 run
+    # (adam_losses, p3:) is itself 8e-5 of the loss and 3e-4 of a parameter away from its fp64 twin
+    # (adam64_small_wire_hi.npz) after 3 steps.  So the restatement is pinned in fp64 against that twin, and its fp32
+    # run against the twin too, by the reference's own fp32 error (err <= 2 err_ref + 1e-6).
+    twin = load_golden("adam64_small_wire_hi")
+    coords, target = torch.tensor(rec["coords"]), torch.tensor(rec["target"])
+    p64 = {k: v.to(torch.complex128 if v.is_complex() else torch.float64) for k, v in p.items()}
+    losses64, q3 = torch_ref.train_steps(p64, coords.double(), target.double(), m["L"], m["om1"], m["om"], m["sc"],
+                                         m["lr"], 3, m["niters"])
+    # (Adam amplifies round-off about 5e3-fold over these 3 steps -- 3e-4 from fp32's 6e-8 -- so fp64 agrees to ~1e-12)
+    np.testing.assert_allclose(losses64, twin["adam_losses64"], rtol=1e-10)
+    for k, v in q3.items():
+        assert np.abs(v.numpy() - twin["p3_64:" + k]).max() < 1e-10, k
+    losses, p3 = torch_ref.train_steps(p, coords, target, m["L"], m["om1"], m["om"], m["sc"], m["lr"], 3, m["niters"])
+    l64 = twin["adam_losses64"]
+    for i in range(3):
+        within_ref(abs(losses[i] - l64[i]) / abs(l64[i]), abs(rec["adam_losses"][i] - l64[i]) / abs(l64[i]),
+                   f"torch_ref fp32 Adam loss, step {i + 1}")
     for k, v in p3.items():
-        assert np.abs(v.numpy() - rec["p3:" + k]).max() < 1e-5
+        t = twin["p3_64:" + k]
+        within_ref(np.abs(v.numpy() - t).max(), np.abs(rec["p3:" + k] - t).max(), f"torch_ref fp32 Adam p3 {k}")
 
 
 def test_torch_ref_init_matches_reference_checksums():
