@@ -144,6 +144,19 @@ int wire_train_fwd_bwd_hooked(void* stream, const wire_net_desc* d, const float*
                               int64_t scratch_bytes, void* const* grads_host,
                               wire_grad_ready_fn ready, void* user);
 
+/* ---- coordinate gradients (first order, fp32) ---------------------------
+ * wire_mlp_bwd_coords: wire_mlp_bwd that can also write g_coords [n][D] = dL/dcoords (f32).
+ *   grads_host NULL: data gradients only (no weight-gradient GEMM, no reduction of the parameter gradients);
+ *   g_coords NULL: exactly what wire_mlp_bwd produces; both NULL is an argument error.
+ *   scratch: wire_bwd_coords_scratch_bytes(d, n) when g_coords is given (>= wire_bwd_scratch_bytes).
+ *   The result is deterministic: every sum runs in a fixed order.
+ * wire_posenc_bwd: backward of wire_posenc_fwd, g_pe [n][D + 2 D F] -> g_coords [n][D].                  */
+int64_t wire_bwd_coords_scratch_bytes(const wire_net_desc* d, int64_t n);
+int wire_mlp_bwd_coords(void* stream, const wire_net_desc* d, const float* packed, const float* coords, int64_t n,
+                        const float* g_y, const void* act, int64_t act_bytes, void* scratch, int64_t scratch_bytes,
+                        void* const* grads_host, float* g_coords);
+int wire_posenc_bwd(void* stream, const float* coords, int64_t n, int D, int F, const float* g_pe, float* g_coords);
+
 /* ---- per-layer path (ComplexGaborLayer.forward, modules/wire.py:88-93) -- */
 /* x: [n][in] f32 when is_first else [n][in] c64; W: [out][in] f32/c64;
  * act_out [n][out] c64 (interleaved); lin_out (optional, may be NULL) receives the pre-activation
@@ -269,6 +282,15 @@ int wire_gabor2d_bwd(void* stream, const void* g_act, const void* x, const void*
                      const void* V, const void* c, float omega0, float scale0, int64_t n,
                      int in_features, int out_features, int is_first, void* g_x, void* g_W, void* g_b,
                      void* g_V, void* g_c, void* ws, int64_t ws_bytes);
+/* first layers (is_first) with the coordinate gradient: g_x [n][in <= 4] f32 = g_u W (+ g_p V for wire2d); the
+ * parameter gradients as wire_gabor_bwd / wire_gabor2d_bwd produce them, or (all NULL) not at all.  Same workspace. */
+int wire_gabor_bwd_first_coords(void* stream, const void* g_act, const float* x, const float* W, const float* b,
+                                float omega0, float scale0, int64_t n, int in_features, int out_features,
+                                float* g_x, float* g_W, float* g_b, void* ws, int64_t ws_bytes);
+int wire_gabor2d_bwd_first_coords(void* stream, const void* g_act, const float* x, const float* W, const float* b,
+                                  const float* V, const float* c, float omega0, float scale0, int64_t n,
+                                  int in_features, int out_features, float* g_x, float* g_W, float* g_b,
+                                  float* g_V, float* g_c, void* ws, int64_t ws_bytes);
 
 /* trainable omega_0 / scale_0 of ComplexGaborLayer2D (modules/wire2d.py:42-43 with trainable=True):
  * out2 (device, 2 floats) = { dL/d omega_0, dL/d scale_0 }; operands and workspace as wire_gabor2d_bwd. */

@@ -29,6 +29,8 @@ SYMBOLS = [
     "wire_final_bwd", "wire_coords_from_index", "wire_mse_grad",
     "wire_adam_step_flat", "wire_blocked_width", "wire_c64_to_blocked",
     "wire_blocked_to_c64", "wire_prof_enable", "wire_prof_read", "wire_tune_set", "wire_tune_get", "wire_avgpool_mse_grad", "wire_layer2d_ws_bytes", "wire_gabor2d_fwd", "wire_gabor2d_bwd", "wire_eval_metric", "wire_real_layer_fwd", "wire_real_layer_bwd", "wire_train_fwd_bwd", "wire_perm_indices", "wire_gabor_hparam_grad", "wire_track_best", "wire_sigmoid_inplace", "wire_radon_fwd", "wire_radon_bwd", "wire_gabor2d_hparam_grad", "wire_posenc_fwd", "wire_act_out_offset", "wire_train_fwd_bwd_hooked",
+    "wire_bwd_coords_scratch_bytes", "wire_mlp_bwd_coords", "wire_posenc_bwd", "wire_gabor_bwd_first_coords",
+    "wire_gabor2d_bwd_first_coords",
 ]
 
 
@@ -76,6 +78,13 @@ def _declare(l: C.CDLL) -> None:
     l.wire_track_best.argtypes = [vp, vp, vp, i32, vp, vp, i64, vp]
     l.wire_sigmoid_inplace.argtypes = [vp, vp, i64]
     l.wire_posenc_fwd.argtypes = [vp, vp, i64, i32, i32, vp]
+    l.wire_bwd_coords_scratch_bytes.argtypes = [dp, i64]
+    l.wire_bwd_coords_scratch_bytes.restype = i64
+    l.wire_mlp_bwd_coords.argtypes = [vp, dp, vp, vp, i64, vp, vp, i64, vp, i64, C.POINTER(vp), vp]
+    l.wire_posenc_bwd.argtypes = [vp, vp, i64, i32, i32, vp, vp]
+    l.wire_gabor_bwd_first_coords.argtypes = [vp, vp, vp, vp, vp, f32, f32, i64, i32, i32, vp, vp, vp, vp, i64]
+    l.wire_gabor2d_bwd_first_coords.argtypes = [vp, vp, vp, vp, vp, vp, vp, f32, f32, i64, i32, i32, vp, vp, vp, vp, vp,
+                                                vp, i64]
     l.wire_act_out_offset.argtypes = [dp, i64, i32]
     l.wire_act_out_offset.restype = i64
     l.wire_radon_fwd.argtypes = [vp, vp, vp, i32, i32, i32, vp]

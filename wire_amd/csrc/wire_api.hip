@@ -354,6 +354,21 @@ ScratchLayout scratch_layout(const Plan& p, int64_t n) {
   return s;
 }
 
+// coordinate-gradient scratch (wire_mlp_bwd_coords), behind the backward's own: the per-row partials of the layer-1
+// data-gradient epilogue, one set per 128-column tile of that GEMM's output [tile][n][D], and positional-encoding nets'
+// g_pe [n][Pin0]
+struct CoordLayout { int64_t cgp, gpe, total; int ntiles; };
+CoordLayout coord_layout(const Plan& p, int64_t n) {
+  CoordLayout c{};
+  int64_t off = (scratch_layout(p, n).total + 63) / 64 * 64;
+  c.ntiles = (p.P + 127) / 128;
+  c.cgp = off; off += (int64_t)c.ntiles * n * p.D;
+  off = (off + 63) / 64 * 64;
+  c.gpe = off; if (p.first_gemm) off += n * p.Pin0;
+  c.total = off;
+  return c;
+}
+
 int epi_fwd(int kind);
 int epi_bwd(int kind);
 // the hidden-layer GEMMs of this call run as 2 x fp16 splits: every forward / data-gradient launch is then a 16 x 16 x 32
@@ -467,6 +482,11 @@ extern "C" int64_t wire_bwd_scratch_bytes(const wire_net_desc* d, int64_t n) {
   Plan p; if (make_plan(d, p)) return WIRE_ERR_ARG;
   if (n < 0) return fail(WIRE_ERR_ARG, "negative n");
   return scratch_layout(p, n).total * 4 + 256;
+}
+extern "C" int64_t wire_bwd_coords_scratch_bytes(const wire_net_desc* d, int64_t n) {
+  Plan p; if (make_plan(d, p)) return WIRE_ERR_ARG;
+  if (n < 0) return fail(WIRE_ERR_ARG, "negative n");
+  return coord_layout(p, n).total * 4 + 256;
 }
 extern "C" int wire_blocked_width(int K) { return rup(2 * K, 64); }
 // float offset of out_l (rows of P floats, l = 0..L) inside an act buffer laid out for n rows with save_for_bwd = 1
@@ -741,15 +761,21 @@ extern "C" int wire_mlp_fwd(void* stream, const wire_net_desc* d, const float* p
 static int mlp_bwd_core(void* stream, const Plan& p, const float* packed, const float* coords, int64_t n,
                         const float* g_y, const void* act, int64_t act_bytes, void* scratch,
                         int64_t scratch_bytes, void* const* grads, bool do_final,
-                        wire_grad_ready_fn ready = nullptr, void* user = nullptr, int final_blocks = 0) {
+                        wire_grad_ready_fn ready = nullptr, void* user = nullptr, int final_blocks = 0,
+                        float* g_coords = nullptr) {
+  // grads == null (wire_mlp_bwd_coords only): the data gradients and g_coords alone -- no weight-gradient GEMM, no reduction
+  const bool want_grads = grads != nullptr;
   if (n <= 0) return fail(WIRE_ERR_ARG, "backward needs n > 0");
-  if (!packed || !coords || (do_final && !g_y) || !act || !scratch || !grads) return fail(WIRE_ERR_ARG, "null pointer");
-  for (int i = 0; i < p.ntens; ++i) if (!grads[i]) return fail(WIRE_ERR_ARG, "grads[%d] is null", i);
+  if (!packed || !coords || (do_final && !g_y) || !act || !scratch || (!grads && !g_coords))
+    return fail(WIRE_ERR_ARG, "null pointer");
+  if (want_grads) for (int i = 0; i < p.ntens; ++i) if (!grads[i]) return fail(WIRE_ERR_ARG, "grads[%d] is null", i);
   const ActLayout a = act_layout(p, n, 1);
   const ScratchLayout sc = scratch_layout(p, n);
+  const CoordLayout cl = coord_layout(p, n);
+  const int64_t need = g_coords ? cl.total : sc.total;
   if (act_bytes < a.total * 4) return fail(WIRE_ERR_SIZE, "act buffer too small");
-  if (scratch_bytes < sc.total * 4) return fail(WIRE_ERR_SIZE, "scratch %lld < %lld bytes",
-                                                (long long)scratch_bytes, (long long)sc.total * 4);
+  if (scratch_bytes < need * 4) return fail(WIRE_ERR_SIZE, "scratch %lld < %lld bytes",
+                                            (long long)scratch_bytes, (long long)need * 4);
   hipStream_t s = (hipStream_t)stream;
   const float* A = (const float*)act;
   float* Sx = (float*)scratch;
@@ -763,12 +789,17 @@ static int mlp_bwd_core(void* stream, const Plan& p, const float* packed, const 
   auto wamax = [&](int l) { return reinterpret_cast<const unsigned*>(packed + p.off_wamax + (int64_t)l * WIRE_AMAX_SLOTS); };
   // (the fused path zeroed the slots before its final stage published max |g_lin_L|)
   if (x2 && do_final) HIPCHK(hipMemsetAsync(gamax, 0, (size_t)(p.L + 2) * WIRE_AMAX_SLOTS * sizeof(unsigned), s));
-  const bool first_sums = p.k_first_sums && p.cplx && p.x3 && p.L >= 1 &&
+  const bool first_sums = want_grads && p.k_first_sums && p.cplx && p.x3 && p.L >= 1 &&
                           gemmx3_nt_is_h16(p.kind == WIRE_KIND_WIRE ? EPI_GABOR_BWD_FIRST : EPI_GABOR2D_BWD_FIRST, n);
   const int64_t crp_set = (int64_t)(colreduce_blocks(n) + 32) * p.ldu * 5;   // wire2d: second set of partial sums
   // the same for siren / gauss / relu with a native first layer: the epilogue of the layer-1 data gradient sums g_lin_0 [x | 1]
-  const bool first_sums_real = p.k_first_sums && !p.cplx && !p.first_gemm && p.x3 && p.L >= 1 &&
+  const bool first_sums_real = want_grads && p.k_first_sums && !p.cplx && !p.first_gemm && p.x3 && p.L >= 1 &&
                                gemmx3_nt_is_h16(epi_bwd(p.kind), n);
+  // the coordinate gradient: the layer-1 data-gradient epilogue of the 16 x 16 x 32 kernels forms its per-row partials
+  // (ep.cg_partial); the other paths store g_lin_0 / g_u / g_p, which coordgrad_rows (or, positional encoding, the fp32
+  // GEMM with the first layer's data-gradient image + posenc_bwd) contracts below
+  const int epi1 = p.cplx ? (p.kind == WIRE_KIND_WIRE ? EPI_GABOR_BWD_FIRST : EPI_GABOR2D_BWD_FIRST) : epi_bwd(p.kind);
+  const bool cg_epi = g_coords && !p.first_gemm && p.L >= 1 && p.x3 && gemmx3_nt_is_h16(epi1, n);
 
   // ---- final linear + activation gradient of layer L
   // (final_blocks: the training forward formed the final layer's partial sums itself, one block per workgroup)
@@ -790,9 +821,11 @@ static int mlp_bwd_core(void* stream, const Plan& p, const float* packed, const 
                               p.K, p.P, wL, p.s, gcur, Sx + sc.fpw, Sx + sc.fpb,
                               x2 ? gamax + p.L * WIRE_AMAX_SLOTS : nullptr));
     }
-    HIPCHK(launch_final_reduce(s, p.kind, Sx + sc.fpw, Sx + sc.fpb, nbf, p.O, p.K, p.P,
-                               (float*)grads[p.ntens - 2], (float*)grads[p.ntens - 1]));
-    if (ready) ready(user, p.ntens - 2, 2);
+    if (want_grads) {
+      HIPCHK(launch_final_reduce(s, p.kind, Sx + sc.fpw, Sx + sc.fpb, nbf, p.O, p.K, p.P,
+                                 (float*)grads[p.ntens - 2], (float*)grads[p.ntens - 1]));
+      if (ready) ready(user, p.ntens - 2, 2);
+    }
   }
   if (p.L == 0 && p.cplx) {
     // no hidden layer (net = first Gabor layer + final linear): gcur holds the raw g_out0; the first layer's
@@ -854,11 +887,13 @@ static int mlp_bwd_core(void* stream, const Plan& p, const float* packed, const 
   // ---- hidden layers L..1
   for (int l = p.L; l >= 1; --l) {
     if (chain) gcur = Sx + sc.gch + (int64_t)l * sc.gch_stride;
-    float* gW = (float*)grads[p.per_layer * l];
-    float* gb = (float*)grads[p.per_layer * l + 1];
-    float* gV = p.per_layer == 4 ? (float*)grads[p.per_layer * l + 2] : nullptr;
-    float* gc = p.per_layer == 4 ? (float*)grads[p.per_layer * l + 3] : nullptr;
-    if (p.m3) {
+    float* gW = want_grads ? (float*)grads[p.per_layer * l] : nullptr;
+    float* gb = want_grads ? (float*)grads[p.per_layer * l + 1] : nullptr;
+    float* gV = want_grads && p.per_layer == 4 ? (float*)grads[p.per_layer * l + 2] : nullptr;
+    float* gc = want_grads && p.per_layer == 4 ? (float*)grads[p.per_layer * l + 3] : nullptr;
+    if (!want_grads) {
+      // data gradients only: no weight gradient of this layer
+    } else if (p.m3) {
       const int S = sc.S;
       { ProfScope ps(s, 2, 2.0 * n * p.Pl * p.P);
         HIPCHK(launch_gemm3m_tn(s, gcur, p.P, out_l(l - 1), p.P, n, p.Kp, p.Kp, S, Sx + sc.slab,
@@ -924,6 +959,10 @@ static int mlp_bwd_core(void* stream, const Plan& p, const float* packed, const 
       if (p.per_layer == 4) { ep.W0b = packed + first_native_off(p, 2); ep.b0b = packed + first_native_off(p, 3); }
     }
     if (!p.cplx && l == 1) ep.ld0 = p.P;
+    if (l == 1 && cg_epi) {
+      ep.cg_partial = Sx + cl.cgp; ep.D = p.D;
+      if (!p.cplx) ep.W0 = packed + first_native_off(p, 0);
+    }
     if (chain) continue;                                    // g_lin_{l-1} (l = 1: the first layer's sums) is already there
     { ProfScope ps(s, 1, 2.0 * n * p.Pl * p.P);
       if (x2) {
@@ -941,6 +980,26 @@ static int mlp_bwd_core(void* stream, const Plan& p, const float* packed, const 
 
   // ---- first layer parameter gradients
   ProfScope ps(s, 3, 0);
+  if (g_coords) {
+    const float* W0 = packed + first_native_off(p, 0);
+    if (cg_epi) {
+      HIPCHK(launch_coordgrad_reduce(s, Sx + cl.cgp, cl.ntiles, n, p.D, g_coords));
+    } else if (p.kind == WIRE_KIND_WIRE) {
+      HIPCHK(launch_coordgrad_rows(s, Sx + sc.gu, p.ldu, nullptr, W0, nullptr, p.K, p.D, n, g_coords));
+    } else if (p.kind == WIRE_KIND_WIRE2D) {
+      HIPCHK(launch_coordgrad_rows(s, Sx + sc.gu, 2 * p.ldu, Sx + sc.gu + p.ldu, W0, packed + first_native_off(p, 2), p.K,
+                                   p.D, n, g_coords));
+    } else if (!p.first_gemm) {
+      HIPCHK(launch_coordgrad_rows(s, p.L == 0 ? Sx + sc.ga : gcur, p.P, nullptr, W0, nullptr, p.K, p.D, n, g_coords));
+    } else {
+      // g_pe = g_lin_0 W0 on the fp32 MFMA (the first layer's data-gradient image, Pin0 x P), then the encoding's chain rule
+      GemmEpiParams ep;
+      ep.o0 = Sx + cl.gpe; ep.ld0 = p.Pin0;
+      HIPCHK(launch_gemm_nt(s, EPI_STORE, p.L == 0 ? Sx + sc.ga : gcur, p.P, packed + p.off_dg[0], p.P, n, p.Pin0, p.P, ep));
+      HIPCHK(launch_posenc_bwd(s, coords, n, p.D, p.F, Sx + cl.gpe, p.Pin0, g_coords));
+    }
+  }
+  if (!want_grads) return WIRE_OK;
   if (p.cplx) {
     const float* gu = Sx + sc.gu;
     if (p.kind == WIRE_KIND_WIRE && first_sums) {
@@ -988,7 +1047,17 @@ extern "C" int wire_mlp_bwd(void* stream, const wire_net_desc* d, const float* p
                             int64_t act_bytes, void* scratch, int64_t scratch_bytes,
                             void* const* grads) {
   Plan p; if (int rc = make_plan(d, p)) return rc;
+  if (!grads) return fail(WIRE_ERR_ARG, "null pointer");
   return mlp_bwd_core(stream, p, packed, coords, n, g_y, act, act_bytes, scratch, scratch_bytes, grads, true);
+}
+
+extern "C" int wire_mlp_bwd_coords(void* stream, const wire_net_desc* d, const float* packed, const float* coords,
+                                   int64_t n, const float* g_y, const void* act, int64_t act_bytes, void* scratch,
+                                   int64_t scratch_bytes, void* const* grads_host, float* g_coords) {
+  Plan p; if (int rc = make_plan(d, p)) return rc;
+  if (!grads_host && !g_coords) return fail(WIRE_ERR_ARG, "wire_mlp_bwd_coords: neither grads_host nor g_coords");
+  return mlp_bwd_core(stream, p, packed, coords, n, g_y, act, act_bytes, scratch, scratch_bytes, grads_host, true,
+                      nullptr, nullptr, 0, g_coords);
 }
 
 // ---------------------------------------------------------------------------
@@ -1152,6 +1221,14 @@ extern "C" int wire_posenc_fwd(void* stream, const float* coords, int64_t n, int
   if (n < 0 || D < 1 || D > 4 || F < 0 || F > 30 || (n > 0 && (!coords || !out)))
     return fail(WIRE_ERR_ARG, "bad argument to wire_posenc_fwd");
   HIPCHK(launch_posenc((hipStream_t)stream, coords, n, D, F, D + 2 * D * F, out));
+  return WIRE_OK;
+}
+extern "C" int wire_posenc_bwd(void* stream, const float* coords, int64_t n, int D, int F, const float* g_pe,
+                               float* g_coords) {
+  if (n < 0 || D < 1 || D > 4 || F < 0 || F > 30 || (n > 0 && (!coords || !g_pe || !g_coords)))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_posenc_bwd");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_posenc_bwd((hipStream_t)stream, coords, n, D, F, g_pe, D + 2 * D * F, g_coords));
   return WIRE_OK;
 }
 extern "C" int wire_sigmoid_inplace(void* stream, float* x, int64_t count) {

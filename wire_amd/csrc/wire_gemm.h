@@ -13,7 +13,11 @@ enum WireEpi {
   EPI_SIREN_BWD = 7, EPI_GAUSS_BWD = 8, EPI_RELU_BWD = 9,   // i0 = lin, i1 = out -> o0 = g_lin
   EPI_GABOR2D_FWD = 10,     // C = (lin|sy)(re|im) 128-col groups: o0 = linsy [M][2P], o1 = out [M][P]
   EPI_GABOR2D_BWD = 11,     // C = g_out: i0 = linsy, i1 = out -> o0 = g_linsy [M][2P]
-  EPI_GABOR2D_BWD_FIRST = 12  // real first layer of wire2d: o0 = g_(u|p) [M][2*ldu]
+  EPI_GABOR2D_BWD_FIRST = 12, // real first layer of wire2d: o0 = g_(u|p) [M][2*ldu]
+  // flag on the layer-1 data-gradient forms of the 16 x 16 x 32 kernels (the real BWD forms, GABOR_BWD_FIRST,
+  // GABOR2D_BWD_FIRST): the instantiation that also writes ep.cg_partial.  Host code passes the plain code; the
+  // launchers pick the flagged instantiation when ep.cg_partial is set
+  EPI_CG = 64
 };
 
 struct GemmEpiParams {
@@ -38,6 +42,9 @@ struct GemmEpiParams {
   float* cr_partial = nullptr;   // EPI_GABOR_BWD_FIRST of wire_gemmx3h.hip: per-256-row-tile sums [tile][cr_C][5] of
   int cr_C = 0;                  //   g_u [x | 1] (the first layer's weight / bias gradient) instead of storing g_u
   int64_t cr_set = 0;            //   wire2d: floats between the sums of the layer's two Linears (g_u, g_p)
+  float* cg_partial = nullptr;   // layer-1 data-gradient epilogues of the 16 x 16 x 32 kernels (wire_gemmh_epi.h): per-row
+                                 //   coordinate-gradient partials [column tile][M][D] of g_lin_0 W0 (real nets; W0 native
+                                 //   [K][D]), g_u W0 (wire), g_u W0 + g_p W0b (wire2d); the stores are unchanged
   int recompute_out = 0;         // EPI_GABOR_BWD of wire_gemmx3h.hip: out = act(lin) again instead of reading i1
   int stagger = 0, stagger_lo = 0, stagger_hi = 0;   // wire_gemmx3g.hip: late start (100 MHz ticks) of blocks [lo, hi)
   // 2 x fp16 split GEMM (wire_gemmx2h.hip): sharded max-|value| slots (WIRE_AMAX_SLOTS unsigned each, wire_dev.h)

@@ -38,12 +38,39 @@ WIRE_DEVINL void h_amax4(float& m, const f32x4& v) {
                                          __builtin_fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3]))));
 }
 
+// Coordinate-gradient partials (ep.cg_partial): a row's 128 columns of the tile lie in ONE wave, in the 8 lanes that share
+// rr (lane bits 3-5: ch, g).  t = this lane's columns' contribution to the row slot e (= 2 rb + hr, 0 .. 2 NRB - 1) is
+// summed over those lanes by a fixed butterfly; lane group j = lane >> 3 keeps slot j's sum.  h_cg_store writes it once
+// per row and column tile -- no atomics, the same bits every run.
+WIRE_DEVINL void h_cg_add(float (&cg)[4], const float (&t)[4], const int e, const int lane) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    float v = t[d];
+    v += __shfl_xor(v, 8); v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+    cg[d] += (lane >> 3) == e ? v : 0.f;
+  }
+}
+template <int NRB>
+WIRE_DEVINL void h_cg_store(const float (&cg)[4], const GemmEpiParams& ep, const int M, const int m_w, const int n_w,
+                            const int lane) {
+  const int j = lane >> 3;
+  if (j >= 2 * NRB) return;
+  const int row = m_w + 16 * (j >> 1) + 8 * (j & 1) + (lane & 7);
+  if (row >= M) return;
+  float* dst = ep.cg_partial + ((size_t)(n_w >> 7) * (size_t)M + (size_t)row) * ep.D;
+  for (int d = 0; d < ep.D; ++d) dst[d] = cg[d];
+}
+
 // NRB = 16-row blocks of the wave's tile (4: 64 rows per wave, 256-row workgroup tiles; 2: 32 rows per wave, 128-row tiles
 // -- not with the first-layer sums (cr_partial), whose per-tile layout is that of the 256-row tile)
-template <int EPI, bool X2 = false, int NRB = 4>
+// EPIX = an EPI_* code, | EPI_CG for the layer-1 data-gradient forms that also write coordinate-gradient partials
+// (ep.cg_partial): a separate instantiation, so the forms without it keep their registers
+template <int EPIX, bool X2 = false, int NRB = 4>
 WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const int M, const int m_w, const int n_w,
                             const int Nc, const int lane, unsigned char* lds, const int wave, const int rt,
                             const float acc_scale = 1.f) {
+  constexpr int EPI = EPIX & ~EPI_CG;
+  constexpr bool CG = (EPIX & EPI_CG) != 0;
   const int rr = lane & 7, ch = (lane >> 3) & 1, g = lane >> 4;
   float amx = 0.f;
   if constexpr (X2) {
@@ -102,6 +129,7 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
     }
   } else if constexpr (EPI == EPI_SIREN_BWD || EPI == EPI_GAUSS_BWD || EPI == EPI_RELU_BWD) {
     constexpr int ACT = EPI - EPI_SIREN_BWD;
+    float cg[4] = {0.f, 0.f, 0.f, 0.f};                           // cg_partial: this lane group's row sums of g_lin_0 W0
 #pragma unroll
     for (int sp = 0; sp < 4; ++sp) {
       if (n_w + 32 * sp >= Nc) continue;
@@ -145,6 +173,17 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
 #pragma unroll
           for (int q = 0; q < 4; ++q) gl[q] = real_act_bwd_lean<ACT>(a2[e][q], lv[e][q], ov[e][q], ep.omega, ep.scale);
           if constexpr (X2) h_amax4(amx, gl);
+          if constexpr (CG) {
+            float t[4] = {0.f, 0.f, 0.f, 0.f};
+            if (row < M) {                                        // (W0 from L1: 16 more registers here spill)
+#pragma unroll
+              for (int q = 0; q < 4; ++q) {
+                if (col + q >= ep.kvalid) continue;
+                for (int d = 0; d < ep.D; ++d) t[d] = __builtin_fmaf(gl[q], ep.W0[(col + q) * ep.D + d], t[d]);
+              }
+            }
+            h_cg_add(cg, t, 2 * (rp + (e >> 1)) + (e & 1), lane);
+          }
           if (row < M) {
             if (ep.cr_partial) {
               // first layer of a real net: its weight / bias gradient sums g_lin_0 [x | 1] are formed here (what
@@ -184,6 +223,7 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
         if (n_w + c < ep.cr_C) ep.cr_partial[((size_t)rt * ep.cr_C + n_w + c) * 5 + d] = v;
       }
     }
+    if constexpr (CG) h_cg_store<NRB>(cg, ep, M, m_w, n_w, lane);
   } else if constexpr (EPI == EPI_GABOR2D_FWD) {
     // the wave's 128 columns = (lin_re | lin_im | sy_re | sy_im) of 32 features (modules/wire2d.py:56-67)
     const int grp = n_w >> 7;
@@ -237,6 +277,7 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
   } else if constexpr (EPI == EPI_GABOR2D_BWD || EPI == EPI_GABOR2D_BWD_FIRST) {
     // C = g_out (re | im pairs, P wide); writes g_(lin | sy) into the 2P-wide row (or the real g_(u | p) of layer 0)
     const float m2s2 = -2.f * ep.scale * ep.scale, w0 = ep.omega;
+    float cg[4] = {0.f, 0.f, 0.f, 0.f};                           // BWD_FIRST with cg_partial: row sums of g_u W0 + g_p V0
 #pragma unroll
     for (int G = 0; G < 2; ++G) {
       if (n_w + 64 * G >= Nc) continue;
@@ -326,6 +367,18 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
             g3[q] = tt * qq[hr][q];
           }
           if constexpr (X2 && EPI == EPI_GABOR2D_BWD) { h_amax4(amx, g0); h_amax4(amx, g1); h_amax4(amx, g2); h_amax4(amx, g3); }
+          if constexpr (EPI == EPI_GABOR2D_BWD_FIRST) {
+            if constexpr (CG) {                                   // (w, wv are 0 for pad features and d >= D)
+              float t[4] = {0.f, 0.f, 0.f, 0.f};
+              if (row < M) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                  for (int d = 0; d < 4; ++d) t[d] = __builtin_fmaf(g2[q], wv[q][d], __builtin_fmaf(g0[q], w[q][d], t[d]));
+              }
+              h_cg_add(cg, t, 2 * rb + hr, lane);
+            }
+          }
           if (row < M) {
             if constexpr (EPI == EPI_GABOR2D_BWD) {
               float* Gp = ep.o0 + (size_t)row * ep.ld0 + lc;
@@ -390,11 +443,13 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
             ep.cr_partial[(size_t)set * ep.cr_set + ((size_t)rt * ep.cr_C + fbase + f) * 5 + d] = v;
         }
       }
+      if constexpr (CG) h_cg_store<NRB>(cg, ep, M, m_w, n_w, lane);
     }
   } else {
     // complex epilogues: 64-column groups (re | im of 32 features) = blocks 4 G, 4 G + 1 (re) and 4 G + 2, 4 G + 3 (im)
     const float w0 = ep.omega, w0l2e = ep.omega * 1.44269502f, ns2l2e = -(ep.scale * ep.scale) * 1.44269502f;
     const float m2s2 = -2.f * ep.scale * ep.scale;
+    float cg[4] = {0.f, 0.f, 0.f, 0.f};                           // BWD_FIRST with cg_partial: row sums of g_u W0
 #pragma unroll
     for (int G = 0; G < 2; ++G) {
       if (n_w + 64 * G >= Nc) continue;
@@ -513,6 +568,7 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
 #pragma unroll
           for (int hr = 0; hr < 2; ++hr) {
             const int row = m_w + 16 * rb + 8 * hr + rr;
+            float t[4] = {0.f, 0.f, 0.f, 0.f};                    // cg_partial: g_u W0 over this lane's 4 features
             if (row < M) {
               float x[4] = {0.f, 0.f, 0.f, 0.f};
               for (int d = 0; d < ep.D; ++d) x[d] = ep.coords[(size_t)row * ep.D + d];
@@ -538,6 +594,12 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
                 const float v = gabor_bwd_real(are[hr][q], aim[hr][q], u, pr[q], pi[q], w0, m2s2);
                 gu[q] = f0 + q < ep.kvalid ? v : 0.f;
               }
+              if constexpr (CG) {                                 // (w is 0 for pad features and d >= D)
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                  for (int d = 0; d < 4; ++d) t[d] = __builtin_fmaf(gu[q], w[q][d], t[d]);
+              }
               if (ep.cr_partial) {
                 // first-layer gradient sums of this lane's rows: g_u [x | 1] (what colreduce_kernel would form from
                 // the stored g_u -- which is then never written)
@@ -551,6 +613,7 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
                 *reinterpret_cast<f32x4*>(ep.o0 + (size_t)row * ep.ldu + f0) = gu;
               }
             }
+            if constexpr (CG) h_cg_add(cg, t, 2 * rb + hr, lane);
           }
         }
       }
@@ -592,6 +655,7 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
           if (fbase + f < ep.cr_C) ep.cr_partial[((size_t)rt * ep.cr_C + fbase + f) * 5 + d] = v;
         }
       }
+      if constexpr (CG) h_cg_store<NRB>(cg, ep, M, m_w, n_w, lane);
     }
   }
   if constexpr (X2) {

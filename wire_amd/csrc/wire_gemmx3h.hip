@@ -271,18 +271,28 @@ hipError_t launch_gemmx3h_nt(hipStream_t s, int epi, const float* A, int lda, co
     case EPI_STORE: return launchx3h_t<EPI_STORE>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_GABOR_FWD: return launchx3h_t<EPI_GABOR_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_GABOR_BWD: return launchx3h_t<EPI_GABOR_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD_FIRST: return launchx3h_t<EPI_GABOR_BWD_FIRST>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_GABOR_BWD_FIRST:
+      return ep.cg_partial ? launchx3h_t<EPI_GABOR_BWD_FIRST | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
+                           : launchx3h_t<EPI_GABOR_BWD_FIRST>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_SIREN_FWD: return launchx3h_t<EPI_SIREN_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_GAUSS_FWD: return launchx3h_t<EPI_GAUSS_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_RELU_FWD: return launchx3h_t<EPI_RELU_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_SIREN_BWD: return launchx3h_t<EPI_SIREN_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GAUSS_BWD: return launchx3h_t<EPI_GAUSS_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_RELU_BWD: return launchx3h_t<EPI_RELU_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_SIREN_BWD:
+      return ep.cg_partial ? launchx3h_t<EPI_SIREN_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
+                           : launchx3h_t<EPI_SIREN_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_GAUSS_BWD:
+      return ep.cg_partial ? launchx3h_t<EPI_GAUSS_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
+                           : launchx3h_t<EPI_GAUSS_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_RELU_BWD:
+      return ep.cg_partial ? launchx3h_t<EPI_RELU_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
+                           : launchx3h_t<EPI_RELU_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_GABOR2D_FWD:
       if (Nc & 127) return hipErrorInvalidValue;
       return launchx3h_t<EPI_GABOR2D_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_GABOR2D_BWD: return launchx3h_t<EPI_GABOR2D_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD_FIRST: return launchx3h_t<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_GABOR2D_BWD_FIRST:
+      return ep.cg_partial ? launchx3h_t<EPI_GABOR2D_BWD_FIRST | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
+                           : launchx3h_t<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bu, M, Nc, Kd, ep);
     default: return hipErrorInvalidValue;
   }
 }

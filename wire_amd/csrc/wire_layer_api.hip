@@ -272,6 +272,28 @@ extern "C" int wire_gabor_bwd(void* stream, const void* g_act, const void* x, co
   return WIRE_OK;
 }
 
+// first layer with the coordinate gradient: g_x [n][in] f32 = g_u W (coordgrad_rows over the g_u the backward forms
+// anyway); g_W / g_b NULL together = the coordinate gradient alone
+extern "C" int wire_gabor_bwd_first_coords(void* stream, const void* g_act, const float* x, const float* W, const float* b,
+                                           float omega0, float scale0, int64_t n, int in_features, int out_features,
+                                           float* g_x, float* g_W, float* g_b, void* ws, int64_t ws_bytes) {
+  if (n <= 0 || in_features < 1 || in_features > 4 || out_features < 1 || !g_act || !x || !W || !b || !g_x || !ws ||
+      (!g_W) != (!g_b))
+    return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_gabor_bwd_first_coords");
+  const LayerWs w = layer_ws(n, in_features, out_features);
+  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  float* W_ = (float*)ws;
+  if (int rc = layer_forward_ws(s, w, W_, x, W, b, omega0, scale0, n, in_features, out_features, 1)) return rc;
+  LCHK(launch_c64_to_blocked(s, (const float*)g_act, n, out_features, w.Pout, W_ + w.gact));
+  const int ldu = w.Pout / 2;
+  LCHK(launch_gabor_bwd_first_point(s, W_ + w.gact, W_ + w.out, x, in_features, W, b, n, out_features, w.Pout,
+                                    omega0, scale0, W_ + w.gu, ldu));
+  if (g_W) LCHK(launch_colreduce(s, W_ + w.gu, ldu, out_features, x, in_features, n, W_ + w.crp, g_W, g_b));
+  LCHK(launch_coordgrad_rows(s, W_ + w.gu, ldu, nullptr, W, nullptr, out_features, in_features, n, g_x));
+  return WIRE_OK;
+}
+
 // trainable omega_0 / scale_0 (ComplexGaborLayer(trainable=True), modules/wire.py:80-81): out2 = {dL/d omega_0,
 // dL/d scale_0} (device).  Recomputes the layer's forward from x, like wire_gabor_bwd.
 extern "C" int wire_gabor_hparam_grad(void* stream, const void* g_act, const void* x, const void* W, const void* b,
@@ -537,5 +559,31 @@ extern "C" int wire_gabor2d_bwd(void* stream, const void* g_act, const void* x, 
   }
   LCHK(g.tn_reduce(s, NK_WIRE2D, W_ + w.glinsy, W_ + w.xb, n, 2 * w.Pout, w.Pin, out_features, in_features,
                    W_ + w.slab, W_ + w.bslab, (float*)g_W, (float*)g_b, (float*)g_V, (float*)g_c));
+  return WIRE_OK;
+}
+
+// wire2d first layer with the coordinate gradient: g_x [n][in] f32 = g_u W + g_p V; g_W .. g_c NULL together = the
+// coordinate gradient alone
+extern "C" int wire_gabor2d_bwd_first_coords(void* stream, const void* g_act, const float* x, const float* W,
+                                             const float* b, const float* V, const float* c, float omega0, float scale0,
+                                             int64_t n, int in_features, int out_features, float* g_x, float* g_W,
+                                             float* g_b, float* g_V, float* g_c, void* ws, int64_t ws_bytes) {
+  const bool pg = g_W && g_b && g_V && g_c;
+  if (n <= 0 || in_features < 1 || in_features > 4 || out_features < 1 || !g_act || !x || !W || !b || !V || !c ||
+      !g_x || !ws || (!pg && (g_W || g_b || g_V || g_c)))
+    return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_gabor2d_bwd_first_coords");
+  const Layer2dWs w = layer2d_ws(n, in_features, out_features);
+  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  float* W_ = (float*)ws;
+  if (int rc = layer2d_forward_ws(s, w, W_, x, W, b, V, c, omega0, scale0, n, in_features, out_features, 1)) return rc;
+  LCHK(launch_c64_to_blocked(s, (const float*)g_act, n, out_features, w.Pout, W_ + w.gact));
+  LCHK(launch_gabor2d_bwd_first_point(s, W_ + w.gact, W_ + w.out, x, in_features, W, b, V, c, n, out_features, w.Pout,
+                                      omega0, scale0, W_ + w.gup, w.ldu));
+  if (pg) {
+    LCHK(launch_colreduce(s, W_ + w.gup, 2 * w.ldu, out_features, x, in_features, n, W_ + w.crp, g_W, g_b));
+    LCHK(launch_colreduce(s, W_ + w.gup + w.ldu, 2 * w.ldu, out_features, x, in_features, n, W_ + w.crp, g_V, g_c));
+  }
+  LCHK(launch_coordgrad_rows(s, W_ + w.gup, 2 * w.ldu, W_ + w.gup + w.ldu, W, V, out_features, in_features, n, g_x));
   return WIRE_OK;
 }

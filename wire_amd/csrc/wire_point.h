@@ -99,6 +99,18 @@ hipError_t launch_real_act_bwd_point(hipStream_t s, int kind, const float* g, co
 hipError_t launch_posenc(hipStream_t s, const float* coords, int64_t n, int D, int F, int Pin,
                          float* dst);
 
+// ---- coordinate gradients (first-order, fp32)
+// g_x[r][d] = sum_k G[r][k] W[k][d] (+ sum_k G2[r][k] V[k][d]) over the K valid features of a stored first-layer gradient
+// (real g_lin_0, wire g_u, wire2d g_u with G2 = g_p); W, V native [K][D].  One wave per row, fixed reduction order.
+hipError_t launch_coordgrad_rows(hipStream_t s, const float* G, int ldg, const float* G2, const float* W, const float* V,
+                                 int K, int D, int64_t n, float* g_x);
+// g_x[r][d] = sum_t partial[t][r][d], t = 0 .. ntiles - 1 in that order (the data-gradient epilogue's per-column-tile
+// partials, GemmEpiParams::cg_partial)
+hipError_t launch_coordgrad_reduce(hipStream_t s, const float* partial, int ntiles, int64_t n, int D, float* g_x);
+// modules/relu.py:62-75 backward: g_pe [n][ldpe] in posenc_kernel's feature order -> g_x [n][D]
+hipError_t launch_posenc_bwd(hipStream_t s, const float* coords, int64_t n, int D, int F, const float* g_pe, int ldpe,
+                             float* g_x);
+
 // ---- training glue
 // idx_out[r] = pi_seed(first + r), r < count: a keyed bijection pi_seed of [0, n_total) (the epoch's shuffle)
 hipError_t launch_perm_indices(hipStream_t s, uint64_t seed, int64_t n_total, int64_t first, int64_t count,

@@ -1296,6 +1296,114 @@ hipError_t launch_posenc(hipStream_t s, const float* coords, int64_t n, int D, i
 }
 
 // ===========================================================================
+// coordinate gradients: one wave per row, features strided over the lanes, a fixed butterfly across them (no atomics:
+// the same bits every run)
+// ===========================================================================
+WIRE_DEVINL float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__global__ __launch_bounds__(256) void coordgrad_rows_kernel(const float* __restrict__ G, int ldg,
+                                                             const float* __restrict__ G2, const float* __restrict__ W,
+                                                             const float* __restrict__ V, int K, int D, long long n,
+                                                             float* __restrict__ g_x) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const int lane = threadIdx.x & 63;
+  float a[4] = {0.f, 0.f, 0.f, 0.f};
+  const float* g = G + (size_t)row * ldg;
+  const float* g2 = G2 ? G2 + (size_t)row * ldg : nullptr;
+  for (int k = lane; k < K; k += 64) {
+    const float gv = g[k];
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      if (d < D) a[d] = __builtin_fmaf(gv, W[k * D + d], a[d]);
+    if (g2) {
+      const float pv = g2[k];
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        if (d < D) a[d] = __builtin_fmaf(pv, V[k * D + d], a[d]);
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 4; ++d) a[d] = wave_sum(a[d]);
+  if (lane < D) {
+    float v = a[0];
+#pragma unroll
+    for (int d = 1; d < 4; ++d) v = lane == d ? a[d] : v;
+    g_x[row * D + lane] = v;
+  }
+}
+hipError_t launch_coordgrad_rows(hipStream_t s, const float* G, int ldg, const float* G2, const float* W, const float* V,
+                                 int K, int D, int64_t n, float* g_x) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(coordgrad_rows_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, G, ldg, G2, W, V, K, D, (long long)n, g_x);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void coordgrad_reduce_kernel(const float* __restrict__ partial, int ntiles,
+                                                               long long count, float* __restrict__ g_x) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= count) return;
+  float v = partial[e];
+  for (int t = 1; t < ntiles; ++t) v += partial[(size_t)t * count + e];
+  g_x[e] = v;
+}
+hipError_t launch_coordgrad_reduce(hipStream_t s, const float* partial, int ntiles, int64_t n, int D, float* g_x) {
+  if (n <= 0) return hipSuccess;
+  const int64_t count = n * D;
+  hipLaunchKernelGGL(coordgrad_reduce_kernel, dim3(cdiv(count, 256)), dim3(256), 0, s, partial, ntiles,
+                     (long long)count, g_x);
+  return hipGetLastError();
+}
+
+// d/dx_j of [x, {sin(2^i pi x_j), cos(2^i pi x_j)}]: 1, 2^i pi cos, -2^i pi sin -- posenc_kernel's feature order and its
+// fp32 arguments
+__global__ __launch_bounds__(256) void posenc_bwd_kernel(const float* __restrict__ coords, long long n, int D, int F,
+                                                         const float* __restrict__ g_pe, int ldpe,
+                                                         float* __restrict__ g_x) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const int lane = threadIdx.x & 63;
+  float a[4] = {0.f, 0.f, 0.f, 0.f};
+  const float* g = g_pe + (size_t)row * ldpe;
+  const int Din = D + 2 * D * F;
+  for (int c = lane; c < Din; c += 64) {
+    int j;
+    float v;
+    if (c < D) {
+      j = c;
+      v = g[c];
+    } else {
+      const int e = c - D;
+      const int i = e / (2 * D);
+      j = (e % (2 * D)) >> 1;
+      const float freq = (float)((double)(1 << i) * 3.14159265358979323846);
+      float sn, cs;
+      wire_sincos(freq * coords[row * D + j], sn, cs);
+      v = g[c] * ((e & 1) ? -freq * sn : freq * cs);
+    }
+#pragma unroll
+    for (int d = 0; d < 4; ++d) a[d] += d == j ? v : 0.f;
+  }
+#pragma unroll
+  for (int d = 0; d < 4; ++d) a[d] = wave_sum(a[d]);
+  if (lane < D) {
+    float v = a[0];
+#pragma unroll
+    for (int d = 1; d < 4; ++d) v = lane == d ? a[d] : v;
+    g_x[row * D + lane] = v;
+  }
+}
+hipError_t launch_posenc_bwd(hipStream_t s, const float* coords, int64_t n, int D, int F, const float* g_pe, int ldpe,
+                             float* g_x) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(posenc_bwd_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, coords, (long long)n, D, F, g_pe, ldpe, g_x);
+  return hipGetLastError();
+}
+
+// ===========================================================================
 // training glue
 // ===========================================================================
 // Keyed bijection of [0, n): the per-epoch shuffle of wire_image_denoise.py:142 / wire_occupancy.py:137

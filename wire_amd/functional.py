@@ -29,6 +29,15 @@ def _require_cuda(t: torch.Tensor, what: str) -> None:
             "Move the model and its inputs to 'cuda'.")
 
 
+def _no_second_order(what: str) -> None:
+    # backward runs with grad mode on only under create_graph=True: the coordinate gradient is computed by kernels that
+    # record no graph of their own, so a second-order request must fail instead of returning a gradient without one
+    if torch.is_grad_enabled():
+        raise NotImplementedError(
+            f"{what}: the gradient with respect to the coordinates is first order only (create_graph=True is not "
+            "supported when the coordinates require a gradient)")
+
+
 def _native(t: torch.Tensor) -> torch.Tensor:
     """Contiguous tensor whose storage is the native layout the ABI expects
     (complex64 = interleaved floats)."""
@@ -58,7 +67,8 @@ class _INRFunction(torch.autograd.Function):
         # (inside torch.no_grad() needs_input_grad still reports the parameters' requires_grad; no graph is recorded
         #  there, so nothing is saved and the forward-only kernels run.  grad_mode = torch.is_grad_enabled() at the call:
         #  inside forward() it is always off)
-        need_bwd = grad_mode and any(ctx.needs_input_grad[3:])
+        # (the coordinates' own requires_grad counts too: a frozen field can still differentiate to its inputs)
+        need_bwd = grad_mode and any(ctx.needs_input_grad)
         act_bytes = _lib.check(L.wire_act_bytes(C.byref(desc), n, int(need_bwd)), "wire_act_bytes")
         act = torch.empty(act_bytes, dtype=torch.uint8, device=dev)
         y = torch.empty(tuple(coords.shape[:-1]) + (O,), dtype=torch.float32, device=dev)
@@ -69,6 +79,7 @@ class _INRFunction(torch.autograd.Function):
             ctx.desc, ctx.n = desc, n
             ctx.packed, ctx.act, ctx.x = packed, act, x
             ctx.meta = [(p.shape, p.dtype) for p in params]
+            ctx.xmeta = (tuple(coords.shape), coords.dtype)
         return y
 
     @staticmethod
@@ -77,17 +88,30 @@ class _INRFunction(torch.autograd.Function):
         desc, n = ctx.desc, ctx.n
         dev = g_y.device
         gy = g_y.detach().to(torch.float32).contiguous()
-        grads = [torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in ctx.meta]
         stream = _stream_ptr(dev)
+        if ctx.needs_input_grad[0]:
+            _no_second_order("wire_amd model")
+            want_p = any(ctx.needs_input_grad[3:])
+            grads = [torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in ctx.meta] if want_p else []
+            g_x = torch.empty(n, desc.in_features, dtype=torch.float32, device=dev)
+            sbytes = _lib.check(L.wire_bwd_coords_scratch_bytes(C.byref(desc), n), "wire_bwd_coords_scratch_bytes")
+            scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+            # grads_host = NULL without trainable parameters: the data-gradient chain alone (no weight-gradient GEMM)
+            _lib.check(L.wire_mlp_bwd_coords(stream, C.byref(desc), ctx.packed.data_ptr(), ctx.x.data_ptr(), n,
+                                             gy.data_ptr(), ctx.act.data_ptr(), ctx.act.numel(), scratch.data_ptr(),
+                                             sbytes, _lib.ptr_array([g.data_ptr() for g in grads]) if want_p else None,
+                                             g_x.data_ptr()), "wire_mlp_bwd_coords")
+            xshape, xdtype = ctx.xmeta
+            g_coords = g_x.reshape(xshape).to(xdtype)
+            return (g_coords, None, None, *(grads if want_p else [None] * len(ctx.meta)))
+        grads = [torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in ctx.meta]
         sbytes = _lib.check(L.wire_bwd_scratch_bytes(C.byref(desc), n), "wire_bwd_scratch_bytes")
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
         _lib.check(L.wire_mlp_bwd(stream, C.byref(desc), ctx.packed.data_ptr(), ctx.x.data_ptr(), n,
                                   gy.data_ptr(), ctx.act.data_ptr(), ctx.act.numel(),
                                   scratch.data_ptr(), sbytes,
                                   _lib.ptr_array([g.data_ptr() for g in grads])), "wire_mlp_bwd")
-        # the saved buffers stay with the graph node (freed with it), so backward(retain_graph=True) can run again.
-        # No gradient is returned for `coords` (the reference's autograd would produce one; no caller in the
-        # reference asks for it -- INTEGRATION.md)
+        # the saved buffers stay with the graph node (freed with it), so backward(retain_graph=True) can run again
         return (None, None, None, *grads)
 
 
@@ -116,6 +140,7 @@ class _GaborLayerFunction(torch.autograd.Function):
                                     act.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor_fwd")
         ctx.save_for_backward(xin, Wn, bn)
         ctx.cfg = (omega0, scale0, is_first, n, in_f, out_f, tuple(x.shape))
+        ctx.xdtype = x.dtype
         return act
 
     @staticmethod
@@ -129,12 +154,40 @@ class _GaborLayerFunction(torch.autograd.Function):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         gW = torch.empty_like(Wn)
         gb = torch.empty_like(bn)
+        if is_first and ctx.needs_input_grad[0]:
+            gx = _gabor_first_coords(L, g, xin, Wn, bn, omega0, scale0, n, in_f, out_f, gW, gb, ws, ws_bytes, xshape,
+                                     ctx.xdtype)
+            return gx, gW, gb, None, None, None
         gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
         _lib.check(L.wire_gabor_bwd(_stream_ptr(dev), g.data_ptr(), xin.data_ptr(), Wn.data_ptr(),
                                     bn.data_ptr(), omega0, scale0, n, in_f, out_f, int(is_first),
                                     None if gx is None else gx.data_ptr(), gW.data_ptr(),
                                     gb.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor_bwd")
         return gx, gW, gb, None, None, None
+
+
+def _gabor_first_coords(L, g, xin, Wn, bn, omega0, scale0, n, in_f, out_f, gW, gb, ws, ws_bytes, xshape, xdtype):
+    """First Gabor layer with the coordinate gradient: wire_gabor_bwd_first_coords (g_x = g_u W)."""
+    _no_second_order("ComplexGaborLayer (is_first)")
+    gx = torch.empty(n, in_f, dtype=torch.float32, device=g.device)
+    _lib.check(L.wire_gabor_bwd_first_coords(_stream_ptr(g.device), g.data_ptr(), xin.data_ptr(), Wn.data_ptr(),
+                                             bn.data_ptr(), omega0, scale0, n, in_f, out_f, gx.data_ptr(),
+                                             gW.data_ptr(), gb.data_ptr(), ws.data_ptr(), ws_bytes),
+               "wire_gabor_bwd_first_coords")
+    return gx.reshape(xshape).to(xdtype)
+
+
+def _gabor2d_first_coords(L, g, xin, Wn, bn, Vn, cn, omega0, scale0, n, in_f, out_f, gW, gb, gV, gc, ws, ws_bytes,
+                          xshape, xdtype):
+    """First Gabor-2D layer with the coordinate gradient: wire_gabor2d_bwd_first_coords (g_x = g_u W + g_p V)."""
+    _no_second_order("ComplexGaborLayer2D (is_first)")
+    gx = torch.empty(n, in_f, dtype=torch.float32, device=g.device)
+    _lib.check(L.wire_gabor2d_bwd_first_coords(_stream_ptr(g.device), g.data_ptr(), xin.data_ptr(), Wn.data_ptr(),
+                                               bn.data_ptr(), Vn.data_ptr(), cn.data_ptr(), omega0, scale0, n, in_f,
+                                               out_f, gx.data_ptr(), gW.data_ptr(), gb.data_ptr(), gV.data_ptr(),
+                                               gc.data_ptr(), ws.data_ptr(), ws_bytes),
+               "wire_gabor2d_bwd_first_coords")
+    return gx.reshape(xshape).to(xdtype)
 
 
 def gabor_layer(x, W, b, omega0: float, scale0: float, is_first: bool):
@@ -155,6 +208,7 @@ class _GaborLayerTrainableFunction(torch.autograd.Function):
         ctx.save_for_backward(xin, _native(W), _native(b))
         ctx.cfg = (omega0, scale0, is_first, xin.numel() // in_f, in_f, W.shape[0], tuple(x.shape), omega.shape,
                    scale.shape)
+        ctx.xdtype = x.dtype
         return act
 
     @staticmethod
@@ -167,11 +221,15 @@ class _GaborLayerTrainableFunction(torch.autograd.Function):
         ws_bytes = _lib.check(L.wire_layer_ws_bytes(n, in_f, out_f), "wire_layer_ws_bytes")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         gW, gb = torch.empty_like(Wn), torch.empty_like(bn)
-        gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
         stream = _stream_ptr(dev)
-        _lib.check(L.wire_gabor_bwd(stream, g.data_ptr(), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(), omega0,
-                                    scale0, n, in_f, out_f, int(is_first), None if gx is None else gx.data_ptr(),
-                                    gW.data_ptr(), gb.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor_bwd")
+        if is_first and ctx.needs_input_grad[0]:
+            gx = _gabor_first_coords(L, g, xin, Wn, bn, omega0, scale0, n, in_f, out_f, gW, gb, ws, ws_bytes, xshape,
+                                     ctx.xdtype)
+        else:
+            gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
+            _lib.check(L.wire_gabor_bwd(stream, g.data_ptr(), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(), omega0,
+                                        scale0, n, in_f, out_f, int(is_first), None if gx is None else gx.data_ptr(),
+                                        gW.data_ptr(), gb.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor_bwd")
         hp = torch.empty(2, dtype=torch.float32, device=dev)
         _lib.check(L.wire_gabor_hparam_grad(stream, g.data_ptr(), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(),
                                             omega0, scale0, n, in_f, out_f, int(is_first), hp.data_ptr(),
@@ -204,6 +262,7 @@ class _Gabor2DLayerFunction(torch.autograd.Function):
                                       int(is_first), act.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor2d_fwd")
         ctx.save_for_backward(xin, Wn, bn, Vn, cn)
         ctx.cfg = (omega0, scale0, is_first, n, in_f, out_f, tuple(x.shape))
+        ctx.xdtype = x.dtype
         return act
 
     @staticmethod
@@ -216,6 +275,10 @@ class _Gabor2DLayerFunction(torch.autograd.Function):
         ws_bytes = _lib.check(L.wire_layer2d_ws_bytes(n, in_f, out_f), "wire_layer2d_ws_bytes")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         gW, gb, gV, gc = (torch.empty_like(t) for t in (Wn, bn, Vn, cn))
+        if is_first and ctx.needs_input_grad[0]:
+            gx = _gabor2d_first_coords(L, g, xin, Wn, bn, Vn, cn, omega0, scale0, n, in_f, out_f, gW, gb, gV, gc, ws,
+                                       ws_bytes, xshape, ctx.xdtype)
+            return gx, gW, gb, gV, gc, None, None, None
         gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
         _lib.check(L.wire_gabor2d_bwd(_stream_ptr(dev), g.data_ptr(), xin.data_ptr(), Wn.data_ptr(),
                                       bn.data_ptr(), Vn.data_ptr(), cn.data_ptr(), omega0, scale0, n, in_f,
@@ -244,6 +307,7 @@ class _Gabor2DLayerTrainableFunction(torch.autograd.Function):
         ctx.save_for_backward(xin, _native(W), _native(b), _native(V), _native(c))
         ctx.cfg = (omega0, scale0, is_first, xin.numel() // in_f, in_f, W.shape[0], tuple(x.shape), omega.shape,
                    scale.shape)
+        ctx.xdtype = x.dtype
         return act
 
     @staticmethod
@@ -256,12 +320,16 @@ class _Gabor2DLayerTrainableFunction(torch.autograd.Function):
         ws_bytes = _lib.check(L.wire_layer2d_ws_bytes(n, in_f, out_f), "wire_layer2d_ws_bytes")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         gW, gb, gV, gc = (torch.empty_like(t) for t in (Wn, bn, Vn, cn))
-        gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
         stream = _stream_ptr(dev)
-        _lib.check(L.wire_gabor2d_bwd(stream, g.data_ptr(), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(), Vn.data_ptr(),
-                                      cn.data_ptr(), omega0, scale0, n, in_f, out_f, int(is_first),
-                                      None if gx is None else gx.data_ptr(), gW.data_ptr(), gb.data_ptr(),
-                                      gV.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor2d_bwd")
+        if is_first and ctx.needs_input_grad[0]:
+            gx = _gabor2d_first_coords(L, g, xin, Wn, bn, Vn, cn, omega0, scale0, n, in_f, out_f, gW, gb, gV, gc, ws,
+                                       ws_bytes, xshape, ctx.xdtype)
+        else:
+            gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
+            _lib.check(L.wire_gabor2d_bwd(stream, g.data_ptr(), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(),
+                                          Vn.data_ptr(), cn.data_ptr(), omega0, scale0, n, in_f, out_f, int(is_first),
+                                          None if gx is None else gx.data_ptr(), gW.data_ptr(), gb.data_ptr(),
+                                          gV.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor2d_bwd")
         hp = torch.empty(2, dtype=torch.float32, device=dev)
         _lib.check(L.wire_gabor2d_hparam_grad(stream, g.data_ptr(), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(),
                                               Vn.data_ptr(), cn.data_ptr(), omega0, scale0, n, in_f, out_f,

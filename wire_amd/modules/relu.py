@@ -67,17 +67,41 @@ class PosEncoding(nn.Module):
 
     def forward(self, coords):
         """modules/relu.py:62-75 on the device: ``wire_posenc_fwd`` (the kernel the fused path runs as its first-layer
-        prologue).  No gradient flows to the coordinates (no caller in the reference asks for one)."""
-        import ctypes  # noqa: F401
+        prologue); its backward ``wire_posenc_bwd`` gives the coordinates their gradient (first order)."""
         from .. import _lib
         if not coords.is_cuda:
             raise _lib.WireHipError(f"PosEncoding input is on {coords.device}; wire_amd runs on an MI355X only")
-        x = coords.detach().to(torch.float32).reshape(coords.shape[0], -1, self.in_features).contiguous()
+        return _PosEncodingFunction.apply(coords, self.in_features, self.num_frequencies)
+
+
+class _PosEncodingFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, coords, D: int, F: int):
+        from .. import _lib
+        x = coords.detach().to(torch.float32).reshape(coords.shape[0], -1, D).contiguous()
         B, n = x.shape[0], x.shape[1]
-        out = torch.empty(B, n, self.out_dim, dtype=torch.float32, device=x.device)
+        out = torch.empty(B, n, D + 2 * D * F, dtype=torch.float32, device=x.device)
         _lib.check(_lib.lib().wire_posenc_fwd(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), B * n,
-                                              self.in_features, self.num_frequencies, out.data_ptr()), "wire_posenc_fwd")
+                                              D, F, out.data_ptr()), "wire_posenc_fwd")
+        ctx.save_for_backward(x)
+        ctx.cfg = (D, F, tuple(coords.shape), coords.dtype)
         return out
+
+    @staticmethod
+    def backward(ctx, g_pe):
+        from .. import _lib
+        from ..functional import _no_second_order
+        (x,) = ctx.saved_tensors
+        D, F, shape, dtype = ctx.cfg
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        _no_second_order("PosEncoding")
+        g = g_pe.detach().to(torch.float32).contiguous()
+        gx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().wire_posenc_bwd(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(),
+                                              x.shape[0] * x.shape[1], D, F, g.data_ptr(), gx.data_ptr()),
+                   "wire_posenc_bwd")
+        return gx.reshape(shape).to(dtype), None, None
 
 
 class INR(HipINR):
