@@ -310,7 +310,9 @@ int wire_blocked_width(int K);   /* P = roundup(2K, 64) */
  * plain features for siren / gauss / relu; l = 0..hidden_layers) inside an act buffer that wire_mlp_fwd / wire_train_fwd_bwd
  * filled for n rows with save_for_bwd = 1: the per-layer activations of modules/utils.py:246-252 without re-running the
  * layers.  (With recompute_out the last hidden layer of a fused training step is not stored, except for relu; with
- * split_out the inner hidden layers 1 .. hidden_layers - 1 hold fp16 pairs, see the knob -- set it to 0 to read them.) */
+ * fused_rstore a sine / Gaussian net whose training step runs the fused data-gradient chain stores no out_l below the last
+ * hidden layer either (r = c lin in their place); with split_out the inner hidden layers 1 .. hidden_layers - 1 hold fp16
+ * pairs, see the knob -- set these knobs to 0 to read the activations.) */
 int64_t wire_act_out_offset(const wire_net_desc* d, int64_t n, int layer);
 int wire_c64_to_blocked(void* stream, const void* src, int64_t n, int K, float* dst);
 int wire_blocked_to_c64(void* stream, const float* src, int64_t n, int K, void* dst);
@@ -361,7 +363,7 @@ int wire_blocked_to_c64(void* stream, const float* src, int64_t n, int K, void* 
  * backward re-derives from them which kernel edition produced the activations (recompute_out: the lean forward form
  * whose bits it reproduces) and whether the forward filled the max-|value| slots the 2 x fp16 kernels scale by.     */
 int wire_tune_set(const char* key, int value);
-int wire_tune_get(const char* key);   /* "split_bf16" | "split_f16" | "split_out" | "x2_amode" | "complex_3m" | "x3_h16" | "x3_tn16" | "recompute_out" -> value; < 0 = error */
+int wire_tune_get(const char* key);   /* any key wire_tune_set accepts (the table: wire_amd/csrc/wire_knobs.hip) -> value; < 0 = error */
 
 /* ---- profiling hooks (bench.py roofline) -------------------------------
  * When enabled, every launch of the hot kernels is bracketed by hipEvents on

@@ -1,4 +1,5 @@
 """Shared helpers of the test-suite (fixture loading, model rebuild, metrics)."""
+import contextlib
 import os
 import sys
 
@@ -124,27 +125,28 @@ def final_bias_within_ref(g, g64, err_y_ref, ymax, O, label, factor=2.0, floor=1
         f"{label}: |dg| / ((2/O) max|y|) = {err:.3e} > {factor} x err_ref_y {err_y_ref:.3e} + {floor:g}"
 
 
+@contextlib.contextmanager
+def tune(**knobs):
+    """Sets libwire_hip tuning knobs (wire_tune_set keys, e.g. tune(fused_train=0)) for the body of a with-statement and
+    restores every one of them to the value wire_tune_get reported before, whatever the body does."""
+    from wire_amd import _lib
+    L = _lib.lib()
+    saved = {k: _lib.check(L.wire_tune_get(k.encode()), f"wire_tune_get {k}") for k in knobs}
+    try:
+        for k, v in knobs.items():
+            _lib.check(L.wire_tune_set(k.encode(), int(v)), f"wire_tune_set {k}={v}")
+        yield L
+    finally:
+        for k, v in saved.items():
+            _lib.check(L.wire_tune_set(k.encode(), v), f"wire_tune_set {k}={v}")
+
+
 def family_ctx(fam):
     """Context manager selecting a GEMM family of libwire_hip -- 'x2': 2 x fp16 split on the f16 MFMA (the default at
     >= 4096 rows and the one bench.py times), 'x3': 3 x bf16 split on the bf16 MFMA (round 2's default; what smaller
-    batches run), '3m' / '4m': fp32 MFMA -- and restoring the default afterwards."""
-    import contextlib
-    from wire_amd import _lib
-
-    @contextlib.contextmanager
-    def ctx():
-        L = _lib.lib()
-        sb, c3, f16 = {"x2": (1, 1, 1), "x3": (1, 1, 0), "3m": (0, 1, 1), "4m": (0, 0, 1)}[fam]
-        _lib.check(L.wire_tune_set(b"split_bf16", sb))
-        _lib.check(L.wire_tune_set(b"complex_3m", c3))
-        _lib.check(L.wire_tune_set(b"split_f16", f16))
-        try:
-            yield L
-        finally:
-            _lib.check(L.wire_tune_set(b"split_bf16", 1))
-            _lib.check(L.wire_tune_set(b"complex_3m", 1))
-            _lib.check(L.wire_tune_set(b"split_f16", 1))
-    return ctx()
+    batches run), '3m' / '4m': fp32 MFMA -- and restoring the previous family afterwards."""
+    sb, c3, f16 = {"x2": (1, 1, 1), "x3": (1, 1, 0), "3m": (0, 1, 1), "4m": (0, 0, 1)}[fam]
+    return tune(split_bf16=sb, complex_3m=c3, split_f16=f16)
 
 
 def _host_threads():

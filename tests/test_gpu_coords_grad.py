@@ -182,33 +182,16 @@ FAMILY_KW = {"wire": BENCH, "wire2d": dict(first_omega_0=10.0, hidden_omega_0=10
              "relu": CLASS}
 
 
-def _set_family(L, fam):
-    knobs = {"split_f16_0": [(b"split_f16", 0)], "split_bf16_0": [(b"split_bf16", 0)],
-             "complex_3m_1": [(b"split_bf16", 0), (b"complex_3m", 1)], "complex_3m_0": [(b"split_bf16", 0), (b"complex_3m", 0)]}
-    for k, v in knobs[fam]:
-        _lib_check(L.wire_tune_set(k, v))
-
-
-def _lib_check(rc):
-    from wire_amd import _lib
-    _lib.check(rc, "wire_tune_set")
-
-
-FAMILIES = ["split_f16_0", "split_bf16_0", "complex_3m_1", "complex_3m_0"]
+FAMILY_KNOBS = {"split_f16_0": dict(split_f16=0), "split_bf16_0": dict(split_bf16=0),
+                "complex_3m_1": dict(split_bf16=0, complex_3m=1), "complex_3m_0": dict(split_bf16=0, complex_3m=0)}
+FAMILIES = list(FAMILY_KNOBS)
 
 
 @pytest.mark.parametrize("fam", FAMILIES)
 def test_coords_grad_families(fam):
-    from wire_amd import _lib
-    L = _lib.lib()
-    saved = {k: L.wire_tune_get(k) for k in (b"split_f16", b"split_bf16", b"complex_3m")}
-    try:
-        _set_family(L, fam)
+    with _util.tune(**FAMILY_KNOBS[fam]):
         for kind, D, hf, nl in FAMILY_CASES:
             check_case(f"{kind}_{fam}_n8192", kind, D, hf, nl, 8192, FAMILY_KW[kind])
-    finally:
-        for k, v in saved.items():
-            _lib_check(L.wire_tune_set(k, v))
 
 
 # ---- 3. nothing that exists changes ----------------------------------------------------------------------------------
@@ -225,12 +208,7 @@ def _fwd_bwd(model, coords, w, want_x):
 
 @pytest.mark.parametrize("fam", ["default"] + FAMILIES)
 def test_params_unchanged_by_coords_grad(fam):
-    from wire_amd import _lib
-    L = _lib.lib()
-    saved = {k: L.wire_tune_get(k) for k in (b"split_f16", b"split_bf16", b"complex_3m")}
-    try:
-        if fam != "default":
-            _set_family(L, fam)
+    with _util.tune(**FAMILY_KNOBS.get(fam, {})):
         for kind, D, hf, nl in FAMILY_CASES:
             model = _model(kind, D, hf, nl, **FAMILY_KW[kind])
             coords, w = _coords(8192, D), _weights(8192, 3)
@@ -241,9 +219,6 @@ def test_params_unchanged_by_coords_grad(fam):
             assert g0.keys() == g1.keys() and len(g0) > 0
             for k in g0:
                 assert torch.equal(g0[k], g1[k]), (kind, fam, k)
-    finally:
-        for k, v in saved.items():
-            _lib_check(L.wire_tune_set(k, v))
 
 
 def _abi_run(model, coords, w, with_coords):

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import params_np, relmax, within_ref
+from _util import params_np, relmax, tune, within_ref
 from oracle import wire_oracle as wo
 
 pytestmark = pytest.mark.gpu
@@ -64,11 +64,8 @@ def test_fused_forward_vs_layerwise_and_fp64_oracle(case):
     assert L.wire_tune_get(b"fused_fwd") == 1
     with torch.no_grad():
         y_fused = model(coords[None])[0].cpu().numpy()
-        _lib.check(L.wire_tune_set(b"fused_fwd", 0))
-        try:
+        with tune(fused_fwd=0):
             y_layer = model(coords[None])[0].cpu().numpy()
-        finally:
-            _lib.check(L.wire_tune_set(b"fused_fwd", 1))
     assert not np.array_equal(y_fused, y_layer), "the knob did not switch kernels"
     P = params_np(model)
     om1, om, sc = kw.get("first_omega_0", 30.0), kw.get("hidden_omega_0", 30.0), kw.get("scale", 10.0)
@@ -144,8 +141,6 @@ def test_fused_training_forward_vs_layerwise_and_fp64_oracle(case, final):
     kind = kw["nonlin"]
     L = _lib.lib()
     assert L.wire_tune_get(b"fused_train") == 1
-    was_final = L.wire_tune_get(b"fused_final")
-    _lib.check(L.wire_tune_set(b"fused_final", final))
     Dn, On = kw.pop("in_features", 2), kw.pop("out_features", 3)
     grid = (131, 97) if Dn == 2 else (23, 29, 19)        # 12 707 rows: 99 workgroups and 35 rows; 12 673 = 99 and 1 row
     N = int(np.prod(grid))
@@ -153,9 +148,8 @@ def test_fused_training_forward_vs_layerwise_and_fp64_oracle(case, final):
     target = torch.rand(N, On, generator=g)
     perm = torch.randperm(N, generator=g)
     res = {}
-    try:
-        for knob in (1, 0):
-            _lib.check(L.wire_tune_set(b"fused_train", knob))
+    for knob in (1, 0):
+        with tune(fused_final=final, fused_train=knob):
             torch.manual_seed(6)
             model = models.get_INR(in_features=Dn, out_features=On, hidden_layers=Ln, **kw).to(DEV)
             tr = FusedTrainer(model, grid, target, lr=0.0, keep_rec=True, coords_style="numpy" if Dn == 3 else "torch")
@@ -163,9 +157,6 @@ def test_fused_training_forward_vs_layerwise_and_fp64_oracle(case, final):
             torch.cuda.synchronize()
             res[knob] = (float(loss.item()), tr.flat_grad.cpu().numpy().copy(), tr.rec.cpu().numpy()[perm.numpy()].copy())
             offsets = list(tr.offsets)
-    finally:
-        _lib.check(L.wire_tune_set(b"fused_train", 1))
-        _lib.check(L.wire_tune_set(b"fused_final", was_final))
     assert not np.array_equal(res[0][1], res[1][1]), "the knob did not switch kernels"
     P = params_np(model)
     coords = (wo.image_coords(*grid) if Dn == 2 else wo.volume_coords(*grid))[perm.numpy()]
@@ -212,9 +203,8 @@ def test_wgrad_batch_matches_per_layer_launches(nonlin):
     target = torch.rand(N, 3, generator=g)
     perm = torch.randperm(N, generator=g)
     res = {}
-    try:
-        for knob in (1, 0):
-            _lib.check(L.wire_tune_set(b"wgrad_batch", knob))
+    for knob in (1, 0):
+        with tune(wgrad_batch=knob):
             torch.manual_seed(8)
             kw = dict(first_omega_0=30.0, hidden_omega_0=30.0) if nonlin == "siren" else {}
             model = models.get_INR(nonlin=nonlin, in_features=2, out_features=3, hidden_features=256, hidden_layers=4, **kw).to(DEV)
@@ -223,8 +213,6 @@ def test_wgrad_batch_matches_per_layer_launches(nonlin):
             torch.cuda.synchronize()
             res[knob] = tr.flat_grad.cpu().numpy().copy()
             offsets, names = list(tr.offsets), [k for k in model.state_dict().keys() if "omega_0" not in k and "scale_0" not in k]
-    finally:
-        _lib.check(L.wire_tune_set(b"wgrad_batch", 1))
     sizes = np.diff(offsets + [res[1].size])
     switched = False
     for name, off, sz in zip(names, offsets, sizes):

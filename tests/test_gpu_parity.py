@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import FULL, ROOT, SMALL, build_model, family_ctx, load_golden, meta, oracle_run, params_np, relmax, within_ref, final_bias_within_ref
+from _util import FULL, ROOT, SMALL, build_model, family_ctx, load_golden, meta, oracle_run, params_np, relmax, tune, within_ref, final_bias_within_ref
 from oracle import wire_oracle as wo
 
 pytestmark = pytest.mark.gpu
@@ -98,12 +98,6 @@ def test_full_configs(name):
         assert np.abs(head - rec["g64head:" + k]).max() <= (2 * ref_err + 1e-6) * scale, k
 
 
-def _set_family(L, split_bf16, complex_3m):
-    from wire_amd import _lib
-    _lib.check(L.wire_tune_set(b"split_bf16", split_bf16))
-    _lib.check(L.wire_tune_set(b"complex_3m", complex_3m))
-
-
 def test_gemm_families_accuracy():
     """Three GEMM families serve the wire layers: split-bf16 on the bf16 MFMA (default), the
     3-multiplication complex product on the fp32 MFMA, the 4-multiplication real-expanded fp32 MFMA.
@@ -114,9 +108,8 @@ def test_gemm_families_accuracy():
     assert L.wire_tune_get(b"split_bf16") == 1 or "WIRE_SPLIT_BF16" in __import__("os").environ
     errs = {}
     fams = {"4m": (0, 0), "3m": (0, 1), "x3": (1, 1)}
-    try:
-        for fam, (sb, c3) in fams.items():
-            _set_family(L, sb, c3)
+    for fam, (sb, c3) in fams.items():
+        with tune(split_bf16=sb, complex_3m=c3):
             for name in ("small_wire_hi", "full_cfg2_wire_4x363_lit"):
                 rec = load_golden(name)
                 model = load_small(rec, build_model(rec)) if name.startswith("small") else build_model(rec).to(DEV)
@@ -125,8 +118,6 @@ def test_gemm_families_accuracy():
                 e = relmax(y, rec["y64"])
                 within_ref(e, err_ref, f"family {fam} {name} y")
                 errs[(fam, name)] = (e, err_ref)
-    finally:
-        _set_family(L, 1, 1)
     for name in ("small_wire_hi", "full_cfg2_wire_4x363_lit"):
         e4, e3, ex = errs[("4m", name)][0], errs[("3m", name)][0], errs[("x3", name)][0]
         print(f"{name}: err 4M {e4:.3e}  3M {e3:.3e}  split-bf16 {ex:.3e}  reference fp32 {errs[('4m', name)][1]:.3e}")
@@ -138,12 +129,9 @@ def test_gemm_families_accuracy():
                                   "full_cfg5_posenc_4x256"])
 def test_fp32_mfma_family_full_configs(name):
     """The fp32-MFMA kernels (split_bf16 = 0) stay covered: same bar as test_full_configs."""
-    from wire_amd import _lib
-    L = _lib.lib()
     if name not in FULL:
         pytest.skip(f"no fixture {name}")
-    try:
-        _set_family(L, 0, 1)
+    with tune(split_bf16=0, complex_3m=1):
         rec = load_golden(name)
         model = build_model(rec).to(DEV)
         P = params_np(model)
@@ -153,8 +141,6 @@ def test_fp32_mfma_family_full_configs(name):
         _, _, g64, _ = oracle_run(rec, P, double=True)
         _, _, g32, _ = oracle_run(rec, P, double=False)
         _check_grads(grads, g64, g32, f"fp32-mfma {name}", err_ref, rec["y64"], target=rec["target"])
-    finally:
-        _set_family(L, 1, 1)
 
 
 @pytest.mark.parametrize("n", [1, 15, 16, 17, 127, 129, 255, 257, 4095, 4129])

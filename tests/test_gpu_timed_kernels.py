@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import (family_ctx, final_bias_within_ref, oracle_grads_chunked, params_np, relmax,
+from _util import (family_ctx, final_bias_within_ref, oracle_grads_chunked, params_np, relmax, tune,
                    wire_oracle_grads_chunked, within_ref)
 from oracle import wire_oracle as wo
 
@@ -106,16 +106,11 @@ def test_weight_gradient_kernels_vs_fp64(tn16, n):
     gl = wo.gabor_act_grad(g.astype(np.complex128), lin64, out64, om, sc)
     L = _lib.lib()
     assert L.wire_tune_get(b"x3_tn16") == 1 and L.wire_tune_get(b"split_f16") == 1    # the defaults
-    _lib.check(L.wire_tune_set(b"x3_tn16", 1 if tn16 == 2 else tn16))
-    _lib.check(L.wire_tune_set(b"split_f16", 1 if tn16 == 2 else 0))
-    try:
+    with tune(x3_tn16=1 if tn16 == 2 else tn16, split_f16=1 if tn16 == 2 else 0):
         x = torch.tensor(x_np, device=DEV, requires_grad=True)
         model.zero_grad()
         model.net[1](x).backward(torch.tensor(g, device=DEV))
         torch.cuda.synchronize()
-    finally:
-        _lib.check(L.wire_tune_set(b"x3_tn16", 1))
-        _lib.check(L.wire_tune_set(b"split_f16", 1))
     lw = model.net[1].linear
     e_w = relmax(lw.weight.grad.cpu().numpy(), gl.T @ np.conj(x_np.astype(np.complex128)))
     e_b = relmax(lw.bias.grad.cpu().numpy(), gl.sum(0))
@@ -444,13 +439,9 @@ def test_fused_trainer_step_every_kind_vs_fp64_oracle_at_bench_size(case):
         # the same accumulator bits (lr = 0: the weights do not move between the two steps)
         from wire_amd import _lib
         Lh = _lib.lib()
-        was = Lh.wire_tune_get(b"fused_final")
-        _lib.check(Lh.wire_tune_set(b"fused_final", 0))
-        try:
+        with tune(fused_final=0):
             tr.step(perm.to(DEV))
             torch.cuda.synchronize()
-        finally:
-            _lib.check(Lh.wire_tune_set(b"fused_final", was))
         act = tr.act.view(torch.float32)
         K = model._arch["width"]
         masks = []
@@ -514,10 +505,8 @@ def test_recompute_out_is_bit_identical(nonlin):
     res = []
     # (the knob also decides whether the training forward may run as one kernel, wire_fused.hip -- other arithmetic; this
     #  test is about the layer-by-layer kernels: "fused_train" = 0)
-    _lib.check(L.wire_tune_set(b"fused_train", 0))
     for knob in (0, 1):
-        _lib.check(L.wire_tune_set(b"recompute_out", knob))
-        try:
+        with tune(fused_train=0, recompute_out=knob):
             if nonlin == "wire":
                 model = _wire_model(4, 20.0, 30.0, hf=363, D=2, O=3, seed=3)
             else:                                      # modules/wire2d.py:56-67 (out = exp(j w0 lin - s0^2 (|lin|^2 + |sy|^2)))
@@ -533,10 +522,6 @@ def test_recompute_out_is_bit_identical(nonlin):
             loss = tr.step(perm)
             torch.cuda.synchronize()
             res.append((loss.clone(), tr.rec.clone(), tr.flat_grad.clone()))
-        finally:
-            _lib.check(L.wire_tune_set(b"recompute_out", 1))
-            if knob == 1:
-                _lib.check(L.wire_tune_set(b"fused_train", 1))
     assert torch.equal(res[0][0], res[1][0])
     assert torch.equal(res[0][1], res[1][1])
     assert torch.equal(res[0][2], res[1][2])
@@ -561,10 +546,9 @@ def test_presplit_activations_agree_with_fp32_activations(nonlin, hf, om_sc):
     L = _lib.lib()
     assert L.wire_tune_get(b"split_out") == 1
     res = []
-    _lib.check(L.wire_tune_set(b"fused_train", 0))      # the layer-by-layer kernels' two formats (wire_fused.hip has its own test)
     for knob in (0, 1):
-        _lib.check(L.wire_tune_set(b"split_out", knob))
-        try:
+        # fused_train = 0: the layer-by-layer kernels' two formats (wire_fused.hip has its own test)
+        with tune(fused_train=0, split_out=knob):
             torch.manual_seed(3)
             kw = dict(first_omega_0=20.0, hidden_omega_0=20.0, scale=30.0) if nonlin == "wire" else \
                 dict(first_omega_0=10.0, hidden_omega_0=10.0, scale=10.0) if nonlin in ("wire2d", "gauss") else \
@@ -583,10 +567,6 @@ def test_presplit_activations_agree_with_fp32_activations(nonlin, hf, om_sc):
             off = _lib.check(L.wire_act_out_offset(C.byref(tr.desc), N, 1))
             out1 = tr.act.view(torch.float32)[off:off + N * 64].clone()
             res.append((loss.clone(), tr.rec.clone(), tr.flat_grad.clone(), out1))
-        finally:
-            _lib.check(L.wire_tune_set(b"split_out", 1))
-            if knob == 1:
-                _lib.check(L.wire_tune_set(b"fused_train", 1))
     engaged = om_sc is None or om_sc[0] / om_sc[1] <= 3.33
     assert torch.equal(res[0][3], res[1][3]) != engaged, "format of the stored out_1 with / without split_out"
     assert abs(float(res[0][0]) - float(res[1][0])) <= 1e-6 * abs(float(res[0][0]))
@@ -608,10 +588,9 @@ def test_operand_load_editions_are_bit_identical(nonlin, hf):
     L = _lib.lib()
     assert L.wire_tune_get(b"x2_amode") == 2
     res = []
-    _lib.check(L.wire_tune_set(b"fused_train", 0))      # the forward GEMMs whose operand path the knob selects must run
     for mode in (2, 1, 0):
-        _lib.check(L.wire_tune_set(b"x2_amode", mode))
-        try:
+        # fused_train = 0: the forward GEMMs whose operand path the knob selects must run
+        with tune(fused_train=0, x2_amode=mode):
             torch.manual_seed(3)
             kw = dict(first_omega_0=20.0, hidden_omega_0=20.0, scale=30.0) if nonlin == "wire" else \
                 dict(first_omega_0=10.0, hidden_omega_0=10.0, scale=10.0) if nonlin == "wire2d" else \
@@ -624,10 +603,6 @@ def test_operand_load_editions_are_bit_identical(nonlin, hf):
             loss = tr.step(torch.randperm(N, generator=g).to(DEV))
             torch.cuda.synchronize()
             res.append((loss.clone(), tr.rec.clone(), tr.flat_grad.clone()))
-        finally:
-            _lib.check(L.wire_tune_set(b"x2_amode", 2))
-            if mode == 0:
-                _lib.check(L.wire_tune_set(b"fused_train", 1))
     for other in res[1:]:
         assert torch.equal(res[0][0], other[0]) and torch.equal(res[0][1], other[1]) and torch.equal(res[0][2], other[2])
     assert float(res[0][2].abs().max()) > 0
@@ -713,8 +688,7 @@ def test_first_layer_sums_in_epilogue_agree_with_separate_pass(nonlin):
     L = _lib.lib()
     res = []
     for knob in (0, 1):
-        _lib.check(L.wire_tune_set(b"first_sums", knob))
-        try:
+        with tune(first_sums=knob):
             if nonlin == "wire":
                 model = _wire_model(2, 20.0, 30.0, hf=363, D=2, O=3, seed=4)
             else:
@@ -728,8 +702,6 @@ def test_first_layer_sums_in_epilogue_agree_with_separate_pass(nonlin):
             tr.step(torch.randperm(N, generator=g).to(DEV))
             torch.cuda.synchronize()
             res.append(tr.flat_grad.clone())
-        finally:
-            _lib.check(L.wire_tune_set(b"first_sums", 1))
     # the first layer's tensors (complex ones count as real pairs; wire2d: linear and scale_orth)
     first = [v for k, v in model.state_dict().items() if k.startswith("net.0.") and "omega" not in k and "scale_0" not in k]
     n0 = sum(v.numel() * (2 if v.is_complex() else 1) for v in first)
@@ -763,9 +735,7 @@ def test_wide_offsets_beyond_4gib():
     # (0: the 32 x 32 x 16 kernels; 15: the 3 x bf16 16 x 16 x 32 ones; 16: the default 2 x fp16 kernels, whose operand
     #  loads address a 256-row tile with 32-bit offsets from a 64-bit tile base)
     for h16 in (0, 15, 16):
-        _lib.check(L.wire_tune_set(b"x3_h16", min(h16, 15)))
-        _lib.check(L.wire_tune_set(b"split_f16", 1 if h16 == 16 else 0))
-        try:
+        with tune(x3_h16=min(h16, 15), split_f16=1 if h16 == 16 else 0):
             model.zero_grad()
             x.grad = None
             out = model.net[1](x)
@@ -776,9 +746,6 @@ def test_wide_offsets_beyond_4gib():
                         model.net[1].linear.weight.grad.cpu().numpy().copy(),
                         model.net[1].linear.bias.grad.cpu().numpy().copy())
             del out
-        finally:
-            _lib.check(L.wire_tune_set(b"x3_h16", 15))
-            _lib.check(L.wire_tune_set(b"split_f16", 1))
     rows = torch.cat([torch.arange(0, n, 104729), torch.arange(n - 300, n)])
     xs = x.detach()[rows.to(DEV)].cpu().numpy().astype(np.complex128)
     gs = gout[rows.to(DEV)].cpu().numpy().astype(np.complex128)

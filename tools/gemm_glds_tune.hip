@@ -51,10 +51,10 @@ int main(int argc, char** argv) {
     ep.o0 = r0; CK(launch_gemmx3_nt(0, EPI_STORE, A, P, Bx3, Nc, P, P, ep));
     std::vector<float> ref((size_t)Nc * P), got((size_t)Nc * P);
     CK(hipMemcpy(ref.data(), r0, ref.size() * 4, hipMemcpyDeviceToHost));
-    gemmx3h_tune_set("x3_h16", 0);
+    knob_set("x3_h16", 0);
     {
       // the 16 x 16 x 32 edition sums the same six products in another grouping: fp32 round-off, not bit equality
-      gemmx3h_tune_set("x3_h16", 3);
+      knob_set("x3_h16", 3);
       CK(hipMemset(o0, 0xff, (size_t)Nc * P * 4));
       ep.o0 = o0; CK(launch_gemmx3_nt(0, EPI_STORE, A, P, Bx3, Nc, P, P, ep));
       CK(hipMemcpy(got.data(), o0, got.size() * 4, hipMemcpyDeviceToHost));
@@ -62,7 +62,7 @@ int main(int argc, char** argv) {
       for (size_t i = 0; i < ref.size(); ++i) { md = fmax(md, fabs((double)ref[i] - got[i])); mx = fmax(mx, fabs((double)ref[i])); }
       printf("check rows %lld  16x16x32 edition vs register-staged: max |diff| %.3e of max |C| %.3e (rel %.2e)\n",
              (long long)Nc, md, mx, md / mx);
-      gemmx3h_tune_set("x3_h16", 0);
+      knob_set("x3_h16", 0);
     }
     for (int mode = 1; mode <= 2; ++mode) {
       gemmx3g_tune_set("x3_glds", mode);
@@ -112,8 +112,8 @@ int main(int argc, char** argv) {
       ep.omega = 20.f; ep.scale = 30.f; ep.kvalid = P / 2;
       if (V.stagger == -100) ep.recompute_out = 1;     // data gradient that recomputes out from lin
       gemmx3g_tune_set("x3_glds", V.mode == 10 ? 0 : V.mode);
-      gemmx3h_tune_set("x3_h16", V.mode == 10 ? 3 : 0);
-      gemmx3h_tune_set("x3h_stagger", V.mode == 10 && V.stagger > 0 ? V.stagger : 0);
+      knob_set("x3_h16", V.mode == 10 ? 3 : 0);
+      knob_set("x3h_stagger", V.mode == 10 && V.stagger > 0 ? V.stagger : 0);
       gemmx3g_tune_set("x3_stagger", V.stagger > 0 ? V.stagger : 0);
       gemmx3g_tune_set("x3_stagger_lo", V.stagger < 0 ? -V.stagger : 256);
       CK(hipEventRecord(e0, 0));

@@ -29,7 +29,7 @@ static float* dalloc(size_t n, unsigned seed, float scale) {
 // sum of the slabs (and bias slabs) of one launch, in double on the host
 static void run_sum(int mode, const float* G, const float* Z, int64_t n, int P, std::vector<double>& W,
                     std::vector<double>& B, int* S_out) {
-  gemmx3_tune_set("x3_tn16", mode);
+  knob_set("x3_tn16", mode);
   const int S = gemmx3_tn_splits(n, P, P, 256);
   float* slab; CK(hipMalloc(&slab, (size_t)S * P * P * 4));
   float* bslab; CK(hipMalloc(&bslab, (size_t)S * P * 4));
@@ -95,7 +95,7 @@ int main(int argc, char** argv) {
   float* bslab; CK(hipMalloc(&bslab, (size_t)256 * P * 4));
   for (int r = 0; r < rounds + 1; ++r)
     for (int mode = 0; mode < 2; ++mode) {
-      gemmx3_tune_set("x3_tn16", mode);
+      knob_set("x3_tn16", mode);
       const int S = gemmx3_tn_splits(N, P, P, 256);
       Ss[mode] = S;
       CK(hipEventRecord(e0, 0));

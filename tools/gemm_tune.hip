@@ -92,7 +92,7 @@ int main(int argc, char** argv) {
     float* slab2; CK(hipMalloc(&slab2, (size_t)64 * P * P * 4));
     float* bslab2; CK(hipMalloc(&bslab2, (size_t)64 * P * 4));
     CK(launch_gemm_tn(0, A, P, out, P, Nc - 5, P, P, 4, slab, bslab));
-    gemmx3_tune_set("x3_tn_tall", argc > 4 ? atoi(argv[4]) : 0);
+    knob_set("x3_tn_tall", argc > 4 ? atoi(argv[4]) : 0);
     CK(launch_gemmx3_tn(0, A, P, out, P, Nc - 5, P, P, 8, slab2, bslab2));   // ragged row count
     std::vector<float> s0((size_t)4 * P * P), s1((size_t)8 * P * P), b0(4 * P), b1(8 * P);
     CK(hipMemcpy(s0.data(), slab, s0.size() * 4, hipMemcpyDeviceToHost));
@@ -147,7 +147,7 @@ int main(int argc, char** argv) {
       ep.omega = 20.f; ep.scale = 30.f; ep.kvalid = P / 2; ep.ablate = V.abl;
       CK(hipEventRecord(e0, 0));
       if (V.kind == 0) {
-        gemm_tune_set("nt_bk", V.bk);
+        knob_set("nt_bk", V.bk);
         CK(launch_gemm_nt(0, V.epi, A, P, Bt, P, N, P, P, ep));
       } else if (V.kind == 1) {
         CK(launch_gemm_tn(0, A, P, out, P, N, P, P, S, slab, bslab));
@@ -156,10 +156,10 @@ int main(int argc, char** argv) {
       } else if (V.kind == 3) {
         CK(launch_gemm3m_tn(0, A, P, out, P, N, Kp, Kp, S3, slab, bslab));
       } else if (V.kind == 4) {
-        gemmx3_tune_set("x3_tall", V.bk);
+        knob_set("x3_tall", V.bk);
         CK(launch_gemmx3_nt(0, V.epi, A, P, Bx3, N, P, P, ep));
       } else {
-        gemmx3_tune_set("x3_tn_tall", V.bk);
+        knob_set("x3_tn_tall", V.bk);
         CK(launch_gemmx3_tn(0, A, P, out, P, N, P, P, SX, slab, bslab));
       }
       CK(hipEventRecord(e1, 0));
@@ -177,7 +177,7 @@ int main(int argc, char** argv) {
     std::vector<unsigned long long> stamps((size_t)nwg * 2);
     for (int v = 0; v < 3; ++v) {
       GemmEpiParams ep; ep.o0 = o0; ep.ld0 = P; ep.ld1 = P; ep.i0 = lin; ep.ablate = abl[v];
-      gemmx3_tune_set("x3_tall", 0);
+      knob_set("x3_tall", 0);
       CK(hipMemset(lin, 0, (size_t)nwg * 16));
       for (int r = 0; r < 20; ++r) CK(launch_gemmx3_nt(0, EPI_STORE, A, P, Bx3, N, P, P, ep));
       CK(hipDeviceSynchronize());

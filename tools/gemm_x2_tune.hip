@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../wire_amd/csrc/wire_gemm.h"
+int gemmx2h_tune_set(const char* key, int value);   // tools/wire_gemmx2h_probe.hip, linked in place of wire_gemmx2h.hip
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); exit(1); } } while (0)
 
@@ -77,7 +78,7 @@ int main(int argc, char** argv) {
     if (Nc > N) continue;
     GemmEpiParams ep; ep.ld0 = P; ep.ld1 = P;
     gemmx3g_tune_set("x3_glds", 0);
-    gemmx3h_tune_set("x3_h16", 3);
+    knob_set("x3_h16", 3);
     ep.o0 = r0; CK(launch_gemmx3_nt(0, EPI_STORE, A, P, Bx3, Nc, P, P, ep));
     std::vector<float> ref((size_t)Nc * P), got((size_t)Nc * P);
     CK(hipMemcpy(ref.data(), r0, ref.size() * 4, hipMemcpyDeviceToHost));
@@ -147,7 +148,7 @@ int main(int argc, char** argv) {
   {
     GemmEpiParams ep;
     ep.bias = bias; ep.o0 = o0; ep.o1 = o1; ep.ld0 = P; ep.ld1 = P; ep.omega = 20.f; ep.scale = 30.f; ep.kvalid = P / 2;
-    gemmx3h_tune_set("x3_h16", 3);
+    knob_set("x3_h16", 3);
     CK(launch_gemmx3_nt(0, EPI_GABOR_FWD, A, P, Bx3, N, P, P, ep));
     std::vector<float> ref((size_t)N * P), got((size_t)N * P);
     CK(hipMemcpy(ref.data(), o1, ref.size() * 4, hipMemcpyDeviceToHost));

@@ -100,71 +100,21 @@ extern "C" int wire_prof_read(double* ms_total, int64_t* launches, double* flops
 }
 
 // ---------------------------------------------------------------------------
-// tuning knobs
+// tuning knobs (the table: wire_knobs.hip)
 // ---------------------------------------------------------------------------
-// wire training step on the 16 x 16 x 32 kernels: backward passes evaluate out = act(lin) again instead of reading it
-// (the data-gradient epilogues and the fused final stage), and the last hidden layer does not store out at all
-static int env_int_(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-// (relaxed atomics: wire_tune_set may run on one thread while autograd's thread reads a knob inside a launch sequence)
-static std::atomic<int> g_recompute_out{env_int_("WIRE_RECOMPUTE_OUT", 1)};
-static std::atomic<int> g_first_sums{env_int_("WIRE_FIRST_SUMS", 1)};
-static std::atomic<int> g_complex_3m{1};   // wire: 3-multiplication complex GEMMs on the fp32 MFMA (wire_gemm3m.hip)
-static int env_flag(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? (atoi(v) != 0) : dflt;
-}
-// every net: split-bf16 GEMMs on the bf16 MFMA (wire_gemmx3.hip); overrides complex_3m
-static std::atomic<int> g_split_bf16{env_flag("WIRE_SPLIT_BF16", 1)};
-// hidden-layer GEMMs of batches >= 4096 rows as a 2 x fp16 split on the f16 MFMA (wire_gemmx2h.hip): 3 instead of 6
-// matrix-core products per fp32 product, operand scales from device-side maxima; needs split_bf16 and the 16 x 16 x 32
-// kernels (x3_h16) for the net kind, falls back to the 3 x bf16 kernels otherwise
-static std::atomic<int> g_split_f16{env_flag("WIRE_SPLIT_F16", 1)};
-// with split_f16: activations with an a-priori bound (Gabor, sine, Gaussian outputs) are stored ALREADY SPLIT into fp16
-// pairs by the epilogue that produces them (wire_dev.h: wire_store_out4), so the GEMMs that read them -- the next layer's
-// forward, the weight gradient -- spend no vector instructions on the split (out_split_scale below)
-static std::atomic<int> g_split_out{env_flag("WIRE_SPLIT_OUT", 1)};
-// with the fused training forward + data-gradient chain of a sine / Gaussian net: store r = c lin and no out_l ("fused_rstore")
-static std::atomic<int> g_fused_rstore{env_flag("WIRE_FUSED_RSTORE", 1)};
-// behind the data-gradient chain: the weight gradients of layers 2 .. L as one launch ("wgrad_batch" / WIRE_WGRAD_BATCH)
-static std::atomic<int> g_wgrad_batch{env_flag("WIRE_WGRAD_BATCH", 1)};
 // family the flags select for a net kind (wire_layer_api.hip): 2 split-bf16, 1 complex 3M (wire only), 0 4M
 int wire_family_(int kind) {
-  if (g_split_bf16) return 2;
-  return (kind == WIRE_KIND_WIRE && g_complex_3m) ? 1 : 0;
+  if (knob(K_SPLIT_BF16)) return 2;
+  return (kind == WIRE_KIND_WIRE && knob(K_COMPLEX_3M)) ? 1 : 0;
 }
-int wire_split_f16_() { return g_split_f16; }   // wire_layer_api.hip
 extern "C" int wire_tune_get(const char* key) {
   if (!key) return fail(WIRE_ERR_ARG, "null key");
-  if (!strcmp(key, "complex_3m")) return g_complex_3m;
-  if (!strcmp(key, "split_bf16")) return g_split_bf16;
-  if (!strcmp(key, "split_out")) return g_split_out;
-  if (!strcmp(key, "fused_rstore")) return g_fused_rstore;
-  if (!strcmp(key, "wgrad_batch")) return g_wgrad_batch;
-  if (!strcmp(key, "x3_h16")) return gemmx3h_mode();
-  if (!strcmp(key, "x3_tn16")) return gemmx3_tn16_mode();
-  if (!strcmp(key, "recompute_out")) return g_recompute_out;
-  if (!strcmp(key, "split_f16")) return g_split_f16;
-  if (gemmx2h_tune_get(key) >= 0) return gemmx2h_tune_get(key);
-  if (fused_tune_get(key) >= 0) return fused_tune_get(key);
-  return fail(WIRE_ERR_ARG, "unknown tuning key: %s", key);
+  const int v = knob_get(key);
+  return v >= 0 ? v : fail(WIRE_ERR_ARG, "unknown tuning key: %s", key);
 }
 extern "C" int wire_tune_set(const char* key, int value) {
   if (!key) return fail(WIRE_ERR_ARG, "null key");
-  if (!strcmp(key, "complex_3m")) { g_complex_3m = value ? 1 : 0; return WIRE_OK; }
-  if (!strcmp(key, "split_bf16")) { g_split_bf16 = value ? 1 : 0; return WIRE_OK; }
-  if (!strcmp(key, "recompute_out")) { g_recompute_out = value ? 1 : 0; return WIRE_OK; }
-  if (!strcmp(key, "first_sums")) { g_first_sums = value ? 1 : 0; return WIRE_OK; }
-  if (!strcmp(key, "split_f16")) { g_split_f16 = value ? 1 : 0; return WIRE_OK; }
-  if (!strcmp(key, "split_out")) { g_split_out = value ? 1 : 0; return WIRE_OK; }
-  if (!strcmp(key, "fused_rstore")) { g_fused_rstore = value ? 1 : 0; return WIRE_OK; }
-  if (!strcmp(key, "wgrad_batch")) { g_wgrad_batch = value ? 1 : 0; return WIRE_OK; }
-  if (gemmx2h_tune_set(key, value) == 0) return WIRE_OK;
-  if (fused_tune_set(key, value) == 0) return WIRE_OK;
-  if (gemm_tune_set(key, value) == 0) return WIRE_OK;
-  if (gemmx3_tune_set(key, value) == 0) return WIRE_OK;
+  if (knob_set(key, value) == 0 || (g_glds_tune && g_glds_tune(key, value) == 0)) return WIRE_OK;
   return fail(WIRE_ERR_ARG, "unknown tuning key or bad value: %s=%d", key, value);
 }
 
@@ -183,7 +133,8 @@ struct Plan {
   std::vector<int64_t> off_fwd, off_dg, off_bias, off_fwd_x3, off_dg_x3, off_fwd_3m, off_dg_3m, off_fwd_x2, off_dg_x2;
   int64_t off_wf, off_bf, off_first, off_wamax, total_packed;   // off_wamax: max-|weight| slots, WIRE_AMAX_SLOTS per layer
   int64_t off_fx;    // k-permuted 2 x fp16 images of the hidden layers for the fused forward (wire_fused.hip), -1 = no such shape
-  bool k_split_out, k_recompute_out, k_first_sums, k_rstore, k_wgrad_batch, k_fused_fwd, k_fused_train, k_fused_bwd, k_fused_final;
+  bool k_split_out, k_recompute_out, k_first_sums, k_rstore, k_wgrad_batch, k_fused_fwd, k_fused_train, k_fused_bwd, k_fused_final,
+       k_fused_train_p384;
   int64_t off_fxd;   // the same of the TRANSPOSED weights of layers L .. 1 (in that order) for the data-gradient chain, -1 = none
   std::vector<int64_t> tfloats;
 };
@@ -204,16 +155,17 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   p.Pl = (p.kind == WIRE_KIND_WIRE2D) ? 2 * p.P : p.P;
   p.ldu = p.P / 2;
   p.Kp = p.P / 2;
-  p.x3 = g_split_bf16 != 0;
-  p.x2 = p.x3 && g_split_f16 != 0;
-  p.m3 = (p.kind == WIRE_KIND_WIRE) && g_complex_3m && !p.x3;
+  p.x3 = knob(K_SPLIT_BF16) != 0;
+  p.x2 = p.x3 && knob(K_SPLIT_F16) != 0;
+  p.m3 = (p.kind == WIRE_KIND_WIRE) && knob(K_COMPLEX_3M) && !p.x3;
   // one snapshot of the knobs that decide FORMATS (what the forward stores and the backward of the same call reads): a
   // wire_tune_set from another thread in the middle of wire_train_fwd_bwd must not split a call between two formats
   // (the forward and the backward of the autograd path are separate calls: knobs must not change between them)
-  p.k_split_out = g_split_out != 0; p.k_recompute_out = g_recompute_out != 0; p.k_first_sums = g_first_sums != 0;
-  p.k_rstore = g_fused_rstore != 0; p.k_wgrad_batch = g_wgrad_batch != 0;
-  p.k_fused_fwd = fused_fwd_enabled(); p.k_fused_train = fused_train_enabled(); p.k_fused_bwd = fused_bwd_enabled();
-  p.k_fused_final = fused_final_enabled();
+  p.k_split_out = knob(K_SPLIT_OUT) != 0; p.k_recompute_out = knob(K_RECOMPUTE_OUT) != 0;
+  p.k_first_sums = knob(K_FIRST_SUMS) != 0; p.k_rstore = knob(K_FUSED_RSTORE) != 0; p.k_wgrad_batch = knob(K_WGRAD_BATCH) != 0;
+  p.k_fused_fwd = knob(K_FUSED_FWD) != 0; p.k_fused_train = p.k_fused_fwd && knob(K_FUSED_TRAIN);
+  p.k_fused_train_p384 = knob(K_FUSED_TRAIN_P384) != 0;
+  p.k_fused_bwd = p.k_fused_train && knob(K_FUSED_BWD); p.k_fused_final = p.k_fused_train && knob(K_FUSED_FINAL);
   p.first_gemm = p.F > 0;
   p.Din = p.first_gemm ? p.D + 2 * p.D * p.F : p.D;
   p.Pin0 = p.first_gemm ? rup(p.Din, 64) : 0;
@@ -394,7 +346,7 @@ float fused_act_scale(const Plan& p);
 bool fused_train_applies(const Plan& p, int64_t n) {
   if (!p.k_fused_train || p.off_fx < 0 || p.L < 1 || p.L > 8) return false;
   if (!use_x2(p, n) || !gemmx2_tn_applies(p.Pl, p.P) || !p.k_split_out || !p.k_recompute_out) return false;
-  if (p.kind == WIRE_KIND_WIRE && p.P > 256 && env_int_("WIRE_FUSED_TRAIN_P384", 0) == 0) return false;
+  if (p.kind == WIRE_KIND_WIRE && p.P > 256 && !p.k_fused_train_p384) return false;
   if (p.kind != WIRE_KIND_RELU && fused_act_scale(p) == 0.f) return false;
   return fused_pre_scale(p.kind, p.w1, p.s) > 0.f && fused_pre_scale(p.kind, p.w, p.s) > 0.f;
 }

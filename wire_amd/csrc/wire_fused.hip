@@ -1152,53 +1152,6 @@ __global__ __launch_bounds__(64 * W, 8 / W) void fused_bwd_kernel(const FusedBwd
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static int fx_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-// "fused_fwd" / WIRE_FUSED_FWD: 1 (default) = forward-only calls of the nets below run the fused kernel
-static std::atomic<int> g_fused_fwd{fx_env("WIRE_FUSED_FWD", 1)};
-#ifdef WIRE_FX_ABLATE
-static std::atomic<int> g_fx_ablate{0};
-#endif
-// "fused_train" / WIRE_FUSED_TRAIN: 1 (default) = training forwards of those nets run it too (storing lin_l / out_l)
-static std::atomic<int> g_fused_train{fx_env("WIRE_FUSED_TRAIN", 1)};
-bool fused_train_enabled() { return g_fused_train != 0 && g_fused_fwd != 0; }
-// "fused_final" / WIRE_FUSED_FINAL: 1 = wire_train_fwd_bwd of the real nets forms loss, dL/dy, g_lin_L and the final layer's
-// gradient sums inside the training forward (fx_tail_loss) instead of a pass over the stored lin_L / out_L.  Default 0:
-// measured neutral to slower (siren 2.05 / 2.03, gauss 2.02 / 1.94, relu 1.95 / 1.93 ms per step with / without,
-// profiles/r04_fused_final_ab.txt) -- the 0.18 ms pass it removes is HBM-bound and cheap, the tail it adds (3500 vector
-// instructions per wave, a third of them the 16-row sums of dL/dy^T h_L by DPP) runs with the matrix cores idle
-static std::atomic<int> g_fused_final{fx_env("WIRE_FUSED_FINAL", 0)};
-bool fused_final_enabled() { return g_fused_final != 0 && fused_train_enabled(); }
-int fused_bwd_knob();
-void fused_bwd_knob_set(int v);
-void fxb_ablate_set(int v);
-void fused_bwd_w_set(int v);
-int fused_bwd_w_get();
-int fused_tune_get(const char* key) {
-  if (!strcmp(key, "fused_fwd")) return g_fused_fwd;
-  if (!strcmp(key, "fused_train")) return g_fused_train;
-  if (!strcmp(key, "fused_bwd")) return fused_bwd_knob();
-  if (!strcmp(key, "fused_final")) return g_fused_final;
-  if (!strcmp(key, "fused_bwd_w")) return fused_bwd_w_get();
-  return -1;
-}
-int fused_tune_set(const char* key, int value) {
-  if (!strcmp(key, "fused_fwd") && value >= 0 && value <= 1) { g_fused_fwd = value; return 0; }
-  if (!strcmp(key, "fused_train") && value >= 0 && value <= 1) { g_fused_train = value; return 0; }
-  if (!strcmp(key, "fused_bwd") && value >= 0 && value <= 1) { fused_bwd_knob_set(value); return 0; }
-  if (!strcmp(key, "fused_final") && value >= 0 && value <= 1) { g_fused_final = value; return 0; }
-#ifdef WIRE_FX_ABLATE
-  if (!strcmp(key, "fxb_ablate") && value >= 0 && value <= 127) { fxb_ablate_set(value); return 0; }
-#endif
-  if (!strcmp(key, "fused_bwd_w") && (value == 4 || value == 8)) { fused_bwd_w_set(value); return 0; }
-#ifdef WIRE_FX_ABLATE
-  if (!strcmp(key, "fx_ablate") && value >= 0 && value <= 15) { g_fx_ablate = value; return 0; }
-#endif
-  return -1;
-}
-
 // shapes with a kernel: the 256-feature real nets (BASELINE.json configs[4]) and `wire` at padded widths 192 / 256 / 384
 // (config 1's K = 90, K <= 128, hidden_features = 256 -> K = 181)
 bool fused_fwd_shape(int kind, int P) {
@@ -1206,7 +1159,6 @@ bool fused_fwd_shape(int kind, int P) {
   if (kind == NK_WIRE) return P == 192 || P == 256 || P == 384;
   return false;
 }
-bool fused_fwd_enabled() { return g_fused_fwd != 0; }
 float fused_pre_scale(int kind, float omega0, float scale0) {
   if (kind == NK_SIREN || kind == NK_WIRE) return (float)((double)omega0 / 6.283185307179586);
   if (kind == NK_GAUSS) return (float)((double)scale0 * 1.2011224087864498);      // sqrt(log2 e)
@@ -1281,7 +1233,7 @@ hipError_t launch_fused_fwd(hipStream_t s, int kind, int P, const FusedFwdParams
     return hipErrorInvalidValue;
 #ifdef WIRE_FX_ABLATE
   if (kind == NK_SIREN) {
-    switch (g_fx_ablate.load()) {
+    switch (knob(K_FX_ABLATE)) {
       case 1: return fx_launch_t<NK_SIREN, 16, 3, 1>(s, fp);
       case 2: return fx_launch_t<NK_SIREN, 16, 3, 2>(s, fp);
       case 3: return fx_launch_t<NK_SIREN, 16, 3, 3>(s, fp);
@@ -1310,17 +1262,8 @@ template __global__ void fused_fwd_kernel<NK_SIREN, 16, 3, FX_PROBE_ABL>(const F
 #endif
 
 // ---- the data-gradient chain (real nets, P = 256)
-static std::atomic<int> g_fused_bwd{fx_env("WIRE_FUSED_BWD", 1)};
-bool fused_bwd_enabled() { return g_fused_bwd != 0 && fused_train_enabled(); }
 bool fused_bwd_shape(int kind, int P) { return (kind == NK_SIREN || kind == NK_GAUSS || kind == NK_RELU) && P == 256; }
-// W = waves per workgroup.  8: one workgroup per CU, ring of three stages.  4: TWO workgroups of 64 rows per CU, each with
-// a ring of two stages (2 x 64 KB of LDS) -- they share nothing, so one's epilogue (no MFMAs: the link's activation
-// derivative, maxima, splits) runs beside the other's MFMAs, which the two waves of a SIMD inside ONE workgroup cannot do
-// (they meet at every stage barrier); price: the weight stream is fetched per 64 rows instead of per 128.
-static std::atomic<int> g_fused_bwd_w{fx_env("WIRE_FUSED_BWD_W", 8)};   // (A/B on three nets, two rounds each: no difference -- profiles/r04_fused_bwd_w_ab.txt)
-#ifdef WIRE_FX_ABLATE
-static std::atomic<int> g_fxb_ablate{0};
-#endif
+// W = waves per workgroup (the "fused_bwd_w" knob, wire_knobs.hip: 8 or 4)
 template <int KIND, int W, int ABL = 0>
 static hipError_t fxb_launch_w(hipStream_t s, const FusedBwdParams& fp) {
   constexpr int NB = 16, RING = W == 8 ? 3 : 2, LDS = RING * NB * 2048;
@@ -1336,7 +1279,7 @@ template <int KIND>
 static hipError_t fxb_launch_t(hipStream_t s, const FusedBwdParams& fp, int W) {
 #ifdef WIRE_FX_ABLATE
   if constexpr (KIND == NK_SIREN) {
-    switch (g_fxb_ablate.load()) {
+    switch (knob(K_FXB_ABLATE)) {
       case 1: return fxb_launch_w<KIND, 8, 1>(s, fp);
       case 2: return fxb_launch_w<KIND, 8, 2>(s, fp);
       case 3: return fxb_launch_w<KIND, 8, 3>(s, fp);
@@ -1358,7 +1301,7 @@ static hipError_t fxb_launch_t(hipStream_t s, const FusedBwdParams& fp, int W) {
 }
 // *tile_rows: rows per workgroup of this launch = rows per block of fp.crp
 hipError_t launch_fused_bwd(hipStream_t s, int kind, int P, const FusedBwdParams& fp, int* tile_rows) {
-  const int W = g_fused_bwd_w;
+  const int W = knob(K_FUSED_BWD_W) == 8 ? 8 : 4;   // what fxb_launch_t launches
   if (tile_rows) *tile_rows = 16 * W;
   if (fp.n <= 0 || fp.L < 1) return hipSuccess;
   if (!fused_bwd_shape(kind, P) || fp.L > FX_LMAX || !fp.g || !fp.aux0 || (fp.L >= 2 && !fp.aux) || !fp.gamax || !fp.wamax ||
@@ -1372,12 +1315,3 @@ hipError_t launch_fused_bwd(hipStream_t s, int kind, int P, const FusedBwdParams
     default: return hipErrorInvalidValue;
   }
 }
-int fused_bwd_knob() { return g_fused_bwd; }
-void fused_bwd_knob_set(int v) { g_fused_bwd = v; }
-void fused_bwd_w_set(int v) { g_fused_bwd_w = v; }
-int fused_bwd_w_get() { return g_fused_bwd_w; }
-#ifdef WIRE_FX_ABLATE
-void fxb_ablate_set(int v) { g_fxb_ablate = v; }
-#else
-void fxb_ablate_set(int) {}
-#endif

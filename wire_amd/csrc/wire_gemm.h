@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wire_knobs.h"
+
 // Epilogue selector of the NT GEMM  C[M][Nc] = A[M][Kd] * Bt[Nc][Kd]^T.
 enum WireEpi {
   EPI_STORE = 0,            // o0 = C
@@ -64,8 +66,6 @@ struct GemmEpiParams {
 hipError_t launch_gemm_nt(hipStream_t s, int epi, const float* A, int lda, const float* Bt,
                           int ldb, int64_t M, int Nc, int Kd, const GemmEpiParams& ep);
 
-int gemm_tune_set(const char* key, int value);
-
 // Split-over-rows TN GEMM  slab[s][Pm][Pn] = G[rows_s][Pm]^T * Z[rows_s][Pn]
 // (+ optional column sums of G into bslab[s][Pm]).  Returns the number of
 // row splits used through *splits (<= max_splits).
@@ -77,7 +77,6 @@ hipError_t launch_gemm_tn(hipStream_t s, const float* G, int ldg, const float* Z
 // NT: C[M][Kp_out] = A[M][Kp_in] * B[Kp_out][Kp_in]^T, all blocked-planar complex rows.
 hipError_t launch_gemm3m_nt(hipStream_t s, int epi, const float* A, int lda, const float* B, int ldb,
                             int64_t M, int Kp_out, int Kp_in, const GemmEpiParams& ep);
-int gemm3m_tune_set(const char* key, int value);
 // TN: slab[split][3][Kp_o][Kp_i] planes (P1,P2,P3), bslab[split][2][Kp_o] column sums of G (re, im)
 int gemm3m_tn_splits(int64_t n, int Kp_o, int Kp_i, int max_splits);
 hipError_t launch_gemm3m_tn(hipStream_t s, const float* G, int ldg, const float* Z, int ldz, int64_t n,
@@ -94,9 +93,7 @@ struct X3SplitBatch { const float* src[X3_SPLIT_MAXB]; void* dst[X3_SPLIT_MAXB];
 hipError_t launch_x3_split_b_batch(hipStream_t s, const X3SplitBatch& sb, int nb, int ldb, int Nc, int Kd);
 hipError_t launch_gemmx3_nt(hipStream_t s, int epi, const float* A, int lda, const void* Bx3, int64_t M,
                             int Nc, int Kd, const GemmEpiParams& ep);
-int gemmx3_tune_set(const char* key, int value);
 bool gemmx3_nt_is_h16(int epi, int64_t M);
-int gemmx3_tn16_mode();
 int gemmx3_tn_splits(int64_t n, int Pm, int Pn, int max_splits);
 int gemmx3_tn_splits_max(int64_t n, int Pm, int Pn, int max_splits);   // over the "x3_tn16" settings (scratch sizing)
 hipError_t launch_gemmx3_tn(hipStream_t s, const float* G, int ldg, const float* Z, int ldz, int64_t n,
@@ -108,6 +105,7 @@ void gemmx3_register_glds(bool (*handles)(int, int64_t),
                           hipError_t (*launch)(hipStream_t, int, const float*, int, const void*, int64_t, int, int,
                                                const GemmEpiParams&),
                           int (*tune)(const char*, int));
+extern int (*g_glds_tune)(const char*, int);   // the registered tune hook: wire_tune_set's fallback for keys not in the table
 bool gemmx3g_handles(int epi, int64_t M);
 int gemmx3g_tune_set(const char* key, int value);
 int gemmx3g_mode();
@@ -116,8 +114,6 @@ hipError_t launch_gemmx3g_nt(hipStream_t s, int epi, const float* A, int lda, co
 
 // ---- 16 x 16 x 32 edition (wire_gemmx3h.hip): reads the second (unswizzled) half of the split image
 bool gemmx3h_handles(int epi, int64_t M);
-int gemmx3h_tune_set(const char* key, int value);
-int gemmx3h_mode();
 hipError_t launch_gemmx3h_nt(hipStream_t s, int epi, const float* A, int lda, const void* Bx3, int64_t M,
                              int Nc, int Kd, const GemmEpiParams& ep);
 
@@ -133,8 +129,6 @@ struct X2SplitBatch { const float* src[X2_SPLIT_MAXB]; void* dst[X2_SPLIT_MAXB];
 hipError_t launch_x2_split_b_batch(hipStream_t s, const X2SplitBatch& sb, int nb, int ldb, int Nc, int Kd);
 hipError_t launch_gemmx2h_nt(hipStream_t s, int epi, const float* A, int lda, const void* Bx2, int64_t M, int Nc,
                              int Kd, const GemmEpiParams& ep);
-int gemmx2h_tune_set(const char* key, int value);
-int gemmx2h_tune_get(const char* key);     // "x2_amode" -> value; -1 = unknown key
 bool gemmx2_tn_applies(int Pm, int Pn);
 int gemmx2_tn_splits(int64_t n, int Pm, int Pn, int max_splits);
 hipError_t launch_gemmx2_tn(hipStream_t s, const float* G, int ldg, const float* Z, int ldz, int64_t n, int Pm,
@@ -189,13 +183,8 @@ struct FusedFwdParams {
   float* loss_partial = nullptr;                          // [block]
   unsigned* amax_g = nullptr;                             // max |g_lin_L| slots
 };
-bool fused_final_enabled();
-bool fused_train_enabled();
 float fused_pre_scale(int kind, float omega0, float scale0);   // the c of a layer with these hyper-parameters
 bool fused_fwd_shape(int kind, int P);
-bool fused_fwd_enabled();
-int fused_tune_get(const char* key);                      // "fused_fwd"; -1 = unknown key
-int fused_tune_set(const char* key, int value);
 hipError_t launch_fused_fwd(hipStream_t s, int kind, int P, const FusedFwdParams& fp);
 
 // ---- the data-gradient chain of the real nets in one kernel (wire_fused.hip: fused_bwd_kernel): g_lin_L .. g_lin_1
@@ -218,6 +207,5 @@ struct FusedBwdParams {
   const float* coords = nullptr; int D = 0;
   float* crp = nullptr; int C = 0;
 };
-bool fused_bwd_enabled();
 bool fused_bwd_shape(int kind, int P);
 hipError_t launch_fused_bwd(hipStream_t s, int kind, int P, const FusedBwdParams& fp, int* tile_rows);

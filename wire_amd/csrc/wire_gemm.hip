@@ -187,18 +187,6 @@ __global__ __launch_bounds__(256, (BKT == 32 ? 2 : 3)) void gemm_nt_kernel(
   gemm_epilogue<EPI, MT, WN>(acc, ep, M, m_base + wave_m * (MT * 32), n_base + wave_n * (WN * 32), l31, h);
 }
 
-// tuning knobs (wire_tune_set; defaults may be overridden by WIRE_NT_BK in the environment)
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-static std::atomic<int> g_nt_bk{env_int("WIRE_NT_BK", 16)};   // K-slab depth of the NT kernel: 16 or 32
-static int nt_bk() { return g_nt_bk; }
-int gemm_tune_set(const char* key, int value) {
-  if (!strcmp(key, "nt_bk") && (value == 16 || value == 32)) { g_nt_bk = value; return 0; }
-  return -1;
-}
-
 template <int EPI, int MT, int WN>
 static hipError_t launch_nt_t(hipStream_t s, const float* A, int lda, const float* Bt, int ldb,
                               int64_t M, int Nc, int Kd, const GemmEpiParams& ep) {
@@ -206,7 +194,7 @@ static hipError_t launch_nt_t(hipStream_t s, const float* A, int lda, const floa
   const int tiles_n = (Nc + BN - 1) / BN;
   const int tiles_m_pad = (tiles_m + 7) & ~7;
   dim3 grid((unsigned)(tiles_m_pad * tiles_n));
-  if (nt_bk() == 16)
+  if (knob(K_NT_BK) == 16)
     hipLaunchKernelGGL((gemm_nt_kernel<EPI, MT, WN, 16>), grid, dim3(256), 0, s, A, lda, Bt, ldb,
                        (int)M, Nc, Kd, tiles_m, tiles_n, ep);
   else

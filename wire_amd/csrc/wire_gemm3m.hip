@@ -333,8 +333,6 @@ static hipError_t launch3m_t(hipStream_t s, const float* A, int lda, const float
   return hipGetLastError();
 }
 
-int gemm3m_tune_set(const char* key, int value) { (void)key; (void)value; return -1; }
-
 // C[M][Kp_out] = A[M][Kp_in] * B[Kp_out][Kp_in]^T, all blocked-planar complex rows (launch_pack3m
 // writes W and conj(W)^T in that layout).
 hipError_t launch_gemm3m_nt(hipStream_t s, int epi, const float* A, int lda, const float* B, int ldb,

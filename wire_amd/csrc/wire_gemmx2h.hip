@@ -439,40 +439,6 @@ __global__ __launch_bounds__(256, (NRB == 2 ? 3 : 2)) void gemmx2h_nt_kernel(con
   h_epilogue<EPI, true, NRB>(acc, ep, M, m_base + wave * (16 * NRB), n_base, Nc, lane, smem, wave, rt, inv_a * inv_b);
 }
 
-static int x2_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-// A/B in one process and on one box (profiles/r03_gemm_x2_nt_tn_ab.txt, N = 262 144, K = 256 complex): A through registers
-// 0.452 / 0.539 / 0.559 ms (store / Gabor forward / data gradient) against 0.470 / 0.556 / 0.563 through LDS.  Measured
-// and dropped (profiles/r03_gemm_x2_prefetch_ablation.txt): an L2 prefetch of the rows three stages ahead (+ 0.02 ms: the
-// cost of the HBM reads is not their latency -- with every A row served from cache the store form takes 0.347 ms, i.e. the
-// 0.54 GB of A cost 0.105 ms, what they cost at 5 TB/s beside a matrix pipe that shares the chip's power budget).
-// Round 3, late: A through the wave-private LDS region in WHOLE cache lines (AMODE 2, default): 0.382 / 0.496 / 0.519 ms -- the
-// half-line pieces of AMODE 0 and the fragment-shaped register loads of AMODE 1 (16 rows x 64 bytes per instruction) put
-// twice the line requests on the vector-memory path for the same bytes (profiles/r03_gemm_x2_whole_line.txt).
-static std::atomic<int> g_x2_amode{x2_env("WIRE_X2_AMODE", 2)};
-// "x2_tn_rows" / WIRE_X2_TN_ROWS: upper bound on the rows ONE weight-gradient workgroup accumulates sequentially in its fp32
-// accumulators (0 = the fill-the-chip policy of gemmx2_tn_splits alone).  A shorter chain means more row splits, i.e.
-// more slabs for wgrad_reduce_kernel: the knob of the summation-order measurement (tools/wgrad_order_probe.py).
-static std::atomic<int> g_x2_tn_rows{x2_env("WIRE_X2_TN_ROWS", 0)};
-// "x2_tn_p384" / WIRE_X2_TN_P384: waves of the weight-gradient workgroup at P = 384 (K = 181) -- 8 (default, round 4): 48
-// features of G per wave, every SIMD carries two waves; 6: 64 features per wave (round 3)
-static std::atomic<int> g_x2_tn_p384{x2_env("WIRE_X2_TN_P384", 8)};
-int gemmx2h_tune_get(const char* key) {
-  if (!strcmp(key, "x2_amode")) return g_x2_amode;
-  if (!strcmp(key, "x2_tn_rows")) return g_x2_tn_rows;
-  if (!strcmp(key, "x2_tn_p384")) return g_x2_tn_p384;
-  return -1;
-}
-int gemmx2h_tune_set(const char* key, int value) {
-  if (!strcmp(key, "x2_amode") && value >= 0 && value <= 2) { g_x2_amode = value; return 0; }
-  if (!strcmp(key, "x2_tn_rows") && value >= 0 && (value == 0 || value >= 256)) { g_x2_tn_rows = value; return 0; }
-  if (!strcmp(key, "x2_tn_p384") && (value == 6 || value == 8)) { g_x2_tn_p384 = value; return 0; }
-  return -1;
-}
-
-
 template <int EPI>
 static hipError_t launchx2h_t(hipStream_t s, const float* A, int lda, const unsigned short* Bx2, int64_t M, int Nc,
                               int Kd, const GemmEpiParams& ep) {
@@ -487,7 +453,7 @@ static hipError_t launchx2h_t(hipStream_t s, const float* A, int lda, const unsi
     // (only the forward forms read an activation; the data gradients read g_lin, which has no a-priori bound)
     if constexpr (EPI == EPI_STORE || EPI == EPI_GABOR_FWD || EPI == EPI_GABOR2D_FWD || EPI == EPI_SIREN_FWD ||
                   EPI == EPI_GAUSS_FWD) {
-      if (g_x2_amode == 2)
+      if (knob(K_X2_AMODE) == 2)
         hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 2, 4, 1, true>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m,
                            tiles_n, ep);
       else
@@ -498,9 +464,9 @@ static hipError_t launchx2h_t(hipStream_t s, const float* A, int lda, const unsi
       return hipErrorInvalidValue;
     }
   }
-  if (g_x2_amode == 2)
+  if (knob(K_X2_AMODE) == 2)
     hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 2, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
-  else if (g_x2_amode == 1)
+  else if (knob(K_X2_AMODE) == 1)
     hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 1, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
   else
     hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 0, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
@@ -881,7 +847,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemmx2_tn16_kernel(
 static int x2_tn_shape(int Pm, int Pn) {
   if ((Pm & 63) || (Pn & 63) || Pm < 64 || Pn < 64) return 0;
   if (Pm % 256 == 0 && Pn % 256 == 0) return 42;
-  if (Pm == 384) return g_x2_tn_p384 == 8 ? 381 : 61;   // 381: 8 waves x 48 features (round 4); 61: 6 waves x 64
+  if (Pm == 384) return knob(K_X2_TN_P384) == 8 ? 381 : 61;   // 381: 8 waves x 48 features (round 4); 61: 6 waves x 64
   if (Pm == 448) return 71;
   return 0;
 }
@@ -905,7 +871,7 @@ int gemmx2_tn_splits(int64_t n, int Pm, int Pn, int max_splits) {
   if (s > max_splits) s = max_splits;
   if (s < 1) s = 1;
   if (n < 1) return s;
-  const int cap_rows = g_x2_tn_rows;                     // bounded accumulation chains: more splits (up to 4096), whatever max_splits
+  const int cap_rows = knob(K_X2_TN_ROWS);                     // bounded accumulation chains: more splits (up to 4096), whatever max_splits
   if (cap_rows > 0) {
     int64_t need = (n + cap_rows - 1) / cap_rows;
     need = (need + 7) / 8 * 8;

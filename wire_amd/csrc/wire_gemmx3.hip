@@ -365,36 +365,17 @@ static hipError_t launchx3_nt_t(hipStream_t s, const float* A, int lda, const vo
   return hipGetLastError();
 }
 
-static int x3_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-static std::atomic<int> g_x3_tn_tall{x3_env("WIRE_X3_TN_TALL", 0)};   // 256 x 128 tiles in the weight-gradient kernel
-static std::atomic<int> g_x3_tn16{x3_env("WIRE_X3_TN16", 1)};         // 256 x 256 tiles on v_mfma_f32_16x16x32_bf16
-// 256-row tiles (4 x 2 MFMA tiles per wave) for the Gabor epilogues of large batches: fewer weight bytes
-// per MFMA through the 64 B/clk L1 path (tools/mfma_bf16_probe.hip), 7-9 % faster at N = 262144
-static std::atomic<int> g_x3_tall{x3_env("WIRE_X3_TALL", 1)};
-static std::atomic<int> g_x3_tall_real{x3_env("WIRE_X3_TALL_REAL", 0)};   // the same for siren / gauss / relu (A/B switch)
-int gemmx3_tn16_mode() { return g_x3_tn16; }
 // The LDS-DMA 32 x 32 x 16 edition (tools/wire_gemmx3g.hip: the staging A/B of round 2) lives outside the product library;
 // a harness that links it registers it here.
 static bool (*g_glds_handles)(int, int64_t) = nullptr;
 static hipError_t (*g_glds_launch)(hipStream_t, int, const float*, int, const void*, int64_t, int, int,
                                    const GemmEpiParams&) = nullptr;
-static int (*g_glds_tune)(const char*, int) = nullptr;
+int (*g_glds_tune)(const char*, int) = nullptr;
 void gemmx3_register_glds(bool (*handles)(int, int64_t),
                           hipError_t (*launch)(hipStream_t, int, const float*, int, const void*, int64_t, int, int,
                                                const GemmEpiParams&),
                           int (*tune)(const char*, int)) {
   g_glds_handles = handles; g_glds_launch = launch; g_glds_tune = tune;
-}
-int gemmx3_tune_set(const char* key, int value) {
-  if (!strcmp(key, "x3_tall") && (value == 0 || value == 1)) { g_x3_tall = value; return 0; }
-  if (!strcmp(key, "x3_tn_tall") && (value == 0 || value == 1)) { g_x3_tn_tall = value; return 0; }
-  if (!strcmp(key, "x3_tn16") && (value == 0 || value == 1)) { g_x3_tn16 = value; return 0; }
-  if (!strcmp(key, "x3_tall_real") && (value == 0 || value == 1)) { g_x3_tall_real = value; return 0; }
-  if (gemmx3h_tune_set(key, value) == 0) return 0;
-  return g_glds_tune ? g_glds_tune(key, value) : -1;
 }
 
 // true when launch_gemmx3_nt runs this epilogue on the 16 x 16 x 32 edition (lean epilogues, optional out store,
@@ -416,7 +397,7 @@ hipError_t launch_gemmx3_nt(hipStream_t s, int epi, const float* A, int lda, con
     ep.wide = 1;
   if ((double)M * (double)(ep.ld1 > ep.ld0 ? ep.ld1 : ep.ld0) * 4.0 >= 4294967296.0) ep.wide = 1;
   // (256-row tiles for wire2d and the real nets were measured 5 % SLOWER on their steps: they stay on 128 rows)
-  if (g_x3_tall_real && M >= 4096) {
+  if (knob(K_X3_TALL_REAL) && M >= 4096) {
     switch (epi) {
       case EPI_SIREN_FWD: return launchx3_nt_t<EPI_SIREN_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
       case EPI_GAUSS_FWD: return launchx3_nt_t<EPI_GAUSS_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
@@ -427,7 +408,7 @@ hipError_t launch_gemmx3_nt(hipStream_t s, int epi, const float* A, int lda, con
       default: break;
     }
   }
-  if (g_x3_tall && M >= 4096) {
+  if (knob(K_X3_TALL) && M >= 4096) {
     switch (epi) {
       case EPI_STORE: return launchx3_nt_t<EPI_STORE, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
       case EPI_GABOR_FWD: return launchx3_nt_t<EPI_GABOR_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
@@ -978,7 +959,7 @@ static int tn_splits_for(int64_t n, int Pm, int Pn, int max_splits, bool tn16) {
   return s < 1 ? 1 : s;
 }
 int gemmx3_tn_splits(int64_t n, int Pm, int Pn, int max_splits) {
-  return tn_splits_for(n, Pm, Pn, max_splits, tn16_applies(Pm, Pn, g_x3_tn16));
+  return tn_splits_for(n, Pm, Pn, max_splits, tn16_applies(Pm, Pn, knob(K_X3_TN16)));
 }
 // the larger of the two kernels' counts: scratch sized with it stays valid when "x3_tn16" is switched
 int gemmx3_tn_splits_max(int64_t n, int Pm, int Pn, int max_splits) {
@@ -991,8 +972,8 @@ hipError_t launch_gemmx3_tn(hipStream_t s, const float* G, int ldg, const float*
                             int Pm, int Pn, int splits, float* slab, float* bslab) {
   // all padded widths are multiples of 64; a ragged last tile clamps its loader column inside the row
   if ((Pm & 63) || (Pn & 63) || (ldg & 3) || (ldz & 3) || splits < 1 || n < 1) return hipErrorInvalidValue;
-  const bool tn16 = tn16_applies(Pm, Pn, g_x3_tn16);
-  const bool tall = !tn16 && g_x3_tn_tall && (Pm % 256 == 0);
+  const bool tn16 = tn16_applies(Pm, Pn, knob(K_X3_TN16));
+  const bool tall = !tn16 && knob(K_X3_TN_TALL) && (Pm % 256 == 0);
   const int tiles_m = tn16 || tall ? Pm / 256 : (Pm + 127) / 128;
   const int tiles_n = tn16 ? Pn / 256 : (Pn + 127) / 128;
   long long chunk = (n + splits - 1) / splits;
@@ -1017,7 +998,7 @@ hipError_t launch_gemmx3_tn(hipStream_t s, const float* G, int ldg, const float*
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 2 * X3T_STAGE);
     if (attr != hipSuccess) return attr;
 #ifdef WIRE_ABLATE_TN
-    static const int abl = x3_env("WIRE_TN_ABL", 0);
+    const int abl = knob(K_TN_ABL);
     hipLaunchKernelGGL(gemmx3_tn16_kernel, grid, dim3(512), 2 * X3T_STAGE, s, G, ldg, Z, ldz, (long long)n, Pm, Pn,
                        tiles_n, used, chunk, slab, bslab, tiles_m * tiles_n, abl);
 #else

@@ -234,28 +234,13 @@ static hipError_t launchx3h_t(hipStream_t s, const float* A, int lda, const unsi
   return hipGetLastError();
 }
 
-static int x3h_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-// bit 0: forward / store epilogues, bit 1: data-gradient epilogues.  In bench.py (same box, interleaved runs,
-// profiles/r02_bench_h16_ab.txt): forward launches 0.758 -> 0.700 ms, data gradient 0.749 -> 0.739 ms, step 9.93 -> 9.63 ms
-// bit 2: siren / gauss / relu epilogues, bit 3: the 2-D Gabor epilogues (sweep A/B, same box: siren 72.4 -> 74.9,
-// relu 81.9 -> 85.0, wire2d 44.2 -> 47.6 M samples/s)
-static std::atomic<int> g_x3_h16{x3h_env("WIRE_X3_H16", 15)};
-static std::atomic<int> g_x3h_stagger{x3h_env("WIRE_X3H_STAGGER", 0)};      // 100 MHz ticks (100 = 1 us)
-int gemmx3h_tune_set(const char* key, int value) {
-  if (!strcmp(key, "x3_h16") && value >= 0 && value <= 15) { g_x3_h16 = value; return 0; }
-  if (!strcmp(key, "x3h_stagger") && value >= 0) { g_x3h_stagger = value; return 0; }
-  return -1;
-}
-int gemmx3h_mode() { return g_x3_h16; }
 bool gemmx3h_handles(int epi, int64_t M) {
-  if (!g_x3_h16 || M < 4096) return false;
-  if (epi == EPI_STORE || epi == EPI_GABOR_FWD) return (g_x3_h16 & 1) != 0;
-  if (epi == EPI_GABOR_BWD || epi == EPI_GABOR_BWD_FIRST) return (g_x3_h16 & 2) != 0;
-  if (epi >= EPI_SIREN_FWD && epi <= EPI_RELU_BWD) return (g_x3_h16 & 4) != 0;
-  if (epi >= EPI_GABOR2D_FWD && epi <= EPI_GABOR2D_BWD_FIRST) return (g_x3_h16 & 8) != 0;
+  const int h16 = knob(K_X3_H16);
+  if (!h16 || M < 4096) return false;
+  if (epi == EPI_STORE || epi == EPI_GABOR_FWD) return (h16 & 1) != 0;
+  if (epi == EPI_GABOR_BWD || epi == EPI_GABOR_BWD_FIRST) return (h16 & 2) != 0;
+  if (epi >= EPI_SIREN_FWD && epi <= EPI_RELU_BWD) return (h16 & 4) != 0;
+  if (epi >= EPI_GABOR2D_FWD && epi <= EPI_GABOR2D_BWD_FIRST) return (h16 & 8) != 0;
   return false;
 }
 
@@ -265,7 +250,7 @@ hipError_t launch_gemmx3h_nt(hipStream_t s, int epi, const float* A, int lda, co
   if (M <= 0) return hipSuccess;
   if ((Nc & 63) || (Kd & 31) || (lda & 3) || M > 0x7fffff00LL) return hipErrorInvalidValue;
   GemmEpiParams ep = ep_in;
-  ep.stagger = g_x3h_stagger; ep.stagger_lo = 256; ep.stagger_hi = 512;
+  ep.stagger = knob(K_X3H_STAGGER); ep.stagger_lo = 256; ep.stagger_hi = 512;
   const unsigned short* Bu = (const unsigned short*)Bx3 + (size_t)gemmx3_b_image_floats(Nc, Kd);   // = half the image, in ushorts
   switch (epi) {
     case EPI_STORE: return launchx3h_t<EPI_STORE>(s, A, lda, Bu, M, Nc, Kd, ep);

@@ -19,7 +19,6 @@ extern int wire_fail_(int code, const char* msg);   // wire_api.hip
 // The per-layer entry points run the SAME kernels as wire_mlp_fwd / wire_mlp_bwd, so the per-layer parity
 // tests (protocol step (i)) check the code the bench times.
 extern int wire_family_(int kind);
-extern int wire_split_f16_();       // wire_api.hip: the "split_f16" knob
 enum { FAM_4M = 0, FAM_3M = 1, FAM_X3 = 2 };
 #ifndef WIRE_AMAX_SLOTS
 #define WIRE_AMAX_SLOTS 64
@@ -99,7 +98,7 @@ struct LayerGemm {
   int fam;
   float* x2ws;       // x2_region_floats(...) of the workspace, or null: never the 2 x fp16 kernels
   bool use_x2(int epi, int64_t n) const {
-    return fam == FAM_X3 && x2ws && wire_split_f16_() && gemmx3_nt_is_h16(epi, n);
+    return fam == FAM_X3 && x2ws && knob(K_SPLIT_F16) && gemmx3_nt_is_h16(epi, n);
   }
   unsigned* slots(int which) const { return reinterpret_cast<unsigned*>(x2ws) + which * WIRE_AMAX_SLOTS; }
   // weights: W_ + btf / btd hold the fp32 images of the family, btf_x3 / btd_x3 the split images
@@ -113,7 +112,7 @@ struct LayerGemm {
     e = launch_x3_split_b(s, btf, Pin, Pout_g, Pin, btf_x3);
     if (e != hipSuccess) return e;
     e = launch_x3_split_b(s, btd, Pout_g, Pin, Pout_g, btd_x3);
-    if (e != hipSuccess || !x2ws || !wire_split_f16_()) return e;
+    if (e != hipSuccess || !x2ws || !knob(K_SPLIT_F16)) return e;
     // 2 x fp16 images: max |weight| (the transposed image holds the same values), then both scaled splits
     e = hipMemsetAsync(x2ws, 0, 4 * WIRE_AMAX_SLOTS * sizeof(float), s);
     if (e != hipSuccess) return e;
