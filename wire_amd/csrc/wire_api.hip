@@ -102,10 +102,10 @@ extern "C" int wire_prof_read(double* ms_total, int64_t* launches, double* flops
 // ---------------------------------------------------------------------------
 // tuning knobs (the table: wire_knobs.hip)
 // ---------------------------------------------------------------------------
-// family the flags select for a net kind (wire_layer_api.hip): 2 split-bf16, 1 complex 3M (wire only), 0 4M
-int wire_family_(int kind) {
-  if (knob(K_SPLIT_BF16)) return 2;
-  return (kind == WIRE_KIND_WIRE && knob(K_COMPLEX_3M)) ? 1 : 0;
+// family the flags select for a net kind (wire_layer_api.hip)
+WireFamily wire_family_(int kind) {
+  if (knob(K_SPLIT_BF16)) return FAM_X3;
+  return (kind == WIRE_KIND_WIRE && knob(K_COMPLEX_3M)) ? FAM_3M : FAM_4M;
 }
 extern "C" int wire_tune_get(const char* key) {
   if (!key) return fail(WIRE_ERR_ARG, "null key");
@@ -321,74 +321,6 @@ CoordLayout coord_layout(const Plan& p, int64_t n) {
   return c;
 }
 
-int epi_fwd(int kind);
-int epi_bwd(int kind);
-// the hidden-layer GEMMs of this call run as 2 x fp16 splits: every forward / data-gradient launch is then a 16 x 16 x 32
-// kernel (M >= 4096, x3_h16 bits of the kind), whose epilogues track the maxima the next GEMM scales by
-bool use_x2(const Plan& p, int64_t n) {
-  return p.x2 && p.L >= 1 && gemmx3_nt_is_h16(epi_fwd(p.kind), n) && gemmx3_nt_is_h16(epi_bwd(p.kind), n);
-}
-// Scale with which out_l of this call is stored pre-split (wire_dev.h: wire_store_out4), 0 = plain fp32.  Pre-split when
-//  * the call runs the 2 x fp16 kernels and every reader of out_l understands the format: the forward GEMM of layer l + 1
-//    (pre-split A edition), the weight-gradient GEMM of layer l + 1 (gemmx2_tn16, pre-split Z) and NOTHING else -- the
-//    data-gradient epilogue of layer l + 1 must evaluate act(lin_l) again rather than read out_l (recompute_out; sine needs
-//    no out), out_L feeds the final linear layer in fp32, relu's out carries its backward's sign decisions;
-//  * l >= 1 (out_0 comes from first_fwd_kernel);
-//  * max |out_l| has a bound that is known here AND is reached in practice, so that a scale fixed on the host wastes no
-//    fp16 range: sine and Gaussian <= 1; Gabor |exp(j w lin - s^2 |lin|^2)| = exp(-w v - s^2 (u^2 + v^2)) <= exp(w^2 / 4 s^2),
-//    attained at lin = -j w / 2 s^2 -- accepted up to 16 (w / s <= 3.33: every configuration of the reference's scripts;
-//    beyond it the maximum is tracked on the device as before).  bound < 2^e  ->  scale 2^(15 - e): |out| scale < 2^15.
-float fused_act_scale(const Plan& p);
-// The training forward of this call runs as ONE kernel (wire_fused.hip) that stores lin_l / out_l on the way: the shapes
-// that have a kernel (256-feature real nets; wire at P = 192 / 256 -- P = 384 spills in its storing edition), the 2 x fp16
-// family with its pre-split activations and recompute_out (the formats that kernel writes), a bound on the activations (all
-// kinds but relu).  Decides the FORMAT of the stored out_l (pre-split at scale 1), so the backward asks the same question.
-bool fused_train_applies(const Plan& p, int64_t n) {
-  if (!p.k_fused_train || p.off_fx < 0 || p.L < 1 || p.L > 8) return false;
-  if (!use_x2(p, n) || !gemmx2_tn_applies(p.Pl, p.P) || !p.k_split_out || !p.k_recompute_out) return false;
-  if (p.kind == WIRE_KIND_WIRE && p.P > 256 && !p.k_fused_train_p384) return false;
-  if (p.kind != WIRE_KIND_RELU && fused_act_scale(p) == 0.f) return false;
-  return fused_pre_scale(p.kind, p.w1, p.s) > 0.f && fused_pre_scale(p.kind, p.w, p.s) > 0.f;
-}
-// ... and its data gradients g_lin_L -> .. -> g_lin_1 -> the first layer's gradient sums as ONE kernel
-bool fused_bwd_applies(const Plan& p, int64_t n) {
-  return p.k_fused_bwd && p.off_fxd >= 0 && p.L >= 1 && fused_train_applies(p, n);
-}
-// ... and then the sine / Gaussian nets store NO out_l below L and their lin_l (l < L, layer 0 included) as r = c lin (the
-// argument the activation was evaluated on): the chain differentiates on r, the weight-gradient loader evaluates act(r) again
-// -- 1.3 GB per step less
-bool fused_rstore(const Plan& p, int64_t n) {
-  return (p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_GAUSS) && p.k_rstore && fused_bwd_applies(p, n);
-}
-float out_split_scale(const Plan& p, int64_t n, int l) {
-  if (!p.k_split_out || l < 1 || l >= p.L || p.kind == WIRE_KIND_RELU) return 0.f;
-  if (!use_x2(p, n) || !gemmx2_tn_applies(p.Pl, p.P)) return 0.f;
-  if (!p.k_recompute_out && p.kind != WIRE_KIND_SIREN) return 0.f;
-  if (fused_train_applies(p, n)) return 1.f;               // the fused forward splits its bounded activations unscaled
-  double bound = 1.0;
-  if (p.cplx) {
-    if (!(p.s > 0.f)) return 0.f;
-    const double r = (double)p.w / (2.0 * (double)p.s);
-    if (!(r * r <= 2.7725887)) return 0.f;                 // ln 16
-    bound = exp(r * r);
-  }
-  const int e = ilogb(bound) + 1;
-  return ldexpf(1.f, 15 - e);
-}
-// Power-of-two scale with which the fused forward (wire_fused.hip) splits the activations it keeps in registers: from
-// their a-priori bound as above (sine, Gaussian <= 1; Gabor <= exp(w^2 / 4 s^2), accepted up to 16); 0 = none known
-// (relu: the kernel takes each wave's own maximum; Gabor beyond the bound: the layer-by-layer path runs)
-float fused_act_scale(const Plan& p) {
-  if (p.kind == WIRE_KIND_RELU || p.kind == WIRE_KIND_WIRE2D) return 0.f;
-  double bound = 1.0;
-  if (p.kind == WIRE_KIND_WIRE) {
-    if (!(p.s > 0.f)) return 0.f;
-    const double r = (double)p.w / (2.0 * (double)p.s);
-    if (!(r * r <= 2.7725887)) return 0.f;
-    bound = exp(r * r);
-  }
-  return ldexpf(1.f, 15 - (ilogb(bound) + 1));
-}
 int epi_fwd(int kind) {
   switch (kind) {
     case WIRE_KIND_WIRE: return EPI_GABOR_FWD;
@@ -405,6 +337,131 @@ int epi_bwd(int kind) {
     case WIRE_KIND_SIREN: return EPI_SIREN_BWD;
     case WIRE_KIND_GAUSS: return EPI_GAUSS_BWD;
     default: return EPI_RELU_BWD;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// route: what one whole-net call runs, decided once from (plan, n, entry point)
+// ---------------------------------------------------------------------------
+// wire_mlp_fwd with save_for_bwd = 0; wire_mlp_fwd with save_for_bwd = 1, wire_mlp_bwd[_coords]; wire_train_fwd_bwd[_hooked]
+enum RouteMode { MODE_INFER, MODE_AUTOGRAD, MODE_TRAIN };
+struct Route {
+  RouteMode mode;
+  WireFamily fam;         // forward and data-gradient GEMMs of the hidden layers
+  WireFamily fam0;        // GEMMs of a positional-encoding first layer: 3 x bf16 or fp32
+  WireFamily tn_fam;      // weight-gradient GEMMs of the hidden layers, in tn_S row splits
+  int tn_S;
+  bool fused_fwd;         // inference: the whole net in one kernel, activations in registers (wire_fused.hip)
+  bool fuse;              // train: final linear + MSE + final backward + activation gradient of layer L in one pass
+  bool fused_train;       // train: the hidden layers in one kernel that stores what the backward reads (wire_fused.hip)
+  bool fused_final;       //   ... with the final stage inside it (fx_tail_loss): lin_L / out_L are not stored at all
+  bool chain;             // the data gradients of layers L .. 1 in one kernel (wire_fused.hip: fused_bwd_kernel)
+  bool rstore;            //   ... sine / Gaussian: lin_l (l < L) stored as r = c lin, out_l (l < L) not at all
+  bool skip_out_L;        // train: out_L is neither written nor read, the final stage evaluates it from lin_L
+  bool recompute_out;     // the data-gradient epilogue of layer l >= 2 evaluates out_{l-1} = act(lin_{l-1}) again
+  bool recompute_out0;    //   ... and wire's first-layer epilogue out_0 (first_fwd_kernel's own form, the same bits)
+  bool first_sums;        // the layer-1 data-gradient epilogue sums the first layer's weight / bias gradient itself
+  bool cg_epi;            //   ... and can form the per-row coordinate-gradient partials
+  int wb_l0, wb_n, wb_S;  // weight-gradient batch: layers wb_l0 .. L, wb_n members of wb_S splits (wb_l0 = L + 1: none)
+  float act_scale;        // split scale of the fused forward's activations, 0 = none known
+  float out_scale[65];    // pre-split scale of out_l, l = 0 .. L (L <= 64); 0 = plain fp32
+};
+
+// Power-of-two split scale of activations with an a-priori bound (bound < 2^e -> 2^(15 - e): |out| scale < 2^15): sine
+// and Gaussian <= 1; Gabor |exp(j w lin - s^2 |lin|^2)| = exp(-w v - s^2 (u^2 + v^2)) <= exp((w / 2s)^2), attained at
+// lin = -j w / 2 s^2 -- accepted up to 16 (w / s <= 3.33: every configuration of the reference's scripts); 0 beyond it
+float act_bound_scale(const Plan& p) {
+  double bound = 1.0;
+  if (p.cplx) {
+    if (!(p.s > 0.f)) return 0.f;
+    const double r = (double)p.w / (2.0 * (double)p.s);
+    if (!(r * r <= 2.7725887)) return 0.f;                 // ln 16
+    bound = exp(r * r);
+  }
+  return ldexpf(1.f, 15 - (ilogb(bound) + 1));
+}
+
+Route make_route(const Plan& p, int64_t n, RouteMode mode) {
+  Route r{};
+  r.mode = mode;
+  const bool h16_fwd = gemmx3_nt_is_h16(epi_fwd(p.kind), n);
+  // 2 x fp16 splits: every forward / data-gradient launch of the hidden layers is then a 16 x 16 x 32 kernel (M >= 4096,
+  // x3_h16 bits of the kind), whose epilogues track the maxima the next GEMM scales by
+  const bool x2 = p.x2 && p.L >= 1 && h16_fwd && gemmx3_nt_is_h16(epi_bwd(p.kind), n);
+  const bool x2tn = x2 && gemmx2_tn_applies(p.Pl, p.P);
+  r.fam = x2 ? FAM_X2 : p.m3 ? FAM_3M : p.x3 ? FAM_X3 : FAM_4M;
+  r.fam0 = p.x3 ? FAM_X3 : FAM_4M;
+  r.tn_fam = p.m3 ? FAM_3M : x2tn ? FAM_X2 : p.x3 ? FAM_X3 : FAM_4M;
+  const int S_max = scratch_layout(p, n).S;
+  r.tn_S = r.tn_fam == FAM_3M ? S_max
+         : r.tn_fam == FAM_X2 ? gemmx2_tn_splits(n, p.Pl, p.P, S_max)
+         : r.tn_fam == FAM_X3 ? gemmx3_tn_splits(n, p.Pl, p.P, S_max) : gemm_tn_splits(n, p.Pl, p.P, S_max);
+  // a hidden layer whose forward ran the lean 16 x 16 x 32 epilogue: its out = act(lin) again, 8 B / element less (real
+  // nets: only below a hidden layer -- the first layer's out comes from first_fwd_kernel's precise form)
+  r.recompute_out = p.k_recompute_out && p.x3 && h16_fwd;
+  // (relu: the fused kernels take each wave's own maximum; Gabor beyond the bound: the layer-by-layer path runs)
+  r.act_scale = (p.kind == WIRE_KIND_RELU || p.kind == WIRE_KIND_WIRE2D) ? 0.f : act_bound_scale(p);
+  // the whole-net kernels: a shape that has one, at most 8 hidden layers, a bound on the activations
+  const bool fx = x2 && p.off_fx >= 0 && p.L <= 8 && (r.act_scale != 0.f || p.kind == WIRE_KIND_RELU) &&
+                  fused_pre_scale(p.kind, p.w1, p.s) > 0.f && fused_pre_scale(p.kind, p.w, p.s) > 0.f;
+  r.fused_fwd = mode == MODE_INFER && fx && p.k_fused_fwd && p.O <= 4;
+  // The training forward as one kernel that stores lin_l / out_l on the way: the 2 x fp16 family with its pre-split
+  // activations and recompute_out (the formats that kernel writes); wire at P = 384 spills in its storing edition.  It
+  // decides the FORMAT of the stored out_l (pre-split at scale 1), so it is asked in every mode
+  const bool ftrain = fx && x2tn && p.k_fused_train && p.k_split_out && p.k_recompute_out &&
+                      !(p.kind == WIRE_KIND_WIRE && p.P > 256 && !p.k_fused_train_p384);
+  r.fuse = mode == MODE_TRAIN && p.L >= 1 && p.O <= 4 && final_fused_supported(p.P, p.O);
+  r.skip_out_L = r.fuse && r.recompute_out && p.kind != WIRE_KIND_RELU;
+  r.fused_train = r.fuse && ftrain && (r.skip_out_L || p.kind == WIRE_KIND_RELU);
+  // chain => fused_train, by construction: the chain reads g_lin_L and lin_l / r_l as only the fused training forward
+  // stores them
+  r.chain = r.fused_train && p.k_fused_bwd && p.off_fxd >= 0;
+  r.fused_final = r.chain && !p.cplx && p.k_fused_final;
+  r.rstore = r.chain && p.k_rstore && (p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_GAUSS);   // 1.3 GB per step less
+  // out_l is stored pre-split (wire_dev.h: wire_store_out4) when the call runs the 2 x fp16 kernels and every reader of
+  // out_l understands the format: the forward GEMM of layer l + 1 (pre-split A edition), the weight-gradient GEMM of layer
+  // l + 1 (gemmx2_tn16, pre-split Z) and NOTHING else -- the data-gradient epilogue of layer l + 1 must evaluate
+  // act(lin_l) again rather than read out_l (recompute_out; sine needs no out), out_0 comes from first_fwd_kernel, out_L
+  // feeds the final linear layer in fp32, relu's out carries its backward's sign decisions
+  const bool split = x2tn && p.k_split_out && p.kind != WIRE_KIND_RELU && (p.k_recompute_out || p.kind == WIRE_KIND_SIREN);
+  for (int l = 1; l < p.L; ++l) r.out_scale[l] = !split ? 0.f : ftrain ? 1.f : act_bound_scale(p);
+  // the layer-1 data gradient of a native first layer on the 16 x 16 x 32 kernel: its epilogue can sum g_lin_0 (wire:
+  // g_u) [x | 1] per tile itself instead of storing it for a separate pass, and form the coordinate-gradient partials
+  const int epi1 = p.kind == WIRE_KIND_WIRE ? EPI_GABOR_BWD_FIRST
+                 : p.kind == WIRE_KIND_WIRE2D ? EPI_GABOR2D_BWD_FIRST : epi_bwd(p.kind);
+  const bool h16_1 = p.x3 && gemmx3_nt_is_h16(epi1, n);
+  r.cg_epi = h16_1 && !p.first_gemm && p.L >= 1;
+  r.first_sums = r.cg_epi && p.k_first_sums;
+  r.recompute_out0 = h16_1 && p.kind == WIRE_KIND_WIRE && p.k_recompute_out;
+  // behind the chain every g_lin_l exists before the first weight gradient starts: those of layers 2 .. L (same shape,
+  // operands a fixed step apart) run as ONE launch, each member accumulating L - 1 times the rows into a third of the
+  // slabs (layer 1 joins when its activation operand has the form of the others': r_0 of rstore, relu's fp32 out_0)
+  r.wb_l0 = p.L + 1;
+  if (r.chain && p.k_wgrad_batch) {                        // (the chain runs on the 2 x fp16 weight-gradient kernel)
+    const int l0 = (r.rstore || p.kind == WIRE_KIND_RELU) ? 1 : 2, nb = p.L - l0 + 1;
+    const int S = nb >= 2 ? gemmx2_tn_batch_splits(n, p.Pl, p.P, S_max, nb) : 0;
+    if (S >= 1 && (int64_t)S * nb <= S_max) { r.wb_l0 = l0; r.wb_n = nb; r.wb_S = S; }
+  }
+  return r;
+}
+
+inline const unsigned* wamax_of(const Plan& p, const float* packed, int l) {   // max |W_l| slots
+  return reinterpret_cast<const unsigned*>(packed + p.off_wamax + (int64_t)l * WIRE_AMAX_SLOTS);
+}
+// C = A W_l^T (the forward of layer l) or, dg, A W_l (its data gradient) on family f, from f's image of layer l.  The
+// 2 x fp16 kernels also take the maximum slots of A, of W_l and of the tensor the epilogue writes (null: none kept)
+hipError_t layer_nt(hipStream_t s, const Plan& p, WireFamily f, const float* packed, int l, bool dg, int epi,
+                    const float* A, int64_t n, GemmEpiParams ep, const unsigned* amax_a = nullptr,
+                    const unsigned* amax_b = nullptr, unsigned* amax_out = nullptr) {
+  const int Pin = l == 0 ? p.Pin0 : p.P, Nc = dg ? Pin : p.Pl, Kd = dg ? p.Pl : Pin;
+  switch (f) {
+    case FAM_X2:
+      ep.amax_a = amax_a; ep.amax_b = amax_b; ep.amax_out = amax_out;
+      return launch_gemmx2h_nt(s, epi, A, Kd, packed + (dg ? p.off_dg_x2 : p.off_fwd_x2)[l], n, Nc, Kd, ep);
+    case FAM_3M:
+      return launch_gemm3m_nt(s, epi, A, Kd, packed + (dg ? p.off_dg_3m : p.off_fwd_3m)[l], Kd, n, Nc / 2, Kd / 2, ep);
+    case FAM_X3: return launch_gemmx3_nt(s, epi, A, Kd, packed + (dg ? p.off_dg_x3 : p.off_fwd_x3)[l], n, Nc, Kd, ep);
+    default: return launch_gemm_nt(s, epi, A, Kd, packed + (dg ? p.off_dg : p.off_fwd)[l], Kd, n, Nc, Kd, ep);
   }
 }
 }  // namespace
@@ -558,140 +615,104 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
 // ---------------------------------------------------------------------------
 // whole-network forward
 // ---------------------------------------------------------------------------
-static int mlp_fwd_core(void* stream, const Plan& p, const float* packed, const float* coords, int64_t n,
-                        float* y, void* act, int64_t act_bytes, int save_for_bwd, bool do_final,
-                        bool skip_last_out = false, const FusedFwdParams* loss = nullptr, bool* loss_done = nullptr) {
+// the parameters of the whole-net kernels (wire_fused.hip) that the inference and the training forward share
+static FusedFwdParams fused_params(const Plan& p, const float* packed, const float* coords, int64_t n) {
+  FusedFwdParams fp;
+  fp.coords = coords; fp.n = n;
+  if (p.first_gemm) {
+    fp.pe_F = p.F; fp.bias0 = packed + p.off_bias[0]; fp.wamax0 = wamax_of(p, packed, 0);
+  } else {
+    fp.W0 = packed + first_native_off(p, 0); fp.b0 = packed + first_native_off(p, 1);
+  }
+  fp.wimg = reinterpret_cast<const unsigned char*>(packed + p.off_fx);
+  fp.bias = packed + p.off_bias[1]; fp.bias_stride = p.L >= 2 ? p.off_bias[2] - p.off_bias[1] : 0;
+  fp.wamax = wamax_of(p, packed, 1); fp.wamax_stride = WIRE_AMAX_SLOTS;
+  fp.D = p.D; fp.K = p.K; fp.L = p.L; fp.O = p.O; fp.w1 = p.w1; fp.w = p.w; fp.s = p.s;
+  fp.c_first = fused_pre_scale(p.kind, p.w1, p.s); fp.c_hidden = fused_pre_scale(p.kind, p.w, p.s);
+  fp.k2_first = p.s * p.s * 1.44269502f / (fp.c_first * fp.c_first);
+  fp.k2 = p.s * p.s * 1.44269502f / (fp.c_hidden * fp.c_hidden);
+  return fp;
+}
+
+// loss (train, r.fused_final): the target and the outputs of the final stage inside the fused training forward
+static int mlp_fwd_core(void* stream, const Plan& p, const Route& r, const float* packed, const float* coords, int64_t n,
+                        float* y, void* act, int64_t act_bytes, const FusedFwdParams* loss = nullptr) {
+  const bool save = r.mode != MODE_INFER;
   if (n < 0) return fail(WIRE_ERR_ARG, "negative n");
   if (n == 0) return WIRE_OK;
-  if (!packed || !coords || (do_final && !y) || !act) return fail(WIRE_ERR_ARG, "null pointer");
-  const ActLayout a = act_layout(p, n, save_for_bwd);
+  if (!packed || !coords || (!r.fuse && !y) || !act) return fail(WIRE_ERR_ARG, "null pointer");
+  const ActLayout a = act_layout(p, n, save);
   if (act_bytes < a.total * 4) return fail(WIRE_ERR_SIZE, "act buffer %lld < %lld bytes",
                                            (long long)act_bytes, (long long)a.total * 4);
   hipStream_t s = (hipStream_t)stream;
   float* A = (float*)act;
-  const bool x2 = use_x2(p, n);
-  if (!save_for_bwd && do_final && x2) {
-    // forward-only: the whole net in one kernel, activations in registers (wire_fused.hip)
-    const float a_scale = fused_act_scale(p);
-    if (p.off_fx >= 0 && p.k_fused_fwd && p.O <= 4 && p.L <= 8 && (a_scale != 0.f || p.kind == WIRE_KIND_RELU) &&
-        fused_pre_scale(p.kind, p.w1, p.s) > 0.f && fused_pre_scale(p.kind, p.w, p.s) > 0.f) {
-      FusedFwdParams fp;
-      fp.coords = coords; fp.n = n;
-      if (p.first_gemm) {
-        fp.pe_F = p.F; fp.bias0 = packed + p.off_bias[0]; fp.wamax0 = reinterpret_cast<const unsigned*>(packed + p.off_wamax);
-      } else {
-        fp.W0 = packed + first_native_off(p, 0); fp.b0 = packed + first_native_off(p, 1);
-      }
-      fp.wimg = reinterpret_cast<const unsigned char*>(packed + p.off_fx);
-      fp.bias = packed + p.off_bias[1]; fp.bias_stride = p.L >= 2 ? p.off_bias[2] - p.off_bias[1] : 0;
-      fp.wamax = reinterpret_cast<const unsigned*>(packed + p.off_wamax) + WIRE_AMAX_SLOTS; fp.wamax_stride = WIRE_AMAX_SLOTS;
-      fp.wf = packed + p.off_wf; fp.bfr = packed + p.off_bf; fp.y = y;
-      fp.D = p.D; fp.K = p.K; fp.L = p.L; fp.O = p.O; fp.w1 = p.w1; fp.w = p.w; fp.s = p.s;
-      fp.c_first = fused_pre_scale(p.kind, p.w1, p.s); fp.c_hidden = fused_pre_scale(p.kind, p.w, p.s);
-      fp.k2_first = p.s * p.s * 1.44269502f / (fp.c_first * fp.c_first);
-      fp.k2 = p.s * p.s * 1.44269502f / (fp.c_hidden * fp.c_hidden);
-      ProfScope ps(s, 0, 2.0 * n * p.Pl * p.P * p.L);
-      HIPCHK(launch_fused_fwd(s, p.kind, p.P, fp));
-      return WIRE_OK;
-    }
+  if (r.fused_fwd) {
+    FusedFwdParams fp = fused_params(p, packed, coords, n);
+    fp.wf = packed + p.off_wf; fp.bfr = packed + p.off_bf; fp.y = y;
+    ProfScope ps(s, 0, 2.0 * n * p.Pl * p.P * p.L);
+    HIPCHK(launch_fused_fwd(s, p.kind, p.P, fp));
+    return WIRE_OK;
   }
   unsigned* const amax = reinterpret_cast<unsigned*>(A + a.amax);            // slots of out_l at amax + 64 l
-  auto wamax = [&](int l) { return reinterpret_cast<const unsigned*>(packed + p.off_wamax + (int64_t)l * WIRE_AMAX_SLOTS); };
-  if (x2) HIPCHK(hipMemsetAsync(amax, 0, (size_t)(p.L + 2) * WIRE_AMAX_SLOTS * sizeof(unsigned), s));
-  if (save_for_bwd && !do_final && p.O <= 4 && fused_train_applies(p, n) &&
-      (skip_last_out || p.kind == WIRE_KIND_RELU)) {
-    // training forward of wire_train_fwd_bwd: the hidden layers in one kernel that stores lin_l (not relu), out_0 (fp32 +
-    // its maximum), out_1 .. out_{L-1} (pre-split pairs; relu: fp32 + maxima, and out_L) -- what the fused final stage,
-    // the data-gradient epilogues and the weight-gradient GEMMs of mlp_bwd_core read (wire_fused.hip)
-    FusedFwdParams fp;
-    fp.coords = coords; fp.n = n;
-    if (p.first_gemm) {
-      // the encoded features themselves are still written: the first layer's weight gradient reads them (mlp_bwd_core)
-      { ProfScope ps(s, 3, 0);
-        HIPCHK(launch_posenc(s, coords, n, p.D, p.F, p.Pin0, A + a.pe)); }
-      fp.pe_F = p.F; fp.bias0 = packed + p.off_bias[0]; fp.wamax0 = reinterpret_cast<const unsigned*>(packed + p.off_wamax);
-    } else {
-      fp.W0 = packed + first_native_off(p, 0); fp.b0 = packed + first_native_off(p, 1);
-    }
-    fp.wimg = reinterpret_cast<const unsigned char*>(packed + p.off_fx);
-    fp.bias = packed + p.off_bias[1]; fp.bias_stride = p.L >= 2 ? p.off_bias[2] - p.off_bias[1] : 0;
-    fp.wamax = reinterpret_cast<const unsigned*>(packed + p.off_wamax) + WIRE_AMAX_SLOTS; fp.wamax_stride = WIRE_AMAX_SLOTS;
-    fp.D = p.D; fp.K = p.K; fp.L = p.L; fp.O = p.O; fp.w1 = p.w1; fp.w = p.w; fp.s = p.s;
-    fp.c_first = fused_pre_scale(p.kind, p.w1, p.s); fp.c_hidden = fused_pre_scale(p.kind, p.w, p.s);
-    fp.k2_first = p.s * p.s * 1.44269502f / (fp.c_first * fp.c_first);
-    fp.k2 = p.s * p.s * 1.44269502f / (fp.c_hidden * fp.c_hidden);
+  if (r.fam == FAM_X2) HIPCHK(hipMemsetAsync(amax, 0, (size_t)(p.L + 2) * WIRE_AMAX_SLOTS * sizeof(unsigned), s));
+  if (p.first_gemm) {   // (also behind the fused training forward: the first layer's weight gradient reads them)
+    ProfScope ps(s, 3, 0);
+    HIPCHK(launch_posenc(s, coords, n, p.D, p.F, p.Pin0, A + a.pe));
+  }
+  if (r.fused_train) {
+    // the hidden layers in one kernel that stores lin_l (not relu), out_0 (fp32 + its maximum), out_1 .. out_{L-1}
+    // (pre-split pairs; relu: fp32 + maxima, and out_L) -- what the final stage, the data-gradient epilogues and the
+    // weight-gradient GEMMs of mlp_bwd_core read
+    FusedFwdParams fp = fused_params(p, packed, coords, n);
     fp.inv_c_first = 1.f / fp.c_first; fp.inv_c_hidden = 1.f / fp.c_hidden;
     fp.lin0 = p.cplx ? nullptr : A + a.lin0;
     fp.lin = p.kind == WIRE_KIND_RELU ? nullptr : A + a.lin1; fp.lin_stride = a.np * p.Pl;
     fp.out = A + a.out0; fp.out_stride = a.np * p.P;
     fp.amax_out = amax;
-    fp.rstore = fused_rstore(p, n) ? 1 : 0;
-    if (loss && loss_done && !p.cplx && p.k_fused_final) {
-      // the final stage inside this kernel (wire_fused.hip: fx_tail_loss): lin_L / out_L are not stored at all
+    fp.rstore = r.rstore ? 1 : 0;
+    if (r.fused_final) {
       fp.wf = packed + p.off_wf; fp.bfr = packed + p.off_bf;
       fp.target = loss->target; fp.idx = loss->idx; fp.first = loss->first; fp.gscale = loss->gscale;
       fp.y = loss->y; fp.rec = loss->rec; fp.g_lin = loss->g_lin; fp.part_w = loss->part_w; fp.part_b = loss->part_b;
       fp.loss_partial = loss->loss_partial; fp.amax_g = loss->amax_g;
-      *loss_done = true;
     }
     ProfScope ps(s, 0, 2.0 * n * p.Pl * p.P * p.L);
     HIPCHK(launch_fused_fwd(s, p.kind, p.P, fp));
     return WIRE_OK;
   }
-  auto out_l = [&](int l) { return save_for_bwd ? A + a.out0 + (int64_t)l * a.np * p.P
-                                                : A + ((l & 1) ? a.pong : a.ping); };
+  auto out_l = [&](int l) { return save ? A + a.out0 + (int64_t)l * a.np * p.P : A + ((l & 1) ? a.pong : a.ping); };
   auto lin_l = [&](int l) -> float* {
     // relu: out = max(lin, 0) carries everything its backward needs (lin > 0 <=> out > 0): lin is never written
-    if (!save_for_bwd || p.kind == WIRE_KIND_RELU) return nullptr;
+    if (!save || p.kind == WIRE_KIND_RELU) return nullptr;
     return l == 0 ? A + a.lin0 : A + a.lin1 + (int64_t)(l - 1) * a.np * p.Pl;
   };
   // ---- layer 0
   if (p.first_gemm) {
-    { ProfScope ps(s, 3, 0);
-      HIPCHK(launch_posenc(s, coords, n, p.D, p.F, p.Pin0, A + a.pe)); }
     GemmEpiParams ep; ep.bias = packed + p.off_bias[0]; ep.o0 = lin_l(0); ep.o1 = out_l(0);
     ep.ld0 = p.Pl; ep.ld1 = p.P; ep.omega = p.w1; ep.scale = p.s; ep.kvalid = p.K;
-    if (x2) ep.amax_out = amax;                          // (the 3 x bf16 16 x 16 x 32 kernel tracks the maximum too)
+    if (r.fam == FAM_X2) ep.amax_out = amax;             // (the 3 x bf16 16 x 16 x 32 kernel tracks the maximum too)
     ProfScope ps(s, 0, 2.0 * n * p.Pl * p.Pin0);
-    if (p.x3)
-      HIPCHK(launch_gemmx3_nt(s, epi_fwd(p.kind), A + a.pe, p.Pin0, packed + p.off_fwd_x3[0], n, p.Pl,
-                              p.Pin0, ep));
-    else
-      HIPCHK(launch_gemm_nt(s, epi_fwd(p.kind), A + a.pe, p.Pin0, packed + p.off_fwd[0], p.Pin0, n,
-                            p.Pl, p.Pin0, ep));
+    HIPCHK(layer_nt(s, p, r.fam0, packed, 0, false, epi_fwd(p.kind), A + a.pe, n, ep));
   } else {
-    const float* W0 = packed + first_native_off(p, 0);
-    const float* b0 = packed + first_native_off(p, 1);
-    const float* V0 = p.per_layer == 4 ? packed + first_native_off(p, 2) : nullptr;
-    const float* c0 = p.per_layer == 4 ? packed + first_native_off(p, 3) : nullptr;
+    auto first = [&](int q) { return q < p.per_layer ? packed + first_native_off(p, q) : nullptr; };   // W0, b0 [, V0, c0]
     ProfScope ps(s, 3, 0);
-    HIPCHK(launch_first_fwd(s, p.kind, coords, n, p.D, W0, b0, V0, c0, p.K, p.P, p.w1, p.s,
-                            p.cplx ? nullptr : lin_l(0), out_l(0), x2 ? amax : nullptr));
+    HIPCHK(launch_first_fwd(s, p.kind, coords, n, p.D, first(0), first(1), first(2), first(3), p.K, p.P, p.w1, p.s,
+                            p.cplx ? nullptr : lin_l(0), out_l(0), r.fam == FAM_X2 ? amax : nullptr));
   }
   // ---- hidden layers
   for (int l = 1; l <= p.L; ++l) {
     GemmEpiParams ep; ep.bias = packed + p.off_bias[l]; ep.o0 = lin_l(l); ep.o1 = out_l(l);
     ep.ld0 = p.Pl; ep.ld1 = p.P; ep.omega = p.w; ep.scale = p.s; ep.kvalid = p.K;
-    if (skip_last_out && l == p.L) ep.o1 = nullptr;       // wire_train_fwd_bwd: the final stage recomputes it
+    if (r.skip_out_L && l == p.L) ep.o1 = nullptr;       // the final stage recomputes it
+    // pre-split activations: out_{l-1} read as such, out_l written as such (its maximum slots stay zero: not read)
+    const float s_in = r.out_scale[l - 1], s_out = r.out_scale[l];
+    if (s_in != 0.f) ep.a_split_inv = 1.f / s_in;
+    if (s_out != 0.f) ep.o1_split = s_out;
     ProfScope ps(s, 0, 2.0 * n * p.Pl * p.P);
-    if (x2) {
-      ep.amax_a = amax + (l - 1) * WIRE_AMAX_SLOTS; ep.amax_b = wamax(l); ep.amax_out = amax + l * WIRE_AMAX_SLOTS;
-      // pre-split activations: out_{l-1} read as such, out_l written as such (its maximum slots stay zero: not read)
-      const float s_in = out_split_scale(p, n, l - 1), s_out = ep.o1 ? out_split_scale(p, n, l) : 0.f;
-      if (s_in != 0.f) ep.a_split_inv = 1.f / s_in;
-      if (s_out != 0.f) { ep.o1_split = s_out; ep.amax_out = nullptr; }
-      HIPCHK(launch_gemmx2h_nt(s, epi_fwd(p.kind), out_l(l - 1), p.P, packed + p.off_fwd_x2[l], n, p.Pl, p.P, ep));
-    } else if (p.m3)
-      HIPCHK(launch_gemm3m_nt(s, EPI_GABOR_FWD, out_l(l - 1), p.P, packed + p.off_fwd_3m[l], p.P, n, p.Kp,
-                              p.Kp, ep));
-    else if (p.x3)
-      HIPCHK(launch_gemmx3_nt(s, epi_fwd(p.kind), out_l(l - 1), p.P, packed + p.off_fwd_x3[l], n, p.Pl,
-                              p.P, ep));
-    else
-      HIPCHK(launch_gemm_nt(s, epi_fwd(p.kind), out_l(l - 1), p.P, packed + p.off_fwd[l], p.P, n,
-                            p.Pl, p.P, ep));
+    HIPCHK(layer_nt(s, p, r.fam, packed, l, false, epi_fwd(p.kind), out_l(l - 1), n, ep, amax + (l - 1) * WIRE_AMAX_SLOTS,
+                    wamax_of(p, packed, l), s_out != 0.f ? nullptr : amax + l * WIRE_AMAX_SLOTS));
   }
-  if (do_final) {
+  if (!r.fuse) {
     ProfScope ps(s, 3, 0);
     HIPCHK(launch_final_fwd(s, out_l(p.L), n, p.P, p.O, packed + p.off_wf, packed + p.off_bf, y));
   }
@@ -702,191 +723,158 @@ extern "C" int wire_mlp_fwd(void* stream, const wire_net_desc* d, const float* p
                             const float* coords, int64_t n, float* y, void* act, int64_t act_bytes,
                             int save_for_bwd) {
   Plan p; if (int rc = make_plan(d, p)) return rc;
-  return mlp_fwd_core(stream, p, packed, coords, n, y, act, act_bytes, save_for_bwd, true);
+  return mlp_fwd_core(stream, p, make_route(p, n, save_for_bwd ? MODE_AUTOGRAD : MODE_INFER), packed, coords, n, y, act,
+                      act_bytes);
 }
 
 // ---------------------------------------------------------------------------
-// whole-network backward
+// whole-network backward, in stages that share one context
 // ---------------------------------------------------------------------------
-// do_final = false: the caller (wire_train_fwd_bwd) has already run the fused final stage, i.e.
-// g_lin of layer L is in the scratch's first gradient buffer and the final-layer partials are there.
-static int mlp_bwd_core(void* stream, const Plan& p, const float* packed, const float* coords, int64_t n,
-                        const float* g_y, const void* act, int64_t act_bytes, void* scratch,
-                        int64_t scratch_bytes, void* const* grads, bool do_final,
-                        wire_grad_ready_fn ready = nullptr, void* user = nullptr, int final_blocks = 0,
-                        float* g_coords = nullptr) {
-  // grads == null (wire_mlp_bwd_coords only): the data gradients and g_coords alone -- no weight-gradient GEMM, no reduction
-  const bool want_grads = grads != nullptr;
-  if (n <= 0) return fail(WIRE_ERR_ARG, "backward needs n > 0");
-  if (!packed || !coords || (do_final && !g_y) || !act || !scratch || (!grads && !g_coords))
-    return fail(WIRE_ERR_ARG, "null pointer");
-  if (want_grads) for (int i = 0; i < p.ntens; ++i) if (!grads[i]) return fail(WIRE_ERR_ARG, "grads[%d] is null", i);
-  const ActLayout a = act_layout(p, n, 1);
-  const ScratchLayout sc = scratch_layout(p, n);
-  const CoordLayout cl = coord_layout(p, n);
-  const int64_t need = g_coords ? cl.total : sc.total;
-  if (act_bytes < a.total * 4) return fail(WIRE_ERR_SIZE, "act buffer too small");
-  if (scratch_bytes < need * 4) return fail(WIRE_ERR_SIZE, "scratch %lld < %lld bytes",
-                                            (long long)scratch_bytes, (long long)need * 4);
-  hipStream_t s = (hipStream_t)stream;
-  const float* A = (const float*)act;
-  float* Sx = (float*)scratch;
-  auto out_l = [&](int l) { return A + a.out0 + (int64_t)l * a.np * p.P; };
-  auto lin_l = [&](int l) { return l == 0 ? A + a.lin0 : A + a.lin1 + (int64_t)(l - 1) * a.np * p.Pl; };
-  float* gcur = Sx + sc.ga;
-  float* gnext = Sx + sc.gb;
-  const bool x2 = use_x2(p, n);
-  unsigned* const gamax = reinterpret_cast<unsigned*>(Sx + sc.gamax);          // slots of g_lin_l at gamax + 64 l
-  const unsigned* const amax = reinterpret_cast<const unsigned*>(A + a.amax);  // slots of out_l, filled by the forward
-  auto wamax = [&](int l) { return reinterpret_cast<const unsigned*>(packed + p.off_wamax + (int64_t)l * WIRE_AMAX_SLOTS); };
-  // (the fused path zeroed the slots before its final stage published max |g_lin_L|)
-  if (x2 && do_final) HIPCHK(hipMemsetAsync(gamax, 0, (size_t)(p.L + 2) * WIRE_AMAX_SLOTS * sizeof(unsigned), s));
-  const bool first_sums = want_grads && p.k_first_sums && p.cplx && p.x3 && p.L >= 1 &&
-                          gemmx3_nt_is_h16(p.kind == WIRE_KIND_WIRE ? EPI_GABOR_BWD_FIRST : EPI_GABOR2D_BWD_FIRST, n);
-  const int64_t crp_set = (int64_t)(colreduce_blocks(n) + 32) * p.ldu * 5;   // wire2d: second set of partial sums
-  // the same for siren / gauss / relu with a native first layer: the epilogue of the layer-1 data gradient sums g_lin_0 [x | 1]
-  const bool first_sums_real = want_grads && p.k_first_sums && !p.cplx && !p.first_gemm && p.x3 && p.L >= 1 &&
-                               gemmx3_nt_is_h16(epi_bwd(p.kind), n);
-  // the coordinate gradient: the layer-1 data-gradient epilogue of the 16 x 16 x 32 kernels forms its per-row partials
-  // (ep.cg_partial); the other paths store g_lin_0 / g_u / g_p, which coordgrad_rows (or, positional encoding, the fp32
-  // GEMM with the first layer's data-gradient image + posenc_bwd) contracts below
-  const int epi1 = p.cplx ? (p.kind == WIRE_KIND_WIRE ? EPI_GABOR_BWD_FIRST : EPI_GABOR2D_BWD_FIRST) : epi_bwd(p.kind);
-  const bool cg_epi = g_coords && !p.first_gemm && p.L >= 1 && p.x3 && gemmx3_nt_is_h16(epi1, n);
+namespace {
+struct Bwd {
+  const Plan& p; const Route& r; hipStream_t s;
+  const float* packed; const float* coords; int64_t n;
+  const float* g_y;            // null when the training call ran the final stage (r.fuse)
+  void* const* grads;          // null (wire_mlp_bwd_coords only): the data gradients and g_coords alone -- no
+                               // weight-gradient GEMM, no reduction
+  float* g_coords; wire_grad_ready_fn ready; void* user;
+  ActLayout a; ScratchLayout sc; CoordLayout cl;
+  const float* A; float* Sx;
+  float* gcur = nullptr; float* gnext = nullptr;   // g_lin of the current layer and of the one below
+  int chain_rows = 0;                              // rows of the chain's workgroups (its first-layer sums)
 
-  // ---- final linear + activation gradient of layer L
-  // (final_blocks: the training forward formed the final layer's partial sums itself, one block per workgroup)
-  const int nbf = final_blocks > 0 ? final_blocks : final_bwd_blocks(n);
-  if (!do_final) {
-    ProfScope ps(s, 3, 0);
-    HIPCHK(launch_final_reduce(s, p.kind, Sx + sc.fpw, Sx + sc.fpb, nbf, p.O, p.K, p.P,
-                               (float*)grads[p.ntens - 2], (float*)grads[p.ntens - 1]));
-    if (ready) ready(user, p.ntens - 2, 2);
-  } else {
-    ProfScope ps(s, 3, 0);
+  const float* out_l(int l) const { return A + a.out0 + (int64_t)l * a.np * p.P; }
+  const float* lin_l(int l) const { return l == 0 ? A + a.lin0 : A + a.lin1 + (int64_t)(l - 1) * a.np * p.Pl; }
+  const float* first(int q) const { return packed + first_native_off(p, q); }
+  unsigned* gslots(int l) const { return reinterpret_cast<unsigned*>(Sx + sc.gamax) + l * WIRE_AMAX_SLOTS; }   // g_lin_l
+  const unsigned* oslots(int l) const { return reinterpret_cast<const unsigned*>(A + a.amax) + l * WIRE_AMAX_SLOTS; }
+  float* grad(int t) const { return grads ? (float*)grads[t] : nullptr; }
+  void done(int t, int count) const { if (ready) ready(user, t, count); }
+  int64_t crp_set() const { return (int64_t)(colreduce_blocks(n) + 32) * p.ldu * 5; }   // wire2d: the second set of sums
+  // the stages, in launch order
+  int final_stage();
+  int first_point();
+  int chain();
+  int wgrad_batch();
+  int layers();
+  int coords_grad();
+  int first_params();
+  hipError_t hidden_tn(int l);
+};
+
+// 1. final linear + activation gradient of layer L.  r.fuse: the training call ran it already -- g_lin_L and the final
+// layer's partial sums are in the scratch (one block per 128-row workgroup when the fused training forward formed them)
+int Bwd::final_stage() {
+  ProfScope ps(s, 3, 0);
+  if (!r.fuse) {
     const float wL = (p.L == 0) ? p.w1 : p.w;
-    if (p.L == 0 && p.cplx) {
-      // no hidden layer: g_out0 is needed raw; handled below through the raw path
-      HIPCHK(launch_final_bwd(s, p.kind, 1, g_y, n, p.O, packed + p.off_wf, nullptr, out_l(0), p.K,
-                              p.P, wL, p.s, gcur, Sx + sc.fpw, Sx + sc.fpb));
-    } else {
-      HIPCHK(launch_final_bwd(s, p.kind, 0, g_y, n, p.O, packed + p.off_wf, lin_l(p.L), out_l(p.L),
-                              p.K, p.P, wL, p.s, gcur, Sx + sc.fpw, Sx + sc.fpb,
-                              x2 ? gamax + p.L * WIRE_AMAX_SLOTS : nullptr));
-    }
-    if (want_grads) {
-      HIPCHK(launch_final_reduce(s, p.kind, Sx + sc.fpw, Sx + sc.fpb, nbf, p.O, p.K, p.P,
-                                 (float*)grads[p.ntens - 2], (float*)grads[p.ntens - 1]));
-      if (ready) ready(user, p.ntens - 2, 2);
-    }
-  }
-  if (p.L == 0 && p.cplx) {
-    // no hidden layer (net = first Gabor layer + final linear): gcur holds the raw g_out0; the first layer's
-    // activation gradient is an elementwise pass (u recomputed from the coordinates), then the column sums below
-    ProfScope ps(s, 3, 0);
-    const float* W0 = packed + first_native_off(p, 0);
-    const float* b0 = packed + first_native_off(p, 1);
-    if (p.kind == WIRE_KIND_WIRE)
-      HIPCHK(launch_gabor_bwd_first_point(s, gcur, out_l(0), coords, p.D, W0, b0, n, p.K, p.P, p.w1, p.s,
-                                          Sx + sc.gu, p.ldu));
+    if (p.L == 0 && p.cplx)   // no hidden layer: g_out0 is needed raw (stage 2)
+      HIPCHK(launch_final_bwd(s, p.kind, 1, g_y, n, p.O, packed + p.off_wf, nullptr, out_l(0), p.K, p.P, wL, p.s, gcur,
+                              Sx + sc.fpw, Sx + sc.fpb));
     else
-      HIPCHK(launch_gabor2d_bwd_first_point(s, gcur, out_l(0), coords, p.D, W0, b0, packed + first_native_off(p, 2),
-                                            packed + first_native_off(p, 3), n, p.K, p.P, p.w1, p.s, Sx + sc.gu,
-                                            p.ldu));
+      HIPCHK(launch_final_bwd(s, p.kind, 0, g_y, n, p.O, packed + p.off_wf, lin_l(p.L), out_l(p.L), p.K, p.P, wL, p.s,
+                              gcur, Sx + sc.fpw, Sx + sc.fpb, r.fam == FAM_X2 ? gslots(p.L) : nullptr));
+    if (!grads) return WIRE_OK;
   }
+  const int nbf = r.fused_final ? (int)((n + 127) / 128) : final_bwd_blocks(n);
+  HIPCHK(launch_final_reduce(s, p.kind, Sx + sc.fpw, Sx + sc.fpb, nbf, p.O, p.K, p.P, grad(p.ntens - 2),
+                             grad(p.ntens - 1)));
+  done(p.ntens - 2, 2);
+  return WIRE_OK;
+}
 
-  // ---- the data gradients of layers L .. 1 as one chain (wire_fused.hip): every g_lin_l (l >= 1) lands in its own buffer,
-  // the weight-gradient GEMMs below read them; the last link forms the first layer's sums g_lin_0^T [x | 1] per workgroup
-  // (positional encoding: stores g_lin_0 for the first layer's weight-gradient GEMM)
-  const bool chain = !do_final && fused_bwd_applies(p, n);
-  int chain_rows = 0;
-  if (chain) {
-    FusedBwdParams bp;
-    bp.n = n;
-    bp.g = Sx + sc.gch; bp.g_stride = sc.gch_stride;
-    bp.gamax = gamax;
-    bp.aux = p.kind == WIRE_KIND_RELU ? A + a.out0 : A + a.lin1 - a.np * p.Pl;   // lin_l at lin1 + (l - 1) * np * Pl
-    bp.aux_stride = p.kind == WIRE_KIND_RELU ? a.np * p.P : a.np * p.Pl;
-    bp.wimg = reinterpret_cast<const unsigned char*>(packed + p.off_fxd);
-    bp.wamax = reinterpret_cast<const unsigned*>(packed + p.off_wamax) + WIRE_AMAX_SLOTS; bp.wamax_stride = WIRE_AMAX_SLOTS;
-    bp.L = p.L; bp.w = p.w; bp.s = p.s;
-    bp.rstore = fused_rstore(p, n) ? 1 : 0; bp.c_hidden = fused_pre_scale(p.kind, p.w, p.s);
-    bp.aux0 = p.kind == WIRE_KIND_RELU ? A + a.out0 : A + a.lin0;
-    bp.w1 = p.w1;
-    if (!p.first_gemm) { bp.coords = coords; bp.D = p.D; bp.crp = Sx + sc.crp; bp.C = p.K; }
-    ProfScope ps(s, 1, 2.0 * n * p.Pl * p.P * p.L);
-    HIPCHK(launch_fused_bwd(s, p.kind, p.P, bp, &chain_rows));
+// 2. no hidden layer (net = first Gabor layer + final linear): gcur holds the raw g_out0; the first layer's activation
+// gradient is an elementwise pass (u recomputed from the coordinates), its column sums follow in stage 7
+int Bwd::first_point() {
+  ProfScope ps(s, 3, 0);
+  if (p.kind == WIRE_KIND_WIRE)
+    HIPCHK(launch_gabor_bwd_first_point(s, gcur, out_l(0), coords, p.D, first(0), first(1), n, p.K, p.P, p.w1, p.s,
+                                        Sx + sc.gu, p.ldu));
+  else
+    HIPCHK(launch_gabor2d_bwd_first_point(s, gcur, out_l(0), coords, p.D, first(0), first(1), first(2), first(3), n, p.K,
+                                          p.P, p.w1, p.s, Sx + sc.gu, p.ldu));
+  return WIRE_OK;
+}
+
+// 3. the data gradients of layers L .. 1 as one chain (wire_fused.hip): every g_lin_l (l >= 1) lands in its own buffer,
+// the weight-gradient GEMMs read them; the last link forms the first layer's sums g_lin_0^T [x | 1] per workgroup
+// (positional encoding: stores g_lin_0 for the first layer's weight-gradient GEMM)
+int Bwd::chain() {
+  const bool relu = p.kind == WIRE_KIND_RELU;
+  FusedBwdParams bp;
+  bp.n = n;
+  bp.g = Sx + sc.gch; bp.g_stride = sc.gch_stride;
+  bp.gamax = gslots(0);
+  bp.aux = relu ? A + a.out0 : A + a.lin1 - a.np * p.Pl;   // lin_l at lin1 + (l - 1) * np * Pl
+  bp.aux_stride = relu ? a.np * p.P : a.np * p.Pl;
+  bp.wimg = reinterpret_cast<const unsigned char*>(packed + p.off_fxd);
+  bp.wamax = wamax_of(p, packed, 1); bp.wamax_stride = WIRE_AMAX_SLOTS;
+  bp.L = p.L; bp.w = p.w; bp.s = p.s;
+  bp.rstore = r.rstore ? 1 : 0; bp.c_hidden = fused_pre_scale(p.kind, p.w, p.s);
+  bp.aux0 = relu ? A + a.out0 : A + a.lin0;
+  bp.w1 = p.w1;
+  if (!p.first_gemm) { bp.coords = coords; bp.D = p.D; bp.crp = Sx + sc.crp; bp.C = p.K; }
+  ProfScope ps(s, 1, 2.0 * n * p.Pl * p.P * p.L);
+  HIPCHK(launch_fused_bwd(s, p.kind, p.P, bp, &chain_rows));
+  return WIRE_OK;
+}
+
+// 4. the weight-gradient batch of layers wb_l0 .. L (make_route), behind the chain
+int Bwd::wgrad_batch() {
+  const int l0 = r.wb_l0, nb = r.wb_n;
+  const bool rs = r.rstore;
+  const float s_z = rs ? 0.f : r.out_scale[l0 - 1];
+  ProfScope ps(s, 2, 2.0 * n * p.Pl * p.P * nb);
+  HIPCHK(launch_gemmx2_tn(s, Sx + sc.gch + l0 * sc.gch_stride, p.Pl, rs ? lin_l(l0 - 1) : out_l(l0 - 1), rs ? p.Pl : p.P,
+                          n, p.Pl, p.P, r.wb_S, Sx + sc.slab, Sx + sc.bslab, gslots(l0), oslots(l0 - 1),
+                          rs ? 1.f / 16384.f : (s_z != 0.f ? 1.f / s_z : 0.f), rs ? (p.kind == WIRE_KIND_SIREN ? 2 : 3) : 0,
+                          nb, sc.gch_stride, rs ? a.np * p.Pl : a.np * p.P, WIRE_AMAX_SLOTS));
+  return WIRE_OK;
+}
+
+// the weight-gradient GEMM of hidden layer l on the route's family: slabs of g_lin_l^T [out_{l-1} | 1]
+hipError_t Bwd::hidden_tn(int l) {
+  const int S = r.tn_S;
+  float* slab = Sx + sc.slab;
+  float* bslab = Sx + sc.bslab;
+  switch (r.tn_fam) {
+    case FAM_3M: return launch_gemm3m_tn(s, gcur, p.P, out_l(l - 1), p.P, n, p.Kp, p.Kp, S, slab, bslab);
+    case FAM_X2:
+      if (r.rstore)   // Z = act(r_{l-1}) evaluated by the loader from the stored pre-activation (no out_{l-1}), scale 2^14
+        return launch_gemmx2_tn(s, gcur, p.Pl, lin_l(l - 1), p.Pl, n, p.Pl, p.P, S, slab, bslab, gslots(l), nullptr,
+                                1.f / 16384.f, p.kind == WIRE_KIND_SIREN ? 2 : 3);
+      return launch_gemmx2_tn(s, gcur, p.Pl, out_l(l - 1), p.P, n, p.Pl, p.P, S, slab, bslab, gslots(l), oslots(l - 1),
+                              r.out_scale[l - 1] != 0.f ? 1.f / r.out_scale[l - 1] : 0.f);
+    case FAM_X3: return launch_gemmx3_tn(s, gcur, p.Pl, out_l(l - 1), p.P, n, p.Pl, p.P, S, slab, bslab);
+    default: return launch_gemm_tn(s, gcur, p.Pl, out_l(l - 1), p.P, n, p.Pl, p.P, S, slab, bslab);
   }
-  // ---- behind the chain every g_lin_l exists before the first weight gradient starts: those of layers 2 .. L (same shape,
-  // operands a fixed step apart) run as ONE launch, each member accumulating L - 1 times the rows into a third of the slabs
-  // (layer 1 joins when its activation operand has the form of the others': r_0 of the sine / Gaussian nets, relu's fp32 out_0)
-  int wbatch = 0, wbatch_S = 0, wbatch_l0 = 2;
-  if (chain && p.k_wgrad_batch && x2 && gemmx2_tn_applies(p.Pl, p.P)) {
-    const bool rs = fused_rstore(p, n);
-    const int l0 = (rs || p.kind == WIRE_KIND_RELU) ? 1 : 2;
-    const int nb = p.L - l0 + 1;
-    const int S = nb >= 2 ? gemmx2_tn_batch_splits(n, p.Pl, p.P, sc.S, nb) : 0;
-    if (S >= 1 && (int64_t)S * nb <= sc.S) {
-      const float s_z = rs ? 0.f : out_split_scale(p, n, l0);
-      ProfScope ps(s, 2, 2.0 * n * p.Pl * p.P * nb);
-      HIPCHK(launch_gemmx2_tn(s, Sx + sc.gch + l0 * sc.gch_stride, p.Pl, rs ? lin_l(l0 - 1) : out_l(l0 - 1), rs ? p.Pl : p.P, n,
-                              p.Pl, p.P, S, Sx + sc.slab, Sx + sc.bslab, gamax + l0 * WIRE_AMAX_SLOTS,
-                              amax + (l0 - 1) * WIRE_AMAX_SLOTS, rs ? 1.f / 16384.f : (s_z != 0.f ? 1.f / s_z : 0.f),
-                              rs ? (p.kind == WIRE_KIND_SIREN ? 2 : 3) : 0, nb, sc.gch_stride,
-                              rs ? a.np * p.Pl : a.np * p.P, WIRE_AMAX_SLOTS));
-      wbatch = nb; wbatch_S = S; wbatch_l0 = l0;
-    }
-  }
-  // ---- hidden layers L..1
+}
+
+// 5. hidden layers L .. 1: the layer's weight gradient, then its data gradient (behind the chain: already there)
+int Bwd::layers() {
+  const int pl = p.per_layer;
   for (int l = p.L; l >= 1; --l) {
-    if (chain) gcur = Sx + sc.gch + (int64_t)l * sc.gch_stride;
-    float* gW = want_grads ? (float*)grads[p.per_layer * l] : nullptr;
-    float* gb = want_grads ? (float*)grads[p.per_layer * l + 1] : nullptr;
-    float* gV = want_grads && p.per_layer == 4 ? (float*)grads[p.per_layer * l + 2] : nullptr;
-    float* gc = want_grads && p.per_layer == 4 ? (float*)grads[p.per_layer * l + 3] : nullptr;
-    if (!want_grads) {
-      // data gradients only: no weight gradient of this layer
-    } else if (p.m3) {
-      const int S = sc.S;
-      { ProfScope ps(s, 2, 2.0 * n * p.Pl * p.P);
-        HIPCHK(launch_gemm3m_tn(s, gcur, p.P, out_l(l - 1), p.P, n, p.Kp, p.Kp, S, Sx + sc.slab,
-                                Sx + sc.bslab)); }
+    if (r.chain) gcur = Sx + sc.gch + (int64_t)l * sc.gch_stride;
+    if (grads) {
+      const bool own = l < r.wb_l0;                         // else the batch wrote this layer's slabs: member l - wb_l0
+      if (own) {
+        ProfScope ps(s, 2, 2.0 * n * p.Pl * p.P);
+        HIPCHK(hidden_tn(l));
+      }
+      const int S = own ? r.tn_S : r.wb_S;
+      const int64_t m = own ? 0 : l - r.wb_l0;
+      float* const slab = Sx + sc.slab + m * S * p.Pl * p.P;
+      float* const bslab = Sx + sc.bslab + m * S * p.Pl;
+      auto g = [&](int q) { return q < pl ? grad(pl * l + q) : nullptr; };   // W, b [, V, c] of layer l
       ProfScope ps(s, 3, 0);
-      HIPCHK(launch_wgrad3m_reduce(s, Sx + sc.slab, Sx + sc.bslab, S, p.K, p.K, p.Kp, p.Kp, gW, gb));
-      if (ready) ready(user, p.per_layer * l, p.per_layer);
-    } else if (wbatch > 0 && l >= wbatch_l0) {
-      // the batch above wrote this layer's slabs: member l - l0
-      ProfScope ps(s, 3, 0);
-      HIPCHK(launch_wgrad_reduce(s, p.kind, Sx + sc.slab + (int64_t)(l - wbatch_l0) * wbatch_S * p.Pl * p.P,
-                                 Sx + sc.bslab + (int64_t)(l - wbatch_l0) * wbatch_S * p.Pl, wbatch_S, p.K, p.K, p.Pl, p.P, gW, gb,
-                                 gV, gc));
-      if (ready) ready(user, p.per_layer * l, p.per_layer);
-    } else {
-      const bool x2tn = x2 && gemmx2_tn_applies(p.Pl, p.P);
-      const int S = x2tn ? gemmx2_tn_splits(n, p.Pl, p.P, sc.S)
-                         : (p.x3 ? gemmx3_tn_splits(n, p.Pl, p.P, sc.S) : gemm_tn_splits(n, p.Pl, p.P, sc.S));
-      { ProfScope ps(s, 2, 2.0 * n * p.Pl * p.P);
-        if (x2tn && chain && fused_rstore(p, n)) {
-          // Z = act(r_{l-1}) evaluated by the loader from the stored pre-activation (no out_{l-1} exists), scale 2^14
-          HIPCHK(launch_gemmx2_tn(s, gcur, p.Pl, lin_l(l - 1), p.Pl, n, p.Pl, p.P, S, Sx + sc.slab, Sx + sc.bslab,
-                                  gamax + l * WIRE_AMAX_SLOTS, nullptr, 1.f / 16384.f,
-                                  p.kind == WIRE_KIND_SIREN ? 2 : 3));
-        } else if (x2tn) {
-          const float s_z = out_split_scale(p, n, l - 1);
-          HIPCHK(launch_gemmx2_tn(s, gcur, p.Pl, out_l(l - 1), p.P, n, p.Pl, p.P, S, Sx + sc.slab, Sx + sc.bslab,
-                                  gamax + l * WIRE_AMAX_SLOTS, amax + (l - 1) * WIRE_AMAX_SLOTS,
-                                  s_z != 0.f ? 1.f / s_z : 0.f));
-        }
-        else if (p.x3)
-          HIPCHK(launch_gemmx3_tn(s, gcur, p.Pl, out_l(l - 1), p.P, n, p.Pl, p.P, S, Sx + sc.slab,
-                                  Sx + sc.bslab));
-        else
-          HIPCHK(launch_gemm_tn(s, gcur, p.Pl, out_l(l - 1), p.P, n, p.Pl, p.P, S, Sx + sc.slab,
-                                Sx + sc.bslab)); }
-      ProfScope ps(s, 3, 0);
-      HIPCHK(launch_wgrad_reduce(s, p.kind, Sx + sc.slab, Sx + sc.bslab, S, p.K, p.K, p.Pl, p.P, gW,
-                                 gb, gV, gc));
-      if (ready) ready(user, p.per_layer * l, p.per_layer);
+      if (r.tn_fam == FAM_3M)
+        HIPCHK(launch_wgrad3m_reduce(s, slab, bslab, S, p.K, p.K, p.Kp, p.Kp, g(0), g(1)));
+      else
+        HIPCHK(launch_wgrad_reduce(s, p.kind, slab, bslab, S, p.K, p.K, p.Pl, p.P, g(0), g(1), g(2), g(3)));
+      done(pl * l, pl);
     }
+    if (r.chain) continue;                                  // g_lin_{l-1} (l = 1: the first layer's sums) is already there
+    const bool first_sums = grads && r.first_sums;
     GemmEpiParams ep;
     ep.scale = p.s; ep.kvalid = p.K; ep.ld1 = p.P; ep.i1 = out_l(l - 1);
     int epi;
@@ -894,104 +882,119 @@ static int mlp_bwd_core(void* stream, const Plan& p, const float* packed, const 
       epi = epi_bwd(p.kind);
       ep.omega = (l - 1 == 0) ? p.w1 : p.w;
       ep.i0 = lin_l(l - 1); ep.o0 = gnext; ep.ld0 = p.Pl;
-      // hidden Gabor layer whose forward ran the lean 16 x 16 x 32 epilogue: out = act(lin) again, 8 B / element less
-      // (real nets: only below a hidden layer -- the first layer's out comes from first_fwd_kernel's precise form)
-      ep.recompute_out = p.k_recompute_out && p.x3 && (p.cplx || l - 1 >= 1) && gemmx3_nt_is_h16(epi_fwd(p.kind), n);
-      if (l == 1 && first_sums_real) { ep.coords = coords; ep.D = p.D; ep.cr_partial = Sx + sc.crp; ep.cr_C = p.K; }
+      ep.recompute_out = r.recompute_out && l >= 2;
+      // (real nets: the layer-1 epilogue sums g_lin_0 [x | 1] itself)
+      if (l == 1 && first_sums) { ep.coords = coords; ep.D = p.D; ep.cr_partial = Sx + sc.crp; ep.cr_C = p.K; }
     } else {
       epi = (p.kind == WIRE_KIND_WIRE) ? EPI_GABOR_BWD_FIRST : EPI_GABOR2D_BWD_FIRST;
       ep.omega = p.w1;
       ep.coords = coords; ep.D = p.D; ep.ldu = p.ldu; ep.o0 = Sx + sc.gu;
-      // wire on the 16 x 16 x 32 kernel: its epilogue sums g_u [x | 1] per 256-row tile itself (the first layer's weight
-      // and bias gradient partials) instead of storing g_u for a separate pass
-      if (first_sums) { ep.cr_partial = Sx + sc.crp; ep.cr_C = p.K; ep.cr_set = crp_set; }
-      // (and re-evaluates out_0 from the u it recomputes anyway: first_fwd_kernel's own form, the same bits)
-      ep.recompute_out = p.k_recompute_out && p.x3 && p.kind == WIRE_KIND_WIRE && gemmx3_nt_is_h16(EPI_GABOR_BWD_FIRST, n);
-      ep.W0 = packed + first_native_off(p, 0); ep.b0 = packed + first_native_off(p, 1);
-      if (p.per_layer == 4) { ep.W0b = packed + first_native_off(p, 2); ep.b0b = packed + first_native_off(p, 3); }
+      // (wire, wire2d: g_u [x | 1] per 256-row tile instead of storing g_u for a separate pass)
+      if (first_sums) { ep.cr_partial = Sx + sc.crp; ep.cr_C = p.K; ep.cr_set = crp_set(); }
+      ep.recompute_out = r.recompute_out0;
+      ep.W0 = first(0); ep.b0 = first(1);
+      if (pl == 4) { ep.W0b = first(2); ep.b0b = first(3); }
     }
     if (!p.cplx && l == 1) ep.ld0 = p.P;
-    if (l == 1 && cg_epi) {
+    if (l == 1 && g_coords && r.cg_epi) {
       ep.cg_partial = Sx + cl.cgp; ep.D = p.D;
-      if (!p.cplx) ep.W0 = packed + first_native_off(p, 0);
+      if (!p.cplx) ep.W0 = first(0);
     }
-    if (chain) continue;                                    // g_lin_{l-1} (l = 1: the first layer's sums) is already there
-    { ProfScope ps(s, 1, 2.0 * n * p.Pl * p.P);
-      if (x2) {
-        ep.amax_a = gamax + l * WIRE_AMAX_SLOTS; ep.amax_b = wamax(l);
-        ep.amax_out = l >= 2 ? gamax + (l - 1) * WIRE_AMAX_SLOTS : nullptr;   // g_lin_0 feeds no 2 x fp16 GEMM
-        HIPCHK(launch_gemmx2h_nt(s, epi, gcur, p.Pl, packed + p.off_dg_x2[l], n, p.P, p.Pl, ep));
-      } else if (p.m3)
-        HIPCHK(launch_gemm3m_nt(s, epi, gcur, p.P, packed + p.off_dg_3m[l], p.P, n, p.Kp, p.Kp, ep));
-      else if (p.x3)
-        HIPCHK(launch_gemmx3_nt(s, epi, gcur, p.Pl, packed + p.off_dg_x3[l], n, p.P, p.Pl, ep));
-      else
-        HIPCHK(launch_gemm_nt(s, epi, gcur, p.Pl, packed + p.off_dg[l], p.Pl, n, p.P, p.Pl, ep)); }
+    { ProfScope ps(s, 1, 2.0 * n * p.Pl * p.P);             // (g_lin_0 feeds no 2 x fp16 GEMM: no maximum kept)
+      HIPCHK(layer_nt(s, p, r.fam, packed, l, true, epi, gcur, n, ep, gslots(l), wamax_of(p, packed, l),
+                      l >= 2 ? gslots(l - 1) : nullptr)); }
     float* t = gcur; gcur = gnext; gnext = t;
   }
+  return WIRE_OK;
+}
 
-  // ---- first layer parameter gradients
-  ProfScope ps(s, 3, 0);
-  if (g_coords) {
-    const float* W0 = packed + first_native_off(p, 0);
-    if (cg_epi) {
-      HIPCHK(launch_coordgrad_reduce(s, Sx + cl.cgp, cl.ntiles, n, p.D, g_coords));
-    } else if (p.kind == WIRE_KIND_WIRE) {
-      HIPCHK(launch_coordgrad_rows(s, Sx + sc.gu, p.ldu, nullptr, W0, nullptr, p.K, p.D, n, g_coords));
-    } else if (p.kind == WIRE_KIND_WIRE2D) {
-      HIPCHK(launch_coordgrad_rows(s, Sx + sc.gu, 2 * p.ldu, Sx + sc.gu + p.ldu, W0, packed + first_native_off(p, 2), p.K,
-                                   p.D, n, g_coords));
-    } else if (!p.first_gemm) {
-      HIPCHK(launch_coordgrad_rows(s, p.L == 0 ? Sx + sc.ga : gcur, p.P, nullptr, W0, nullptr, p.K, p.D, n, g_coords));
-    } else {
-      // g_pe = g_lin_0 W0 on the fp32 MFMA (the first layer's data-gradient image, Pin0 x P), then the encoding's chain rule
-      GemmEpiParams ep;
-      ep.o0 = Sx + cl.gpe; ep.ld0 = p.Pin0;
-      HIPCHK(launch_gemm_nt(s, EPI_STORE, p.L == 0 ? Sx + sc.ga : gcur, p.P, packed + p.off_dg[0], p.P, n, p.Pin0, p.P, ep));
-      HIPCHK(launch_posenc_bwd(s, coords, n, p.D, p.F, Sx + cl.gpe, p.Pin0, g_coords));
-    }
+// 6. the coordinate gradient: the layer-1 data-gradient epilogue formed its per-row partials (cg_epi); the other paths
+// stored g_lin_0 / g_u / g_p, which coordgrad_rows (positional encoding: the fp32 GEMM with the first layer's
+// data-gradient image, then posenc_bwd) contracts
+int Bwd::coords_grad() {
+  if (!g_coords) return WIRE_OK;
+  const float* gu = Sx + sc.gu;
+  if (r.cg_epi) {
+    HIPCHK(launch_coordgrad_reduce(s, Sx + cl.cgp, cl.ntiles, n, p.D, g_coords));
+  } else if (p.kind == WIRE_KIND_WIRE) {
+    HIPCHK(launch_coordgrad_rows(s, gu, p.ldu, nullptr, first(0), nullptr, p.K, p.D, n, g_coords));
+  } else if (p.kind == WIRE_KIND_WIRE2D) {
+    HIPCHK(launch_coordgrad_rows(s, gu, 2 * p.ldu, gu + p.ldu, first(0), first(2), p.K, p.D, n, g_coords));
+  } else if (!p.first_gemm) {
+    HIPCHK(launch_coordgrad_rows(s, gcur, p.P, nullptr, first(0), nullptr, p.K, p.D, n, g_coords));
+  } else {
+    // g_pe = g_lin_0 W0 on the fp32 MFMA (the first layer's data-gradient image, Pin0 x P), then the encoding's chain rule
+    GemmEpiParams ep;
+    ep.o0 = Sx + cl.gpe; ep.ld0 = p.Pin0;
+    HIPCHK(layer_nt(s, p, FAM_4M, packed, 0, true, EPI_STORE, gcur, n, ep));
+    HIPCHK(launch_posenc_bwd(s, coords, n, p.D, p.F, Sx + cl.gpe, p.Pin0, g_coords));
   }
-  if (!want_grads) return WIRE_OK;
+  return WIRE_OK;
+}
+
+// 7. the first layer's parameter gradients
+int Bwd::first_params() {
+  if (!grads) return WIRE_OK;
+  float* const crp = Sx + sc.crp;
   if (p.cplx) {
     const float* gu = Sx + sc.gu;
-    if (p.kind == WIRE_KIND_WIRE && first_sums) {
-      HIPCHK(launch_colreduce_final(s, p.K, p.D, n, Sx + sc.crp, (float*)grads[0], (float*)grads[1]));
+    if (r.first_sums) {
+      HIPCHK(launch_colreduce_final(s, p.K, p.D, n, crp, grad(0), grad(1)));
+      if (p.kind == WIRE_KIND_WIRE2D) HIPCHK(launch_colreduce_final(s, p.K, p.D, n, crp + crp_set(), grad(2), grad(3)));
     } else if (p.kind == WIRE_KIND_WIRE) {
-      HIPCHK(launch_colreduce(s, gu, p.ldu, p.K, coords, p.D, n, Sx + sc.crp, (float*)grads[0],
-                              (float*)grads[1]));
-    } else if (first_sums) {
-      HIPCHK(launch_colreduce_final(s, p.K, p.D, n, Sx + sc.crp, (float*)grads[0], (float*)grads[1]));
-      HIPCHK(launch_colreduce_final(s, p.K, p.D, n, Sx + sc.crp + crp_set, (float*)grads[2], (float*)grads[3]));
+      HIPCHK(launch_colreduce(s, gu, p.ldu, p.K, coords, p.D, n, crp, grad(0), grad(1)));
     } else {
-      HIPCHK(launch_colreduce(s, gu, 2 * p.ldu, p.K, coords, p.D, n, Sx + sc.crp, (float*)grads[0],
-                              (float*)grads[1]));
-      HIPCHK(launch_colreduce(s, gu + p.ldu, 2 * p.ldu, p.K, coords, p.D, n, Sx + sc.crp,
-                              (float*)grads[2], (float*)grads[3]));
+      HIPCHK(launch_colreduce(s, gu, 2 * p.ldu, p.K, coords, p.D, n, crp, grad(0), grad(1)));
+      HIPCHK(launch_colreduce(s, gu + p.ldu, 2 * p.ldu, p.K, coords, p.D, n, crp, grad(2), grad(3)));
     }
-  } else if (!p.first_gemm && chain) {
-    HIPCHK(launch_colreduce_final_blocks(s, p.K, p.D, (int)((n + chain_rows - 1) / chain_rows), Sx + sc.crp, (float*)grads[0],
-                                         (float*)grads[1]));
-  } else if (!p.first_gemm && first_sums_real) {
-    HIPCHK(launch_colreduce_final(s, p.K, p.D, n, Sx + sc.crp, (float*)grads[0], (float*)grads[1]));
+  } else if (!p.first_gemm && r.chain) {
+    HIPCHK(launch_colreduce_final_blocks(s, p.K, p.D, (int)((n + chain_rows - 1) / chain_rows), crp, grad(0), grad(1)));
+  } else if (!p.first_gemm && r.first_sums) {
+    HIPCHK(launch_colreduce_final(s, p.K, p.D, n, crp, grad(0), grad(1)));
   } else if (!p.first_gemm) {
-    // gcur holds g_lin_0 [n][P]
-    const float* g0 = (p.L == 0) ? Sx + sc.ga : gcur;
-    HIPCHK(launch_colreduce(s, g0, p.P, p.K, coords, p.D, n, Sx + sc.crp, (float*)grads[0],
-                            (float*)grads[1]));
+    HIPCHK(launch_colreduce(s, gcur, p.P, p.K, coords, p.D, n, crp, grad(0), grad(1)));   // gcur: g_lin_0 [n][P]
   } else {
-    const float* g0 = (p.L == 0) ? Sx + sc.ga : (chain ? Sx + sc.gch : gcur);   // the chain stored g_lin_0 in its slot 0
-    const int S = p.x3 ? gemmx3_tn_splits(n, p.P, p.Pin0, sc.S) : gemm_tn_splits(n, p.P, p.Pin0, sc.S);
-    if (p.x3)
-      HIPCHK(launch_gemmx3_tn(s, g0, p.P, A + a.pe, p.Pin0, n, p.P, p.Pin0, S, Sx + sc.slab,
-                              Sx + sc.bslab));
-    else
-      HIPCHK(launch_gemm_tn(s, g0, p.P, A + a.pe, p.Pin0, n, p.P, p.Pin0, S, Sx + sc.slab,
-                            Sx + sc.bslab));
-    HIPCHK(launch_wgrad_reduce(s, p.kind, Sx + sc.slab, Sx + sc.bslab, S, p.K, p.Din, p.P, p.Pin0,
-                               (float*)grads[0], (float*)grads[1], nullptr, nullptr));
+    const float* g0 = r.chain ? Sx + sc.gch : gcur;         // the chain stored g_lin_0 in its slot 0
+    const bool x3 = r.fam0 == FAM_X3;
+    const int S = x3 ? gemmx3_tn_splits(n, p.P, p.Pin0, sc.S) : gemm_tn_splits(n, p.P, p.Pin0, sc.S);
+    HIPCHK(x3 ? launch_gemmx3_tn(s, g0, p.P, A + a.pe, p.Pin0, n, p.P, p.Pin0, S, Sx + sc.slab, Sx + sc.bslab)
+              : launch_gemm_tn(s, g0, p.P, A + a.pe, p.Pin0, n, p.P, p.Pin0, S, Sx + sc.slab, Sx + sc.bslab));
+    HIPCHK(launch_wgrad_reduce(s, p.kind, Sx + sc.slab, Sx + sc.bslab, S, p.K, p.Din, p.P, p.Pin0, grad(0), grad(1),
+                               nullptr, nullptr));
   }
-  if (ready) ready(user, 0, p.per_layer);
+  done(0, p.per_layer);
   return WIRE_OK;
+}
+}  // namespace
+
+static int mlp_bwd_core(void* stream, const Plan& p, const Route& r, const float* packed, const float* coords, int64_t n,
+                        const float* g_y, const void* act, int64_t act_bytes, void* scratch, int64_t scratch_bytes,
+                        void* const* grads, wire_grad_ready_fn ready = nullptr, void* user = nullptr,
+                        float* g_coords = nullptr) {
+  if (n <= 0) return fail(WIRE_ERR_ARG, "backward needs n > 0");
+  if (!packed || !coords || (!r.fuse && !g_y) || !act || !scratch || (!grads && !g_coords))
+    return fail(WIRE_ERR_ARG, "null pointer");
+  if (grads) for (int i = 0; i < p.ntens; ++i) if (!grads[i]) return fail(WIRE_ERR_ARG, "grads[%d] is null", i);
+  Bwd c{p, r, (hipStream_t)stream, packed, coords, n, g_y, grads, g_coords, ready, user, act_layout(p, n, 1),
+        scratch_layout(p, n), coord_layout(p, n), (const float*)act, (float*)scratch};
+  const int64_t need = g_coords ? c.cl.total : c.sc.total;
+  if (act_bytes < c.a.total * 4) return fail(WIRE_ERR_SIZE, "act buffer too small");
+  if (scratch_bytes < need * 4) return fail(WIRE_ERR_SIZE, "scratch %lld < %lld bytes",
+                                            (long long)scratch_bytes, (long long)need * 4);
+  c.gcur = c.Sx + c.sc.ga;
+  c.gnext = c.Sx + c.sc.gb;
+  // (the fused path zeroed the slots before its final stage published max |g_lin_L|)
+  if (r.fam == FAM_X2 && !r.fuse)
+    HIPCHK(hipMemsetAsync(c.gslots(0), 0, (size_t)(p.L + 2) * WIRE_AMAX_SLOTS * sizeof(unsigned), c.s));
+  int rc = c.final_stage();
+  if (!rc && p.L == 0 && p.cplx) rc = c.first_point();
+  if (!rc && r.chain) rc = c.chain();
+  if (!rc && r.wb_n > 0) rc = c.wgrad_batch();
+  if (!rc) rc = c.layers();
+  if (rc) return rc;
+  ProfScope ps(c.s, 3, 0);                                  // stages 6 and 7: one profiled span
+  rc = c.coords_grad();
+  return rc ? rc : c.first_params();
 }
 
 extern "C" int wire_mlp_bwd(void* stream, const wire_net_desc* d, const float* packed,
@@ -1000,7 +1003,8 @@ extern "C" int wire_mlp_bwd(void* stream, const wire_net_desc* d, const float* p
                             void* const* grads) {
   Plan p; if (int rc = make_plan(d, p)) return rc;
   if (!grads) return fail(WIRE_ERR_ARG, "null pointer");
-  return mlp_bwd_core(stream, p, packed, coords, n, g_y, act, act_bytes, scratch, scratch_bytes, grads, true);
+  return mlp_bwd_core(stream, p, make_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
+                      scratch_bytes, grads);
 }
 
 extern "C" int wire_mlp_bwd_coords(void* stream, const wire_net_desc* d, const float* packed, const float* coords,
@@ -1008,8 +1012,8 @@ extern "C" int wire_mlp_bwd_coords(void* stream, const wire_net_desc* d, const f
                                    int64_t scratch_bytes, void* const* grads_host, float* g_coords) {
   Plan p; if (int rc = make_plan(d, p)) return rc;
   if (!grads_host && !g_coords) return fail(WIRE_ERR_ARG, "wire_mlp_bwd_coords: neither grads_host nor g_coords");
-  return mlp_bwd_core(stream, p, packed, coords, n, g_y, act, act_bytes, scratch, scratch_bytes, grads_host, true,
-                      nullptr, nullptr, 0, g_coords);
+  return mlp_bwd_core(stream, p, make_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
+                      scratch_bytes, grads_host, nullptr, nullptr, g_coords);
 }
 
 // ---------------------------------------------------------------------------
@@ -1025,56 +1029,44 @@ extern "C" int wire_train_fwd_bwd_hooked(void* stream, const wire_net_desc* d, c
   if (n <= 0) return fail(WIRE_ERR_ARG, "wire_train_fwd_bwd needs n > 0");
   if (!target || !y || !g_y || !loss_out || !partial) return fail(WIRE_ERR_ARG, "null pointer");
   hipStream_t s = (hipStream_t)stream;
-  // every net kind with at least one hidden layer: final linear + loss + final backward + activation gradient of layer L
-  // in one pass (wire_point.hip: final_fused_kernel)
-  const bool fuse = p.L >= 1 && p.O <= 4 && final_fused_supported(p.P, p.O);
-  if (!fuse) {
-    if (int rc = mlp_fwd_core(stream, p, packed, coords, n, y, act, act_bytes, 1, true)) return rc;
+  const Route r = make_route(p, n, MODE_TRAIN);
+  if (!r.fuse) {
+    if (int rc = mlp_fwd_core(stream, p, r, packed, coords, n, y, act, act_bytes)) return rc;
     { ProfScope ps(s, 3, 0);
       HIPCHK(launch_mse_grad(s, y, target, idx, first, n, p.O, weight, g_y, loss_out, rec, partial)); }
-    return mlp_bwd_core(stream, p, packed, coords, n, g_y, act, act_bytes, scratch, scratch_bytes, grads, true, ready,
-                        user);
+    return mlp_bwd_core(stream, p, r, packed, coords, n, g_y, act, act_bytes, scratch, scratch_bytes, grads, ready, user);
   }
-  // with layer L on the 16 x 16 x 32 forward kernel (lean epilogue) the final stage evaluates out_L from lin_L itself,
-  // bit for bit what that epilogue would have stored: out_L is neither written nor read (1 GB less HBM traffic)
-  const bool recomp = p.k_recompute_out && p.x3 && p.kind != WIRE_KIND_RELU && gemmx3_nt_is_h16(epi_fwd(p.kind), n);
   const ActLayout a = act_layout(p, n, 1);
   const ScratchLayout sc = scratch_layout(p, n);
   if (!scratch || scratch_bytes < sc.total * 4) return fail(WIRE_ERR_SIZE, "scratch too small");
   const float* A = (const float*)act;
   float* Sx = (float*)scratch;
-  const bool x2 = use_x2(p, n);
   unsigned* const gamax = reinterpret_cast<unsigned*>(Sx + sc.gamax);
-  if (x2) HIPCHK(hipMemsetAsync(gamax, 0, (size_t)(p.L + 2) * WIRE_AMAX_SLOTS * sizeof(unsigned), s));
-  float* gL = fused_bwd_applies(p, n) ? Sx + sc.gch + (int64_t)p.L * sc.gch_stride : Sx + sc.ga;
-  // real nets on the whole-net training kernel: the final stage runs inside it (fx_tail_loss)
+  if (r.fam == FAM_X2) HIPCHK(hipMemsetAsync(gamax, 0, (size_t)(p.L + 2) * WIRE_AMAX_SLOTS * sizeof(unsigned), s));
+  float* gL = r.chain ? Sx + sc.gch + (int64_t)p.L * sc.gch_stride : Sx + sc.ga;
+  // the final stage inside the fused training forward (real nets, r.fused_final)
   FusedFwdParams lp;
   const int fblocks = (int)((n + 127) / 128);
   const double inv_no = 1.0 / ((double)n * (double)p.O);
   lp.target = target; lp.idx = idx; lp.first = first; lp.gscale = (float)(weight * 2.0 * inv_no);
   lp.y = y; lp.rec = rec; lp.g_lin = gL; lp.part_w = Sx + sc.fpw; lp.part_b = Sx + sc.fpb; lp.loss_partial = Sx + sc.crp;
   lp.amax_g = gamax + p.L * WIRE_AMAX_SLOTS;
-  bool loss_done = false;
-  if (int rc = mlp_fwd_core(stream, p, packed, coords, n, nullptr, act, act_bytes, 1, false, recomp,
-                            x2 && fused_bwd_applies(p, n) ? &lp : nullptr, &loss_done)) return rc;
-  if (loss_done) {
-    { ProfScope ps(s, 3, 0);
-      HIPCHK(launch_mse_final(s, Sx + sc.crp, fblocks, (float)(weight * inv_no), loss_out)); }
-    return mlp_bwd_core(stream, p, packed, coords, n, nullptr, act, act_bytes, scratch, scratch_bytes, grads, false, ready,
-                        user, fblocks);
-  }
-  {
-    // final linear forward + MSE (loss, rec) + final linear backward + Gabor gradient of layer L:
-    // one pass over out_L / lin_L instead of three
+  if (int rc = mlp_fwd_core(stream, p, r, packed, coords, n, nullptr, act, act_bytes, &lp)) return rc;
+  if (r.fused_final) {
+    ProfScope ps(s, 3, 0);
+    HIPCHK(launch_mse_final(s, Sx + sc.crp, fblocks, (float)(weight * inv_no), loss_out));
+  } else {
+    // final linear forward + MSE (loss, rec) + final linear backward + activation gradient of layer L: one pass over
+    // out_L / lin_L instead of three (r.skip_out_L: out_L evaluated from lin_L, bit for bit what the lean epilogue of
+    // the 16 x 16 x 32 forward kernel would have stored -- 1 GB less HBM traffic)
     ProfScope ps(s, 3, 0);
     const float* linL = p.kind == WIRE_KIND_RELU ? nullptr : A + a.lin1 + (int64_t)(p.L - 1) * a.np * p.Pl;
-    HIPCHK(launch_final_fused(s, p.kind, recomp ? nullptr : A + a.out0 + (int64_t)p.L * a.np * p.P, linL, n, p.P, p.O,
-                              p.K, packed + p.off_wf, packed + p.off_bf, target, idx, first, weight,
+    HIPCHK(launch_final_fused(s, p.kind, r.skip_out_L ? nullptr : A + a.out0 + (int64_t)p.L * a.np * p.P, linL, n, p.P,
+                              p.O, p.K, packed + p.off_wf, packed + p.off_bf, target, idx, first, weight,
                               p.w, p.s, y, rec, gL, Sx + sc.fpw, Sx + sc.fpb, Sx + sc.crp, loss_out,
-                              x2 ? gamax + p.L * WIRE_AMAX_SLOTS : nullptr));
+                              r.fam == FAM_X2 ? gamax + p.L * WIRE_AMAX_SLOTS : nullptr));
   }
-  return mlp_bwd_core(stream, p, packed, coords, n, nullptr, act, act_bytes, scratch, scratch_bytes, grads, false, ready,
-                      user);
+  return mlp_bwd_core(stream, p, r, packed, coords, n, nullptr, act, act_bytes, scratch, scratch_bytes, grads, ready, user);
 }
 extern "C" int wire_train_fwd_bwd(void* stream, const wire_net_desc* d, const float* packed,
                                   const float* coords, int64_t n, const float* target, const int64_t* idx,

@@ -5,6 +5,12 @@
 
 #include "wire_knobs.h"
 
+// GEMM family of a net's hidden layers: 4-multiplication fp32 MFMA, 3-multiplication complex fp32 MFMA (wire only), fp32
+// operands split into 3 x bf16 (wire_gemmx3*.hip) or 2 x fp16 (wire_gemmx2h.hip).  wire_api.hip picks one per whole-net
+// call; wire_family_ is what the knobs select for the per-layer entry points (wire_layer_api.hip: 3 x bf16 covers 2 x fp16)
+enum WireFamily { FAM_4M = 0, FAM_3M = 1, FAM_X3 = 2, FAM_X2 = 3 };
+WireFamily wire_family_(int kind);   // wire_api.hip
+
 // Epilogue selector of the NT GEMM  C[M][Nc] = A[M][Kd] * Bt[Nc][Kd]^T.
 enum WireEpi {
   EPI_STORE = 0,            // o0 = C

@@ -49,7 +49,7 @@ constexpr KnobDef kKnobs[] = {
     // ---- storage formats of the activations (make_plan snapshots these: a forward and its backward agree on them)
     // with split_f16: activations with an a-priori bound (Gabor, sine, Gaussian outputs) are stored ALREADY SPLIT into fp16
     // pairs by the epilogue that produces them (wire_dev.h: wire_store_out4), so the GEMMs that read them -- the next layer's
-    // forward, the weight gradient -- spend no vector instructions on the split (wire_api.hip: out_split_scale)
+    // forward, the weight gradient -- spend no vector instructions on the split (wire_api.hip: make_route, out_scale)
     flag_knob(K_SPLIT_OUT, "split_out", "WIRE_SPLIT_OUT", 1),
     // wire training step on the 16 x 16 x 32 kernels: backward passes evaluate out = act(lin) again instead of reading it
     // (the data-gradient epilogues and the fused final stage), and the last hidden layer does not store out at all
@@ -66,7 +66,7 @@ constexpr KnobDef kKnobs[] = {
     range_knob(K_FUSED_FWD, "fused_fwd", "WIRE_FUSED_FWD", 1, 0, 1),
     // 1 = training forwards of those nets run it too (storing lin_l / out_l); needs fused_fwd
     range_knob(K_FUSED_TRAIN, "fused_train", "WIRE_FUSED_TRAIN", 1, 0, 1),
-    // 1 = also for wire at P = 384 (K = 181), whose storing edition spills (wire_api.hip: fused_train_applies)
+    // 1 = also for wire at P = 384 (K = 181), whose storing edition spills (wire_api.hip: make_route)
     flag_knob(K_FUSED_TRAIN_P384, "fused_train_p384", "WIRE_FUSED_TRAIN_P384", 0),
     // 1 = wire_train_fwd_bwd of the real nets forms loss, dL/dy, g_lin_L and the final layer's gradient sums inside the
     // training forward (fx_tail_loss) instead of a pass over the stored lin_L / out_L.  Default 0: measured neutral to

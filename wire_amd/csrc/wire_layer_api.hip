@@ -14,12 +14,10 @@
 #include "wire_point.h"
 
 extern int wire_fail_(int code, const char* msg);   // wire_api.hip
-// GEMM family the tuning flags select (wire_api.hip): 2 = split-bf16 (wire_gemmx3.hip, every kind),
-// 1 = 3-multiplication complex fp32 MFMA (wire_gemm3m.hip, ComplexGaborLayer only), 0 = 4M fp32 MFMA.
+// GEMM family the tuning flags select (wire_family_, wire_gemm.h): FAM_X3 = split-bf16 (wire_gemmx3.hip, every kind),
+// FAM_3M = 3-multiplication complex fp32 MFMA (wire_gemm3m.hip, ComplexGaborLayer only), FAM_4M = 4M fp32 MFMA.
 // The per-layer entry points run the SAME kernels as wire_mlp_fwd / wire_mlp_bwd, so the per-layer parity
 // tests (protocol step (i)) check the code the bench times.
-extern int wire_family_(int kind);
-enum { FAM_4M = 0, FAM_3M = 1, FAM_X3 = 2 };
 #ifndef WIRE_AMAX_SLOTS
 #define WIRE_AMAX_SLOTS 64
 #endif
@@ -95,7 +93,7 @@ LayerWs layer_ws(int64_t n, int in, int out) {
 // One layer's GEMMs on the selected family.  All three take blocked rows (wire_dev.h) and leave the same
 // outputs; they differ in the weight image (pack_*) and in the slab format of the weight gradient.
 struct LayerGemm {
-  int fam;
+  WireFamily fam;
   float* x2ws;       // x2_region_floats(...) of the workspace, or null: never the 2 x fp16 kernels
   bool use_x2(int epi, int64_t n) const {
     return fam == FAM_X3 && x2ws && knob(K_SPLIT_F16) && gemmx3_nt_is_h16(epi, n);
