@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- coord-samples/sec, forward+backward(+Adam), 4x256 complex WIRE MLP.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 and no WORLD_SIZE in the environment: this process starts N fresh rank processes itself
 (``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...``) BEFORE it
@@ -20,7 +20,9 @@ on-device coordinates -> forward -> MSE -> backward -> all-reduce -> Adam.
 Synthetic data (U[0,1) target), reference init under torch.manual_seed(0), rank 0's
 parameters broadcast to every replica.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the JSON line; besides the
+headline (metric, value, unit, higher_is_better, dtype, ms_per_step) the line carries what the timed steps themselves
+measured:
   roofline     : dominant kernel class (the layer GEMMs) timed live with HIP
                  events on the launch stream (inside the timed region, on every
                  5th step: see prof_step); achieved = algorithmic flops (8
@@ -34,12 +36,15 @@ The JSON line also carries
                  (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs) of that kernel from profiles/pmc_traffic.json, which
                  tools/pmc_traffic.py writes from rocprofv3 --pmc passes (their own runs) together with the hash
                  of the library sources; null when this tree's sources differ.
+
+Everything else runs only with --full (after the timed steps and the dump; --no-cpu-baseline / --no-extras drop a leg):
+  config.rccl* : what RCCL itself reports about a job with an active gradient all-reduce (rccl_probe).
   cpu_baseline : the oracle's eager-PyTorch restatement of the reference's CPU
                  path (kind "port"), timed on this host's cores on a bounded
                  sample of the same workload.
   extras       : the exact-fp32 family on the same workload, the reference-API width, forward-only
                  inference, and BASELINE.json configs[3] / [4] (wire2d 1024^2; siren / gauss / relu /
-                 relu+posenc at 4x256) with bounded step counts.
+                 relu+posenc at 4x256) with bounded step counts; `secondary` is their flat copy.
 """
 import argparse
 import ctypes as C
@@ -506,9 +511,9 @@ def dump_outputs(tr, out_dir):
 def rccl_probe(dev, tr, timeout_s=45.0):
     """What RCCL ITSELF reports about the job: ncclCommCount / ncclCommCuDevice of a communicator
     built from librccl's C ABI (the trainer's own when WIRE_DP_DIRECT=1, else one made here with the symmetric set-up of
-    parallel.RcclDirect) and one all-reduce of ones on it, which must come back as the world size.  Runs on every rank
-    AFTER the timed region, in a thread with a deadline: a communicator that cannot be built must not cost the run its
-    number.  Returns a dict for config.rccl_*; "timeout" marks a probe that did not finish (the caller then leaves through
+    parallel.RcclDirect) and one all-reduce of ones on it, which must come back as the world size.  With --full only, it
+    runs on every rank AFTER the timed region, in a thread with a deadline: a communicator that cannot be built must not
+    cost the run its number.  Returns a dict for config.rccl_*; "timeout" marks a probe that did not finish (the caller then leaves through
     os._exit so that a stuck rendezvous cannot hang the teardown)."""
     import threading
     import torch
@@ -550,8 +555,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--micro-shards", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the RCCL probe, the CPU baseline and the GPU extras (secondary "
+                         "configurations, precisions and reference loops); off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the GPU extras")
     ap.add_argument("--hidden-features", type=int, default=HIDDEN_FEATURES)
     ap.add_argument("--overlap", choices=["none", "layer", "micro"], default=None,
                     help="shape of the gradient exchange at N > 1 (VERDICT r03 item 6b): none = one all-reduce of the whole "
@@ -668,7 +676,7 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(tr, args.dump_outputs)
     rccl = None
-    if tr.reducers[0].active:
+    if args.full and tr.reducers[0].active:
         rccl = rccl_probe(dev, tr)
 
     if rank == 0:
@@ -767,14 +775,14 @@ def main():
             out["hbm"] = hbm
         # order of the slow legs: a CPU leg, the GPU extras, the remaining CPU legs -- GPU work in the MIDDLE of the run,
         # so that an outside activity sampler meets it (the extras used to be 5 % at the very start)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # N = 65 536 and 262 144, 4 x 256 and 4 x 181 complex (bounded: 3 + 1 iterations each)
             out["cpu_baseline"] = cpu_baseline(65536, 3)
             out["cpu_baseline"]["more"] = {"n65536_k181_api_hidden_features_256": cpu_baseline(65536, 3, 256)}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             out["extras"] = extras(dev, lib)
             out["secondary"] = secondary(out["extras"])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"]["more"]["n262144_k256"] = cpu_baseline(262144, 2)
             out["cpu_baseline"]["more"]["n262144_k181_api_hidden_features_256"] = cpu_baseline(262144, 2, 256)
         print(json.dumps(out), flush=True)
