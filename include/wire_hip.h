@@ -22,8 +22,10 @@
  *                W_f[O][K] c64, b_f[O] c64        (modules/wire.py:127-157)
  *       wire2d : per layer l=0..L: W, b, V(scale_orth), c; then W_f, b_f
  *                                                  (modules/wire2d.py:98-123)
- *       siren/gauss/relu : {W_l, b_l} l=0..L, W_f, b_f, all f32
- *                (modules/siren.py:64-88, gauss.py:44-67, relu.py:99-120)
+ *       siren/gauss/relu/bspline : {W_l, b_l} l=0..L, W_f, b_f, all f32
+ *                (modules/siren.py:64-88, gauss.py:44-67, relu.py:99-120,
+ *                 bspline_form.py:73-110; its scale_0 buffers are not
+ *                 trainable and travel in wire_net_desc.scale0)
  *  - internal activation layout ("blocked planar"): a
  *    complex row of K features is stored as P = roundup(2K,64) floats; group
  *    g of 32 features occupies columns [64g,64g+32) = real parts and
@@ -54,7 +56,9 @@ typedef enum wire_kind {
   WIRE_KIND_WIRE2D = 1,  /* modules/wire2d.py ComplexGaborLayer2D        */
   WIRE_KIND_SIREN = 2,   /* modules/siren.py  SineLayer                  */
   WIRE_KIND_GAUSS = 3,   /* modules/gauss.py  GaussLayer                 */
-  WIRE_KIND_RELU = 4     /* modules/relu.py   ReLULayer (+PosEncoding)   */
+  WIRE_KIND_RELU = 4,    /* modules/relu.py   ReLULayer (+PosEncoding)   */
+  WIRE_KIND_BSPLINE = 5  /* modules/bspline_form.py Bsplines_form: the
+                            quadratic B-spline of lin / scale0           */
 } wire_kind;
 
 /* Architecture + hyper-parameters of one INR (modules/wire.py:96-159). */
@@ -66,9 +70,10 @@ typedef struct wire_net_desc {
   int32_t hidden_layers;   /* L                                                   */
   int32_t out_features;    /* O (<= 8)                                            */
   int32_t posenc_freqs;    /* relu only: PosEncoding.num_frequencies, 0 = off     */
-  float first_omega0;      /* omega of net[0]                                     */
-  float hidden_omega0;     /* omega of net[1..L]                                  */
-  float scale0;            /* Gaussian scale s0                                   */
+  float first_omega0;      /* omega of net[0] (bspline: carried, unused)          */
+  float hidden_omega0;     /* omega of net[1..L] (bspline: carried, unused)       */
+  float scale0;            /* Gaussian scale s0; bspline: the divisor sigma0
+                              (zero or not finite -> WIRE_ERR_ARG)                */
 } wire_net_desc;
 
 int wire_abi_version(void);
@@ -95,7 +100,7 @@ int wire_pack_params(void* stream, const wire_net_desc* d,
                      const void* const* params_host, float* packed);
 
 /* INR.forward (modules/wire.py:161-167; wire2d.py:122-127; siren.py:90-96;
- * gauss.py:71-74; relu.py:124-130): coords[n][D] f32 -> y[n][O] f32.
+ * gauss.py:71-74; relu.py:124-130; bspline_form.py:112-114): coords[n][D] f32 -> y[n][O] f32.
  * `act` receives the per-layer activations (wire_act_bytes).               */
 int wire_mlp_fwd(void* stream, const wire_net_desc* d, const float* packed,
                  const float* coords, int64_t n, float* y,
@@ -188,10 +193,11 @@ int wire_final_bwd(void* stream, const float* g_y, const void* z,
                    int out_features, void* g_z, void* g_Wf, void* g_bf,
                    void* ws, int64_t ws_bytes);
 
-/* SineLayer / GaussLayer / ReLULayer .forward (modules/siren.py:48-49,
- * gauss.py:27-28, relu.py:28-29) and their backward on native f32 tensors:
+/* SineLayer / GaussLayer / ReLULayer / Bsplines_form .forward (modules/siren.py:48-49,
+ * gauss.py:27-28, relu.py:28-29, bspline_form.py:38-49) and their backward on native f32 tensors:
  * x [n][in], W [out][in], b [out] -> act [n][out].  kind = WIRE_KIND_SIREN /
- * _GAUSS / _RELU; ws as for wire_gabor_fwd.                                   */
+ * _GAUSS / _RELU / _BSPLINE (scale0 = sigma0, the divisor; zero or not finite -> WIRE_ERR_ARG);
+ * ws as for wire_gabor_fwd.                                                   */
 int wire_real_layer_fwd(void* stream, int kind, const float* x, const float* W,
                         const float* b, float omega0, float scale0, int64_t n,
                         int in_features, int out_features, float* act_out,
@@ -307,10 +313,10 @@ int wire_posenc_fwd(void* stream, const float* coords, int64_t n, int D, int F, 
 /* ---- layout helpers ---------------------------------------------------- */
 int wire_blocked_width(int K);   /* P = roundup(2K, 64) */
 /* Float offset of the stored activations out_l (n rows of P floats -- blocked planar for wire / wire2d, P = roundup(K, 64)
- * plain features for siren / gauss / relu; l = 0..hidden_layers) inside an act buffer that wire_mlp_fwd / wire_train_fwd_bwd
+ * plain features for siren / gauss / relu / bspline; l = 0..hidden_layers) inside an act buffer that wire_mlp_fwd / wire_train_fwd_bwd
  * filled for n rows with save_for_bwd = 1: the per-layer activations of modules/utils.py:246-252 without re-running the
  * layers.  (With recompute_out the last hidden layer of a fused training step is not stored, except for relu; with
- * fused_rstore a sine / Gaussian net whose training step runs the fused data-gradient chain stores no out_l below the last
+ * fused_rstore a sine / Gaussian / B-spline net whose training step runs the fused data-gradient chain stores no out_l below the last
  * hidden layer either (r = c lin in their place); with split_out the inner hidden layers 1 .. hidden_layers - 1 hold fp16
  * pairs, see the knob -- set these knobs to 0 to read the activations.) */
 int64_t wire_act_out_offset(const wire_net_desc* d, int64_t n, int layer);
@@ -330,9 +336,9 @@ int wire_blocked_to_c64(void* stream, const float* src, int64_t n, int K, void* 
  *     bytes per instruction), 0 = through LDS in such half-line pieces; bit-identical results.
  *     0 = the 3 x bf16 kernels below for every batch size.
  * "split_out" (default 1; environment WIRE_SPLIT_OUT; with split_f16): the activations out_l of the INNER hidden layers
- *     (1 <= l < hidden_layers) of a wire / wire2d / siren / gauss net are stored ALREADY SPLIT by the forward epilogue --
+ *     (1 <= l < hidden_layers) of a wire / wire2d / siren / gauss / bspline net are stored ALREADY SPLIT by the forward epilogue --
  *     per 4 consecutive columns the 16 bytes [h h h h | l l l l] (fp16) instead of 4 floats, scale 2^(15 - e) from the
- *     activation's a-priori bound exp(w0^2 / 4 s0^2) < 2^e (sine, Gaussian: 1) -- and read in that form by the next
+ *     activation's a-priori bound exp(w0^2 / 4 s0^2) < 2^e (sine, Gaussian, B-spline: 1) -- and read in that form by the next
  *     layer's forward GEMM and by the weight-gradient GEMM, which then spend no vector instructions on the split.  Used
  *     when the bound is <= 16 (w0 / s0 <= 3.33), recompute_out = 1 (nothing else reads out_l) and the widths have a
  *     2 x fp16 weight-gradient shape; otherwise, and always for out_0, out_L and relu, activations stay fp32 with the
@@ -347,11 +353,11 @@ int wire_blocked_to_c64(void* stream, const float* src, int64_t n, int K, void* 
  * "x3_tall" (default 1), "x3_tn_tall" (default 0): 256-row tiles in the split-bf16
  *     NT / TN kernels.   "nt_bk" (16 | 32): K-slab depth of the fp32 4M NT kernel.
  * "x3_h16" (default 15): the v_mfma_f32_16x16x32_bf16 edition (wire_gemmx3h.hip) of the NT GEMMs at M >= 4096:
- *     bit 0 wire forward, bit 1 wire data gradient, bit 2 siren / gauss / relu, bit 3 wire2d; 0 = the 32x32x16 kernels.
+ *     bit 0 wire forward, bit 1 wire data gradient, bit 2 siren / gauss / relu / bspline, bit 3 wire2d; 0 = the 32x32x16 kernels.
  * "x3_tn16" (default 1): the weight-gradient (TN) GEMM of the split-bf16 family runs its 256 x 256-tile
  *     v_mfma_f32_16x16x32_bf16 kernel when both padded widths are multiples of 256 (up to 256 row splits); 0 = the
  *     128 x 128 kernel.
- * "recompute_out" (default 1): on the 16x16x32 kernels the backward of a wire / wire2d / siren / gauss net evaluates out = act(lin) again
+ * "recompute_out" (default 1): on the 16x16x32 kernels the backward of a wire / wire2d / siren / gauss / bspline net evaluates out = act(lin) again
  *     (same lean form, same bits) instead of reading it back: data-gradient epilogues, the fused final stage of
  *     wire_train_fwd_bwd (whose last hidden layer then does not store out at all).  0 = read the stored activations.
  * "first_sums" (default 1): wire nets on the 16x16x32 kernels -- the epilogue of the last data-gradient GEMM forms the

@@ -4,7 +4,7 @@ grid: samples/s of every net of BASELINE.json's sweep, with the whole-net kernel
 layer by layer ("fused_fwd" = 0) in alternating rounds of one process.  Under rocprofv3 --kernel-trace --stats it shows
 the per-kernel split.
 
-    python3 tools/forward_only.py [name ...]        names: wire_k256 wire_k181 siren gauss relu wire_k128 wire_k90
+    python3 tools/forward_only.py [name ...]        names: wire_k256 wire_k181 siren gauss relu bspline wire_k128 wire_k90
 """
 import json
 import os
@@ -27,6 +27,7 @@ NETS = {
     "siren": dict(nonlin="siren", hidden_features=256, first_omega_0=30.0, hidden_omega_0=30.0),
     "gauss": dict(nonlin="gauss", hidden_features=256, scale=10.0),
     "relu": dict(nonlin="relu", hidden_features=256),
+    "bspline": dict(nonlin="bspline_form", hidden_features=256, scale=1 / 4),
 }
 
 

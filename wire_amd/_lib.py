@@ -17,7 +17,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libwire_hip.so")
 
-KIND = {"wire": 0, "wire2d": 1, "siren": 2, "gauss": 3, "relu": 4}
+KIND = {"wire": 0, "wire2d": 1, "siren": 2, "gauss": 3, "relu": 4, "bspline_form": 5}
 ABI_VERSION = 1
 
 # every symbol include/wire_hip.h declares (tests check the .so exports them)

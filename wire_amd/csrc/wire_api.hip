@@ -144,7 +144,12 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   p.kind = d->kind; p.D = d->in_features; p.K = d->width; p.L = d->hidden_layers;
   p.O = d->out_features; p.F = d->posenc_freqs;
   p.w1 = d->first_omega0; p.w = d->hidden_omega0; p.s = d->scale0;
-  if (p.kind < WIRE_KIND_WIRE || p.kind > WIRE_KIND_RELU) return fail(WIRE_ERR_ARG, "unknown kind %d", p.kind);
+  if (p.kind < WIRE_KIND_WIRE || p.kind > WIRE_KIND_BSPLINE) return fail(WIRE_ERR_ARG, "unknown kind %d", p.kind);
+  if (p.kind == WIRE_KIND_BSPLINE) {
+    // sigma0 divides lin (modules/bspline_form.py:44); B is even, so every kernel multiplies by c = 1 / |sigma0| instead
+    if (!(std::isfinite(p.s) && p.s != 0.f)) return fail(WIRE_ERR_ARG, "bspline scale0 %g is zero or not finite", (double)p.s);
+    p.s = (float)(1.0 / fabs((double)p.s));
+  }
   if (p.D < 1 || p.D > 4) return fail(WIRE_ERR_ARG, "in_features %d outside 1..4", p.D);
   if (p.K < 1 || p.K > 4096) return fail(WIRE_ERR_ARG, "width %d outside 1..4096", p.K);
   if (p.L < 0 || p.L > 64) return fail(WIRE_ERR_ARG, "hidden_layers %d outside 0..64", p.L);
@@ -327,6 +332,7 @@ int epi_fwd(int kind) {
     case WIRE_KIND_WIRE2D: return EPI_GABOR2D_FWD;
     case WIRE_KIND_SIREN: return EPI_SIREN_FWD;
     case WIRE_KIND_GAUSS: return EPI_GAUSS_FWD;
+    case WIRE_KIND_BSPLINE: return EPI_BSPLINE_FWD;
     default: return EPI_RELU_FWD;
   }
 }
@@ -336,6 +342,7 @@ int epi_bwd(int kind) {
     case WIRE_KIND_WIRE2D: return EPI_GABOR2D_BWD;
     case WIRE_KIND_SIREN: return EPI_SIREN_BWD;
     case WIRE_KIND_GAUSS: return EPI_GAUSS_BWD;
+    case WIRE_KIND_BSPLINE: return EPI_BSPLINE_BWD;
     default: return EPI_RELU_BWD;
   }
 }
@@ -356,7 +363,7 @@ struct Route {
   bool fused_train;       // train: the hidden layers in one kernel that stores what the backward reads (wire_fused.hip)
   bool fused_final;       //   ... with the final stage inside it (fx_tail_loss): lin_L / out_L are not stored at all
   bool chain;             // the data gradients of layers L .. 1 in one kernel (wire_fused.hip: fused_bwd_kernel)
-  bool rstore;            //   ... sine / Gaussian: lin_l (l < L) stored as r = c lin, out_l (l < L) not at all
+  bool rstore;            //   ... sine / Gaussian / B-spline: lin_l (l < L) stored as r = c lin, out_l (l < L) not at all
   bool skip_out_L;        // train: out_L is neither written nor read, the final stage evaluates it from lin_L
   bool recompute_out;     // the data-gradient epilogue of layer l >= 2 evaluates out_{l-1} = act(lin_{l-1}) again
   bool recompute_out0;    //   ... and wire's first-layer epilogue out_0 (first_fwd_kernel's own form, the same bits)
@@ -417,13 +424,15 @@ Route make_route(const Plan& p, int64_t n, RouteMode mode) {
   // stores them
   r.chain = r.fused_train && p.k_fused_bwd && p.off_fxd >= 0;
   r.fused_final = r.chain && !p.cplx && p.k_fused_final;
-  r.rstore = r.chain && p.k_rstore && (p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_GAUSS);   // 1.3 GB per step less
+  r.rstore = r.chain && p.k_rstore &&
+             (p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_GAUSS || p.kind == WIRE_KIND_BSPLINE);   // 1.3 GB per step less
   // out_l is stored pre-split (wire_dev.h: wire_store_out4) when the call runs the 2 x fp16 kernels and every reader of
   // out_l understands the format: the forward GEMM of layer l + 1 (pre-split A edition), the weight-gradient GEMM of layer
   // l + 1 (gemmx2_tn16, pre-split Z) and NOTHING else -- the data-gradient epilogue of layer l + 1 must evaluate
-  // act(lin_l) again rather than read out_l (recompute_out; sine needs no out), out_0 comes from first_fwd_kernel, out_L
+  // act(lin_l) again rather than read out_l (recompute_out; sine and B-spline need no out), out_0 comes from first_fwd_kernel, out_L
   // feeds the final linear layer in fp32, relu's out carries its backward's sign decisions
-  const bool split = x2tn && p.k_split_out && p.kind != WIRE_KIND_RELU && (p.k_recompute_out || p.kind == WIRE_KIND_SIREN);
+  const bool split = x2tn && p.k_split_out && p.kind != WIRE_KIND_RELU &&
+                     (p.k_recompute_out || p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_BSPLINE);
   for (int l = 1; l < p.L; ++l) r.out_scale[l] = !split ? 0.f : ftrain ? 1.f : act_bound_scale(p);
   // the layer-1 data gradient of a native first layer on the 16 x 16 x 32 kernel: its epilogue can sum g_lin_0 (wire:
   // g_u) [x | 1] per tile itself instead of storing it for a separate pass, and form the coordinate-gradient partials
@@ -819,6 +828,9 @@ int Bwd::chain() {
   return WIRE_OK;
 }
 
+// the weight-gradient loader's form of Z = act(r) under rstore (launch_gemmx2_tn, z_act): sine 2, Gaussian 3, B-spline 4
+static int rstore_zmode(int kind) { return kind == WIRE_KIND_SIREN ? 2 : kind == WIRE_KIND_GAUSS ? 3 : 4; }
+
 // 4. the weight-gradient batch of layers wb_l0 .. L (make_route), behind the chain
 int Bwd::wgrad_batch() {
   const int l0 = r.wb_l0, nb = r.wb_n;
@@ -827,7 +839,7 @@ int Bwd::wgrad_batch() {
   ProfScope ps(s, 2, 2.0 * n * p.Pl * p.P * nb);
   HIPCHK(launch_gemmx2_tn(s, Sx + sc.gch + l0 * sc.gch_stride, p.Pl, rs ? lin_l(l0 - 1) : out_l(l0 - 1), rs ? p.Pl : p.P,
                           n, p.Pl, p.P, r.wb_S, Sx + sc.slab, Sx + sc.bslab, gslots(l0), oslots(l0 - 1),
-                          rs ? 1.f / 16384.f : (s_z != 0.f ? 1.f / s_z : 0.f), rs ? (p.kind == WIRE_KIND_SIREN ? 2 : 3) : 0,
+                          rs ? 1.f / 16384.f : (s_z != 0.f ? 1.f / s_z : 0.f), rs ? rstore_zmode(p.kind) : 0,
                           nb, sc.gch_stride, rs ? a.np * p.Pl : a.np * p.P, WIRE_AMAX_SLOTS));
   return WIRE_OK;
 }
@@ -842,7 +854,7 @@ hipError_t Bwd::hidden_tn(int l) {
     case FAM_X2:
       if (r.rstore)   // Z = act(r_{l-1}) evaluated by the loader from the stored pre-activation (no out_{l-1}), scale 2^14
         return launch_gemmx2_tn(s, gcur, p.Pl, lin_l(l - 1), p.Pl, n, p.Pl, p.P, S, slab, bslab, gslots(l), nullptr,
-                                1.f / 16384.f, p.kind == WIRE_KIND_SIREN ? 2 : 3);
+                                1.f / 16384.f, rstore_zmode(p.kind));
       return launch_gemmx2_tn(s, gcur, p.Pl, out_l(l - 1), p.P, n, p.Pl, p.P, S, slab, bslab, gslots(l), oslots(l - 1),
                               r.out_scale[l - 1] != 0.f ? 1.f / r.out_scale[l - 1] : 0.f);
     case FAM_X3: return launch_gemmx3_tn(s, gcur, p.Pl, out_l(l - 1), p.P, n, p.Pl, p.P, S, slab, bslab);

@@ -141,8 +141,28 @@ WIRE_DEVINL void gabor2d_fwd(float u, float v, float p, float q, float w0, float
   o_im = e * sn;
 }
 
-// real sweep activations (config 5)
-enum { ACT_SIREN = 0, ACT_GAUSS = 1, ACT_RELU = 2 };
+// real sweep activations (config 5) and the quadratic B-spline (modules/bspline_form.py)
+enum { ACT_SIREN = 0, ACT_GAUSS = 1, ACT_RELU = 2, ACT_BSPLINE = 3 };
+// whether act'(lin) reads the stored activation out (gauss: -2 s^2 lin out; relu: [out > 0]); siren and the B-spline
+// need lin alone
+constexpr bool act_bwd_reads_out(int act) { return act == ACT_GAUSS || act == ACT_RELU; }
+
+// Centred quadratic B-spline of r = c lin, c = 1 / |sigma0| (modules/bspline_form.py:38-49 computes it as
+// 0.5 relu(r+1.5)^2 - 1.5 relu(r+0.5)^2 + 1.5 relu(r-0.5)^2 - 0.5 relu(r-1.5)^2 with r = lin / sigma0; B is even, so
+// dividing by |sigma0| is the same function).  Evaluated piecewise: exactly 0 outside |r| < 1.5, where the four-term
+// form leaves an fp32 cancellation residue.  No transcendental: the precise and the lean forms are one.
+//   B(r)  = 0.75 - r^2 (|r| <= 0.5),  0.5 (1.5 - |r|)^2 (0.5 <= |r| <= 1.5),  0 otherwise
+//   B'(r) = -2 r,                    -sign(r) (1.5 - |r|),                   0
+WIRE_DEVINL float bspline2(float r) {
+  const float a = __builtin_fabsf(r);
+  const float t = __builtin_fmaxf(1.5f - a, 0.f);
+  return a <= 0.5f ? __builtin_fmaf(-r, r, 0.75f) : 0.5f * t * t;
+}
+WIRE_DEVINL float bspline2_d(float r) {
+  const float a = __builtin_fabsf(r);
+  const float t = __builtin_fmaxf(1.5f - a, 0.f);
+  return a <= 0.5f ? -2.f * r : __builtin_copysignf(t, -r);
+}
 template <int ACT>
 WIRE_DEVINL float real_act_fwd(float lin, float w0, float s0) {
   if (ACT == ACT_SIREN) {            // modules/siren.py:48-49
@@ -152,6 +172,8 @@ WIRE_DEVINL float real_act_fwd(float lin, float w0, float s0) {
   } else if (ACT == ACT_GAUSS) {     // modules/gauss.py:27-28
     float t = s0 * lin;
     return wire_exp(-(t * t));
+  } else if (ACT == ACT_BSPLINE) {   // s0 = c = 1 / |sigma0|
+    return bspline2(s0 * lin);
   } else {                           // modules/relu.py:28-29
     return lin > 0.f ? lin : 0.f;
   }
@@ -164,6 +186,8 @@ WIRE_DEVINL float real_act_bwd(float g, float lin, float out, float w0, float s0
     return g * w0 * cs;
   } else if (ACT == ACT_GAUSS) {
     return g * out * (-2.f * s0 * s0) * lin;
+  } else if (ACT == ACT_BSPLINE) {     // dL/dlin = g B'(c lin) c
+    return g * s0 * bspline2_d(s0 * lin);
   } else {
     return out > 0.f ? g : 0.f;        // out = max(lin, 0): out > 0 <=> lin > 0, so relu never needs lin stored
   }
@@ -180,6 +204,8 @@ WIRE_DEVINL float real_act_fwd_lean(float lin, float w0, float s0) {
   } else if (ACT == ACT_GAUSS) {
     const float t = s0 * lin;
     return __builtin_amdgcn_exp2f(-(t * t) * 1.44269502f);
+  } else if (ACT == ACT_BSPLINE) {
+    return bspline2(s0 * lin);
   } else {
     return lin > 0.f ? lin : 0.f;
   }
@@ -192,6 +218,8 @@ WIRE_DEVINL float real_act_bwd_lean(float g, float lin, float out, float w0, flo
     return g * w0 * cs;
   } else if (ACT == ACT_GAUSS) {
     return g * out * (-2.f * s0 * s0) * lin;
+  } else if (ACT == ACT_BSPLINE) {
+    return g * s0 * bspline2_d(s0 * lin);
   } else {
     return out > 0.f ? g : 0.f;
   }

@@ -22,11 +22,24 @@ enum WireEpi {
   EPI_GABOR2D_FWD = 10,     // C = (lin|sy)(re|im) 128-col groups: o0 = linsy [M][2P], o1 = out [M][P]
   EPI_GABOR2D_BWD = 11,     // C = g_out: i0 = linsy, i1 = out -> o0 = g_linsy [M][2P]
   EPI_GABOR2D_BWD_FIRST = 12, // real first layer of wire2d: o0 = g_(u|p) [M][2*ldu]
+  EPI_BSPLINE_FWD = 13,     // quadratic B-spline (scale = c = 1 / |sigma0|): o0 = lin, o1 = act
+  EPI_BSPLINE_BWD = 14,     // i0 = lin -> o0 = g_lin (no out read)
   // flag on the layer-1 data-gradient forms of the 16 x 16 x 32 kernels (the real BWD forms, GABOR_BWD_FIRST,
   // GABOR2D_BWD_FIRST): the instantiation that also writes ep.cg_partial.  Host code passes the plain code; the
   // launchers pick the flagged instantiation when ep.cg_partial is set
   EPI_CG = 64
 };
+
+// the real-valued activation epilogues (siren / gauss / relu / B-spline) and their ACT_* code (wire_dev.h)
+constexpr bool epi_real_fwd(int e) {
+  return e == EPI_SIREN_FWD || e == EPI_GAUSS_FWD || e == EPI_RELU_FWD || e == EPI_BSPLINE_FWD;
+}
+constexpr bool epi_real_bwd(int e) {
+  return e == EPI_SIREN_BWD || e == EPI_GAUSS_BWD || e == EPI_RELU_BWD || e == EPI_BSPLINE_BWD;
+}
+constexpr int epi_real_act(int e) {
+  return (e == EPI_BSPLINE_FWD || e == EPI_BSPLINE_BWD) ? 3 : epi_real_fwd(e) ? e - EPI_SIREN_FWD : e - EPI_SIREN_BWD;
+}
 
 struct GemmEpiParams {
   const float* bias = nullptr;   // [Nc], GEMM column order

@@ -148,9 +148,9 @@ WIRE_DEVINL void gemm_epilogue(f32x16 (&acc)[MT][WN], const GemmEpiParams& ep, c
   // base pointers + 32-bit byte offsets (no 64-bit multiply per element, no row test), loads of 8 rows in flight.
   // The short GEMMs of these nets (K = 256 real: 16 stages per tile) spend as long in the epilogue as in the main
   // loop when every element pays a dependent load -> store chain (profiles/r02_siren_kernel_stats.csv).
-  if constexpr (LEAN && (EPI == EPI_SIREN_FWD || EPI == EPI_GAUSS_FWD || EPI == EPI_RELU_FWD)) {
+  if constexpr (LEAN && epi_real_fwd(EPI)) {
     if (m_w + MT * 32 <= M && !ep.wide && n_w + WN * 32 <= ep.kvalid) {
-      constexpr int ACT = EPI - EPI_SIREN_FWD;
+      constexpr int ACT = epi_real_act(EPI);
       char* __restrict__ lin_b = reinterpret_cast<char*>(ep.o0);
       char* __restrict__ out_b = reinterpret_cast<char*>(ep.o1);
       const unsigned ldb4 = (unsigned)ep.ld0 * 4u;
@@ -173,9 +173,9 @@ WIRE_DEVINL void gemm_epilogue(f32x16 (&acc)[MT][WN], const GemmEpiParams& ep, c
       return;
     }
   }
-  if constexpr (LEAN && (EPI == EPI_SIREN_BWD || EPI == EPI_GAUSS_BWD || EPI == EPI_RELU_BWD)) {
+  if constexpr (LEAN && epi_real_bwd(EPI)) {
     if (m_w + MT * 32 <= M && !ep.wide) {
-      constexpr int ACT = EPI - EPI_SIREN_BWD;
+      constexpr int ACT = epi_real_act(EPI);
       const char* __restrict__ lin_b = reinterpret_cast<const char*>(ep.i0);
       const char* __restrict__ out_b = reinterpret_cast<const char*>(ep.i1);
       char* __restrict__ gl_b = reinterpret_cast<char*>(ep.o0);
@@ -193,9 +193,9 @@ WIRE_DEVINL void gemm_epilogue(f32x16 (&acc)[MT][WN], const GemmEpiParams& ep, c
             for (int q = 0; q < 8; ++q) {
               const int r = rb0 + q;
               const unsigned off = off0 + (unsigned)((r & 3) + 8 * (r >> 2)) * ldb4;
-              // siren needs lin, relu needs out (lin > 0 <=> out > 0; its lin is never stored), gauss both
+              // siren / B-spline need lin, relu needs out (lin > 0 <=> out > 0; its lin is never stored), gauss both
               lv[q] = (ACT != ACT_RELU) ? *reinterpret_cast<const float*>(lin_b + off) : 0.f;
-              ov[q] = (ACT != ACT_SIREN) ? *reinterpret_cast<const float*>(out_b + off) : 0.f;
+              ov[q] = act_bwd_reads_out(ACT) ? *reinterpret_cast<const float*>(out_b + off) : 0.f;
             }
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
@@ -380,8 +380,8 @@ WIRE_DEVINL void gemm_epilogue(f32x16 (&acc)[MT][WN], const GemmEpiParams& ep, c
           }
         }
     }
-  } else if constexpr (EPI == EPI_SIREN_FWD || EPI == EPI_GAUSS_FWD || EPI == EPI_RELU_FWD) {
-    constexpr int ACT = EPI - EPI_SIREN_FWD;
+  } else if constexpr (epi_real_fwd(EPI)) {
+    constexpr int ACT = epi_real_act(EPI);
 #pragma unroll
     for (int j = 0; j < WN; ++j) {
       const int col = n_w + 32 * j + l31;
@@ -401,8 +401,8 @@ WIRE_DEVINL void gemm_epilogue(f32x16 (&acc)[MT][WN], const GemmEpiParams& ep, c
           }
         }
     }
-  } else if constexpr (EPI == EPI_SIREN_BWD || EPI == EPI_GAUSS_BWD || EPI == EPI_RELU_BWD) {
-    constexpr int ACT = EPI - EPI_SIREN_BWD;
+  } else if constexpr (epi_real_bwd(EPI)) {
+    constexpr int ACT = epi_real_act(EPI);
 #pragma unroll
     for (int j = 0; j < WN; ++j) {
       const int col = n_w + 32 * j + l31;
@@ -413,7 +413,7 @@ WIRE_DEVINL void gemm_epilogue(f32x16 (&acc)[MT][WN], const GemmEpiParams& ep, c
           const int row = m_w + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
           if (row < M) {
             const float lin = (ACT != ACT_RELU) ? ep.i0[(size_t)row * ep.ld0 + col] : 0.f;   // relu: lin is not stored
-            const float out = ep.i1[(size_t)row * ep.ld1 + col];
+            const float out = act_bwd_reads_out(ACT) ? ep.i1[(size_t)row * ep.ld1 + col] : 0.f;
             ep.o0[(size_t)row * ep.ld0 + col] =
                 LEAN ? real_act_bwd_lean<ACT>(acc[i][j][r], lin, out, ep.omega, ep.scale)
                      : real_act_bwd<ACT>(acc[i][j][r], lin, out, ep.omega, ep.scale);

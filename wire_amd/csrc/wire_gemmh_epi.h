@@ -96,8 +96,8 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
         if (row + 8 < M) *reinterpret_cast<f32x4*>(ep.o0 + (size_t)(row + 8) * ep.ld0 + col) = yp;
       }
     }
-  } else if constexpr (EPI == EPI_SIREN_FWD || EPI == EPI_GAUSS_FWD || EPI == EPI_RELU_FWD) {
-    constexpr int ACT = EPI - EPI_SIREN_FWD;
+  } else if constexpr (epi_real_fwd(EPI)) {
+    constexpr int ACT = epi_real_act(EPI);
 #pragma unroll
     for (int sp = 0; sp < 4; ++sp) {
       if (n_w + 32 * sp >= Nc) continue;
@@ -127,8 +127,8 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
         }
       }
     }
-  } else if constexpr (EPI == EPI_SIREN_BWD || EPI == EPI_GAUSS_BWD || EPI == EPI_RELU_BWD) {
-    constexpr int ACT = EPI - EPI_SIREN_BWD;
+  } else if constexpr (epi_real_bwd(EPI)) {
+    constexpr int ACT = epi_real_act(EPI);
     float cg[4] = {0.f, 0.f, 0.f, 0.f};                           // cg_partial: this lane group's row sums of g_lin_0 W0
 #pragma unroll
     for (int sp = 0; sp < 4; ++sp) {
@@ -149,7 +149,7 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
           for (int hr = 0; hr < 2; ++hr) {
             int row = m_w + 16 * (rp + r2) + 8 * hr + rr;
             row = row < M ? row : M - 1;
-            // siren needs lin, relu needs out (its lin is never stored), gauss both
+            // siren / B-spline need lin, relu needs out (its lin is never stored), gauss both
             lv[2 * r2 + hr] = (ACT != ACT_RELU) ? *reinterpret_cast<const f32x4*>(ep.i0 + (size_t)row * ep.ld0 + col)
                                                 : f32x4{0.f, 0.f, 0.f, 0.f};
             const bool load_out = ACT == ACT_RELU || (ACT == ACT_GAUSS && !ep.recompute_out);

@@ -392,7 +392,7 @@ hipError_t launch_gemmx3_nt(hipStream_t s, int epi, const float* A, int lda, con
   if ((Nc & 63) || (Kd & 31) || (lda & 3) || M > 0x7fffff00LL) return hipErrorInvalidValue;
   // the lean Gabor epilogues share one 32-bit byte offset between their buffers
   GemmEpiParams ep = ep_in;
-  if ((epi == EPI_GABOR_FWD || epi == EPI_GABOR_BWD || (epi >= EPI_SIREN_FWD && epi <= EPI_RELU_BWD)) &&
+  if ((epi == EPI_GABOR_FWD || epi == EPI_GABOR_BWD || epi_real_fwd(epi) || epi_real_bwd(epi)) &&
       ep.ld0 != ep.ld1)
     ep.wide = 1;
   if ((double)M * (double)(ep.ld1 > ep.ld0 ? ep.ld1 : ep.ld0) * 4.0 >= 4294967296.0) ep.wide = 1;
@@ -405,6 +405,8 @@ hipError_t launch_gemmx3_nt(hipStream_t s, int epi, const float* A, int lda, con
       case EPI_SIREN_BWD: return launchx3_nt_t<EPI_SIREN_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
       case EPI_GAUSS_BWD: return launchx3_nt_t<EPI_GAUSS_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
       case EPI_RELU_BWD: return launchx3_nt_t<EPI_RELU_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+      case EPI_BSPLINE_FWD: return launchx3_nt_t<EPI_BSPLINE_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+      case EPI_BSPLINE_BWD: return launchx3_nt_t<EPI_BSPLINE_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
       default: break;
     }
   }
@@ -428,6 +430,8 @@ hipError_t launch_gemmx3_nt(hipStream_t s, int epi, const float* A, int lda, con
     case EPI_SIREN_BWD: return launchx3_nt_t<EPI_SIREN_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_GAUSS_BWD: return launchx3_nt_t<EPI_GAUSS_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_RELU_BWD: return launchx3_nt_t<EPI_RELU_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+    case EPI_BSPLINE_FWD: return launchx3_nt_t<EPI_BSPLINE_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+    case EPI_BSPLINE_BWD: return launchx3_nt_t<EPI_BSPLINE_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_GABOR2D_FWD:
       if (Nc & 127) return hipErrorInvalidValue;
       return launchx3_nt_t<EPI_GABOR2D_FWD, 1, 4>(s, A, lda, Bx3, M, Nc, Kd, ep);

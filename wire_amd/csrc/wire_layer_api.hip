@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "../../include/wire_hip.h"
 #include "wire_gemm.h"
@@ -351,11 +352,20 @@ extern "C" int wire_final_bwd(void* stream, const float* g_y, const void* z, con
 }
 
 // ---------------------------------------------------------------------------
-// real-valued layers: SineLayer / GaussLayer / ReLULayer .forward
-// (modules/siren.py:48-49, gauss.py:27-28, relu.py:28-29) on native [n][in] f32 tensors.
+// real-valued layers: SineLayer / GaussLayer / ReLULayer / Bsplines_form .forward
+// (modules/siren.py:48-49, gauss.py:27-28, relu.py:28-29, bspline_form.py:38-49) on native [n][in] f32 tensors.
 // ---------------------------------------------------------------------------
 static int real_epi_fwd(int kind) {
-  return kind == WIRE_KIND_SIREN ? EPI_SIREN_FWD : kind == WIRE_KIND_GAUSS ? EPI_GAUSS_FWD : EPI_RELU_FWD;
+  return kind == WIRE_KIND_SIREN ? EPI_SIREN_FWD : kind == WIRE_KIND_GAUSS ? EPI_GAUSS_FWD
+       : kind == WIRE_KIND_BSPLINE ? EPI_BSPLINE_FWD : EPI_RELU_FWD;
+}
+// the kernels' scale of a real layer: the B-spline's sigma0 is a divisor, passed on as c = 1 / |sigma0| (B is even); false:
+// sigma0 is zero or not finite
+static bool real_scale(int kind, float& scale0) {
+  if (kind != WIRE_KIND_BSPLINE) return true;
+  if (!(std::isfinite(scale0) && scale0 != 0.f)) return false;
+  scale0 = (float)(1.0 / fabs((double)scale0));
+  return true;
 }
 static int real_forward_ws(hipStream_t s, const LayerWs& w, float* W_, int kind, const void* x, const void* Wt,
                            const void* b, float omega0, float scale0, int64_t n, int in, int out, int Pin,
@@ -375,8 +385,8 @@ static int real_forward_ws(hipStream_t s, const LayerWs& w, float* W_, int kind,
 extern "C" int wire_real_layer_fwd(void* stream, int kind, const float* x, const float* W, const float* b,
                                    float omega0, float scale0, int64_t n, int in_features, int out_features,
                                    float* act_out, void* ws, int64_t ws_bytes) {
-  if (kind < WIRE_KIND_SIREN || kind > WIRE_KIND_RELU || n < 0 || in_features < 1 || out_features < 1 || !x ||
-      !W || !b || !act_out || !ws)
+  if (kind < WIRE_KIND_SIREN || kind > WIRE_KIND_BSPLINE || n < 0 || in_features < 1 || out_features < 1 || !x ||
+      !W || !b || !act_out || !ws || !real_scale(kind, scale0))
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_real_layer_fwd");
   if (n == 0) return WIRE_OK;
   const LayerWs w = layer_ws(n, in_features, out_features);   // complex sizing is an upper bound
@@ -394,8 +404,8 @@ extern "C" int wire_real_layer_bwd(void* stream, int kind, const float* g_act, c
                                    const float* b, float omega0, float scale0, int64_t n, int in_features,
                                    int out_features, float* g_x, float* g_W, float* g_b, void* ws,
                                    int64_t ws_bytes) {
-  if (kind < WIRE_KIND_SIREN || kind > WIRE_KIND_RELU || n <= 0 || in_features < 1 || out_features < 1 ||
-      !g_act || !x || !W || !b || !g_W || !g_b || !ws)
+  if (kind < WIRE_KIND_SIREN || kind > WIRE_KIND_BSPLINE || n <= 0 || in_features < 1 || out_features < 1 ||
+      !g_act || !x || !W || !b || !g_W || !g_b || !ws || !real_scale(kind, scale0))
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_real_layer_bwd");
   const LayerWs w = layer_ws(n, in_features, out_features);
   if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-enum { NK_WIRE = 0, NK_WIRE2D = 1, NK_SIREN = 2, NK_GAUSS = 3, NK_RELU = 4 };
+enum { NK_WIRE = 0, NK_WIRE2D = 1, NK_SIREN = 2, NK_GAUSS = 3, NK_RELU = 4, NK_BSPLINE = 5 };
 
 // ---- weight packing (native nn.Parameter layout -> padded real-expanded image)
 hipError_t launch_pack_hidden(hipStream_t s, int kind, const float* W, const float* b,

@@ -216,6 +216,7 @@ hipError_t launch_first_fwd(hipStream_t s, int kind, const float* coords, int64_
     case NK_SIREN: FIRST_LAUNCH(NK_SIREN); break;
     case NK_GAUSS: FIRST_LAUNCH(NK_GAUSS); break;
     case NK_RELU: FIRST_LAUNCH(NK_RELU); break;
+    case NK_BSPLINE: FIRST_LAUNCH(NK_BSPLINE); break;
     default: return hipErrorInvalidValue;
   }
 #undef FIRST_LAUNCH
@@ -412,6 +413,7 @@ hipError_t launch_final_bwd(hipStream_t s, int kind, int raw, const float* g_y, 
       case NK_SIREN: FB_LAUNCH(NK_SIREN, false); break;
       case NK_GAUSS: FB_LAUNCH(NK_GAUSS, false); break;
       case NK_RELU: FB_LAUNCH(NK_RELU, false); break;
+      case NK_BSPLINE: FB_LAUNCH(NK_BSPLINE, false); break;
       default: return hipErrorInvalidValue;
     }
   }
@@ -790,6 +792,9 @@ hipError_t launch_final_fused(hipStream_t s, int kind, const float* out, const f
       if (out) { FF_LAUNCH_O(NP, RW, NK_GAUSS, false); } else { FF_LAUNCH_O(NP, RW, NK_GAUSS, true); }       \
       break;                                                                                                 \
     case NK_RELU: FF_LAUNCH_O(NP, RW, NK_RELU, false); break;                                                \
+    case NK_BSPLINE:                                                                                         \
+      if (out) { FF_LAUNCH_O(NP, RW, NK_BSPLINE, false); } else { FF_LAUNCH_O(NP, RW, NK_BSPLINE, true); }   \
+      break;                                                                                                 \
     default: return hipErrorInvalidValue;                                                                    \
   }
   if (P <= 256) { FF_LAUNCH_K(1, 2); } else if (P <= 512) { FF_LAUNCH_K(1, 1); } else { FF_LAUNCH_K(2, 1); }
@@ -1242,6 +1247,7 @@ hipError_t launch_real_act_bwd_point(hipStream_t s, int kind, const float* g, co
     case NK_SIREN: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_SIREN>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
     case NK_GAUSS: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_GAUSS>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
     case NK_RELU: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_RELU>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
+    case NK_BSPLINE: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_BSPLINE>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

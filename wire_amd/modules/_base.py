@@ -58,9 +58,9 @@ class HipINR(nn.Module):
         # one more activation layer (K -> O).  The fused whole-net path ends in a linear layer, so such a net
         # runs layer by layer through the per-layer HIP entry points (same kernels, one autograd node each).
         self._layerwise = not outermost_linear
-        if any(isinstance(getattr(m, "omega_0", None), nn.Parameter) for m in layers):
-            # omega_0 / scale_0 live in the state_dict (modules/wire.py:80-81, wire2d.py:44-45): a checkpoint
-            # or a manual edit must reach the fused path's descriptor
+        if any(_has_hparams(m) for m in layers):
+            # omega_0 / scale_0 live in the state_dict (modules/wire.py:80-81, wire2d.py:44-45; scale_0 alone:
+            # bspline_form.py:23): a checkpoint or a manual edit must reach the fused path's descriptor
             self.register_load_state_dict_post_hook(lambda m, _keys: m.refresh_hparams())
 
     def refresh_hparams(self) -> None:
@@ -68,7 +68,7 @@ class HipINR(nn.Module):
         ``load_state_dict`` -- done automatically -- or a manual edit such as ``net[0].omega_0.fill_()``).
         One host sync; not on the hot path.  The fused kernels take ONE first-layer omega, one hidden omega and
         one scale: per-layer values that differ raise."""
-        acts = [m for m in self.net if isinstance(getattr(m, "omega_0", None), nn.Parameter)]
+        acts = [m for m in self.net if _has_hparams(m)]
         if not acts:
             return
         for m in acts:
@@ -118,6 +118,11 @@ class HipINR(nn.Module):
                     out = m(out)
             return out
         return Fh.inr_forward(coords, self.net_desc(), self.param_tensors())
+
+
+def _has_hparams(m: nn.Module) -> bool:
+    """Whether a layer keeps omega_0 or scale_0 as a Parameter (read back by ``refresh_hparams``)."""
+    return any(isinstance(getattr(m, a, None), nn.Parameter) for a in ("omega_0", "scale_0"))
 
 
 def _scalar_param(value: float, trainable: bool) -> nn.Parameter:
