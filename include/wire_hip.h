@@ -26,6 +26,10 @@
  *                (modules/siren.py:64-88, gauss.py:44-67, relu.py:99-120,
  *                 bspline_form.py:73-110; its scale_0 buffers are not
  *                 trainable and travel in wire_net_desc.scale0)
+ *       bspline_ms : W0[SHF][D], b0[SHF] (the frozen first stage), W1[K][SHF],
+ *                b1[K], {W_l[K][K], b_l[K]} l=2..max(L,1), W_f, b_f, all f32
+ *                (modules/bspline_mscale_HL.py; its scales travel in
+ *                 wire_net_desc_ms, see below)
  *  - internal activation layout ("blocked planar"): a
  *    complex row of K features is stored as P = roundup(2K,64) floats; group
  *    g of 32 features occupies columns [64g,64g+32) = real parts and
@@ -57,8 +61,11 @@ typedef enum wire_kind {
   WIRE_KIND_SIREN = 2,   /* modules/siren.py  SineLayer                  */
   WIRE_KIND_GAUSS = 3,   /* modules/gauss.py  GaussLayer                 */
   WIRE_KIND_RELU = 4,    /* modules/relu.py   ReLULayer (+PosEncoding)   */
-  WIRE_KIND_BSPLINE = 5  /* modules/bspline_form.py Bsplines_form: the
+  WIRE_KIND_BSPLINE = 5, /* modules/bspline_form.py Bsplines_form: the
                             quadratic B-spline of lin / scale0           */
+  WIRE_KIND_BSPLINE_MS = 6 /* modules/bspline_mscale_HL.py: a frozen
+                            Scaled_Bsplines_form D -> SHF, then Bsplines_form
+                            SHF -> K; described by wire_net_desc_ms        */
 } wire_kind;
 
 /* Architecture + hyper-parameters of one INR (modules/wire.py:96-159). */
@@ -75,6 +82,24 @@ typedef struct wire_net_desc {
   float scale0;            /* Gaussian scale s0; bspline: the divisor sigma0
                               (zero or not finite -> WIRE_ERR_ARG)                */
 } wire_net_desc;
+
+/* The multi-scale B-spline net (WIRE_KIND_BSPLINE_MS, modules/bspline_mscale_HL.py): a wire_net_desc followed by the
+ * shape of its frozen first stage.  Callers pass &desc.base wherever a const wire_net_desc* is taken; the library reads
+ * the tail only when base.kind is WIRE_KIND_BSPLINE_MS.
+ *   base.width = K (hidden_features), base.hidden_layers = the reference's value (0 builds the net of 1: one SHF -> K
+ *   layer, then max(L - 1, 0) K -> K layers), base.scale0 = the hidden divisor `scale`, base.posenc_freqs = 0.
+ *   First stage: lin = x W0^T + b0, column j divided by scales[g(j)]: g = 0 for j < min(256, SHF), else
+ *   g = 1 + (j - 256) / split with split = (SHF - 256) / (nscales - 1), which must divide SHF - 256 exactly; then B.
+ *   Every scale must be finite and non-zero (the plan uses c = 1 / |s|).  No gradient reaches W0, b0 or the
+ *   coordinates: the backward never writes grads[0] / grads[1] (NULL accepted there; the hooked call still announces
+ *   them, holding whatever the caller put there), and a g_coords request is WIRE_ERR_ARG.                          */
+#define WIRE_MS_MAX_SCALES 8
+typedef struct wire_net_desc_ms {
+  wire_net_desc base;      /* base.kind = WIRE_KIND_BSPLINE_MS                    */
+  int32_t first_width;     /* SHF: scaled_hidden_features, 1..4096                */
+  int32_t nscales;         /* T: entries of scale_tensor, 2..WIRE_MS_MAX_SCALES   */
+  float scales[WIRE_MS_MAX_SCALES];   /* scale_tensor[0 .. T)                     */
+} wire_net_desc_ms;
 
 int wire_abi_version(void);
 const char* wire_last_error(void);
@@ -303,6 +328,12 @@ int wire_gabor2d_bwd_first_coords(void* stream, const void* g_act, const float* 
 int wire_gabor2d_hparam_grad(void* stream, const void* g_act, const void* x, const void* W, const void* b,
                              const void* V, const void* c, float omega0, float scale0, int64_t n, int in_features,
                              int out_features, int is_first, float* out2, void* ws, int64_t ws_bytes);
+
+/* ---- the frozen first stage of WIRE_KIND_BSPLINE_MS (Scaled_Bsplines_form.forward) on native tensors -------------
+ * x [n][in] f32, W [out][in], b [out] -> out [n][out] f32: B(lin_j / scales[g(j)]) with the column groups of
+ * wire_net_desc_ms: out = SHF, nscales = T, scales_host in HOST memory.  No backward: the stage is frozen.        */
+int wire_mscale_first_fwd(void* stream, const float* x, const float* W, const float* b, int64_t n, int in_features,
+                          int out_features, int nscales, const float* scales_host, float* out);
 
 /* ---- positional encoding (PosEncoding.forward, modules/relu.py:62-75) ----
  * out[n][D + 2 D F]: the raw coordinates, then for each frequency i < F and dimension j < D: sin(2^i pi c_j),

@@ -17,7 +17,8 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libwire_hip.so")
 
-KIND = {"wire": 0, "wire2d": 1, "siren": 2, "gauss": 3, "relu": 4, "bspline_form": 5}
+KIND = {"wire": 0, "wire2d": 1, "siren": 2, "gauss": 3, "relu": 4, "bspline_form": 5, "bspline_mscale_HL": 6}
+MS_MAX_SCALES = 8   # WIRE_MS_MAX_SCALES
 ABI_VERSION = 1
 
 # every symbol include/wire_hip.h declares (tests check the .so exports them)
@@ -30,7 +31,7 @@ SYMBOLS = [
     "wire_adam_step_flat", "wire_blocked_width", "wire_c64_to_blocked",
     "wire_blocked_to_c64", "wire_prof_enable", "wire_prof_read", "wire_tune_set", "wire_tune_get", "wire_avgpool_mse_grad", "wire_layer2d_ws_bytes", "wire_gabor2d_fwd", "wire_gabor2d_bwd", "wire_eval_metric", "wire_real_layer_fwd", "wire_real_layer_bwd", "wire_train_fwd_bwd", "wire_perm_indices", "wire_gabor_hparam_grad", "wire_track_best", "wire_sigmoid_inplace", "wire_radon_fwd", "wire_radon_bwd", "wire_gabor2d_hparam_grad", "wire_posenc_fwd", "wire_act_out_offset", "wire_train_fwd_bwd_hooked",
     "wire_bwd_coords_scratch_bytes", "wire_mlp_bwd_coords", "wire_posenc_bwd", "wire_gabor_bwd_first_coords",
-    "wire_gabor2d_bwd_first_coords",
+    "wire_gabor2d_bwd_first_coords", "wire_mscale_first_fwd",
 ]
 
 
@@ -40,6 +41,13 @@ class NetDesc(C.Structure):
                 ("hidden_layers", C.c_int32), ("out_features", C.c_int32),
                 ("posenc_freqs", C.c_int32), ("first_omega0", C.c_float),
                 ("hidden_omega0", C.c_float), ("scale0", C.c_float)]
+
+
+class NetDescMS(C.Structure):
+    """struct wire_net_desc_ms: the multi-scale B-spline net's descriptor (kind 6).  The library takes a pointer to its
+    ``base`` member; ``make_desc_ms`` returns that member, which keeps this struct alive and lies at its start."""
+    _fields_ = [("base", NetDesc), ("first_width", C.c_int32), ("nscales", C.c_int32),
+                ("scales", C.c_float * MS_MAX_SCALES)]
 
 
 # wire_grad_ready_fn (include/wire_hip.h): void (*)(void* user, int first_tensor, int n_tensors)
@@ -78,6 +86,7 @@ def _declare(l: C.CDLL) -> None:
     l.wire_track_best.argtypes = [vp, vp, vp, i32, vp, vp, i64, vp]
     l.wire_sigmoid_inplace.argtypes = [vp, vp, i64]
     l.wire_posenc_fwd.argtypes = [vp, vp, i64, i32, i32, vp]
+    l.wire_mscale_first_fwd.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, C.POINTER(C.c_float), vp]
     l.wire_bwd_coords_scratch_bytes.argtypes = [dp, i64]
     l.wire_bwd_coords_scratch_bytes.restype = i64
     l.wire_mlp_bwd_coords.argtypes = [vp, dp, vp, vp, i64, vp, vp, i64, vp, i64, C.POINTER(vp), vp]
@@ -148,6 +157,18 @@ def make_desc(kind: str, in_features: int, width: int, hidden_layers: int, out_f
     return NetDesc(KIND[kind], int(in_features), int(width), int(hidden_layers),
                    int(out_features), int(posenc_freqs), float(first_omega0),
                    float(hidden_omega0), float(scale0))
+
+
+def make_desc_ms(in_features: int, width: int, hidden_layers: int, out_features: int, first_omega0: float,
+                 hidden_omega0: float, scale0: float, first_width: int, scales) -> NetDesc:
+    """Descriptor of a bspline_mscale_HL net: the ``base`` NetDesc of a NetDescMS (pass it wherever a NetDesc goes)."""
+    scales = [float(v) for v in scales]
+    if not 2 <= len(scales) <= MS_MAX_SCALES:
+        raise ValueError(f"{len(scales)} scales: the descriptor takes 2..{MS_MAX_SCALES}")
+    ms = NetDescMS(make_desc("bspline_mscale_HL", in_features, width, hidden_layers, out_features, first_omega0,
+                             hidden_omega0, scale0), int(first_width), len(scales),
+                   (C.c_float * MS_MAX_SCALES)(*scales))
+    return ms.base
 
 
 def ptr_array(ptrs):

@@ -129,6 +129,11 @@ struct Plan {
   float w1, w, s;
   bool cplx, first_gemm, m3, x3, x2;
   int P, Pl, Din, Pin0, ldu, ntens, per_layer, Kp;
+  // WIRE_KIND_BSPLINE_MS (kind then reads WIRE_KIND_BSPLINE, the activation of every layer behind the first stage): a frozen
+  // first stage D -> SHF (its W0, b0 are tensors 0, 1) feeds layer 0, the GEMM SHF -> K; the plan's own tensors start at t0
+  bool ms = false;
+  int SHF = 0, T = 0, ms_split = 0, t0 = 0;
+  float ms_c[WIRE_MS_MAX_SCALES] = {};
   // packed image offsets (floats); index l = 0..L (l = 0 only when first_gemm)
   std::vector<int64_t> off_fwd, off_dg, off_bias, off_fwd_x3, off_dg_x3, off_fwd_3m, off_dg_3m, off_fwd_x2, off_dg_x2;
   int64_t off_wf, off_bf, off_first, off_wamax, total_packed;   // off_wamax: max-|weight| slots, WIRE_AMAX_SLOTS per layer
@@ -144,7 +149,29 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   p.kind = d->kind; p.D = d->in_features; p.K = d->width; p.L = d->hidden_layers;
   p.O = d->out_features; p.F = d->posenc_freqs;
   p.w1 = d->first_omega0; p.w = d->hidden_omega0; p.s = d->scale0;
-  if (p.kind < WIRE_KIND_WIRE || p.kind > WIRE_KIND_BSPLINE) return fail(WIRE_ERR_ARG, "unknown kind %d", p.kind);
+  if (p.kind < WIRE_KIND_WIRE || p.kind > WIRE_KIND_BSPLINE_MS) return fail(WIRE_ERR_ARG, "unknown kind %d", p.kind);
+  if (p.kind == WIRE_KIND_BSPLINE_MS) {
+    // modules/bspline_mscale_HL.py: columns [0, min(256, SHF)) divided by scale_tensor[0], group g >= 1 by scale_tensor[g]
+    // over [256 + (g - 1) split, 256 + g split); the groups must cover SHF exactly (the next Linear takes SHF columns)
+    const wire_net_desc_ms* m = reinterpret_cast<const wire_net_desc_ms*>(d);
+    p.ms = true; p.SHF = m->first_width; p.T = m->nscales;
+    if (p.SHF < 1 || p.SHF > 4096) return fail(WIRE_ERR_ARG, "first_width %d outside 1..4096", p.SHF);
+    if (p.T < 2 || p.T > WIRE_MS_MAX_SCALES) return fail(WIRE_ERR_ARG, "nscales %d outside 2..%d", p.T, WIRE_MS_MAX_SCALES);
+    if (p.SHF > 256) {
+      p.ms_split = (p.SHF - 256) / (p.T - 1);
+      if (p.ms_split < 1 || 256 + (p.T - 1) * p.ms_split != p.SHF)
+        return fail(WIRE_ERR_ARG, "first_width %d is not 256 + %d equal column groups", p.SHF, p.T - 1);
+    }
+    for (int g = 0; g < p.T; ++g) {
+      const float sg = m->scales[g];
+      if (!(std::isfinite(sg) && sg != 0.f)) return fail(WIRE_ERR_ARG, "scales[%d] %g is zero or not finite", g, (double)sg);
+      p.ms_c[g] = (float)(1.0 / fabs((double)sg));
+    }
+    if (p.L < 0 || p.L > 65) return fail(WIRE_ERR_ARG, "hidden_layers %d outside 0..65", p.L);
+    p.L = p.L > 1 ? p.L - 1 : 0;   // K -> K layers behind the SHF -> K one (hidden_layers = 0 builds the net of 1)
+    p.kind = WIRE_KIND_BSPLINE;
+    p.t0 = 2;
+  }
   if (p.kind == WIRE_KIND_BSPLINE) {
     // sigma0 divides lin (modules/bspline_form.py:44); B is even, so every kernel multiplies by c = 1 / |sigma0| instead
     if (!(std::isfinite(p.s) && p.s != 0.f)) return fail(WIRE_ERR_ARG, "bspline scale0 %g is zero or not finite", (double)p.s);
@@ -171,19 +198,20 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   p.k_fused_fwd = knob(K_FUSED_FWD) != 0; p.k_fused_train = p.k_fused_fwd && knob(K_FUSED_TRAIN);
   p.k_fused_train_p384 = knob(K_FUSED_TRAIN_P384) != 0;
   p.k_fused_bwd = p.k_fused_train && knob(K_FUSED_BWD); p.k_fused_final = p.k_fused_train && knob(K_FUSED_FINAL);
-  p.first_gemm = p.F > 0;
-  p.Din = p.first_gemm ? p.D + 2 * p.D * p.F : p.D;
+  p.first_gemm = p.F > 0 || p.ms;
+  p.Din = p.ms ? p.SHF : p.first_gemm ? p.D + 2 * p.D * p.F : p.D;
   p.Pin0 = p.first_gemm ? rup(p.Din, 64) : 0;
   p.per_layer = (p.kind == WIRE_KIND_WIRE2D) ? 4 : 2;
-  p.ntens = p.per_layer * (p.L + 1) + 2;
+  p.ntens = p.t0 + p.per_layer * (p.L + 1) + 2;
   p.tfloats.assign(p.ntens, 0);
+  if (p.ms) { p.tfloats[0] = (int64_t)p.SHF * p.D; p.tfloats[1] = p.SHF; }
   const int64_t K = p.K, cm = p.cplx ? 2 : 1;
   for (int l = 0; l <= p.L; ++l) {
     const int64_t in = (l == 0) ? p.Din : K;
     const int64_t m = (l == 0) ? 1 : cm;   // first layer is real-valued
     for (int q = 0; q < p.per_layer; q += 2) {
-      p.tfloats[p.per_layer * l + q] = m * K * in;
-      p.tfloats[p.per_layer * l + q + 1] = m * K;
+      p.tfloats[p.t0 + p.per_layer * l + q] = m * K * in;
+      p.tfloats[p.t0 + p.per_layer * l + q + 1] = m * K;
     }
   }
   p.tfloats[p.ntens - 2] = cm * p.O * K;
@@ -212,6 +240,8 @@ int make_plan(const wire_net_desc* d, Plan& p) {
     if (l >= 1) {                                         // 2 x fp16 images of the hidden layers
       p.off_fwd_x2[l] = off; off += gemmx2_b_image_floats(p.Pl, (int)pin);
       p.off_dg_x2[l] = off; off += gemmx2_b_image_floats((int)pin, p.Pl);
+    } else if (p.ms) {                                    // ... and the forward one of the SHF -> K layer (no data gradient)
+      p.off_fwd_x2[l] = off; off += gemmx2_b_image_floats(p.Pl, (int)pin);
     }
   }
   p.off_wamax = off; off += (int64_t)(p.L + 1) * WIRE_AMAX_SLOTS;
@@ -223,8 +253,8 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   if (fx_ok && p.L >= 1 && fused_bwd_shape(p.kind, p.P)) { p.off_fxd = off; off += (int64_t)p.L * fused_b_image_floats(p.P); }
   p.off_wf = off; off += (int64_t)p.O * p.P;
   p.off_bf = off; off += 64;
-  p.off_first = off;   // native copies of the first layer's tensors (W0,b0[,V0,c0])
-  if (!p.first_gemm) for (int q = 0; q < p.per_layer; ++q) off += rup((int)p.tfloats[q], 4);
+  p.off_first = off;   // native copies of the first layer's tensors (W0,b0[,V0,c0]; the multi-scale net's first stage)
+  if (!p.first_gemm || p.ms) for (int q = 0; q < p.per_layer; ++q) off += rup((int)p.tfloats[q], 4);
   p.total_packed = off;
   return WIRE_OK;
 }
@@ -241,6 +271,7 @@ struct ActLayout {
   int64_t pe, out0, lin0, lin1, total;   // out_l = out0 + l*np*P ; lin_l = lin1 + (l-1)*np*Pl
   int64_t ping, pong;                    // inference
   int64_t amax;                          // max |out_l| slots, WIRE_AMAX_SLOTS per layer l = 0..L (2 x fp16 GEMMs)
+  int64_t pe_amax;                       // the multi-scale net: max |pe| slots right behind them (fp32 pe on 2 x fp16)
   int64_t np;                            // rows each saved buffer is spaced by: n rounded up to 128 -- the fused training
                                          // forward (wire_fused.hip) stores whole 128-row workgroup tiles unconditionally
 };
@@ -249,6 +280,7 @@ ActLayout act_layout(const Plan& p, int64_t n, int save) {
   int64_t off = 0;
   a.np = (n + 127) / 128 * 128;
   a.amax = off; off += (int64_t)(p.L + 2) * WIRE_AMAX_SLOTS;
+  a.pe_amax = off; if (p.ms) off += WIRE_AMAX_SLOTS;
   a.pe = off; if (p.first_gemm) off += n * p.Pin0;
   if (save) {
     a.out0 = off; off += a.np * p.P * (p.L + 1);
@@ -355,7 +387,10 @@ enum RouteMode { MODE_INFER, MODE_AUTOGRAD, MODE_TRAIN };
 struct Route {
   RouteMode mode;
   WireFamily fam;         // forward and data-gradient GEMMs of the hidden layers
-  WireFamily fam0;        // GEMMs of a positional-encoding first layer: 3 x bf16 or fp32
+  WireFamily fam0;        // GEMMs of a positional-encoding first layer: 3 x bf16 or fp32 (the multi-scale net's SHF -> K
+                          //   forward: 2 x fp16 with the hidden layers)
+  WireFamily tn0;         // the multi-scale net: weight gradient of its SHF -> K layer
+  float pe_split;         //   ... and the fixed split scale of its first-stage map pe when both read it pre-split, 0 = fp32
   WireFamily tn_fam;      // weight-gradient GEMMs of the hidden layers, in tn_S row splits
   int tn_S;
   bool fused_fwd;         // inference: the whole net in one kernel, activations in registers (wire_fused.hip)
@@ -398,6 +433,14 @@ Route make_route(const Plan& p, int64_t n, RouteMode mode) {
   const bool x2tn = x2 && gemmx2_tn_applies(p.Pl, p.P);
   r.fam = x2 ? FAM_X2 : p.m3 ? FAM_3M : p.x3 ? FAM_X3 : FAM_4M;
   r.fam0 = p.x3 ? FAM_X3 : FAM_4M;
+  r.tn0 = r.fam0;
+  if (p.ms && x2) {
+    // the SHF -> K layer is the widest GEMM of the net: its forward joins the hidden layers' family; its weight gradient
+    // runs 2 x fp16 where the TN kernel has a shape (and the scratch was sized for it: Pin0 >= P).  Then both readers take
+    // the first stage's map pre-split at 2^15 (B <= 0.75 < 2^0: scaled below 2^15, no device-side maximum)
+    r.fam0 = FAM_X2;
+    if (p.Pin0 >= p.P && gemmx2_tn_applies(p.Pl, p.Pin0)) { r.tn0 = FAM_X2; r.pe_split = 32768.f; }
+  }
   r.tn_fam = p.m3 ? FAM_3M : x2tn ? FAM_X2 : p.x3 ? FAM_X3 : FAM_4M;
   const int S_max = scratch_layout(p, n).S;
   r.tn_S = r.tn_fam == FAM_3M ? S_max
@@ -528,8 +571,8 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
     if (!params[i]) return fail(WIRE_ERR_ARG, "params[%d] is null", i);
   HIPCHK(hipMemsetAsync(packed + p.off_wamax, 0, (size_t)(p.L + 1) * WIRE_AMAX_SLOTS * sizeof(float), s));
   if (p.first_gemm) {                                    // layer 0 as a GEMM (positional encoding): its own shape
-    const float* W = (const float*)params[0];
-    const float* b = (const float*)params[1];
+    const float* W = (const float*)params[p.t0];
+    const float* b = (const float*)params[p.t0 + 1];
     HIPCHK(launch_pack_hidden(s, p.kind, W, b, nullptr, nullptr, p.K, p.Din, p.P, p.Pin0, packed + p.off_fwd[0],
                               packed + p.off_dg[0], packed + p.off_bias[0]));
     HIPCHK(launch_x3_split_b(s, packed + p.off_fwd[0], p.Pin0, p.Pl, p.Pin0, packed + p.off_fwd_x3[0]));
@@ -541,6 +584,15 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
       f0.src[0] = packed + p.off_fwd[0]; f0.dst[0] = packed + p.off_fx; f0.slots[0] = slots0;
       HIPCHK(launch_fx_split_b_batch(s, f0, 1, p.Pin0, p.P, 1.f, p.Pin0));
     }
+    if (p.ms) {                                            // the SHF -> K layer's 2 x fp16 forward image + its maximum
+      X2AmaxBatch ab{};
+      X2SplitBatch xf{};
+      ab.src[0] = xf.src[0] = packed + p.off_fwd[0];
+      ab.slots[0] = reinterpret_cast<unsigned*>(packed + p.off_wamax);
+      xf.dst[0] = packed + p.off_fwd_x2[0]; xf.slots[0] = ab.slots[0];
+      HIPCHK(launch_amax_batch(s, ab, 1, (int64_t)p.Pl * p.Pin0));
+      HIPCHK(launch_x2_split_b_batch(s, xf, 1, p.Pin0, p.Pl, p.Pin0));
+    }
   }
   // hidden layers share one shape: every family's image of up to PACK_MAXB layers per launch (3 - 4 launches per step
   // instead of 4 per layer; this runs once per optimizer step and is all launch gaps)
@@ -550,8 +602,8 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
     X3SplitBatch sf{}, sd{};
     for (int i = 0; i < nb; ++i) {
       const int l = l0 + i;
-      pb.W[i] = (const float*)params[p.per_layer * l];
-      pb.b[i] = (const float*)params[p.per_layer * l + 1];
+      pb.W[i] = (const float*)params[p.t0 + p.per_layer * l];
+      pb.b[i] = (const float*)params[p.t0 + p.per_layer * l + 1];
       pb.V[i] = p.per_layer == 4 ? (const float*)params[p.per_layer * l + 2] : nullptr;
       pb.c[i] = p.per_layer == 4 ? (const float*)params[p.per_layer * l + 3] : nullptr;
       pb.fwd[i] = packed + p.off_fwd[l]; pb.dg[i] = packed + p.off_dg[l]; pb.bias[i] = packed + p.off_bias[l];
@@ -614,7 +666,7 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
   HIPCHK(launch_pack_final(s, p.kind, (const float*)params[p.ntens - 2],
                            (const float*)params[p.ntens - 1], p.K, p.P, p.O, packed + p.off_wf,
                            packed + p.off_bf));
-  if (!p.first_gemm)
+  if (!p.first_gemm || p.ms)   // (the multi-scale net: its first stage, read by mscale_first_kernel)
     for (int q = 0; q < p.per_layer; ++q)
       HIPCHK(hipMemcpyAsync(packed + first_native_off(p, q), params[q], p.tfloats[q] * 4,
                             hipMemcpyDeviceToDevice, s));
@@ -663,8 +715,17 @@ static int mlp_fwd_core(void* stream, const Plan& p, const Route& r, const float
     return WIRE_OK;
   }
   unsigned* const amax = reinterpret_cast<unsigned*>(A + a.amax);            // slots of out_l at amax + 64 l
-  if (r.fam == FAM_X2) HIPCHK(hipMemsetAsync(amax, 0, (size_t)(p.L + 2) * WIRE_AMAX_SLOTS * sizeof(unsigned), s));
-  if (p.first_gemm) {   // (also behind the fused training forward: the first layer's weight gradient reads them)
+  if (r.fam == FAM_X2)   // (the multi-scale net's pe slots lie right behind)
+    HIPCHK(hipMemsetAsync(amax, 0, (size_t)(p.L + 2 + (p.ms ? 1 : 0)) * WIRE_AMAX_SLOTS * sizeof(unsigned), s));
+  unsigned* const pe_amax = reinterpret_cast<unsigned*>(A + a.pe_amax);
+  if (p.ms) {
+    MscaleC c{};
+    for (int g = 0; g < p.T; ++g) c.c[g] = p.ms_c[g];
+    ProfScope ps(s, 3, 0);
+    HIPCHK(launch_mscale_first(s, coords, n, p.D, packed + first_native_off(p, 0), packed + first_native_off(p, 1), p.SHF,
+                               c, p.ms_split, p.Pin0, r.pe_split,
+                               r.fam0 == FAM_X2 && r.pe_split == 0.f ? pe_amax : nullptr, A + a.pe));
+  } else if (p.first_gemm) {   // (also behind the fused training forward: the first layer's weight gradient reads them)
     ProfScope ps(s, 3, 0);
     HIPCHK(launch_posenc(s, coords, n, p.D, p.F, p.Pin0, A + a.pe));
   }
@@ -700,8 +761,10 @@ static int mlp_fwd_core(void* stream, const Plan& p, const Route& r, const float
     GemmEpiParams ep; ep.bias = packed + p.off_bias[0]; ep.o0 = lin_l(0); ep.o1 = out_l(0);
     ep.ld0 = p.Pl; ep.ld1 = p.P; ep.omega = p.w1; ep.scale = p.s; ep.kvalid = p.K;
     if (r.fam == FAM_X2) ep.amax_out = amax;             // (the 3 x bf16 16 x 16 x 32 kernel tracks the maximum too)
+    if (r.pe_split != 0.f) ep.a_split_inv = 1.f / r.pe_split;
     ProfScope ps(s, 0, 2.0 * n * p.Pl * p.Pin0);
-    HIPCHK(layer_nt(s, p, r.fam0, packed, 0, false, epi_fwd(p.kind), A + a.pe, n, ep));
+    HIPCHK(layer_nt(s, p, r.fam0, packed, 0, false, epi_fwd(p.kind), A + a.pe, n, ep, pe_amax, wamax_of(p, packed, 0),
+                    amax));
   } else {
     auto first = [&](int q) { return q < p.per_layer ? packed + first_native_off(p, q) : nullptr; };   // W0, b0 [, V0, c0]
     ProfScope ps(s, 3, 0);
@@ -877,13 +940,13 @@ int Bwd::layers() {
       const int64_t m = own ? 0 : l - r.wb_l0;
       float* const slab = Sx + sc.slab + m * S * p.Pl * p.P;
       float* const bslab = Sx + sc.bslab + m * S * p.Pl;
-      auto g = [&](int q) { return q < pl ? grad(pl * l + q) : nullptr; };   // W, b [, V, c] of layer l
+      auto g = [&](int q) { return q < pl ? grad(p.t0 + pl * l + q) : nullptr; };   // W, b [, V, c] of layer l
       ProfScope ps(s, 3, 0);
       if (r.tn_fam == FAM_3M)
         HIPCHK(launch_wgrad3m_reduce(s, slab, bslab, S, p.K, p.K, p.Kp, p.Kp, g(0), g(1)));
       else
         HIPCHK(launch_wgrad_reduce(s, p.kind, slab, bslab, S, p.K, p.K, p.Pl, p.P, g(0), g(1), g(2), g(3)));
-      done(pl * l, pl);
+      done(p.t0 + pl * l, pl);
     }
     if (r.chain) continue;                                  // g_lin_{l-1} (l = 1: the first layer's sums) is already there
     const bool first_sums = grads && r.first_sums;
@@ -912,9 +975,10 @@ int Bwd::layers() {
       ep.cg_partial = Sx + cl.cgp; ep.D = p.D;
       if (!p.cplx) ep.W0 = first(0);
     }
-    { ProfScope ps(s, 1, 2.0 * n * p.Pl * p.P);             // (g_lin_0 feeds no 2 x fp16 GEMM: no maximum kept)
+    // (g_lin_0 feeds no 2 x fp16 GEMM -- no maximum kept -- except the multi-scale net's SHF -> K weight gradient)
+    { ProfScope ps(s, 1, 2.0 * n * p.Pl * p.P);
       HIPCHK(layer_nt(s, p, r.fam, packed, l, true, epi, gcur, n, ep, gslots(l), wamax_of(p, packed, l),
-                      l >= 2 ? gslots(l - 1) : nullptr)); }
+                      l >= 2 || r.tn0 == FAM_X2 ? gslots(l - 1) : nullptr)); }
     float* t = gcur; gcur = gnext; gnext = t;
   }
   return WIRE_OK;
@@ -965,16 +1029,23 @@ int Bwd::first_params() {
     HIPCHK(launch_colreduce_final(s, p.K, p.D, n, crp, grad(0), grad(1)));
   } else if (!p.first_gemm) {
     HIPCHK(launch_colreduce(s, gcur, p.P, p.K, coords, p.D, n, crp, grad(0), grad(1)));   // gcur: g_lin_0 [n][P]
+  } else if (r.tn0 == FAM_X2) {                             // the multi-scale net: g_lin_0^T [pe | 1], pe pre-split
+    const int S = gemmx2_tn_splits(n, p.P, p.Pin0, sc.S);
+    HIPCHK(launch_gemmx2_tn(s, gcur, p.P, A + a.pe, p.Pin0, n, p.P, p.Pin0, S, Sx + sc.slab, Sx + sc.bslab, gslots(0),
+                            nullptr, 1.f / r.pe_split));
+    HIPCHK(launch_wgrad_reduce(s, p.kind, Sx + sc.slab, Sx + sc.bslab, S, p.K, p.Din, p.P, p.Pin0, grad(p.t0),
+                               grad(p.t0 + 1), nullptr, nullptr));
   } else {
     const float* g0 = r.chain ? Sx + sc.gch : gcur;         // the chain stored g_lin_0 in its slot 0
-    const bool x3 = r.fam0 == FAM_X3;
+    const bool x3 = r.tn0 == FAM_X3;
     const int S = x3 ? gemmx3_tn_splits(n, p.P, p.Pin0, sc.S) : gemm_tn_splits(n, p.P, p.Pin0, sc.S);
     HIPCHK(x3 ? launch_gemmx3_tn(s, g0, p.P, A + a.pe, p.Pin0, n, p.P, p.Pin0, S, Sx + sc.slab, Sx + sc.bslab)
               : launch_gemm_tn(s, g0, p.P, A + a.pe, p.Pin0, n, p.P, p.Pin0, S, Sx + sc.slab, Sx + sc.bslab));
-    HIPCHK(launch_wgrad_reduce(s, p.kind, Sx + sc.slab, Sx + sc.bslab, S, p.K, p.Din, p.P, p.Pin0, grad(0), grad(1),
-                               nullptr, nullptr));
+    HIPCHK(launch_wgrad_reduce(s, p.kind, Sx + sc.slab, Sx + sc.bslab, S, p.K, p.Din, p.P, p.Pin0, grad(p.t0),
+                               grad(p.t0 + 1), nullptr, nullptr));
   }
-  done(0, p.per_layer);
+  done(p.t0, p.per_layer);
+  if (p.ms) done(0, 2);                                     // the frozen first stage: never written, announced last
   return WIRE_OK;
 }
 }  // namespace
@@ -986,7 +1057,9 @@ static int mlp_bwd_core(void* stream, const Plan& p, const Route& r, const float
   if (n <= 0) return fail(WIRE_ERR_ARG, "backward needs n > 0");
   if (!packed || !coords || (!r.fuse && !g_y) || !act || !scratch || (!grads && !g_coords))
     return fail(WIRE_ERR_ARG, "null pointer");
-  if (grads) for (int i = 0; i < p.ntens; ++i) if (!grads[i]) return fail(WIRE_ERR_ARG, "grads[%d] is null", i);
+  if (grads) for (int i = p.t0; i < p.ntens; ++i) if (!grads[i]) return fail(WIRE_ERR_ARG, "grads[%d] is null", i);
+  if (p.ms && g_coords) return fail(WIRE_ERR_ARG, "no coordinate gradient through the frozen first stage of kind %d",
+                                    (int)WIRE_KIND_BSPLINE_MS);
   Bwd c{p, r, (hipStream_t)stream, packed, coords, n, g_y, grads, g_coords, ready, user, act_layout(p, n, 1),
         scratch_layout(p, n), coord_layout(p, n), (const float*)act, (float*)scratch};
   const int64_t need = g_coords ? c.cl.total : c.sc.total;
@@ -1171,6 +1244,22 @@ extern "C" int wire_radon_bwd(void* stream, const float* g_sino, const float* an
   if (H < 1 || W < 1 || nangles < 1 || !g_sino || !angles_deg || !g_img) return fail(WIRE_ERR_ARG, "bad argument to wire_radon_bwd");
   ProfScope ps((hipStream_t)stream, 3, 0);
   HIPCHK(launch_radon_bwd((hipStream_t)stream, g_sino, angles_deg, H, W, nangles, g_img));
+  return WIRE_OK;
+}
+extern "C" int wire_mscale_first_fwd(void* stream, const float* x, const float* W, const float* b, int64_t n,
+                                     int in_features, int out_features, int nscales, const float* scales_host, float* out) {
+  if (n < 0 || in_features < 1 || in_features > 4 || (n > 0 && (!x || !W || !b || !out)) || !scales_host)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_mscale_first_fwd");
+  // the descriptor's checks of the first stage (make_plan), on a net around it
+  wire_net_desc_ms m{};
+  m.base.kind = WIRE_KIND_BSPLINE_MS; m.base.in_features = in_features; m.base.width = 1; m.base.out_features = 1;
+  m.base.scale0 = 1.f; m.first_width = out_features; m.nscales = nscales;
+  if (nscales >= 2 && nscales <= WIRE_MS_MAX_SCALES)
+    for (int g = 0; g < nscales; ++g) m.scales[g] = scales_host[g];
+  Plan p; if (int rc = make_plan(&m.base, p)) return rc;
+  MscaleC c{};
+  for (int g = 0; g < p.T; ++g) c.c[g] = p.ms_c[g];
+  HIPCHK(launch_mscale_first((hipStream_t)stream, x, n, in_features, W, b, p.SHF, c, p.ms_split, p.SHF, 0.f, nullptr, out));
   return WIRE_OK;
 }
 extern "C" int wire_posenc_fwd(void* stream, const float* coords, int64_t n, int D, int F, float* out) {

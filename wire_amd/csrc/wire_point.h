@@ -99,6 +99,15 @@ hipError_t launch_real_act_bwd_point(hipStream_t s, int kind, const float* g, co
 hipError_t launch_posenc(hipStream_t s, const float* coords, int64_t n, int D, int F, int Pin,
                          float* dst);
 
+// ---- the frozen first stage of the multi-scale B-spline net (modules/bspline_mscale_HL.py: Scaled_Bsplines_form)
+// dst[r][j] = B(c[g(j)] (x_r . W0[j] + b0[j])) for j < SHF, 0 for SHF <= j < ld; g(j) = 0 below 256, else
+// 1 + (j - 256) / split.  split_scale != 0 (ld % 4 == 0, 16-byte aligned rows): stored pre-split as wire_store_out4 does
+// (B <= 0.75); else fp32, and amax (optional) receives max |value| for the 2 x fp16 GEMM that reads it.
+struct MscaleC { float c[8]; };
+hipError_t launch_mscale_first(hipStream_t s, const float* coords, int64_t n, int D, const float* W0, const float* b0,
+                               int SHF, const MscaleC& c, int split, int ld, float split_scale, unsigned* amax,
+                               float* dst);
+
 // ---- coordinate gradients (first-order, fp32)
 // g_x[r][d] = sum_k G[r][k] W[k][d] (+ sum_k G2[r][k] V[k][d]) over the K valid features of a stored first-layer gradient
 // (real g_lin_0, wire g_u, wire2d g_u with G2 = g_p); W, V native [K][D].  One wave per row, fixed reduction order.

@@ -1302,6 +1302,63 @@ hipError_t launch_posenc(hipStream_t s, const float* coords, int64_t n, int D, i
 }
 
 // ===========================================================================
+// frozen first stage of the multi-scale B-spline net (modules/bspline_mscale_HL.py, Scaled_Bsplines_form.forward):
+// B(lin_j / s_g(j)) per column, pad columns exactly 0 (B(0) = 0.75 would leak into the next GEMM otherwise)
+// ===========================================================================
+// one lane per 4 consecutive columns of a row: the 16-byte unit wire_store_out4 writes (pre-split or fp32)
+__global__ __launch_bounds__(256) void mscale_first_kernel(const float* __restrict__ coords, long long n, int D,
+                                                           const float* __restrict__ W0, const float* __restrict__ b0,
+                                                           int SHF, MscaleC c, int split, int ld, int qpr,
+                                                           float split_scale, unsigned* __restrict__ amax,
+                                                           float* __restrict__ dst) {
+  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long row = q / qpr;
+  const int col0 = (int)(q - row * qpr) * 4;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (row < n) {
+    float x[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) x[d] = d < D ? coords[row * D + d] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int j = col0 + i;
+      if (j < SHF) {
+        float lin = b0[j];
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+          if (d < D) lin = __builtin_fmaf(x[d], W0[(long long)j * D + d], lin);
+        const int g = j < 256 ? 0 : 1 + (j - 256) / split;
+        v[i] = bspline2(c.c[g] * lin);
+      }
+    }
+    float* p = dst + row * ld + col0;
+    if (split_scale != 0.f || (ld & 3) == 0) {
+      wire_store_out4(p, v, split_scale);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (col0 + i < ld) p[i] = v[i];
+    }
+  }
+  if (amax) {   // every lane of the wave takes part in the reduction (B >= 0: the maximum is max |value|)
+    const float m = __builtin_fmaxf(__builtin_fmaxf(v[0], v[1]), __builtin_fmaxf(v[2], v[3]));
+    wire_amax_publish(amax, m, threadIdx.x & 63);
+  }
+}
+hipError_t launch_mscale_first(hipStream_t s, const float* coords, int64_t n, int D, const float* W0, const float* b0,
+                               int SHF, const MscaleC& c, int split, int ld, float split_scale, unsigned* amax,
+                               float* dst) {
+  if (n <= 0) return hipSuccess;
+  if (D < 1 || D > 4 || SHF < 1 || ld < SHF || (SHF > 256 && split < 1) ||
+      (split_scale != 0.f && ((ld & 3) || (reinterpret_cast<uintptr_t>(dst) & 15))))
+    return hipErrorInvalidValue;
+  const int qpr = (ld + 3) / 4;
+  hipLaunchKernelGGL(mscale_first_kernel, dim3(cdiv(n * qpr, 256)), dim3(256), 0, s, coords, (long long)n, D, W0, b0,
+                     SHF, c, split, ld, qpr, split_scale, amax, dst);
+  return hipGetLastError();
+}
+
+// ===========================================================================
 // coordinate gradients: one wave per row, features strided over the lanes, a fixed butterfly across them (no atomics:
 // the same bits every run)
 // ===========================================================================

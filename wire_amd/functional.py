@@ -104,19 +104,42 @@ class _INRFunction(torch.autograd.Function):
             xshape, xdtype = ctx.xmeta
             g_coords = g_x.reshape(xshape).to(xdtype)
             return (g_coords, None, None, *(grads if want_p else [None] * len(ctx.meta)))
-        grads = [torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in ctx.meta]
+        # (bspline_mscale_HL: its first stage W0, b0 is frozen -- no gradient, a NULL slot for the library)
+        frozen = 2 if desc.kind == _lib.KIND["bspline_mscale_HL"] else 0
+        grads = [None if i < frozen else torch.empty(shape, dtype=dtype, device=dev)
+                 for i, (shape, dtype) in enumerate(ctx.meta)]
         sbytes = _lib.check(L.wire_bwd_scratch_bytes(C.byref(desc), n), "wire_bwd_scratch_bytes")
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
         _lib.check(L.wire_mlp_bwd(stream, C.byref(desc), ctx.packed.data_ptr(), ctx.x.data_ptr(), n,
                                   gy.data_ptr(), ctx.act.data_ptr(), ctx.act.numel(),
                                   scratch.data_ptr(), sbytes,
-                                  _lib.ptr_array([g.data_ptr() for g in grads])), "wire_mlp_bwd")
+                                  _lib.ptr_array([None if g is None else g.data_ptr() for g in grads])),
+                   "wire_mlp_bwd")
         # the saved buffers stay with the graph node (freed with it), so backward(retain_graph=True) can run again
         return (None, None, None, *grads)
 
 
 def inr_forward(coords: torch.Tensor, desc: _lib.NetDesc, params: Sequence[torch.Tensor]) -> torch.Tensor:
     return _INRFunction.apply(coords, desc, torch.is_grad_enabled(), *params)
+
+
+def mscale_first(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor, scales: Sequence[float]) -> torch.Tensor:
+    """The frozen first stage of bspline_mscale_HL (Scaled_Bsplines_form.forward) on the device:
+    x [..., D] -> [..., SHF] through wire_mscale_first_fwd.  Records no graph: the stage passes no gradient."""
+    L = _lib.lib()
+    _require_cuda(x, "layer input")
+    _require_cuda(W, "layer weight")
+    out_f, in_f = W.shape
+    if x.shape[-1] != in_f:
+        raise ValueError(f"input last dim {x.shape[-1]} != in_features {in_f}")
+    xin = x.detach().to(torch.float32).contiguous()
+    n = xin.numel() // in_f
+    sc = (C.c_float * len(scales))(*[float(v) for v in scales])
+    out = torch.empty(tuple(x.shape[:-1]) + (out_f,), dtype=torch.float32, device=x.device)
+    _lib.check(L.wire_mscale_first_fwd(_stream_ptr(x.device), xin.data_ptr(), _native(W).data_ptr(),
+                                       _native(b).data_ptr(), n, in_f, out_f, len(scales), sc, out.data_ptr()),
+               "wire_mscale_first_fwd")
+    return out
 
 
 class _GaborLayerFunction(torch.autograd.Function):

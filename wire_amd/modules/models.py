@@ -12,19 +12,19 @@ arguments its own signature has, so both call styles work:
             hidden_layers=2, first_omega_0=7., hidden_omega_0=7., scale=6.)
     get_INR('wire', 2, 300, 0, 2, 3, scale_tensor=[0.0], ...)   # bspline_* style
 """
-from . import bspline_form, gauss, relu, siren, wire, wire2d
+from . import bspline_form, bspline_mscale_HL, gauss, relu, siren, wire, wire2d
 
 # keys of modules/models.py:15-25 that are on the MI355X path; 'mfn', 'bspline_cubic'
-# and the bspline_mscale_* family are out of scope (SURVEY.md section 2.1 rows 7-8).
+# and the other bspline_mscale_* nets are out of scope (SURVEY.md section 2.1 rows 7-8).
 model_dict = {'bspline_form': bspline_form,
+              'bspline_mscale_HL': bspline_mscale_HL,
               'gauss': gauss,
               'relu': relu,
               'siren': siren,
               'wire': wire,
               'wire2d': wire2d}
 
-_OUT_OF_SCOPE = ('mfn', 'bspline_cubic', 'bspline_mscale_2',
-                 'bspline_mscale_HL', 'bspline_mscale_hier')
+_OUT_OF_SCOPE = ('mfn', 'bspline_cubic', 'bspline_mscale_2', 'bspline_mscale_hier')
 
 
 def get_INR(nonlin, in_features, hidden_features, scaled_hidden_features=None,
@@ -33,7 +33,7 @@ def get_INR(nonlin, in_features, hidden_features, scaled_hidden_features=None,
             pos_encode=False, sidelength=512, fn_samples=None, use_nyquist=True):
     """Return an INR ``nn.Module`` whose forward/backward run on MI355X.
 
-    nonlin: 'wire', 'wire2d', 'siren', 'gauss', 'relu' or 'bspline_form' ('posenc' is 'relu'
+    nonlin: 'wire', 'wire2d', 'siren', 'gauss', 'relu', 'bspline_form' or 'bspline_mscale_HL' ('posenc' is 'relu'
     with ``pos_encode=True``, as the reference's drivers spell it).
     Remaining arguments: see modules/models.py:31-56 of the reference.
     """
@@ -51,6 +51,14 @@ def get_INR(nonlin, in_features, hidden_features, scaled_hidden_features=None,
                        hidden_layers, out_features, outermost_linear, first_omega_0,
                        hidden_omega_0, scale, scale_tensor, pos_encode, sidelength, fn_samples,
                        use_nyquist)
+    if nonlin == 'bspline_mscale_HL':
+        # 15-argument form with `multiscale`, modules/bspline_mscale_HL.py; passed by keyword
+        return mod.INR(in_features=in_features, hidden_features=hidden_features,
+                       scaled_hidden_features=0 if scaled_hidden_features is None else scaled_hidden_features,
+                       hidden_layers=hidden_layers, out_features=out_features, outermost_linear=outermost_linear,
+                       first_omega_0=first_omega_0, hidden_omega_0=hidden_omega_0, scale=scale,
+                       scale_tensor=scale_tensor, pos_encode=pos_encode,
+                       sidelength=sidelength, fn_samples=fn_samples, use_nyquist=use_nyquist)
     if nonlin == 'wire':
         # 15-argument form, modules/wire.py:96-111
         return mod.INR(in_features, hidden_features,

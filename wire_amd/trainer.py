@@ -165,11 +165,16 @@ class FusedTrainer:
         """(first_tensor, n_tensors) in the order wire_train_fwd_bwd_hooked announces them (include/wire_hip.h)."""
         nt = len(self.offsets)
         hidden = int(self.desc.hidden_layers)
-        per = (nt - 2) // (hidden + 1)
+        t0 = 0
+        if self.desc.kind == _lib.KIND["bspline_mscale_HL"]:   # its frozen first stage (tensors 0, 1) comes last
+            t0, hidden = 2, max(hidden - 1, 0)
+        per = (nt - 2 - t0) // (hidden + 1)
         yield nt - 2, 2
         for l in range(hidden, 0, -1):
-            yield per * l, per
-        yield 0, per
+            yield t0 + per * l, per
+        yield t0, per
+        if t0:
+            yield 0, t0
 
     def _on_grad_ready(self, user, first: int, n: int) -> None:
         """wire_grad_ready_fn: parameter tensors [first, first + n) have their final gradient enqueued on the compute
