@@ -63,9 +63,13 @@ typedef enum wire_kind {
   WIRE_KIND_RELU = 4,    /* modules/relu.py   ReLULayer (+PosEncoding)   */
   WIRE_KIND_BSPLINE = 5, /* modules/bspline_form.py Bsplines_form: the
                             quadratic B-spline of lin / scale0           */
-  WIRE_KIND_BSPLINE_MS = 6 /* modules/bspline_mscale_HL.py: a frozen
+  WIRE_KIND_BSPLINE_MS = 6, /* modules/bspline_mscale_HL.py: a frozen
                             Scaled_Bsplines_form D -> SHF, then Bsplines_form
                             SHF -> K; described by wire_net_desc_ms        */
+  /* 7 stays unassigned: a plain descriptor of kind 7 is WIRE_ERR_ARG, and callers rely on that */
+  WIRE_KIND_BSPLINE_M2 = 8 /* modules/bspline_mscale_2.py: the bspline_form
+                            trunk run once per scale, the S outputs through
+                            freq_mlp; described by wire_net_desc_ms        */
 } wire_kind;
 
 /* Architecture + hyper-parameters of one INR (modules/wire.py:96-159). */
@@ -93,11 +97,21 @@ typedef struct wire_net_desc {
  *   Every scale must be finite and non-zero (the plan uses c = 1 / |s|).  No gradient reaches W0, b0 or the
  *   coordinates: the backward never writes grads[0] / grads[1] (NULL accepted there; the hooked call still announces
  *   them, holding whatever the caller put there), and a g_coords request is WIRE_ERR_ARG.                          */
+/* The multi-pass B-spline net (WIRE_KIND_BSPLINE_M2, modules/bspline_mscale_2.py) uses the same struct:
+ *   base.width = K, base.hidden_layers = L (trunk: D -> K, L x K -> K, then K -> O linear -- kind 5's), base.scale0 is
+ *   carried and ignored (the reference's `scale`: 0 is accepted), first_width = 0, nscales = S (1..8), scales[] = the
+ *   divisor of each pass: pass k computes the trunk with c_k = 1 / |scales[k]| (each finite and non-zero).
+ *   The S outputs of a row, [t_0 | t_1 | ..], go through freq_mlp = Linear(S O -> 128), ReLU, Linear(128 -> O).
+ *   params[] / grads[]: freq_mlp.0.weight [128][S O], freq_mlp.0.bias [128], freq_mlp.2.weight [O][128],
+ *   freq_mlp.2.bias [O], then the trunk in kind 5's order (its tensors start at index 4).  combine_scales.scale_weights
+ *   and combine_scales.refine.* receive no gradient in the reference's loop and are not ABI tensors.  The hooked call
+ *   announces tensors 0 .. 3 first.  n is the number of coordinate rows; the library runs the trunk on S n rows.       */
 #define WIRE_MS_MAX_SCALES 8
 typedef struct wire_net_desc_ms {
   wire_net_desc base;      /* base.kind = WIRE_KIND_BSPLINE_MS                    */
-  int32_t first_width;     /* SHF: scaled_hidden_features, 1..4096                */
-  int32_t nscales;         /* T: entries of scale_tensor, 2..WIRE_MS_MAX_SCALES   */
+  int32_t first_width;     /* SHF: scaled_hidden_features, 1..4096 (kind 8: 0)    */
+  int32_t nscales;         /* T: entries of scale_tensor, 2..WIRE_MS_MAX_SCALES
+                              (kind 8: S, 1..WIRE_MS_MAX_SCALES)                 */
   float scales[WIRE_MS_MAX_SCALES];   /* scale_tensor[0 .. T)                     */
 } wire_net_desc_ms;
 
@@ -334,6 +348,17 @@ int wire_gabor2d_hparam_grad(void* stream, const void* g_act, const void* x, con
  * wire_net_desc_ms: out = SHF, nscales = T, scales_host in HOST memory.  No backward: the stage is frozen.        */
 int wire_mscale_first_fwd(void* stream, const float* x, const float* W, const float* b, int64_t n, int in_features,
                           int out_features, int nscales, const float* scales_host, float* out);
+
+/* ---- the scale combiner of WIRE_KIND_BSPLINE_M2 (AdaptiveScaleCombiner 'freq_combine') on native tensors -----------
+ * t [S][n][O] f32 (pass k's outputs at rows k n ..), W1 [128][S O], b1 [128], W2 [O][128], b2 [O] -> y [n][O];
+ * S in 1..8, O in 1..8.  The backward writes g_t [S][n][O] and gW1, gb1, gW2, gb2 (deterministic: per-block partials
+ * reduced in a fixed order in ws, wire_m2_combine_ws_bytes(nscales, out_features, n) bytes).                         */
+int wire_m2_combine_fwd(void* stream, int nscales, int out_features, const float* W1, const float* b1, const float* W2,
+                        const float* b2, const float* t, int64_t n, float* y);
+int64_t wire_m2_combine_ws_bytes(int nscales, int out_features, int64_t n);
+int wire_m2_combine_bwd(void* stream, int nscales, int out_features, const float* W1, const float* b1, const float* W2,
+                        const float* b2, const float* t, int64_t n, const float* g_y, float* g_t, float* gW1,
+                        float* gb1, float* gW2, float* gb2, void* ws, int64_t ws_bytes);
 
 /* ---- positional encoding (PosEncoding.forward, modules/relu.py:62-75) ----
  * out[n][D + 2 D F]: the raw coordinates, then for each frequency i < F and dimension j < D: sin(2^i pi c_j),

@@ -17,7 +17,8 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libwire_hip.so")
 
-KIND = {"wire": 0, "wire2d": 1, "siren": 2, "gauss": 3, "relu": 4, "bspline_form": 5, "bspline_mscale_HL": 6}
+KIND = {"wire": 0, "wire2d": 1, "siren": 2, "gauss": 3, "relu": 4, "bspline_form": 5, "bspline_mscale_HL": 6,
+        "bspline_mscale_2": 8}
 MS_MAX_SCALES = 8   # WIRE_MS_MAX_SCALES
 ABI_VERSION = 1
 
@@ -31,7 +32,8 @@ SYMBOLS = [
     "wire_adam_step_flat", "wire_blocked_width", "wire_c64_to_blocked",
     "wire_blocked_to_c64", "wire_prof_enable", "wire_prof_read", "wire_tune_set", "wire_tune_get", "wire_avgpool_mse_grad", "wire_layer2d_ws_bytes", "wire_gabor2d_fwd", "wire_gabor2d_bwd", "wire_eval_metric", "wire_real_layer_fwd", "wire_real_layer_bwd", "wire_train_fwd_bwd", "wire_perm_indices", "wire_gabor_hparam_grad", "wire_track_best", "wire_sigmoid_inplace", "wire_radon_fwd", "wire_radon_bwd", "wire_gabor2d_hparam_grad", "wire_posenc_fwd", "wire_act_out_offset", "wire_train_fwd_bwd_hooked",
     "wire_bwd_coords_scratch_bytes", "wire_mlp_bwd_coords", "wire_posenc_bwd", "wire_gabor_bwd_first_coords",
-    "wire_gabor2d_bwd_first_coords", "wire_mscale_first_fwd",
+    "wire_gabor2d_bwd_first_coords", "wire_mscale_first_fwd", "wire_m2_combine_fwd", "wire_m2_combine_ws_bytes",
+    "wire_m2_combine_bwd",
 ]
 
 
@@ -87,6 +89,10 @@ def _declare(l: C.CDLL) -> None:
     l.wire_sigmoid_inplace.argtypes = [vp, vp, i64]
     l.wire_posenc_fwd.argtypes = [vp, vp, i64, i32, i32, vp]
     l.wire_mscale_first_fwd.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, C.POINTER(C.c_float), vp]
+    l.wire_m2_combine_fwd.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]
+    l.wire_m2_combine_ws_bytes.argtypes = [i32, i32, i64]
+    l.wire_m2_combine_ws_bytes.restype = i64
+    l.wire_m2_combine_bwd.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64]
     l.wire_bwd_coords_scratch_bytes.argtypes = [dp, i64]
     l.wire_bwd_coords_scratch_bytes.restype = i64
     l.wire_mlp_bwd_coords.argtypes = [vp, dp, vp, vp, i64, vp, vp, i64, vp, i64, C.POINTER(vp), vp]
@@ -169,6 +175,19 @@ def make_desc_ms(in_features: int, width: int, hidden_layers: int, out_features:
                              hidden_omega0, scale0), int(first_width), len(scales),
                    (C.c_float * MS_MAX_SCALES)(*scales))
     return ms.base
+
+
+def make_desc_m2(in_features: int, width: int, hidden_layers: int, out_features: int, first_omega0: float,
+                 hidden_omega0: float, scale0: float, scales) -> NetDesc:
+    """Descriptor of a bspline_mscale_2 net (kind 8): the ``base`` NetDesc of a NetDescMS with first_width = 0 and one
+    scale per trunk pass; ``scale0`` is carried and ignored."""
+    scales = [float(v) for v in scales]
+    if not 1 <= len(scales) <= MS_MAX_SCALES:
+        raise ValueError(f"{len(scales)} scales: the descriptor takes 1..{MS_MAX_SCALES}")
+    m2 = NetDescMS(make_desc("bspline_mscale_2", in_features, width, hidden_layers, out_features, first_omega0,
+                             hidden_omega0, scale0), 0, len(scales),
+                   (C.c_float * MS_MAX_SCALES)(*(scales + [0.0] * (MS_MAX_SCALES - len(scales)))))
+    return m2.base
 
 
 def ptr_array(ptrs):

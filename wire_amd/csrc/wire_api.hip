@@ -134,6 +134,13 @@ struct Plan {
   bool ms = false;
   int SHF = 0, T = 0, ms_split = 0, t0 = 0;
   float ms_c[WIRE_MS_MAX_SCALES] = {};
+  // WIRE_KIND_BSPLINE_M2 (kind then reads WIRE_KIND_BSPLINE): the trunk runs S2 passes, pass k with c = m2_c[k] (s = the
+  // pass-0 value), its rows at k n of buffers sized for S2 n rows; the combiner's four tensors come first (t0 = 4, the
+  // trunk's native first layer at t0), their copy in the packed buffer at off_comb.  Every other kind: S2 = 1
+  bool m2 = false;
+  int S2 = 1;
+  float m2_c[WIRE_MS_MAX_SCALES] = {};
+  int64_t off_comb = -1;
   // packed image offsets (floats); index l = 0..L (l = 0 only when first_gemm)
   std::vector<int64_t> off_fwd, off_dg, off_bias, off_fwd_x3, off_dg_x3, off_fwd_3m, off_dg_3m, off_fwd_x2, off_dg_x2;
   int64_t off_wf, off_bf, off_first, off_wamax, total_packed;   // off_wamax: max-|weight| slots, WIRE_AMAX_SLOTS per layer
@@ -144,12 +151,34 @@ struct Plan {
   std::vector<int64_t> tfloats;
 };
 
+// params[] index of tensor q of the native first layer: the multi-scale net's frozen first stage is tensors 0, 1; the
+// multi-pass net's first trunk layer follows the combiner (t0)
+inline int first_tensor(const Plan& p, int q) { return p.ms ? q : p.t0 + q; }
+
 int make_plan(const wire_net_desc* d, Plan& p) {
   if (!d) return fail(WIRE_ERR_ARG, "null descriptor");
   p.kind = d->kind; p.D = d->in_features; p.K = d->width; p.L = d->hidden_layers;
   p.O = d->out_features; p.F = d->posenc_freqs;
   p.w1 = d->first_omega0; p.w = d->hidden_omega0; p.s = d->scale0;
-  if (p.kind < WIRE_KIND_WIRE || p.kind > WIRE_KIND_BSPLINE_MS) return fail(WIRE_ERR_ARG, "unknown kind %d", p.kind);
+  if (p.kind < WIRE_KIND_WIRE || (p.kind > WIRE_KIND_BSPLINE_MS && p.kind != WIRE_KIND_BSPLINE_M2))
+    return fail(WIRE_ERR_ARG, "unknown kind %d", p.kind);
+  if (p.kind == WIRE_KIND_BSPLINE_M2) {
+    // modules/bspline_mscale_2.py: the trunk of bspline_form once per entry of scale_tensor (lin / scale_k), `scale` unused
+    const wire_net_desc_ms* m = reinterpret_cast<const wire_net_desc_ms*>(d);
+    if (m->first_width != 0) return fail(WIRE_ERR_ARG, "first_width %d: kind %d has no first stage", m->first_width,
+                                         (int)WIRE_KIND_BSPLINE_M2);
+    p.S2 = m->nscales;
+    if (p.S2 < 1 || p.S2 > WIRE_MS_MAX_SCALES) return fail(WIRE_ERR_ARG, "nscales %d outside 1..%d", p.S2, WIRE_MS_MAX_SCALES);
+    for (int k = 0; k < p.S2; ++k) {
+      const float sk = m->scales[k];
+      if (!(std::isfinite(sk) && sk != 0.f)) return fail(WIRE_ERR_ARG, "scales[%d] %g is zero or not finite", k, (double)sk);
+      p.m2_c[k] = (float)(1.0 / fabs((double)sk));
+    }
+    p.m2 = true;
+    p.kind = WIRE_KIND_BSPLINE;
+    p.s = m->scales[0];
+    p.t0 = 4;
+  }
   if (p.kind == WIRE_KIND_BSPLINE_MS) {
     // modules/bspline_mscale_HL.py: columns [0, min(256, SHF)) divided by scale_tensor[0], group g >= 1 by scale_tensor[g]
     // over [256 + (g - 1) split, 256 + g split); the groups must cover SHF exactly (the next Linear takes SHF columns)
@@ -205,6 +234,9 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   p.ntens = p.t0 + p.per_layer * (p.L + 1) + 2;
   p.tfloats.assign(p.ntens, 0);
   if (p.ms) { p.tfloats[0] = (int64_t)p.SHF * p.D; p.tfloats[1] = p.SHF; }
+  if (p.m2) {   // freq_mlp.0.weight, .0.bias, .2.weight, .2.bias
+    p.tfloats[0] = (int64_t)M2_H * p.S2 * p.O; p.tfloats[1] = M2_H; p.tfloats[2] = (int64_t)p.O * M2_H; p.tfloats[3] = p.O;
+  }
   const int64_t K = p.K, cm = p.cplx ? 2 : 1;
   for (int l = 0; l <= p.L; ++l) {
     const int64_t in = (l == 0) ? p.Din : K;
@@ -247,23 +279,46 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   p.off_wamax = off; off += (int64_t)(p.L + 1) * WIRE_AMAX_SLOTS;
   p.off_fx = -1;
   // (a positional-encoding net -- relu, 64 padded encoded features -- has its GEMM first layer's image, P x 64, in front)
-  const bool fx_ok = p.L >= 1 && fused_fwd_shape(p.kind, p.P) && (!p.first_gemm || (p.kind == WIRE_KIND_RELU && p.Pin0 == 64));
-  if (fx_ok) { p.off_fx = off; off += (p.first_gemm ? (int64_t)p.P * p.Pin0 : 0) + (int64_t)p.L * fused_b_image_floats(p.P); }
+  // (the multi-pass net: one set of hidden images per pass, each with its own c folded in -- fx_pass_off; the chain's
+  // transposed images below carry no c and serve every pass)
+  const bool fx_ok = p.L >= 1 && fused_fwd_shape(p.kind, p.P) &&
+                     (!p.first_gemm || (p.kind == WIRE_KIND_RELU && p.Pin0 == 64));
+  if (fx_ok) {
+    p.off_fx = off;
+    off += (p.first_gemm ? (int64_t)p.P * p.Pin0 : 0) + (int64_t)p.S2 * p.L * fused_b_image_floats(p.P);
+  }
   p.off_fxd = -1;
   if (fx_ok && p.L >= 1 && fused_bwd_shape(p.kind, p.P)) { p.off_fxd = off; off += (int64_t)p.L * fused_b_image_floats(p.P); }
   p.off_wf = off; off += (int64_t)p.O * p.P;
   p.off_bf = off; off += 64;
   p.off_first = off;   // native copies of the first layer's tensors (W0,b0[,V0,c0]; the multi-scale net's first stage)
-  if (!p.first_gemm || p.ms) for (int q = 0; q < p.per_layer; ++q) off += rup((int)p.tfloats[q], 4);
+  if (!p.first_gemm || p.ms) for (int q = 0; q < p.per_layer; ++q) off += rup((int)p.tfloats[first_tensor(p, q)], 4);
+  if (p.m2) {                                              // the combiner's native copy
+    p.off_comb = off;
+    for (int q = 0; q < 4; ++q) off += rup((int)p.tfloats[q], 4);
+  }
   p.total_packed = off;
   return WIRE_OK;
 }
 
 inline int64_t fx_hidden_off(const Plan& p) { return p.off_fx + (p.first_gemm ? (int64_t)p.P * p.Pin0 : 0); }
+// the whole-net forward's hidden images of pass k (the multi-pass net; every other kind: k = 0) and that pass's c
+inline int64_t fx_pass_off(const Plan& p, int k) { return fx_hidden_off(p) + (int64_t)k * p.L * fused_b_image_floats(p.P); }
+inline float pass_c(const Plan& p, int k) { return p.m2 ? p.m2_c[k] : p.s; }
 inline int64_t first_native_off(const Plan& p, int q) {
   int64_t off = p.off_first;
-  for (int i = 0; i < q; ++i) off += rup((int)p.tfloats[i], 4);
+  for (int i = 0; i < q; ++i) off += rup((int)p.tfloats[first_tensor(p, i)], 4);
   return off;
+}
+// the combiner's weights in the packed buffer (the multi-pass net)
+inline M2Comb comb_of(const Plan& p, const float* packed) {
+  M2Comb w;
+  const float* c = packed + p.off_comb;
+  w.W1 = c; c += rup((int)p.tfloats[0], 4);
+  w.b1 = c; c += rup((int)p.tfloats[1], 4);
+  w.W2 = c; c += rup((int)p.tfloats[2], 4);
+  w.b2 = c;
+  return w;
 }
 
 // activation carve (floats)
@@ -272,13 +327,15 @@ struct ActLayout {
   int64_t ping, pong;                    // inference
   int64_t amax;                          // max |out_l| slots, WIRE_AMAX_SLOTS per layer l = 0..L (2 x fp16 GEMMs)
   int64_t pe_amax;                       // the multi-scale net: max |pe| slots right behind them (fp32 pe on 2 x fp16)
+  int64_t ytr;                           // the multi-pass net: the trunk's outputs
   int64_t np;                            // rows each saved buffer is spaced by: n rounded up to 128 -- the fused training
                                          // forward (wire_fused.hip) stores whole 128-row workgroup tiles unconditionally
 };
-ActLayout act_layout(const Plan& p, int64_t n, int save) {
+ActLayout act_layout(const Plan& p, int64_t n1, int save) {
   ActLayout a{};
   int64_t off = 0;
-  a.np = (n + 127) / 128 * 128;
+  const int64_t n = n1 * p.S2;                // the trunk's rows (the multi-pass net: S2 passes of n1)
+  a.np = (n + 127) / 128 * 128 + (p.m2 ? 128 : 0);   // (the multi-pass net: the chain's last tiles read past S2 n1)
   a.amax = off; off += (int64_t)(p.L + 2) * WIRE_AMAX_SLOTS;
   a.pe_amax = off; if (p.ms) off += WIRE_AMAX_SLOTS;
   a.pe = off; if (p.first_gemm) off += n * p.Pin0;
@@ -290,20 +347,25 @@ ActLayout act_layout(const Plan& p, int64_t n, int save) {
     a.ping = off; off += n * p.P;
     a.pong = off; off += n * p.P;
   }
+  a.ytr = off; if (p.m2) off += n * p.O;     // the trunk's outputs [S2][n1][O], the combiner's input
   a.total = off;
   return a;
 }
 
-struct ScratchLayout { int64_t ga, gb, gu, slab, bslab, fpw, fpb, crp, gamax, gch, gch_stride, total; int S; };
-ScratchLayout scratch_layout(const Plan& p, int64_t n) {
+// (the multi-pass net: gtr = the combiner's gradient of the trunk's outputs [S2][n1][O], cpart = its weight-gradient
+// partials, crep = the coordinates once per pass [S2][n1][D] for the first layer's sums over all rows)
+struct ScratchLayout { int64_t ga, gb, gu, slab, bslab, fpw, fpb, crp, gamax, gch, gch_stride, gtr, cpart, crep, total; int S; };
+ScratchLayout scratch_layout(const Plan& p, int64_t n1) {
   ScratchLayout s{};
   int64_t off = 0;
+  const int64_t n = n1 * p.S2;
   s.gamax = off; off += (int64_t)(p.L + 2) * WIRE_AMAX_SLOTS;   // max |g_lin_l| slots (2 x fp16 GEMMs)
   s.ga = off; off += n * p.Pl;
   s.gb = off; off += n * p.Pl;
   // the data-gradient chain (wire_fused.hip: fused_bwd_kernel) keeps EVERY g_lin_l (l = 1 .. L; the weight-gradient GEMMs
   // run after it), rows padded to 128: g_lin_l at gch + l * gch_stride
-  s.gch = -1; s.gch_stride = (n + 127) / 128 * 128 * p.Pl;
+  // (the multi-pass net: 128 rows more -- the last pass's whole workgroup tiles start at (S2 - 1) n1)
+  s.gch = -1; s.gch_stride = ((n + 127) / 128 * 128 + (p.m2 ? 128 : 0)) * p.Pl;
   if (p.off_fxd >= 0) { s.gch = off; off += (int64_t)(p.L + 1) * s.gch_stride; }
   s.gu = off; if (p.cplx) off += n * p.ldu * (p.kind == WIRE_KIND_WIRE2D ? 2 : 1);
   const int64_t pn = p.first_gemm && p.Pin0 > p.P ? p.Pin0 : p.P;
@@ -332,13 +394,20 @@ ScratchLayout scratch_layout(const Plan& p, int64_t n) {
     s.bslab = off; off += needb3 > full ? needb3 : full;
   }
   // + pre-reduction scratch; the training forward with the final stage inside writes one block per 128-row workgroup
-  const int nbf = (p.off_fx >= 0 && !p.cplx ? 2 : 1) * final_bwd_blocks(n) + 32;
+  // (the multi-pass net: one set of blocks per pass)
+  const int nbf = (p.off_fx >= 0 && !p.cplx ? 2 : 1) * p.S2 * final_bwd_blocks(n1) + 32;
   s.fpw = off; off += (int64_t)nbf * p.O * p.P;
   s.fpb = off; off += (int64_t)nbf * p.O + 64;
   // (wire2d: two sets, one per Linear of the first layer, when the data-gradient epilogue forms the sums itself)
   // (the data-gradient chain writes one block of first-layer sums per 64- or 128-row workgroup: 4 x the 256-row blocks)
   s.crp = off; off += (int64_t)((p.off_fxd >= 0 ? 4 : 1) * colreduce_blocks(n) + 32) * (p.cplx ? p.ldu : p.P) * 5 *
                       (p.kind == WIRE_KIND_WIRE2D ? 2 : 1);
+  s.gtr = s.cpart = s.crep = off;
+  if (p.m2) {
+    s.gtr = off; off += n * p.O;
+    s.cpart = off; off += (int64_t)m2_comb_blocks(n1) * m2_comb_grad_floats(p.S2, p.O) + M2_COMB_MAXBLK;   // + loss partials
+    s.crep = off; off += n * p.D;
+  }
   s.total = off;
   return s;
 }
@@ -347,11 +416,12 @@ ScratchLayout scratch_layout(const Plan& p, int64_t n) {
 // data-gradient epilogue, one set per 128-column tile of that GEMM's output [tile][n][D], and positional-encoding nets'
 // g_pe [n][Pin0]
 struct CoordLayout { int64_t cgp, gpe, total; int ntiles; };
+// (the multi-pass net: cgp holds the per-pass coordinate gradients [S2][n1][D] before their sum)
 CoordLayout coord_layout(const Plan& p, int64_t n) {
   CoordLayout c{};
   int64_t off = (scratch_layout(p, n).total + 63) / 64 * 64;
   c.ntiles = (p.P + 127) / 128;
-  c.cgp = off; off += (int64_t)c.ntiles * n * p.D;
+  c.cgp = off; off += (int64_t)c.ntiles * n * p.S2 * p.D;
   off = (off + 63) / 64 * 64;
   c.gpe = off; if (p.first_gemm) off += n * p.Pin0;
   c.total = off;
@@ -442,10 +512,13 @@ Route make_route(const Plan& p, int64_t n, RouteMode mode) {
     if (p.Pin0 >= p.P && gemmx2_tn_applies(p.Pl, p.Pin0)) { r.tn0 = FAM_X2; r.pe_split = 32768.f; }
   }
   r.tn_fam = p.m3 ? FAM_3M : x2tn ? FAM_X2 : p.x3 ? FAM_X3 : FAM_4M;
+  // (the multi-pass net: n rows per pass decide the forward and data-gradient kernels, its weight gradients reduce over
+  // all S2 n rows at once)
+  const int64_t nt = n * p.S2;
   const int S_max = scratch_layout(p, n).S;
   r.tn_S = r.tn_fam == FAM_3M ? S_max
-         : r.tn_fam == FAM_X2 ? gemmx2_tn_splits(n, p.Pl, p.P, S_max)
-         : r.tn_fam == FAM_X3 ? gemmx3_tn_splits(n, p.Pl, p.P, S_max) : gemm_tn_splits(n, p.Pl, p.P, S_max);
+         : r.tn_fam == FAM_X2 ? gemmx2_tn_splits(nt, p.Pl, p.P, S_max)
+         : r.tn_fam == FAM_X3 ? gemmx3_tn_splits(nt, p.Pl, p.P, S_max) : gemm_tn_splits(nt, p.Pl, p.P, S_max);
   // a hidden layer whose forward ran the lean 16 x 16 x 32 epilogue: its out = act(lin) again, 8 B / element less (real
   // nets: only below a hidden layer -- the first layer's out comes from first_fwd_kernel's precise form)
   r.recompute_out = p.k_recompute_out && p.x3 && h16_fwd;
@@ -460,14 +533,18 @@ Route make_route(const Plan& p, int64_t n, RouteMode mode) {
   // decides the FORMAT of the stored out_l (pre-split at scale 1), so it is asked in every mode
   const bool ftrain = fx && x2tn && p.k_fused_train && p.k_split_out && p.k_recompute_out &&
                       !(p.kind == WIRE_KIND_WIRE && p.P > 256 && !p.k_fused_train_p384);
-  r.fuse = mode == MODE_TRAIN && p.L >= 1 && p.O <= 4 && final_fused_supported(p.P, p.O);
+  // (the multi-pass net's loss sits behind its combiner: no final stage with the MSE inside)
+  r.fuse = mode == MODE_TRAIN && p.L >= 1 && p.O <= 4 && !p.m2 && final_fused_supported(p.P, p.O);
   r.skip_out_L = r.fuse && r.recompute_out && p.kind != WIRE_KIND_RELU;
   r.fused_train = r.fuse && ftrain && (r.skip_out_L || p.kind == WIRE_KIND_RELU);
   // chain => fused_train, by construction: the chain reads g_lin_L and lin_l / r_l as only the fused training forward
-  // stores them
-  r.chain = r.fused_train && p.k_fused_bwd && p.off_fxd >= 0;
-  r.fused_final = r.chain && !p.cplx && p.k_fused_final;
-  r.rstore = r.chain && p.k_rstore &&
+  // stores them.  The multi-pass net's training forward runs layer by layer (its loss sits behind the combiner); that
+  // stores every lin_l in fp32 in the reference's units, the form the chain reads without rstore, and its per-pass
+  // final backward leaves g_lin_L where the chain reads it: the chain runs once per pass with that pass's c
+  const bool m2_chain = p.m2 && mode == MODE_TRAIN && fx && x2tn;
+  r.chain = (r.fused_train || m2_chain) && p.k_fused_bwd && p.off_fxd >= 0;
+  r.fused_final = r.chain && r.fused_train && !p.cplx && p.k_fused_final;
+  r.rstore = r.chain && r.fused_train && p.k_rstore &&
              (p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_GAUSS || p.kind == WIRE_KIND_BSPLINE);   // 1.3 GB per step less
   // out_l is stored pre-split (wire_dev.h: wire_store_out4) when the call runs the 2 x fp16 kernels and every reader of
   // out_l understands the format: the forward GEMM of layer l + 1 (pre-split A edition), the weight-gradient GEMM of layer
@@ -482,7 +559,8 @@ Route make_route(const Plan& p, int64_t n, RouteMode mode) {
   const int epi1 = p.kind == WIRE_KIND_WIRE ? EPI_GABOR_BWD_FIRST
                  : p.kind == WIRE_KIND_WIRE2D ? EPI_GABOR2D_BWD_FIRST : epi_bwd(p.kind);
   const bool h16_1 = p.x3 && gemmx3_nt_is_h16(epi1, n);
-  r.cg_epi = h16_1 && !p.first_gemm && p.L >= 1;
+  // (the multi-pass net: its layer-1 data gradient runs once per pass, its first-layer sums over all passes at once)
+  r.cg_epi = h16_1 && !p.first_gemm && p.L >= 1 && !p.m2;
   r.first_sums = r.cg_epi && p.k_first_sums;
   r.recompute_out0 = h16_1 && p.kind == WIRE_KIND_WIRE && p.k_recompute_out;
   // behind the chain every g_lin_l exists before the first weight gradient starts: those of layers 2 .. L (same shape,
@@ -639,15 +717,16 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
       HIPCHK(launch_amax_batch(s, ab, nb, (int64_t)p.Pl * p.P));
       HIPCHK(launch_x2_split_b_batch(s, xf, nb, p.P, p.Pl, p.P));
       HIPCHK(launch_x2_split_b_batch(s, xd, nb, p.Pl, p.P, p.Pl));
-      if (p.off_fx >= 0 && fused_pre_scale(p.kind, p.w, p.s) > 0.f) {   // the fused forward's edition of the forward image
+      // the fused forward's edition of the forward image (the multi-pass net: one per pass, its c folded in)
+      for (int k = 0; k < p.S2 && p.off_fx >= 0 && fused_pre_scale(p.kind, p.w, pass_c(p, k)) > 0.f; ++k) {
         FxSplitBatch fx{};
         for (int i = 0; i < nb; ++i) {
           const int l = l0 + i;
           fx.src[i] = packed + p.off_fwd[l];
-          fx.dst[i] = packed + fx_hidden_off(p) + (int64_t)(l - 1) * fused_b_image_floats(p.P);
+          fx.dst[i] = packed + fx_pass_off(p, k) + (int64_t)(l - 1) * fused_b_image_floats(p.P);
           fx.slots[i] = ab.slots[i];
         }
-        HIPCHK(launch_fx_split_b_batch(s, fx, nb, p.P, p.P, fused_pre_scale(p.kind, p.w, p.s)));
+        HIPCHK(launch_fx_split_b_batch(s, fx, nb, p.P, p.P, fused_pre_scale(p.kind, p.w, pass_c(p, k))));
       }
       if (p.off_fxd >= 0) {                                // the data-gradient chain's: transposed images, layers L .. 1
         FxSplitBatch fd{};
@@ -668,8 +747,14 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
                            packed + p.off_bf));
   if (!p.first_gemm || p.ms)   // (the multi-scale net: its first stage, read by mscale_first_kernel)
     for (int q = 0; q < p.per_layer; ++q)
-      HIPCHK(hipMemcpyAsync(packed + first_native_off(p, q), params[q], p.tfloats[q] * 4,
+      HIPCHK(hipMemcpyAsync(packed + first_native_off(p, q), params[first_tensor(p, q)], p.tfloats[first_tensor(p, q)] * 4,
                             hipMemcpyDeviceToDevice, s));
+  if (p.m2) {                  // the combiner, read by the m2_comb kernels
+    const M2Comb w = comb_of(p, packed);
+    const float* dst[4] = {w.W1, w.b1, w.W2, w.b2};
+    for (int q = 0; q < 4; ++q)
+      HIPCHK(hipMemcpyAsync(const_cast<float*>(dst[q]), params[q], p.tfloats[q] * 4, hipMemcpyDeviceToDevice, s));
+  }
   return WIRE_OK;
 }
 
@@ -710,6 +795,21 @@ static int mlp_fwd_core(void* stream, const Plan& p, const Route& r, const float
   if (r.fused_fwd) {
     FusedFwdParams fp = fused_params(p, packed, coords, n);
     fp.wf = packed + p.off_wf; fp.bfr = packed + p.off_bf; fp.y = y;
+    if (p.m2) {
+      // once per pass: that pass's images (its c folded in) and c, the trunk's outputs at rows k n; then the combiner
+      for (int k = 0; k < p.S2; ++k) {
+        FusedFwdParams f = fp;
+        f.wimg = reinterpret_cast<const unsigned char*>(packed + fx_pass_off(p, k));
+        f.s = p.m2_c[k];
+        f.c_first = fused_pre_scale(p.kind, p.w1, f.s); f.c_hidden = fused_pre_scale(p.kind, p.w, f.s);
+        f.y = A + a.ytr + (int64_t)k * n * p.O;
+        ProfScope ps(s, 0, 2.0 * n * p.Pl * p.P * p.L);
+        HIPCHK(launch_fused_fwd(s, p.kind, p.P, f));
+      }
+      ProfScope ps(s, 3, 0);
+      HIPCHK(launch_m2_comb_fwd(s, comb_of(p, packed), p.S2, p.O, A + a.ytr, n, y));
+      return WIRE_OK;
+    }
     ProfScope ps(s, 0, 2.0 * n * p.Pl * p.P * p.L);
     HIPCHK(launch_fused_fwd(s, p.kind, p.P, fp));
     return WIRE_OK;
@@ -756,37 +856,51 @@ static int mlp_fwd_core(void* stream, const Plan& p, const Route& r, const float
     if (!save || p.kind == WIRE_KIND_RELU) return nullptr;
     return l == 0 ? A + a.lin0 : A + a.lin1 + (int64_t)(l - 1) * a.np * p.Pl;
   };
-  // ---- layer 0
-  if (p.first_gemm) {
-    GemmEpiParams ep; ep.bias = packed + p.off_bias[0]; ep.o0 = lin_l(0); ep.o1 = out_l(0);
-    ep.ld0 = p.Pl; ep.ld1 = p.P; ep.omega = p.w1; ep.scale = p.s; ep.kvalid = p.K;
-    if (r.fam == FAM_X2) ep.amax_out = amax;             // (the 3 x bf16 16 x 16 x 32 kernel tracks the maximum too)
-    if (r.pe_split != 0.f) ep.a_split_inv = 1.f / r.pe_split;
-    ProfScope ps(s, 0, 2.0 * n * p.Pl * p.Pin0);
-    HIPCHK(layer_nt(s, p, r.fam0, packed, 0, false, epi_fwd(p.kind), A + a.pe, n, ep, pe_amax, wamax_of(p, packed, 0),
-                    amax));
-  } else {
-    auto first = [&](int q) { return q < p.per_layer ? packed + first_native_off(p, q) : nullptr; };   // W0, b0 [, V0, c0]
-    ProfScope ps(s, 3, 0);
-    HIPCHK(launch_first_fwd(s, p.kind, coords, n, p.D, first(0), first(1), first(2), first(3), p.K, p.P, p.w1, p.s,
-                            p.cplx ? nullptr : lin_l(0), out_l(0), r.fam == FAM_X2 ? amax : nullptr));
-  }
-  // ---- hidden layers
-  for (int l = 1; l <= p.L; ++l) {
-    GemmEpiParams ep; ep.bias = packed + p.off_bias[l]; ep.o0 = lin_l(l); ep.o1 = out_l(l);
-    ep.ld0 = p.Pl; ep.ld1 = p.P; ep.omega = p.w; ep.scale = p.s; ep.kvalid = p.K;
-    if (r.skip_out_L && l == p.L) ep.o1 = nullptr;       // the final stage recomputes it
-    // pre-split activations: out_{l-1} read as such, out_l written as such (its maximum slots stay zero: not read)
-    const float s_in = r.out_scale[l - 1], s_out = r.out_scale[l];
-    if (s_in != 0.f) ep.a_split_inv = 1.f / s_in;
-    if (s_out != 0.f) ep.o1_split = s_out;
-    ProfScope ps(s, 0, 2.0 * n * p.Pl * p.P);
-    HIPCHK(layer_nt(s, p, r.fam, packed, l, false, epi_fwd(p.kind), out_l(l - 1), n, ep, amax + (l - 1) * WIRE_AMAX_SLOTS,
-                    wamax_of(p, packed, l), s_out != 0.f ? nullptr : amax + l * WIRE_AMAX_SLOTS));
+  // the multi-pass net: the trunk once per pass k with c = m2_c[k], its rows at k n of every buffer (every other kind:
+  // one pass, offset 0, c = s); the maxima of the 2 x fp16 kernels gather over the passes (slots zeroed once above)
+  auto at = [](float* b, int64_t off) -> float* { return b ? b + off : nullptr; };
+  for (int k = 0; k < p.S2; ++k) {
+    const float ck = p.m2 ? p.m2_c[k] : p.s;
+    const int64_t ro = (int64_t)k * n;
+    // ---- layer 0
+    if (p.first_gemm) {
+      GemmEpiParams ep; ep.bias = packed + p.off_bias[0]; ep.o0 = lin_l(0); ep.o1 = out_l(0);
+      ep.ld0 = p.Pl; ep.ld1 = p.P; ep.omega = p.w1; ep.scale = p.s; ep.kvalid = p.K;
+      if (r.fam == FAM_X2) ep.amax_out = amax;             // (the 3 x bf16 16 x 16 x 32 kernel tracks the maximum too)
+      if (r.pe_split != 0.f) ep.a_split_inv = 1.f / r.pe_split;
+      ProfScope ps(s, 0, 2.0 * n * p.Pl * p.Pin0);
+      HIPCHK(layer_nt(s, p, r.fam0, packed, 0, false, epi_fwd(p.kind), A + a.pe, n, ep, pe_amax, wamax_of(p, packed, 0),
+                      amax));
+    } else {
+      // W0, b0 [, V0, c0]
+      auto first = [&](int q) { return q < p.per_layer ? packed + first_native_off(p, q) : nullptr; };
+      ProfScope ps(s, 3, 0);
+      HIPCHK(launch_first_fwd(s, p.kind, coords, n, p.D, first(0), first(1), first(2), first(3), p.K, p.P, p.w1, ck,
+                              p.cplx ? nullptr : at(lin_l(0), ro * p.P), out_l(0) + ro * p.P,
+                              r.fam == FAM_X2 ? amax : nullptr));
+    }
+    // ---- hidden layers
+    for (int l = 1; l <= p.L; ++l) {
+      GemmEpiParams ep; ep.bias = packed + p.off_bias[l]; ep.o0 = at(lin_l(l), ro * p.Pl); ep.o1 = out_l(l) + ro * p.P;
+      ep.ld0 = p.Pl; ep.ld1 = p.P; ep.omega = p.w; ep.scale = ck; ep.kvalid = p.K;
+      if (r.skip_out_L && l == p.L) ep.o1 = nullptr;       // the final stage recomputes it
+      // pre-split activations: out_{l-1} read as such, out_l written as such (its maximum slots stay zero: not read)
+      const float s_in = r.out_scale[l - 1], s_out = r.out_scale[l];
+      if (s_in != 0.f) ep.a_split_inv = 1.f / s_in;
+      if (s_out != 0.f) ep.o1_split = s_out;
+      ProfScope ps(s, 0, 2.0 * n * p.Pl * p.P);
+      HIPCHK(layer_nt(s, p, r.fam, packed, l, false, epi_fwd(p.kind), out_l(l - 1) + ro * p.P, n, ep,
+                      amax + (l - 1) * WIRE_AMAX_SLOTS, wamax_of(p, packed, l),
+                      s_out != 0.f ? nullptr : amax + l * WIRE_AMAX_SLOTS));
+    }
   }
   if (!r.fuse) {
     ProfScope ps(s, 3, 0);
-    HIPCHK(launch_final_fwd(s, out_l(p.L), n, p.P, p.O, packed + p.off_wf, packed + p.off_bf, y));
+    // (the multi-pass net: the final linear of every pass in one launch, then the combiner -- the training call runs
+    // the combiner inside its backward, with the loss)
+    HIPCHK(launch_final_fwd(s, out_l(p.L), n * p.S2, p.P, p.O, packed + p.off_wf, packed + p.off_bf,
+                            p.m2 ? A + a.ytr : y));
+    if (p.m2 && r.mode != MODE_TRAIN) HIPCHK(launch_m2_comb_fwd(s, comb_of(p, packed), p.S2, p.O, A + a.ytr, n, y));
   }
   return WIRE_OK;
 }
@@ -805,7 +919,8 @@ extern "C" int wire_mlp_fwd(void* stream, const wire_net_desc* d, const float* p
 namespace {
 struct Bwd {
   const Plan& p; const Route& r; hipStream_t s;
-  const float* packed; const float* coords; int64_t n;
+  const float* packed; const float* coords; int64_t n;   // (coords: the multi-pass net's per-pass copies, see below)
+  int64_t n1;                  // rows of one pass: the multi-pass net runs S2 passes (n = S2 n1), every other kind n1 = n
   const float* g_y;            // null when the training call ran the final stage (r.fuse)
   void* const* grads;          // null (wire_mlp_bwd_coords only): the data gradients and g_coords alone -- no
                                // weight-gradient GEMM, no reduction
@@ -844,11 +959,16 @@ int Bwd::final_stage() {
       HIPCHK(launch_final_bwd(s, p.kind, 1, g_y, n, p.O, packed + p.off_wf, nullptr, out_l(0), p.K, p.P, wL, p.s, gcur,
                               Sx + sc.fpw, Sx + sc.fpb));
     else
-      HIPCHK(launch_final_bwd(s, p.kind, 0, g_y, n, p.O, packed + p.off_wf, lin_l(p.L), out_l(p.L), p.K, p.P, wL, p.s,
-                              gcur, Sx + sc.fpw, Sx + sc.fpb, r.fam == FAM_X2 ? gslots(p.L) : nullptr));
+      for (int k = 0; k < p.S2; ++k) {   // (the multi-pass net: per pass, with its c; partial blocks side by side)
+        const int64_t ro = (int64_t)k * n1, bo = (int64_t)k * final_bwd_blocks(n1);
+        HIPCHK(launch_final_bwd(s, p.kind, 0, g_y + ro * p.O, n1, p.O, packed + p.off_wf, lin_l(p.L) + ro * p.Pl,
+                                out_l(p.L) + ro * p.P, p.K, p.P, wL, p.m2 ? p.m2_c[k] : p.s, gcur + ro * p.P,
+                                Sx + sc.fpw + bo * p.O * p.P, Sx + sc.fpb + bo * p.O,
+                                r.fam == FAM_X2 ? gslots(p.L) : nullptr));
+      }
     if (!grads) return WIRE_OK;
   }
-  const int nbf = r.fused_final ? (int)((n + 127) / 128) : final_bwd_blocks(n);
+  const int nbf = r.fused_final ? (int)((n + 127) / 128) : p.S2 * final_bwd_blocks(n1);
   HIPCHK(launch_final_reduce(s, p.kind, Sx + sc.fpw, Sx + sc.fpb, nbf, p.O, p.K, p.P, grad(p.ntens - 2),
                              grad(p.ntens - 1)));
   done(p.ntens - 2, 2);
@@ -886,6 +1006,21 @@ int Bwd::chain() {
   bp.aux0 = relu ? A + a.out0 : A + a.lin0;
   bp.w1 = p.w1;
   if (!p.first_gemm) { bp.coords = coords; bp.D = p.D; bp.crp = Sx + sc.crp; bp.C = p.K; }
+  if (p.m2) {
+    // once per pass: its rows, its c, its blocks of first-layer sums behind the previous pass's (the coordinates are the
+    // same n1 rows for every pass); first_params reduces all S2 sets at once
+    bp.n = n1;
+    for (int k = 0; k < p.S2; ++k) {
+      const int64_t ro = (int64_t)k * n1;
+      FusedBwdParams b = bp;
+      b.g = bp.g + ro * p.P; b.aux = bp.aux + ro * p.P; b.aux0 = bp.aux0 + ro * p.P;
+      b.s = p.m2_c[k]; b.c_hidden = fused_pre_scale(p.kind, p.w, p.m2_c[k]);
+      if (k > 0) b.crp = bp.crp + (int64_t)k * ((n1 + chain_rows - 1) / chain_rows) * p.K * 5;
+      ProfScope ps(s, 1, 2.0 * n1 * p.Pl * p.P * p.L);
+      HIPCHK(launch_fused_bwd(s, p.kind, p.P, b, &chain_rows));   // (pass 0 sets chain_rows before pass 1 reads it)
+    }
+    return WIRE_OK;
+  }
   ProfScope ps(s, 1, 2.0 * n * p.Pl * p.P * p.L);
   HIPCHK(launch_fused_bwd(s, p.kind, p.P, bp, &chain_rows));
   return WIRE_OK;
@@ -976,9 +1111,15 @@ int Bwd::layers() {
       if (!p.cplx) ep.W0 = first(0);
     }
     // (g_lin_0 feeds no 2 x fp16 GEMM -- no maximum kept -- except the multi-scale net's SHF -> K weight gradient)
-    { ProfScope ps(s, 1, 2.0 * n * p.Pl * p.P);
-      HIPCHK(layer_nt(s, p, r.fam, packed, l, true, epi, gcur, n, ep, gslots(l), wamax_of(p, packed, l),
-                      l >= 2 || r.tn0 == FAM_X2 ? gslots(l - 1) : nullptr)); }
+    // (the multi-pass net: once per pass, with its c and its rows; g_lin_{l-1}'s maximum gathers over the passes)
+    for (int k = 0; k < p.S2; ++k) {
+      const int64_t ro = (int64_t)k * n1;
+      GemmEpiParams e = ep;
+      if (k > 0) { e.scale = p.m2_c[k]; e.i0 += ro * p.Pl; e.i1 += ro * p.P; e.o0 += ro * e.ld0; }
+      ProfScope ps(s, 1, 2.0 * n1 * p.Pl * p.P);
+      HIPCHK(layer_nt(s, p, r.fam, packed, l, true, epi, gcur + ro * p.Pl, n1, e, gslots(l), wamax_of(p, packed, l),
+                      l >= 2 || r.tn0 == FAM_X2 ? gslots(l - 1) : nullptr));
+    }
     float* t = gcur; gcur = gnext; gnext = t;
   }
   return WIRE_OK;
@@ -996,6 +1137,9 @@ int Bwd::coords_grad() {
     HIPCHK(launch_coordgrad_rows(s, gu, p.ldu, nullptr, first(0), nullptr, p.K, p.D, n, g_coords));
   } else if (p.kind == WIRE_KIND_WIRE2D) {
     HIPCHK(launch_coordgrad_rows(s, gu, 2 * p.ldu, gu + p.ldu, first(0), first(2), p.K, p.D, n, g_coords));
+  } else if (p.m2) {           // every pass's rows, then their sum (g_lin_0 holds each pass's c already)
+    HIPCHK(launch_coordgrad_rows(s, gcur, p.P, nullptr, first(0), nullptr, p.K, p.D, n, Sx + cl.cgp));
+    HIPCHK(launch_m2_sum_passes(s, Sx + cl.cgp, p.S2, n1, p.D, g_coords));
   } else if (!p.first_gemm) {
     HIPCHK(launch_coordgrad_rows(s, gcur, p.P, nullptr, first(0), nullptr, p.K, p.D, n, g_coords));
   } else {
@@ -1024,11 +1168,13 @@ int Bwd::first_params() {
       HIPCHK(launch_colreduce(s, gu + p.ldu, 2 * p.ldu, p.K, coords, p.D, n, crp, grad(2), grad(3)));
     }
   } else if (!p.first_gemm && r.chain) {
-    HIPCHK(launch_colreduce_final_blocks(s, p.K, p.D, (int)((n + chain_rows - 1) / chain_rows), crp, grad(0), grad(1)));
+    // (the multi-pass net: S2 sets of blocks, one per pass)
+    HIPCHK(launch_colreduce_final_blocks(s, p.K, p.D, p.S2 * (int)((n1 + chain_rows - 1) / chain_rows), crp, grad(p.t0),
+                                         grad(p.t0 + 1)));
   } else if (!p.first_gemm && r.first_sums) {
     HIPCHK(launch_colreduce_final(s, p.K, p.D, n, crp, grad(0), grad(1)));
-  } else if (!p.first_gemm) {
-    HIPCHK(launch_colreduce(s, gcur, p.P, p.K, coords, p.D, n, crp, grad(0), grad(1)));   // gcur: g_lin_0 [n][P]
+  } else if (!p.first_gemm) {   // (the multi-pass net: coords = the per-pass copies, n = all passes' rows)
+    HIPCHK(launch_colreduce(s, gcur, p.P, p.K, coords, p.D, n, crp, grad(p.t0), grad(p.t0 + 1)));   // gcur: g_lin_0 [n][P]
   } else if (r.tn0 == FAM_X2) {                             // the multi-scale net: g_lin_0^T [pe | 1], pe pre-split
     const int S = gemmx2_tn_splits(n, p.P, p.Pin0, sc.S);
     HIPCHK(launch_gemmx2_tn(s, gcur, p.P, A + a.pe, p.Pin0, n, p.P, p.Pin0, S, Sx + sc.slab, Sx + sc.bslab, gslots(0),
@@ -1053,14 +1199,16 @@ int Bwd::first_params() {
 static int mlp_bwd_core(void* stream, const Plan& p, const Route& r, const float* packed, const float* coords, int64_t n,
                         const float* g_y, const void* act, int64_t act_bytes, void* scratch, int64_t scratch_bytes,
                         void* const* grads, wire_grad_ready_fn ready = nullptr, void* user = nullptr,
-                        float* g_coords = nullptr) {
+                        float* g_coords = nullptr, bool comb_done = false) {
   if (n <= 0) return fail(WIRE_ERR_ARG, "backward needs n > 0");
-  if (!packed || !coords || (!r.fuse && !g_y) || !act || !scratch || (!grads && !g_coords))
+  // (the multi-pass net's training call ran its combiner's backward with the loss: comb_done, g_y not read)
+  if (!packed || !coords || (!r.fuse && !g_y && !comb_done) || !act || !scratch || (!grads && !g_coords))
     return fail(WIRE_ERR_ARG, "null pointer");
-  if (grads) for (int i = p.t0; i < p.ntens; ++i) if (!grads[i]) return fail(WIRE_ERR_ARG, "grads[%d] is null", i);
+  if (grads)
+    for (int i = p.ms ? p.t0 : 0; i < p.ntens; ++i) if (!grads[i]) return fail(WIRE_ERR_ARG, "grads[%d] is null", i);
   if (p.ms && g_coords) return fail(WIRE_ERR_ARG, "no coordinate gradient through the frozen first stage of kind %d",
                                     (int)WIRE_KIND_BSPLINE_MS);
-  Bwd c{p, r, (hipStream_t)stream, packed, coords, n, g_y, grads, g_coords, ready, user, act_layout(p, n, 1),
+  Bwd c{p, r, (hipStream_t)stream, packed, coords, n * p.S2, n, g_y, grads, g_coords, ready, user, act_layout(p, n, 1),
         scratch_layout(p, n), coord_layout(p, n), (const float*)act, (float*)scratch};
   const int64_t need = g_coords ? c.cl.total : c.sc.total;
   if (act_bytes < c.a.total * 4) return fail(WIRE_ERR_SIZE, "act buffer too small");
@@ -1068,6 +1216,27 @@ static int mlp_bwd_core(void* stream, const Plan& p, const Route& r, const float
                                             (long long)scratch_bytes, (long long)need * 4);
   c.gcur = c.Sx + c.sc.ga;
   c.gnext = c.Sx + c.sc.gb;
+  if (p.m2) {
+    // the combiner: g_y -> the trunk's output gradients (all passes) and its weight gradients, announced first; the
+    // trunk's backward then reads them as its g_y.  Without the chain its first-layer sums (colreduce over all S2 n1
+    // rows) read the coordinates once per pass; the chain reads the n1 rows per pass itself
+    ProfScope ps(c.s, 3, 0);
+    float* const part = c.Sx + c.sc.cpart;
+    if (!comb_done)
+      HIPCHK(launch_m2_comb_bwd(c.s, comb_of(p, packed), p.S2, p.O, c.A + c.a.ytr, n, M2Loss{}, g_y, c.Sx + c.sc.gtr,
+                                grads ? part : nullptr, nullptr));
+    if (r.chain) c.gcur = c.Sx + c.sc.gch + (int64_t)p.L * c.sc.gch_stride;   // g_lin_L where the chain reads it
+    if (grads) {
+      HIPCHK(launch_m2_comb_reduce(c.s, part, n, p.S2, p.O,
+                                   M2Grads{c.grad(0), c.grad(1), c.grad(2), c.grad(3)}));
+      c.done(0, 4);
+      for (int k = 0; k < p.S2 && !r.chain; ++k)
+        HIPCHK(hipMemcpyAsync(c.Sx + c.sc.crep + (int64_t)k * n * p.D, coords, (size_t)n * p.D * sizeof(float),
+                              hipMemcpyDeviceToDevice, c.s));
+      if (!r.chain) c.coords = c.Sx + c.sc.crep;
+    }
+    c.g_y = c.Sx + c.sc.gtr;
+  }
   // (the fused path zeroed the slots before its final stage published max |g_lin_L|)
   if (r.fam == FAM_X2 && !r.fuse)
     HIPCHK(hipMemsetAsync(c.gslots(0), 0, (size_t)(p.L + 2) * WIRE_AMAX_SLOTS * sizeof(unsigned), c.s));
@@ -1115,6 +1284,27 @@ extern "C" int wire_train_fwd_bwd_hooked(void* stream, const wire_net_desc* d, c
   if (!target || !y || !g_y || !loss_out || !partial) return fail(WIRE_ERR_ARG, "null pointer");
   hipStream_t s = (hipStream_t)stream;
   const Route r = make_route(p, n, MODE_TRAIN);
+  if (p.m2) {
+    // the trunk's passes; then ONE kernel runs the combiner's forward, the MSE, its gradient and the combiner's backward
+    // (g_y of every trunk row + per-block weight-gradient and loss partials); the trunk's backward follows
+    const ScratchLayout sc = scratch_layout(p, n);
+    if (!scratch || scratch_bytes < sc.total * 4) return fail(WIRE_ERR_SIZE, "scratch too small");
+    if (!act || act_bytes < act_layout(p, n, 1).total * 4) return fail(WIRE_ERR_SIZE, "act buffer too small");
+    if (int rc = mlp_fwd_core(stream, p, r, packed, coords, n, y, act, act_bytes)) return rc;
+    float* Sx = (float*)scratch;
+    const int nblk = m2_comb_blocks(n);
+    float* const loss_part = Sx + sc.cpart + (int64_t)nblk * m2_comb_grad_floats(p.S2, p.O);
+    const double inv_no = 1.0 / ((double)n * (double)p.O);
+    M2Loss ls;
+    ls.target = target; ls.idx = idx; ls.first = first; ls.gscale = (float)(weight * 2.0 * inv_no);
+    ls.y = y; ls.g_y = g_y; ls.rec = rec;
+    { ProfScope ps(s, 3, 0);
+      HIPCHK(launch_m2_comb_bwd(s, comb_of(p, packed), p.S2, p.O, (const float*)act + act_layout(p, n, 1).ytr, n, ls,
+                                nullptr, Sx + sc.gtr, Sx + sc.cpart, loss_part));
+      HIPCHK(launch_mse_final(s, loss_part, nblk, (float)(weight * inv_no), loss_out)); }
+    return mlp_bwd_core(stream, p, r, packed, coords, n, nullptr, act, act_bytes, scratch, scratch_bytes, grads, ready, user,
+                        nullptr, true);
+  }
   if (!r.fuse) {
     if (int rc = mlp_fwd_core(stream, p, r, packed, coords, n, y, act, act_bytes)) return rc;
     { ProfScope ps(s, 3, 0);
@@ -1260,6 +1450,34 @@ extern "C" int wire_mscale_first_fwd(void* stream, const float* x, const float* 
   MscaleC c{};
   for (int g = 0; g < p.T; ++g) c.c[g] = p.ms_c[g];
   HIPCHK(launch_mscale_first((hipStream_t)stream, x, n, in_features, W, b, p.SHF, c, p.ms_split, p.SHF, 0.f, nullptr, out));
+  return WIRE_OK;
+}
+static bool m2_shape_ok(int S, int O) { return S >= 1 && S <= WIRE_MS_MAX_SCALES && O >= 1 && O <= 8; }
+extern "C" int wire_m2_combine_fwd(void* stream, int nscales, int out_features, const float* W1, const float* b1,
+                                   const float* W2, const float* b2, const float* t, int64_t n, float* y) {
+  if (!m2_shape_ok(nscales, out_features) || n < 0 || !W1 || !b1 || !W2 || !b2 || (n > 0 && (!t || !y)))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_m2_combine_fwd");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_m2_comb_fwd((hipStream_t)stream, M2Comb{W1, b1, W2, b2}, nscales, out_features, t, n, y));
+  return WIRE_OK;
+}
+extern "C" int64_t wire_m2_combine_ws_bytes(int nscales, int out_features, int64_t n) {
+  if (!m2_shape_ok(nscales, out_features) || n < 0) return fail(WIRE_ERR_ARG, "bad argument to wire_m2_combine_ws_bytes");
+  return (int64_t)m2_comb_blocks(n) * m2_comb_grad_floats(nscales, out_features) * 4 + 256;
+}
+extern "C" int wire_m2_combine_bwd(void* stream, int nscales, int out_features, const float* W1, const float* b1,
+                                   const float* W2, const float* b2, const float* t, int64_t n, const float* g_y,
+                                   float* g_t, float* gW1, float* gb1, float* gW2, float* gb2, void* ws,
+                                   int64_t ws_bytes) {
+  if (!m2_shape_ok(nscales, out_features) || n < 1 || !W1 || !b1 || !W2 || !b2 || !t || !g_y || !g_t || !gW1 || !gb1 ||
+      !gW2 || !gb2 || !ws)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_m2_combine_bwd");
+  if (ws_bytes < wire_m2_combine_ws_bytes(nscales, out_features, n)) return fail(WIRE_ERR_SIZE, "ws too small");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(s, 3, 0);
+  const M2Comb w{W1, b1, W2, b2};
+  HIPCHK(launch_m2_comb_bwd(s, w, nscales, out_features, t, n, M2Loss{}, g_y, g_t, (float*)ws, nullptr));
+  HIPCHK(launch_m2_comb_reduce(s, (const float*)ws, n, nscales, out_features, M2Grads{gW1, gb1, gW2, gb2}));
   return WIRE_OK;
 }
 extern "C" int wire_posenc_fwd(void* stream, const float* coords, int64_t n, int D, int F, float* out) {

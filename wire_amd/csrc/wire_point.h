@@ -108,6 +108,32 @@ hipError_t launch_mscale_first(hipStream_t s, const float* coords, int64_t n, in
                                int SHF, const MscaleC& c, int split, int ld, float split_scale, unsigned* amax,
                                float* dst);
 
+// ---- the scale combiner of the multi-pass B-spline net (wire_m2.hip): t [S][n][O] (the trunk's outputs, pass-major)
+// -> y [n][O] = W2 relu(W1 [t_0 | .. | t_{S-1}] + b1) + b2, W1 [128][S O], W2 [O][128]; S <= 8, O <= 8
+#define M2_MAX_SCALES 8
+#define M2_H 128                 // freq_mlp's hidden width
+#define M2_COMB_MAXBLK 512
+struct M2Comb { const float* W1; const float* b1; const float* W2; const float* b2; };
+struct M2Grads { float* W1; float* b1; float* W2; float* b2; };
+// the loss of a training step inside the backward: target [.][O] at rows idx[r] (null: first + r); y, g_y (optional),
+// rec (optional) written; gscale = 2 weight / (n O)
+struct M2Loss {
+  const float* target = nullptr; const int64_t* idx = nullptr; int64_t first = 0; float gscale = 0.f;
+  float* y = nullptr; float* g_y = nullptr; float* rec = nullptr;
+};
+__host__ __device__ inline int m2_comb_grad_floats(int S, int O) {   // |gW1| + |gb1| + |gW2| + |gb2|
+  return M2_H * S * O + M2_H + O * M2_H + O;
+}
+int m2_comb_blocks(int64_t n);                   // blocks of the backward: part has room for this many x grad_floats
+hipError_t launch_m2_comb_fwd(hipStream_t s, const M2Comb& w, int S, int O, const float* t, int64_t n, float* y);
+// g_t [S][n][O] = dL/dt; part[block][grad_floats] (null: no weight gradient); ls.target: the MSE of y against it gives
+// g_y (and loss_part[block]), else g_y is read
+hipError_t launch_m2_comb_bwd(hipStream_t s, const M2Comb& w, int S, int O, const float* t, int64_t n, const M2Loss& ls,
+                              const float* g_y, float* g_t, float* part, float* loss_part);
+hipError_t launch_m2_comb_reduce(hipStream_t s, const float* part, int64_t n, int S, int O, const M2Grads& g);
+// out [n][D] = sum_k g[k][n][D]
+hipError_t launch_m2_sum_passes(hipStream_t s, const float* g, int S, int64_t n, int D, float* out);
+
 // ---- coordinate gradients (first-order, fp32)
 // g_x[r][d] = sum_k G[r][k] W[k][d] (+ sum_k G2[r][k] V[k][d]) over the K valid features of a stored first-layer gradient
 // (real g_lin_0, wire g_u, wire2d g_u with G2 = g_p); W, V native [K][D].  One wave per row, fixed reduction order.

@@ -142,6 +142,50 @@ def mscale_first(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor, scales: Sequ
     return out
 
 
+class _M2CombineFunction(torch.autograd.Function):
+    """AdaptiveScaleCombiner 'freq_combine' of bspline_mscale_2 (Linear(S O -> 128), ReLU, Linear(128 -> O) of the
+    concatenated pass outputs): wire_m2_combine_fwd / wire_m2_combine_bwd on t [S][..., O], the outputs stacked."""
+
+    @staticmethod
+    def forward(ctx, t, W1, b1, W2, b2):
+        L = _lib.lib()
+        _require_cuda(t, "combiner input")
+        _require_cuda(W1, "combiner weight")
+        S, O = t.shape[0], t.shape[-1]
+        if W1.shape != (128, S * O) or W2.shape != (O, 128):
+            raise ValueError(f"combiner weights {tuple(W1.shape)} / {tuple(W2.shape)} do not take {S} outputs of {O}")
+        tin = t.detach().to(torch.float32).contiguous()
+        n = tin.numel() // (S * O)
+        nat = [_native(w) for w in (W1, b1, W2, b2)]
+        y = torch.empty(tuple(t.shape[1:]), dtype=torch.float32, device=t.device)
+        _lib.check(L.wire_m2_combine_fwd(_stream_ptr(t.device), S, O, *[w.data_ptr() for w in nat], tin.data_ptr(), n,
+                                         y.data_ptr()), "wire_m2_combine_fwd")
+        ctx.save_for_backward(tin, *nat)
+        ctx.cfg = (S, O, n)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        L = _lib.lib()
+        tin, W1, b1, W2, b2 = ctx.saved_tensors
+        S, O, n = ctx.cfg
+        dev = g_y.device
+        gy = g_y.detach().to(torch.float32).contiguous()
+        g_t = torch.empty_like(tin)
+        gw = [torch.empty_like(w) for w in (W1, b1, W2, b2)]
+        ws_bytes = _lib.check(L.wire_m2_combine_ws_bytes(S, O, n), "wire_m2_combine_ws_bytes")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(L.wire_m2_combine_bwd(_stream_ptr(dev), S, O, W1.data_ptr(), b1.data_ptr(), W2.data_ptr(),
+                                         b2.data_ptr(), tin.data_ptr(), n, gy.data_ptr(), g_t.data_ptr(),
+                                         *[g.data_ptr() for g in gw], ws.data_ptr(), ws_bytes), "wire_m2_combine_bwd")
+        return (g_t, *gw)
+
+
+def m2_combine(outputs: Sequence[torch.Tensor], W1, b1, W2, b2) -> torch.Tensor:
+    """freq_mlp(cat(outputs, -1)) of bspline_mscale_2's combiner; outputs: S tensors of one shape [..., O]."""
+    return _M2CombineFunction.apply(torch.stack(list(outputs)), W1, b1, W2, b2)
+
+
 class _GaborLayerFunction(torch.autograd.Function):
     """One ComplexGaborLayer on native tensors: wire_gabor_fwd / wire_gabor_bwd."""
 

@@ -168,12 +168,16 @@ class FusedTrainer:
         t0 = 0
         if self.desc.kind == _lib.KIND["bspline_mscale_HL"]:   # its frozen first stage (tensors 0, 1) comes last
             t0, hidden = 2, max(hidden - 1, 0)
+        m2 = self.desc.kind == _lib.KIND["bspline_mscale_2"]
+        if m2:                                                  # its combiner (tensors 0 .. 3) comes first
+            t0 = 4
+            yield 0, t0
         per = (nt - 2 - t0) // (hidden + 1)
         yield nt - 2, 2
         for l in range(hidden, 0, -1):
             yield t0 + per * l, per
         yield t0, per
-        if t0:
+        if t0 and not m2:
             yield 0, t0
 
     def _on_grad_ready(self, user, first: int, n: int) -> None:
