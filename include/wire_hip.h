@@ -30,6 +30,7 @@
  *                b1[K], {W_l[K][K], b_l[K]} l=2..max(L,1), W_f, b_f, all f32
  *                (modules/bspline_mscale_HL.py; its scales travel in
  *                 wire_net_desc_ms, see below)
+ *       bspline_m2, bspline_hier : see wire_net_desc_ms below
  *  - internal activation layout ("blocked planar"): a
  *    complex row of K features is stored as P = roundup(2K,64) floats; group
  *    g of 32 features occupies columns [64g,64g+32) = real parts and
@@ -67,9 +68,13 @@ typedef enum wire_kind {
                             Scaled_Bsplines_form D -> SHF, then Bsplines_form
                             SHF -> K; described by wire_net_desc_ms        */
   /* 7 stays unassigned: a plain descriptor of kind 7 is WIRE_ERR_ARG, and callers rely on that */
-  WIRE_KIND_BSPLINE_M2 = 8 /* modules/bspline_mscale_2.py: the bspline_form
+  WIRE_KIND_BSPLINE_M2 = 8, /* modules/bspline_mscale_2.py: the bspline_form
                             trunk run once per scale, the S outputs through
                             freq_mlp; described by wire_net_desc_ms        */
+  WIRE_KIND_BSPLINE_HIER = 9 /* modules/bspline_mscale_hier.py: one stage per
+                            scale, stage s > 0 joins its first layer with the
+                            previous stage's output (2K -> K), one linear head
+                            per stage; described by wire_net_desc_ms       */
 } wire_kind;
 
 /* Architecture + hyper-parameters of one INR (modules/wire.py:96-159). */
@@ -106,12 +111,22 @@ typedef struct wire_net_desc {
  *   freq_mlp.2.bias [O], then the trunk in kind 5's order (its tensors start at index 4).  combine_scales.scale_weights
  *   and combine_scales.refine.* receive no gradient in the reference's loop and are not ABI tensors.  The hooked call
  *   announces tensors 0 .. 3 first.  n is the number of coordinate rows; the library runs the trunk on S n rows.       */
+/* The hierarchical B-spline net (WIRE_KIND_BSPLINE_HIER, modules/bspline_mscale_hier.py) uses the same struct:
+ *   base.width = K, base.hidden_layers = L (>= 1; L = 1 only with one scale), base.scale0 carried and ignored,
+ *   first_width = 0, nscales = S (1..8), scales[s] = the divisor of every layer of stage s (finite, non-zero).
+ *   Stage 0: Bsplines_form D -> K, then L x K -> K, on the coordinates.  Stage s > 0: x_in = layer 0 (D -> K) of the
+ *   coordinates, layer 1 (2K -> K) of [x_in | x_{s-1}], layer 2 (K -> K); layers 3.. of such a stage exist in the
+ *   reference's state_dict, are never run and are not ABI tensors.  y = sum_s (x_s Wh_s^T + bh_s).
+ *   params[] / grads[]: stage 0's {W, b} x (L + 1), then per stage s > 0 its three {W, b} (layer 1's W [K][2K], the
+ *   x_in columns first), then the S heads {Wh_s [O][K], bh_s [O]} as one block at the end.  Every stage's first layer
+ *   contributes to g_coords.  The hooked call announces the heads first, then the stages from the last to the first,
+ *   each from its last layer to its first.  out_features x roundup(K, 64) <= 16384 (a head's weights in 64 KB).      */
 #define WIRE_MS_MAX_SCALES 8
 typedef struct wire_net_desc_ms {
   wire_net_desc base;      /* base.kind = WIRE_KIND_BSPLINE_MS                    */
-  int32_t first_width;     /* SHF: scaled_hidden_features, 1..4096 (kind 8: 0)    */
+  int32_t first_width;     /* SHF: scaled_hidden_features, 1..4096 (kinds 8, 9: 0) */
   int32_t nscales;         /* T: entries of scale_tensor, 2..WIRE_MS_MAX_SCALES
-                              (kind 8: S, 1..WIRE_MS_MAX_SCALES)                 */
+                              (kinds 8, 9: S, 1..WIRE_MS_MAX_SCALES)             */
   float scales[WIRE_MS_MAX_SCALES];   /* scale_tensor[0 .. T)                     */
 } wire_net_desc_ms;
 

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libwire_hip.so")
 
 KIND = {"wire": 0, "wire2d": 1, "siren": 2, "gauss": 3, "relu": 4, "bspline_form": 5, "bspline_mscale_HL": 6,
-        "bspline_mscale_2": 8}
+        "bspline_mscale_2": 8, "bspline_mscale_hier": 9}
 MS_MAX_SCALES = 8   # WIRE_MS_MAX_SCALES
 ABI_VERSION = 1
 
@@ -188,6 +188,19 @@ def make_desc_m2(in_features: int, width: int, hidden_layers: int, out_features:
                              hidden_omega0, scale0), 0, len(scales),
                    (C.c_float * MS_MAX_SCALES)(*(scales + [0.0] * (MS_MAX_SCALES - len(scales)))))
     return m2.base
+
+
+def make_desc_hier(in_features: int, width: int, hidden_layers: int, out_features: int, first_omega0: float,
+                   hidden_omega0: float, scale0: float, scales) -> NetDesc:
+    """Descriptor of a bspline_mscale_hier net (kind 9): the ``base`` NetDesc of a NetDescMS with first_width = 0 and one
+    scale per stage; ``scale0`` is carried and ignored."""
+    scales = [float(v) for v in scales]
+    if not 1 <= len(scales) <= MS_MAX_SCALES:
+        raise ValueError(f"{len(scales)} scales: the descriptor takes 1..{MS_MAX_SCALES}")
+    h = NetDescMS(make_desc("bspline_mscale_hier", in_features, width, hidden_layers, out_features, first_omega0,
+                            hidden_omega0, scale0), 0, len(scales),
+                  (C.c_float * MS_MAX_SCALES)(*(scales + [0.0] * (MS_MAX_SCALES - len(scales)))))
+    return h.base
 
 
 def ptr_array(ptrs):

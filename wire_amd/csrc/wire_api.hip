@@ -141,6 +141,16 @@ struct Plan {
   int S2 = 1;
   float m2_c[WIRE_MS_MAX_SCALES] = {};
   int64_t off_comb = -1;
+  // WIRE_KIND_BSPLINE_HIER (kind then reads WIRE_KIND_BSPLINE): HS stages of the reference's HL hidden layers, stage s
+  // with c = h_c[s].  Every K -> K GEMM of the net is a "hidden layer" of this plan (L of them, hier_v): stage 0's HL, then
+  // per stage s >= 1 its layer 2 and the two halves of its join (packed for the join's two data-gradient GEMMs).  The
+  // join's own forward image [P][2P] (all families), bias and max-|weight| slots sit at hj_*[s]; hj_half: the halves as
+  // [K][K] matrices; h_nat: native copies of every first layer and head
+  bool hier = false;
+  int HS = 0, HL = 0;
+  float h_c[WIRE_MS_MAX_SCALES] = {};
+  int64_t hj_fwd[WIRE_MS_MAX_SCALES] = {}, hj_fwd_x3[WIRE_MS_MAX_SCALES] = {}, hj_fwd_x2[WIRE_MS_MAX_SCALES] = {},
+          hj_bias[WIRE_MS_MAX_SCALES] = {}, hj_half[WIRE_MS_MAX_SCALES] = {}, hj_wamax = -1, h_nat = -1;
   // packed image offsets (floats); index l = 0..L (l = 0 only when first_gemm)
   std::vector<int64_t> off_fwd, off_dg, off_bias, off_fwd_x3, off_dg_x3, off_fwd_3m, off_dg_3m, off_fwd_x2, off_dg_x2;
   int64_t off_wf, off_bf, off_first, off_wamax, total_packed;   // off_wamax: max-|weight| slots, WIRE_AMAX_SLOTS per layer
@@ -155,13 +165,62 @@ struct Plan {
 // multi-pass net's first trunk layer follows the combiner (t0)
 inline int first_tensor(const Plan& p, int q) { return p.ms ? q : p.t0 + q; }
 
+// ---- the hierarchical net's index maps
+inline int hier_last(const Plan& p, int st) { return st == 0 ? p.HL : 2; }           // index of stage st's last layer
+inline int hier_t(const Plan& p, int st, int l) {                                     // params[] index of W of (st, l)
+  return st == 0 ? 2 * l : 2 * (p.HL + 1) + 6 * (st - 1) + 2 * l;
+}
+inline int hier_th(const Plan& p, int st) { return 2 * (p.HL + 1) + 6 * (p.HS - 1) + 2 * st; }   // ... of head st's W
+// the plan's hidden-layer index of a K -> K GEMM: stage 0 layer l; stage st >= 1: its layer 2, its join's halves
+inline int hier_v(const Plan& p, int st, int l) { return st == 0 ? l : p.HL + 3 * (st - 1) + 1; }
+inline int hier_vhalf(const Plan& p, int st, int half) { return p.HL + 3 * (st - 1) + 2 + half; }
+inline int64_t hier_nat_stride(const Plan& p) {
+  return rup(p.K * p.D, 4) + rup(p.K, 4) + rup(p.O * p.K, 4) + rup(p.O, 4);
+}
+struct HierNat { const float* W0; const float* b0; const float* Wh; const float* bh; };
+inline HierNat hier_nat(const Plan& p, const float* packed, int st) {
+  HierNat h;
+  const float* c = packed + p.h_nat + (int64_t)st * hier_nat_stride(p);
+  h.W0 = c; c += rup(p.K * p.D, 4);
+  h.b0 = c; c += rup(p.K, 4);
+  h.Wh = c; c += rup(p.O * p.K, 4);
+  h.bh = c;
+  return h;
+}
+
 int make_plan(const wire_net_desc* d, Plan& p) {
   if (!d) return fail(WIRE_ERR_ARG, "null descriptor");
   p.kind = d->kind; p.D = d->in_features; p.K = d->width; p.L = d->hidden_layers;
   p.O = d->out_features; p.F = d->posenc_freqs;
   p.w1 = d->first_omega0; p.w = d->hidden_omega0; p.s = d->scale0;
-  if (p.kind < WIRE_KIND_WIRE || (p.kind > WIRE_KIND_BSPLINE_MS && p.kind != WIRE_KIND_BSPLINE_M2))
+  if (p.kind < WIRE_KIND_WIRE || (p.kind > WIRE_KIND_BSPLINE_MS && p.kind != WIRE_KIND_BSPLINE_M2 &&
+                                  p.kind != WIRE_KIND_BSPLINE_HIER))
     return fail(WIRE_ERR_ARG, "unknown kind %d", p.kind);
+  if (p.kind == WIRE_KIND_BSPLINE_HIER) {
+    // modules/bspline_mscale_hier.py: one stage per entry of scale_tensor, `scale` unused
+    const wire_net_desc_ms* m = reinterpret_cast<const wire_net_desc_ms*>(d);
+    if (m->first_width != 0) return fail(WIRE_ERR_ARG, "first_width %d: kind %d has no first stage", m->first_width,
+                                         (int)WIRE_KIND_BSPLINE_HIER);
+    p.HS = m->nscales;
+    if (p.HS < 1 || p.HS > WIRE_MS_MAX_SCALES) return fail(WIRE_ERR_ARG, "nscales %d outside 1..%d", p.HS, WIRE_MS_MAX_SCALES);
+    for (int k = 0; k < p.HS; ++k) {
+      const float sk = m->scales[k];
+      if (!(std::isfinite(sk) && sk != 0.f)) return fail(WIRE_ERR_ARG, "scales[%d] %g is zero or not finite", k, (double)sk);
+      p.h_c[k] = (float)(1.0 / fabs((double)sk));
+    }
+    p.HL = p.L;
+    if (p.HL < 1 || p.HL > 40) return fail(WIRE_ERR_ARG, "hidden_layers %d outside 1..40 (kind %d)", p.HL,
+                                           (int)WIRE_KIND_BSPLINE_HIER);
+    if (p.HL == 1 && p.HS > 1)
+      return fail(WIRE_ERR_ARG, "hidden_layers 1 with %d scales: a later stage runs its layers 0, 1 and 2", p.HS);
+    if (p.O >= 1 && p.O <= 8 && p.K >= 1 && p.K <= 4096 && (int64_t)p.O * rup(p.K, 64) > 16384)
+      return fail(WIRE_ERR_ARG, "out_features %d x padded width %d > 16384 (kind %d)", p.O, rup(p.K, 64),
+                  (int)WIRE_KIND_BSPLINE_HIER);
+    p.hier = true;
+    p.kind = WIRE_KIND_BSPLINE;
+    p.s = m->scales[0];
+    p.L = p.HL + 3 * (p.HS - 1);
+  }
   if (p.kind == WIRE_KIND_BSPLINE_M2) {
     // modules/bspline_mscale_2.py: the trunk of bspline_form once per entry of scale_tensor (lin / scale_k), `scale` unused
     const wire_net_desc_ms* m = reinterpret_cast<const wire_net_desc_ms*>(d);
@@ -248,6 +307,16 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   }
   p.tfloats[p.ntens - 2] = cm * p.O * K;
   p.tfloats[p.ntens - 1] = cm * p.O;
+  if (p.hier) {   // stage 0: HL + 1 pairs; stages s >= 1: three pairs (layer 1: [K][2K]); the HS heads at the end
+    p.ntens = 2 * (p.HL + 1) + 6 * (p.HS - 1) + 2 * p.HS;
+    p.tfloats.assign(p.ntens, 0);
+    for (int st = 0; st < p.HS; ++st)
+      for (int l = 0; l <= hier_last(p, st); ++l) {
+        p.tfloats[hier_t(p, st, l)] = K * (l == 0 ? p.D : (st > 0 && l == 1) ? 2 * K : K);
+        p.tfloats[hier_t(p, st, l) + 1] = K;
+      }
+    for (int st = 0; st < p.HS; ++st) { p.tfloats[hier_th(p, st)] = p.O * K; p.tfloats[hier_th(p, st) + 1] = p.O; }
+  }
   // packed image
   int64_t off = 0;
   p.off_fwd.assign(p.L + 1, -1); p.off_dg.assign(p.L + 1, -1); p.off_bias.assign(p.L + 1, -1);
@@ -281,7 +350,7 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   // (a positional-encoding net -- relu, 64 padded encoded features -- has its GEMM first layer's image, P x 64, in front)
   // (the multi-pass net: one set of hidden images per pass, each with its own c folded in -- fx_pass_off; the chain's
   // transposed images below carry no c and serve every pass)
-  const bool fx_ok = p.L >= 1 && fused_fwd_shape(p.kind, p.P) &&
+  const bool fx_ok = !p.hier && p.L >= 1 && fused_fwd_shape(p.kind, p.P) &&
                      (!p.first_gemm || (p.kind == WIRE_KIND_RELU && p.Pin0 == 64));
   if (fx_ok) {
     p.off_fx = off;
@@ -292,7 +361,21 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   p.off_wf = off; off += (int64_t)p.O * p.P;
   p.off_bf = off; off += 64;
   p.off_first = off;   // native copies of the first layer's tensors (W0,b0[,V0,c0]; the multi-scale net's first stage)
-  if (!p.first_gemm || p.ms) for (int q = 0; q < p.per_layer; ++q) off += rup((int)p.tfloats[first_tensor(p, q)], 4);
+  if (p.hier) {
+    for (int st = 1; st < p.HS; ++st) {
+      const int64_t img = (int64_t)p.P * 2 * p.P;
+      p.hj_fwd[st] = off; off += img;
+      p.hj_bias[st] = off; off += p.P;
+      p.hj_fwd_x3[st] = off; off += gemmx3_b_image_floats(p.P, 2 * p.P);
+      p.hj_fwd_x2[st] = off; off += gemmx2_b_image_floats(p.P, 2 * p.P);
+      p.hj_half[st] = off; off += 2 * rup(p.K * p.K, 4);
+    }
+    p.hj_wamax = off; off += (int64_t)p.HS * WIRE_AMAX_SLOTS;
+    p.h_nat = off;                                         // per stage: W0 [K][D], b0 [K], Wh [O][K], bh [O]
+    off += (int64_t)p.HS * hier_nat_stride(p);
+  } else if (!p.first_gemm || p.ms) {
+    for (int q = 0; q < p.per_layer; ++q) off += rup((int)p.tfloats[first_tensor(p, q)], 4);
+  }
   if (p.m2) {                                              // the combiner's native copy
     p.off_comb = off;
     for (int q = 0; q < 4; ++q) off += rup((int)p.tfloats[q], 4);
@@ -599,6 +682,8 @@ hipError_t layer_nt(hipStream_t s, const Plan& p, WireFamily f, const float* pac
 // ---------------------------------------------------------------------------
 // size queries
 // ---------------------------------------------------------------------------
+static int64_t hier_act_total(const Plan& p, int64_t n, int save);          // the hierarchical net's layouts, below
+static int64_t hier_scratch_total(const Plan& p, int64_t n, bool coords);
 extern "C" int wire_num_param_tensors(const wire_net_desc* d) {
   Plan p; if (make_plan(d, p)) return WIRE_ERR_ARG;
   return p.ntens;
@@ -615,22 +700,26 @@ extern "C" int64_t wire_packed_floats(const wire_net_desc* d) {
 extern "C" int64_t wire_act_bytes(const wire_net_desc* d, int64_t n, int save_for_bwd) {
   Plan p; if (make_plan(d, p)) return WIRE_ERR_ARG;
   if (n < 0) return fail(WIRE_ERR_ARG, "negative n");
+  if (p.hier) return hier_act_total(p, n, save_for_bwd) * 4 + 256;
   return act_layout(p, n, save_for_bwd).total * 4 + 256;
 }
 extern "C" int64_t wire_bwd_scratch_bytes(const wire_net_desc* d, int64_t n) {
   Plan p; if (make_plan(d, p)) return WIRE_ERR_ARG;
   if (n < 0) return fail(WIRE_ERR_ARG, "negative n");
+  if (p.hier) return hier_scratch_total(p, n, false) * 4 + 256;
   return scratch_layout(p, n).total * 4 + 256;
 }
 extern "C" int64_t wire_bwd_coords_scratch_bytes(const wire_net_desc* d, int64_t n) {
   Plan p; if (make_plan(d, p)) return WIRE_ERR_ARG;
   if (n < 0) return fail(WIRE_ERR_ARG, "negative n");
+  if (p.hier) return hier_scratch_total(p, n, true) * 4 + 256;
   return coord_layout(p, n).total * 4 + 256;
 }
 extern "C" int wire_blocked_width(int K) { return rup(2 * K, 64); }
 // float offset of out_l (rows of P floats, l = 0..L) inside an act buffer laid out for n rows with save_for_bwd = 1
 extern "C" int64_t wire_act_out_offset(const wire_net_desc* d, int64_t n, int layer) {
   Plan p; if (make_plan(d, p)) return WIRE_ERR_ARG;
+  if (p.hier) return fail(WIRE_ERR_ARG, "wire_act_out_offset: kind %d keeps its activations per stage", (int)WIRE_KIND_BSPLINE_HIER);
   if (n < 0 || layer < 0 || layer > p.L) return fail(WIRE_ERR_ARG, "bad argument to wire_act_out_offset");
   const ActLayout a = act_layout(p, n, 1);
   return a.out0 + (int64_t)layer * a.np * p.P;
@@ -672,6 +761,39 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
       HIPCHK(launch_x2_split_b_batch(s, xf, 1, p.Pin0, p.Pl, p.Pin0));
     }
   }
+  // W, b of the plan's hidden layer l (the hierarchical net: the K -> K GEMMs of every stage, hier_v / hier_vhalf)
+  std::vector<const float*> hW(p.L + 1, nullptr), hb(p.L + 1, nullptr);
+  for (int l = 1; l <= p.L && !p.hier; ++l) {
+    hW[l] = (const float*)params[p.t0 + p.per_layer * l]; hb[l] = (const float*)params[p.t0 + p.per_layer * l + 1];
+  }
+  if (p.hier) {
+    HIPCHK(hipMemsetAsync(packed + p.hj_wamax, 0, (size_t)p.HS * WIRE_AMAX_SLOTS * sizeof(float), s));
+    for (int l = 1; l <= p.HL; ++l) {
+      hW[l] = (const float*)params[hier_t(p, 0, l)]; hb[l] = (const float*)params[hier_t(p, 0, l) + 1];
+    }
+    for (int st = 1; st < p.HS; ++st) {
+      // the join: its forward image in every family; its halves as two more hidden layers (their transposed images
+      // serve the join's two data-gradient GEMMs, their forward images are not used)
+      const float* Wj = (const float*)params[hier_t(p, st, 1)];
+      const float* bj = (const float*)params[hier_t(p, st, 1) + 1];
+      float* Wa = packed + p.hj_half[st];
+      float* Wb = Wa + rup(p.K * p.K, 4);
+      float* img = packed + p.hj_fwd[st];
+      HIPCHK(launch_hier_pack_join(s, Wj, bj, p.K, p.P, img, packed + p.hj_bias[st], Wa, Wb));
+      HIPCHK(launch_x3_split_b(s, img, 2 * p.P, p.P, 2 * p.P, packed + p.hj_fwd_x3[st]));
+      X2AmaxBatch ab{};
+      X2SplitBatch xf{};
+      ab.src[0] = xf.src[0] = img;
+      ab.slots[0] = reinterpret_cast<unsigned*>(packed + p.hj_wamax) + st * WIRE_AMAX_SLOTS;
+      xf.dst[0] = packed + p.hj_fwd_x2[st]; xf.slots[0] = ab.slots[0];
+      HIPCHK(launch_amax_batch(s, ab, 1, (int64_t)p.P * 2 * p.P));
+      HIPCHK(launch_x2_split_b_batch(s, xf, 1, 2 * p.P, p.P, 2 * p.P));
+      hW[hier_v(p, st, 2)] = (const float*)params[hier_t(p, st, 2)];
+      hb[hier_v(p, st, 2)] = (const float*)params[hier_t(p, st, 2) + 1];
+      hW[hier_vhalf(p, st, 0)] = Wa; hb[hier_vhalf(p, st, 0)] = bj;
+      hW[hier_vhalf(p, st, 1)] = Wb; hb[hier_vhalf(p, st, 1)] = bj;
+    }
+  }
   // hidden layers share one shape: every family's image of up to PACK_MAXB layers per launch (3 - 4 launches per step
   // instead of 4 per layer; this runs once per optimizer step and is all launch gaps)
   for (int l0 = 1; l0 <= p.L; l0 += PACK_MAXB) {
@@ -680,8 +802,8 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
     X3SplitBatch sf{}, sd{};
     for (int i = 0; i < nb; ++i) {
       const int l = l0 + i;
-      pb.W[i] = (const float*)params[p.t0 + p.per_layer * l];
-      pb.b[i] = (const float*)params[p.t0 + p.per_layer * l + 1];
+      pb.W[i] = hW[l];
+      pb.b[i] = hb[l];
       pb.V[i] = p.per_layer == 4 ? (const float*)params[p.per_layer * l + 2] : nullptr;
       pb.c[i] = p.per_layer == 4 ? (const float*)params[p.per_layer * l + 3] : nullptr;
       pb.fwd[i] = packed + p.off_fwd[l]; pb.dg[i] = packed + p.off_dg[l]; pb.bias[i] = packed + p.off_bias[l];
@@ -741,6 +863,17 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
         if (m > 0) HIPCHK(launch_fx_split_b_batch(s, fd, m, p.Pl, p.P, 1.f));
       }
     }
+  }
+  if (p.hier) {                // every stage's first layer and head, read in their native layout
+    for (int st = 0; st < p.HS; ++st) {
+      const HierNat h = hier_nat(p, packed, st);
+      const float* dst[4] = {h.W0, h.b0, h.Wh, h.bh};
+      const int src[4] = {hier_t(p, st, 0), hier_t(p, st, 0) + 1, hier_th(p, st), hier_th(p, st) + 1};
+      for (int q = 0; q < 4; ++q)
+        HIPCHK(hipMemcpyAsync(const_cast<float*>(dst[q]), params[src[q]], p.tfloats[src[q]] * 4, hipMemcpyDeviceToDevice,
+                              s));
+    }
+    return WIRE_OK;
   }
   HIPCHK(launch_pack_final(s, p.kind, (const float*)params[p.ntens - 2],
                            (const float*)params[p.ntens - 1], p.K, p.P, p.O, packed + p.off_wf,
@@ -905,10 +1038,13 @@ static int mlp_fwd_core(void* stream, const Plan& p, const Route& r, const float
   return WIRE_OK;
 }
 
+static int hier_fwd_dispatch(void* stream, const Plan& p, const float* packed, const float* coords, int64_t n, float* y,
+                             void* act, int64_t act_bytes, int save_for_bwd);   // the hierarchical net, below
 extern "C" int wire_mlp_fwd(void* stream, const wire_net_desc* d, const float* packed,
                             const float* coords, int64_t n, float* y, void* act, int64_t act_bytes,
                             int save_for_bwd) {
   Plan p; if (int rc = make_plan(d, p)) return rc;
+  if (p.hier) return hier_fwd_dispatch(stream, p, packed, coords, n, y, act, act_bytes, save_for_bwd);
   return mlp_fwd_core(stream, p, make_route(p, n, save_for_bwd ? MODE_AUTOGRAD : MODE_INFER), packed, coords, n, y, act,
                       act_bytes);
 }
@@ -1251,12 +1387,322 @@ static int mlp_bwd_core(void* stream, const Plan& p, const Route& r, const float
   return rc ? rc : c.first_params();
 }
 
+
+// ---------------------------------------------------------------------------
+// the hierarchical B-spline net (WIRE_KIND_BSPLINE_HIER): layer by layer in every mode
+// ---------------------------------------------------------------------------
+namespace {
+// where a layer's activation goes: rows of ld floats (P, or 2P inside a join's input), aset = the max-|value| slot set
+// its 2 x fp16 reader scales by (-1: no GEMM reads it)
+struct HierOut { int64_t off; int ld; int aset; };
+struct HierAct {
+  int64_t amax, total;
+  std::vector<std::vector<int64_t>> lin;   // [stage][layer]; -1 = not stored (inference)
+  std::vector<std::vector<HierOut>> out;   // [stage][layer]
+  std::vector<int64_t> cat;                // [stage >= 1]: the join's input [n][2P] = [x_in | x_{stage-1}]
+};
+inline int hier_sets(const Plan& p) { return p.HS * (p.HL + 2); }
+// Training / autograd: every lin and out has its own buffer; a stage's last out is written straight into the right half
+// of the next stage's join input, its first layer's out into the left half.  Inference: two [n][P] and two [n][2P]
+// buffers in turns (stage st reads join input st & 1 and writes the right half of the other)
+HierAct hier_act(const Plan& p, int64_t n, int save) {
+  HierAct a;
+  const int S = p.HS, per = p.HL + 2;
+  const int64_t nP = n * p.P;
+  int64_t off = 0;
+  a.amax = off; off += (int64_t)hier_sets(p) * WIRE_AMAX_SLOTS;
+  a.lin.resize(S); a.out.resize(S); a.cat.assign(S, -1);
+  int64_t tmp[2] = {-1, -1}, catb[2] = {-1, -1};
+  if (!save) {
+    tmp[0] = off; off += nP; tmp[1] = off; off += nP;
+    if (S > 1) { catb[0] = off; off += 2 * nP; catb[1] = off; off += 2 * nP; }
+  }
+  for (int st = 1; st < S; ++st) {
+    if (save) { a.cat[st] = off; off += 2 * nP; } else a.cat[st] = catb[st & 1];
+  }
+  for (int st = 0; st < S; ++st) {
+    const int last = hier_last(p, st);
+    a.lin[st].assign(last + 1, -1);
+    a.out[st].resize(last + 1);
+    for (int l = 0; l <= last; ++l) {
+      if (save) { a.lin[st][l] = off; off += nP; }
+      HierOut o{};
+      if (st > 0 && l == 0) {                 // x_in: the left half of this stage's join input
+        o.off = a.cat[st]; o.ld = 2 * p.P; o.aset = st * per;
+      } else if (l == last && st + 1 < S) {   // x_st: the right half of the next stage's
+        o.off = a.cat[st + 1] + p.P; o.ld = 2 * p.P; o.aset = (st + 1) * per;
+      } else {
+        o.ld = p.P;
+        o.aset = l == last ? -1 : st * per + (st == 0 ? l : 1);
+        if (save) { o.off = off; off += nP; } else o.off = tmp[st == 0 ? (l & 1) : (l == 1 ? 0 : 1)];
+      }
+      a.out[st][l] = o;
+    }
+  }
+  a.total = off;
+  return a;
+}
+
+// three g buffers [n][P] (the current layer's g_lin, the next one's, and T = the join's right-half gradient on its way to
+// the previous stage's head backward), slabs for the widest weight gradient ([P][2P] with a join), the heads' and the
+// first layers' pre-reduction blocks, the loss partials; cgp (behind everything, wire_bwd_coords_scratch_bytes): the
+// per-stage coordinate gradients before their sum
+struct HierScratch { int64_t gamax, g[3], slab, bslab, fpw, fpb, crp, lpart, total, cgp, total_coords; int S; };
+HierScratch hier_scratch(const Plan& p, int64_t n) {
+  HierScratch s{};
+  int64_t off = 0;
+  s.gamax = off; off += (int64_t)hier_sets(p) * WIRE_AMAX_SLOTS;
+  for (int i = 0; i < 3; ++i) { s.g[i] = off; off += n * p.P; }
+  const int pn = p.HS > 1 ? 2 * p.P : p.P;
+  auto mx = [](int a, int b) { return a > b ? a : b; };
+  const int s_x3k = mx(gemmx3_tn_splits_max(n, p.P, pn, 256), gemmx3_tn_splits_max(n, p.P, p.P, 256));
+  const int s_4m = mx(gemm_tn_splits(n, p.P, pn, 64), gemm_tn_splits(n, p.P, p.P, 64));
+  const int s_x2 = mx(gemmx2_tn_splits(n, p.P, pn, 256), gemmx2_tn_splits(n, p.P, p.P, 256));
+  const int s_x3 = mx(s_x3k, s_x2), s_max = mx(mx(s_x3, s_4m), 1);
+  s.S = mx(p.x3 ? s_x3 : s_4m, 1);
+  s.slab = off; off += (int64_t)s_max * p.P * pn;
+  s.bslab = off; off += (int64_t)s_max * p.P;
+  const int nbf = final_bwd_blocks(n) + 32;
+  s.fpw = off; off += (int64_t)nbf * p.O * p.P;
+  s.fpb = off; off += (int64_t)nbf * p.O + 64;
+  s.crp = off; off += (int64_t)(colreduce_blocks(n) + 32) * p.P * 5;
+  s.lpart = off; off += HIER_HEAD_MAXBLK;
+  s.total = off;
+  off = (off + 63) / 64 * 64;
+  s.cgp = off; off += (int64_t)p.HS * n * p.D;
+  s.total_coords = off;
+  return s;
+}
+
+// the join's forward GEMM [n][2P] x [P][2P]^T on family f
+hipError_t hier_join_nt(hipStream_t s, const Plan& p, WireFamily f, const float* packed, int st, const float* A, int64_t n,
+                        GemmEpiParams ep, const unsigned* amax_a, unsigned* amax_out) {
+  const int Kd = 2 * p.P, Nc = p.P;
+  switch (f) {
+    case FAM_X2:
+      ep.amax_a = amax_a; ep.amax_out = amax_out;
+      ep.amax_b = reinterpret_cast<const unsigned*>(packed + p.hj_wamax) + st * WIRE_AMAX_SLOTS;
+      return launch_gemmx2h_nt(s, EPI_BSPLINE_FWD, A, Kd, packed + p.hj_fwd_x2[st], n, Nc, Kd, ep);
+    case FAM_X3: return launch_gemmx3_nt(s, EPI_BSPLINE_FWD, A, Kd, packed + p.hj_fwd_x3[st], n, Nc, Kd, ep);
+    default: return launch_gemm_nt(s, EPI_BSPLINE_FWD, A, Kd, packed + p.hj_fwd[st], Kd, n, Nc, Kd, ep);
+  }
+}
+// slabs of G^T [Z | 1], G [n][P], Z [n][Pn] rows of ldz floats, on family f in S splits
+hipError_t hier_tn(hipStream_t s, const Plan& p, WireFamily f, const float* G, const float* Z, int ldz, int Pn, int64_t n,
+                   int S, float* slab, float* bslab, const unsigned* amax_g, const unsigned* amax_z) {
+  switch (f) {
+    case FAM_X2: return launch_gemmx2_tn(s, G, p.P, Z, ldz, n, p.P, Pn, S, slab, bslab, amax_g, amax_z);
+    case FAM_X3: return launch_gemmx3_tn(s, G, p.P, Z, ldz, n, p.P, Pn, S, slab, bslab);
+    default: return launch_gemm_tn(s, G, p.P, Z, ldz, n, p.P, Pn, S, slab, bslab);
+  }
+}
+int hier_tn_splits(WireFamily f, int64_t n, int Pm, int Pn, int cap) {
+  const int S = f == FAM_X2 ? gemmx2_tn_splits(n, Pm, Pn, cap) : f == FAM_X3 ? gemmx3_tn_splits(n, Pm, Pn, cap)
+                                                                             : gemm_tn_splits(n, Pm, Pn, cap);
+  return S < 1 ? 1 : S;
+}
+
+// forward.  loss (training): the last head's launch forms the MSE terms, g_y and the loss partials
+int hier_fwd_core(void* stream, const Plan& p, const Route& r, const float* packed, const float* coords, int64_t n, float* y,
+                  void* act, int64_t act_bytes, const M2Loss* loss = nullptr, float* loss_part = nullptr) {
+  const bool save = r.mode != MODE_INFER;
+  if (n < 0) return fail(WIRE_ERR_ARG, "negative n");
+  if (n == 0) return WIRE_OK;
+  if (!packed || !coords || !y || !act) return fail(WIRE_ERR_ARG, "null pointer");
+  const HierAct a = hier_act(p, n, save);
+  if (act_bytes < a.total * 4) return fail(WIRE_ERR_SIZE, "act buffer %lld < %lld bytes", (long long)act_bytes,
+                                           (long long)a.total * 4);
+  hipStream_t s = (hipStream_t)stream;
+  float* A = (float*)act;
+  const bool x2 = r.fam == FAM_X2;
+  unsigned* const slots = reinterpret_cast<unsigned*>(A + a.amax);
+  auto sl = [&](int aset) -> unsigned* { return (x2 && aset >= 0) ? slots + (int64_t)aset * WIRE_AMAX_SLOTS : nullptr; };
+  if (x2) HIPCHK(hipMemsetAsync(slots, 0, (size_t)hier_sets(p) * WIRE_AMAX_SLOTS * sizeof(unsigned), s));
+  for (int st = 0; st < p.HS; ++st) {
+    const float c = p.h_c[st];
+    const HierNat nat = hier_nat(p, packed, st);
+    const int last = hier_last(p, st);
+    auto lin = [&](int l) -> float* { return a.lin[st][l] >= 0 ? A + a.lin[st][l] : nullptr; };
+    {
+      const HierOut& o = a.out[st][0];
+      ProfScope ps(s, 3, 0);
+      HIPCHK(launch_hier_first_fwd(s, coords, n, p.D, nat.W0, nat.b0, p.K, p.P, c, lin(0), A + o.off, o.ld, sl(o.aset)));
+    }
+    for (int l = 1; l <= last; ++l) {
+      const HierOut& o = a.out[st][l];
+      GemmEpiParams ep;
+      ep.o0 = lin(l); ep.o1 = A + o.off; ep.ld0 = p.P; ep.ld1 = o.ld; ep.omega = p.w; ep.scale = c; ep.kvalid = p.K;
+      if (st > 0 && l == 1) {
+        ep.bias = packed + p.hj_bias[st];
+        ProfScope ps(s, 0, 2.0 * n * p.P * 2 * p.P);
+        HIPCHK(hier_join_nt(s, p, r.fam, packed, st, A + a.cat[st], n, ep, sl(a.out[st][0].aset), sl(o.aset)));
+      } else {
+        const int v = hier_v(p, st, l);
+        const HierOut& in = a.out[st][l - 1];
+        ep.bias = packed + p.off_bias[v];
+        ProfScope ps(s, 0, 2.0 * n * p.P * p.P);
+        HIPCHK(layer_nt(s, p, r.fam, packed, v, false, EPI_BSPLINE_FWD, A + in.off, n, ep, sl(in.aset), wamax_of(p, packed, v),
+                        sl(o.aset)));
+      }
+    }
+    const HierOut& xl = a.out[st][last];
+    const bool fin = loss && st == p.HS - 1;
+    ProfScope ps(s, 3, 0);
+    HIPCHK(launch_hier_head_fwd(s, A + xl.off, xl.ld, nat.Wh, nat.bh, n, p.K, p.P, p.O, st > 0, y, fin ? *loss : M2Loss{},
+                                fin ? loss_part : nullptr));
+  }
+  return WIRE_OK;
+}
+
+int hier_bwd_core(void* stream, const Plan& p, const Route& r, const float* packed, const float* coords, int64_t n,
+                  const float* g_y, const void* act, int64_t act_bytes, void* scratch, int64_t scratch_bytes,
+                  void* const* grads, wire_grad_ready_fn ready, void* user, float* g_coords) {
+  if (n <= 0) return fail(WIRE_ERR_ARG, "backward needs n > 0");
+  if (!packed || !coords || !g_y || !act || !scratch || (!grads && !g_coords)) return fail(WIRE_ERR_ARG, "null pointer");
+  if (grads)
+    for (int i = 0; i < p.ntens; ++i) if (!grads[i]) return fail(WIRE_ERR_ARG, "grads[%d] is null", i);
+  const HierAct a = hier_act(p, n, 1);
+  const HierScratch sc = hier_scratch(p, n);
+  const int64_t need = g_coords ? sc.total_coords : sc.total;
+  if (act_bytes < a.total * 4) return fail(WIRE_ERR_SIZE, "act buffer too small");
+  if (scratch_bytes < need * 4) return fail(WIRE_ERR_SIZE, "scratch %lld < %lld bytes", (long long)scratch_bytes,
+                                            (long long)need * 4);
+  hipStream_t s = (hipStream_t)stream;
+  const float* A = (const float*)act;
+  float* Sx = (float*)scratch;
+  const int S = p.HS, per = p.HL + 2;
+  const bool x2 = r.fam == FAM_X2;
+  // weight gradients: the K x K layers on the route's family; the join's [P] x [2P] on 2 x fp16 where that kernel has
+  // the shape, else on the family below it
+  const WireFamily tnj = (x2 && gemmx2_tn_applies(p.P, 2 * p.P)) ? FAM_X2 : p.x3 ? FAM_X3 : FAM_4M;
+  const WireFamily tnk = r.tn_fam == FAM_3M ? FAM_4M : r.tn_fam;
+  const int tnk_S = hier_tn_splits(tnk, n, p.P, p.P, sc.S), tnj_S = hier_tn_splits(tnj, n, p.P, 2 * p.P, sc.S);
+  unsigned* const gs = reinterpret_cast<unsigned*>(Sx + sc.gamax);
+  const unsigned* const os = reinterpret_cast<const unsigned*>(A + a.amax);
+  auto gsl = [&](int st, int l) -> unsigned* { return x2 ? gs + (int64_t)(st * per + l) * WIRE_AMAX_SLOTS : nullptr; };
+  auto osl = [&](int aset) -> const unsigned* { return (x2 && aset >= 0) ? os + (int64_t)aset * WIRE_AMAX_SLOTS : nullptr; };
+  auto grad = [&](int t) -> float* { return (float*)grads[t]; };
+  auto done = [&](int t, int cnt) { if (ready) ready(user, t, cnt); };
+  if (x2) HIPCHK(hipMemsetAsync(gs, 0, (size_t)hier_sets(p) * WIRE_AMAX_SLOTS * sizeof(unsigned), s));
+  // 1. the heads' weight gradients: g_y^T x_st needs nothing of the backward below, so they are final first
+  if (grads) {
+    ProfScope ps(s, 3, 0);
+    for (int st = 0; st < S; ++st) {
+      const HierOut& xl = a.out[st][hier_last(p, st)];
+      HIPCHK(launch_hier_head_bwd(s, g_y, n, p.O, hier_nat(p, packed, st).Wh, A + xl.off, xl.ld, nullptr, nullptr, p.K, p.P,
+                                  p.h_c[st], nullptr, Sx + sc.fpw, Sx + sc.fpb, nullptr));
+      HIPCHK(launch_final_reduce(s, WIRE_KIND_BSPLINE, Sx + sc.fpw, Sx + sc.fpb, final_bwd_blocks(n), p.O, p.K, p.P,
+                                 grad(hier_th(p, st)), grad(hier_th(p, st) + 1)));
+    }
+    done(hier_th(p, 0), 2 * S);
+  }
+  // 2. the stages from the last to the first
+  float* gcur = Sx + sc.g[0];
+  float* gnext = Sx + sc.g[1];
+  float* const T = Sx + sc.g[2];
+  for (int st = S - 1; st >= 0; --st) {
+    const float c = p.h_c[st];
+    const HierNat nat = hier_nat(p, packed, st);
+    const int last = hier_last(p, st);
+    {   // g_lin of the stage's last layer: its head's g_y Wh plus what the next stage's join sent back (T)
+      ProfScope ps(s, 3, 0);
+      HIPCHK(launch_hier_head_bwd(s, g_y, n, p.O, nat.Wh, nullptr, 0, A + a.lin[st][last], st + 1 < S ? T : nullptr, p.K,
+                                  p.P, c, gcur, nullptr, nullptr, gsl(st, last)));
+    }
+    for (int l = last; l >= 1; --l) {
+      const bool join = st > 0 && l == 1;
+      if (grads) {
+        const int t = hier_t(p, st, l);
+        if (join) {   // ONE launch over [x_in | x_{st-1}]
+          { ProfScope ps(s, 2, 2.0 * n * p.P * 2 * p.P);
+            HIPCHK(hier_tn(s, p, tnj, gcur, A + a.cat[st], 2 * p.P, 2 * p.P, n, tnj_S, Sx + sc.slab, Sx + sc.bslab, gsl(st, l),
+                           osl(st * per))); }
+          ProfScope ps(s, 3, 0);
+          HIPCHK(launch_hier_join_reduce(s, Sx + sc.slab, Sx + sc.bslab, tnj_S, p.K, p.P, grad(t), grad(t + 1)));
+        } else {
+          const HierOut& in = a.out[st][l - 1];
+          { ProfScope ps(s, 2, 2.0 * n * p.P * p.P);
+            HIPCHK(hier_tn(s, p, tnk, gcur, A + in.off, in.ld, p.P, n, tnk_S, Sx + sc.slab, Sx + sc.bslab, gsl(st, l),
+                           osl(in.aset))); }
+          ProfScope ps(s, 3, 0);
+          HIPCHK(launch_wgrad_reduce(s, WIRE_KIND_BSPLINE, Sx + sc.slab, Sx + sc.bslab, tnk_S, p.K, p.K, p.P, p.P, grad(t),
+                                     grad(t + 1), nullptr, nullptr));
+        }
+        done(t, 2);
+      }
+      GemmEpiParams ep;
+      ep.kvalid = p.K; ep.ld0 = p.P; ep.ld1 = p.P; ep.omega = p.w;
+      if (join) {
+        // left half: this stage's first layer; right half: the previous stage's last layer, with ITS c -- T waits there
+        // for that stage's head backward to add g_y Wh
+        ep.scale = c; ep.i0 = A + a.lin[st][0]; ep.o0 = gnext;
+        { ProfScope ps(s, 1, 2.0 * n * p.P * p.P);
+          const int v = hier_vhalf(p, st, 0);
+          HIPCHK(layer_nt(s, p, r.fam, packed, v, true, EPI_BSPLINE_BWD, gcur, n, ep, gsl(st, l), wamax_of(p, packed, v),
+                          nullptr)); }
+        ep.scale = p.h_c[st - 1]; ep.i0 = A + a.lin[st - 1][hier_last(p, st - 1)]; ep.o0 = T;
+        ProfScope ps(s, 1, 2.0 * n * p.P * p.P);
+        const int v = hier_vhalf(p, st, 1);
+        HIPCHK(layer_nt(s, p, r.fam, packed, v, true, EPI_BSPLINE_BWD, gcur, n, ep, gsl(st, l), wamax_of(p, packed, v),
+                        nullptr));
+      } else {
+        ep.scale = c; ep.i0 = A + a.lin[st][l - 1]; ep.o0 = gnext;
+        const int v = hier_v(p, st, l);
+        ProfScope ps(s, 1, 2.0 * n * p.P * p.P);
+        HIPCHK(layer_nt(s, p, r.fam, packed, v, true, EPI_BSPLINE_BWD, gcur, n, ep, gsl(st, l), wamax_of(p, packed, v),
+                        l >= 2 ? gsl(st, l - 1) : nullptr));
+      }
+      float* t = gcur; gcur = gnext; gnext = t;
+    }
+    // gcur = g_lin_0 of the stage: its first layer's sums and its share of the coordinate gradient
+    ProfScope ps(s, 3, 0);
+    if (grads) {
+      HIPCHK(launch_colreduce(s, gcur, p.P, p.K, coords, p.D, n, Sx + sc.crp, grad(hier_t(p, st, 0)),
+                              grad(hier_t(p, st, 0) + 1)));
+      done(hier_t(p, st, 0), 2);
+    }
+    if (g_coords)
+      HIPCHK(launch_coordgrad_rows(s, gcur, p.P, nullptr, nat.W0, nullptr, p.K, p.D, n,
+                                   S == 1 ? g_coords : Sx + sc.cgp + (int64_t)st * n * p.D));
+  }
+  if (g_coords && S > 1) {   // stage 0 first, in order
+    ProfScope ps(s, 3, 0);
+    HIPCHK(launch_m2_sum_passes(s, Sx + sc.cgp, S, n, p.D, g_coords));
+  }
+  return WIRE_OK;
+}
+
+// the route of a hierarchical net: the families of make_route, nothing fused, nothing pre-split
+Route hier_route(const Plan& p, int64_t n, RouteMode mode) {
+  Route r = make_route(p, n, mode);
+  r.fused_fwd = r.fuse = r.fused_train = r.fused_final = r.chain = r.rstore = r.skip_out_L = false;
+  r.first_sums = r.cg_epi = false;
+  r.wb_l0 = p.L + 1; r.wb_n = 0;
+  for (float& v : r.out_scale) v = 0.f;
+  return r;
+}
+}  // namespace
+
+static int64_t hier_act_total(const Plan& p, int64_t n, int save) { return hier_act(p, n, save).total; }
+static int64_t hier_scratch_total(const Plan& p, int64_t n, bool coords) {
+  const HierScratch s = hier_scratch(p, n);
+  return coords ? s.total_coords : s.total;
+}
+static int hier_fwd_dispatch(void* stream, const Plan& p, const float* packed, const float* coords, int64_t n, float* y,
+                             void* act, int64_t act_bytes, int save_for_bwd) {
+  return hier_fwd_core(stream, p, hier_route(p, n, save_for_bwd ? MODE_AUTOGRAD : MODE_INFER), packed, coords, n, y, act,
+                       act_bytes);
+}
+
 extern "C" int wire_mlp_bwd(void* stream, const wire_net_desc* d, const float* packed,
                             const float* coords, int64_t n, const float* g_y, const void* act,
                             int64_t act_bytes, void* scratch, int64_t scratch_bytes,
                             void* const* grads) {
   Plan p; if (int rc = make_plan(d, p)) return rc;
   if (!grads) return fail(WIRE_ERR_ARG, "null pointer");
+  if (p.hier)
+    return hier_bwd_core(stream, p, hier_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
+                         scratch_bytes, grads, nullptr, nullptr, nullptr);
   return mlp_bwd_core(stream, p, make_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
                       scratch_bytes, grads);
 }
@@ -1266,6 +1712,9 @@ extern "C" int wire_mlp_bwd_coords(void* stream, const wire_net_desc* d, const f
                                    int64_t scratch_bytes, void* const* grads_host, float* g_coords) {
   Plan p; if (int rc = make_plan(d, p)) return rc;
   if (!grads_host && !g_coords) return fail(WIRE_ERR_ARG, "wire_mlp_bwd_coords: neither grads_host nor g_coords");
+  if (p.hier)
+    return hier_bwd_core(stream, p, hier_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
+                         scratch_bytes, grads_host, nullptr, nullptr, g_coords);
   return mlp_bwd_core(stream, p, make_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
                       scratch_bytes, grads_host, nullptr, nullptr, g_coords);
 }
@@ -1283,6 +1732,22 @@ extern "C" int wire_train_fwd_bwd_hooked(void* stream, const wire_net_desc* d, c
   if (n <= 0) return fail(WIRE_ERR_ARG, "wire_train_fwd_bwd needs n > 0");
   if (!target || !y || !g_y || !loss_out || !partial) return fail(WIRE_ERR_ARG, "null pointer");
   hipStream_t s = (hipStream_t)stream;
+  if (p.hier) {
+    // the stages' forward; the last head's launch finishes y and forms the MSE terms and g_y; then the backward
+    const Route hr = hier_route(p, n, MODE_TRAIN);
+    const HierScratch sc = hier_scratch(p, n);
+    if (!scratch || scratch_bytes < sc.total * 4) return fail(WIRE_ERR_SIZE, "scratch too small");
+    float* Sx = (float*)scratch;
+    const double inv_no = 1.0 / ((double)n * (double)p.O);
+    M2Loss ls;
+    ls.target = target; ls.idx = idx; ls.first = first; ls.gscale = (float)(weight * 2.0 * inv_no);
+    ls.y = y; ls.g_y = g_y; ls.rec = rec;
+    if (int rc = hier_fwd_core(stream, p, hr, packed, coords, n, y, act, act_bytes, &ls, Sx + sc.lpart)) return rc;
+    { ProfScope ps(s, 3, 0);
+      HIPCHK(launch_mse_final(s, Sx + sc.lpart, hier_head_blocks(n), (float)(weight * inv_no), loss_out)); }
+    return hier_bwd_core(stream, p, hr, packed, coords, n, g_y, act, act_bytes, scratch, scratch_bytes, grads, ready, user,
+                         nullptr);
+  }
   const Route r = make_route(p, n, MODE_TRAIN);
   if (p.m2) {
     // the trunk's passes; then ONE kernel runs the combiner's forward, the MSE, its gradient and the combiner's backward

@@ -134,6 +134,29 @@ hipError_t launch_m2_comb_reduce(hipStream_t s, const float* part, int64_t n, in
 // out [n][D] = sum_k g[k][n][D]
 hipError_t launch_m2_sum_passes(hipStream_t s, const float* g, int S, int64_t n, int D, float* out);
 
+// ---- the hierarchical B-spline net (wire_hier.hip): stages coupled by a 2K -> K join, one head per stage
+// first layer of a stage: lin (optional) [n][P], out rows of ldo floats (the left half of the join's [n][2P] input, or
+// [n][P]); pad features 0; amax_out: max |out| slots or null
+hipError_t launch_hier_first_fwd(hipStream_t s, const float* coords, int64_t n, int D, const float* W0, const float* b0,
+                                 int K, int P, float c, float* lin, float* out, int ldo, unsigned* amax_out);
+// y [n][O] = (acc ? y : 0) + (x Wh^T + bh), x rows of ldx floats (P of them read; pad features 0), Wh native [O][K];
+// ls.target: y is complete -- its MSE terms, g_y, rec and loss_part[hier_head_blocks(n)]; O P floats of LDS (<= 64 KB)
+#define HIER_HEAD_MAXBLK 1024
+int hier_head_blocks(int64_t n);
+hipError_t launch_hier_head_fwd(hipStream_t s, const float* x, int ldx, const float* Wh, const float* bh, int64_t n, int K,
+                                int P, int O, int acc, float* y, const M2Loss& ls, float* loss_part);
+// part_w / part_b (optional, launch_final_bwd's layout and room): partials of gWh = g_y^T x, gbh;  g_lin (optional)
+// [n][P] = (g_y Wh) c B'(c lin) + add (add optional, [n][P]), amax_g its max-|value| slots or null
+hipError_t launch_hier_head_bwd(hipStream_t s, const float* g_y, int64_t n, int O, const float* Wh, const float* x, int ldx,
+                                const float* lin, const float* add, int K, int P, float c, float* g_lin, float* part_w,
+                                float* part_b, unsigned* amax_g);
+// W [K][2K], b [K] -> fwd [P][2P] (halves at columns 0 and P), bias [P], Wa / Wb [K][K] (the halves, contiguous)
+hipError_t launch_hier_pack_join(hipStream_t s, const float* W, const float* b, int K, int P, float* fwd, float* bias,
+                                 float* Wa, float* Wb);
+// slab [S][P][2P], bslab [S][P] -> gW [K][2K], gb [K]
+hipError_t launch_hier_join_reduce(hipStream_t s, const float* slab, const float* bslab, int S, int K, int P, float* gW,
+                                   float* gb);
+
 // ---- coordinate gradients (first-order, fp32)
 // g_x[r][d] = sum_k G[r][k] W[k][d] (+ sum_k G2[r][k] V[k][d]) over the K valid features of a stored first-layer gradient
 // (real g_lin_0, wire g_u, wire2d g_u with G2 = g_p); W, V native [K][D].  One wave per row, fixed reduction order.

@@ -12,20 +12,21 @@ arguments its own signature has, so both call styles work:
             hidden_layers=2, first_omega_0=7., hidden_omega_0=7., scale=6.)
     get_INR('wire', 2, 300, 0, 2, 3, scale_tensor=[0.0], ...)   # bspline_* style
 """
-from . import bspline_form, bspline_mscale_2, bspline_mscale_HL, gauss, relu, siren, wire, wire2d
+from . import bspline_form, bspline_mscale_2, bspline_mscale_HL, bspline_mscale_hier, gauss, relu, siren, wire, wire2d
 
-# keys of modules/models.py:15-25 that are on the MI355X path; 'mfn', 'bspline_cubic'
-# and bspline_mscale_hier are out of scope (SURVEY.md section 2.1 rows 7-8).
+# keys of modules/models.py:15-25 that are on the MI355X path; 'mfn' and 'bspline_cubic'
+# are out of scope (SURVEY.md section 2.1 rows 7-8).
 model_dict = {'bspline_form': bspline_form,
               'bspline_mscale_2': bspline_mscale_2,
               'bspline_mscale_HL': bspline_mscale_HL,
+              'bspline_mscale_hier': bspline_mscale_hier,
               'gauss': gauss,
               'relu': relu,
               'siren': siren,
               'wire': wire,
               'wire2d': wire2d}
 
-_OUT_OF_SCOPE = ('mfn', 'bspline_cubic', 'bspline_mscale_hier')
+_OUT_OF_SCOPE = ('mfn', 'bspline_cubic')
 
 
 def get_INR(nonlin, in_features, hidden_features, scaled_hidden_features=None,
@@ -34,7 +35,8 @@ def get_INR(nonlin, in_features, hidden_features, scaled_hidden_features=None,
             pos_encode=False, sidelength=512, fn_samples=None, use_nyquist=True):
     """Return an INR ``nn.Module`` whose forward/backward run on MI355X.
 
-    nonlin: 'wire', 'wire2d', 'siren', 'gauss', 'relu', 'bspline_form' or 'bspline_mscale_HL' ('posenc' is 'relu'
+    nonlin: 'wire', 'wire2d', 'siren', 'gauss', 'relu', 'bspline_form', 'bspline_mscale_HL', 'bspline_mscale_2' or
+    'bspline_mscale_hier' ('posenc' is 'relu'
     with ``pos_encode=True``, as the reference's drivers spell it).
     Remaining arguments: see modules/models.py:31-56 of the reference.
     """
@@ -52,8 +54,9 @@ def get_INR(nonlin, in_features, hidden_features, scaled_hidden_features=None,
                        hidden_layers, out_features, outermost_linear, first_omega_0,
                        hidden_omega_0, scale, scale_tensor, pos_encode, sidelength, fn_samples,
                        use_nyquist)
-    if nonlin in ('bspline_mscale_HL', 'bspline_mscale_2'):
-        # 15-argument form with `multiscale`, modules/bspline_mscale_HL.py / bspline_mscale_2.py; passed by keyword
+    if nonlin in ('bspline_mscale_HL', 'bspline_mscale_2', 'bspline_mscale_hier'):
+        # 15-argument form with `multiscale`, modules/bspline_mscale_HL.py / bspline_mscale_2.py / bspline_mscale_hier.py;
+        # passed by keyword
         return mod.INR(in_features=in_features, hidden_features=hidden_features,
                        scaled_hidden_features=0 if scaled_hidden_features is None else scaled_hidden_features,
                        hidden_layers=hidden_layers, out_features=out_features, outermost_linear=outermost_linear,

@@ -36,6 +36,13 @@ from .parallel import FlatGradAllReducer, replicas_identical, shard_bounds
 
 
 class FusedTrainer:
+    """``lr`` is a number for every net kind.  bspline_mscale_hier also takes a sequence of one rate per stage, the two
+    loops of the reference's bspline_*.py drivers: a number steps the stages' tensors only -- the heads are not in
+    ``model.parameters()`` there and keep their initial values, though their gradients are computed and present in
+    ``flat_grad`` -- and a sequence steps stage s and head s with ``lr[s]`` (times the schedule's factor).  A sequence
+    for any other kind, or of the wrong length, is a ValueError.  ``step_downsampled`` and ``step_radon`` work for
+    bspline_mscale_hier as for the other kinds."""
+
     def __init__(self, model: HipINR, grid: Sequence[int], target: torch.Tensor, lr: float = 5e-3,
                  betas=(0.9, 0.999), eps: float = 1e-8, gamma: float = 0.1, niters: int = 2000,
                  coords_style: str = "torch", keep_rec: bool = False, micro_shards: int = 1,
@@ -105,7 +112,8 @@ class FusedTrainer:
                                   device=self.dev)
         self.partial = torch.empty(4096, dtype=torch.float32, device=self.dev)
 
-        self.base_lr, self.betas, self.eps = float(lr), betas, float(eps)
+        self.betas, self.eps = betas, float(eps)
+        self._set_lr(lr)
         self.gamma, self.niters = float(gamma), int(niters)
         self.epoch = 0
         self.t = 0
@@ -151,6 +159,42 @@ class FusedTrainer:
             # identical because every rank applies the same Adam update to the same reduced gradient
             self._broadcast_from_rank0(self.flat)
 
+    def _set_lr(self, lr) -> None:
+        """base_lr and the slices (lo, hi, rate) of the flat buffer that Adam steps."""
+        hier = self.desc.kind == _lib.KIND["bspline_mscale_hier"]
+        if isinstance(lr, (list, tuple)) or (isinstance(lr, torch.Tensor) and lr.dim() > 0):
+            rates = [float(v) for v in lr]
+            S = int(self.desc._b_base_.nscales) if hier else 0
+            if not hier:
+                raise ValueError("a sequence of learning rates is the per-stage loop of bspline_mscale_hier only")
+            if len(rates) != S:
+                raise ValueError(f"{len(rates)} learning rates for {S} stages")
+        else:
+            rates = None
+        self.base_lr = rates if rates is not None else float(lr)
+        if not hier:
+            self._adam_slices = [(0, self.count, self.base_lr)]
+            return
+        S, L = int(self.desc._b_base_.nscales), int(self.desc.hidden_layers)
+        first = [0] + [2 * (L + 1) + 6 * (s - 1) for s in range(1, S)]       # first tensor of each stage
+        head0 = 2 * (L + 1) + 6 * (S - 1)
+        lo = [self.offsets[t] for t in first] + [self.offsets[head0]]
+        if rates is None:                                                    # the stages alone: the heads keep their bits
+            self._adam_slices = [(0, lo[-1], self.base_lr)]
+            return
+        hl = [self.offsets[head0 + 2 * s] for s in range(S)] + [self.count]
+        self._adam_slices = [(lo[s], lo[s + 1], rates[s]) for s in range(S)] + \
+                            [(hl[s], hl[s + 1], rates[s]) for s in range(S)]
+
+    def _adam(self, stream, g: torch.Tensor) -> None:
+        """torch.optim.Adam's step over the slices of the flat buffer, each with its rate times the schedule's factor."""
+        f = self.lr_factor()
+        for lo, hi, rate in self._adam_slices:
+            _lib.check(self.L.wire_adam_step_flat(stream, self.flat.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo,
+                                                  self.exp_avg.data_ptr() + 4 * lo, self.exp_avg_sq.data_ptr() + 4 * lo,
+                                                  hi - lo, rate * f, self.betas[0], self.betas[1], self.eps, self.t),
+                       "adam")
+
     def _broadcast_from_rank0(self, t: torch.Tensor) -> None:
         if dist.get_backend(self.group) == "gloo" and t.is_cuda:     # rehearsal backend: stage through the host
             host = t.detach().cpu()
@@ -165,6 +209,15 @@ class FusedTrainer:
         """(first_tensor, n_tensors) in the order wire_train_fwd_bwd_hooked announces them (include/wire_hip.h)."""
         nt = len(self.offsets)
         hidden = int(self.desc.hidden_layers)
+        if self.desc.kind == _lib.KIND["bspline_mscale_hier"]:
+            # the heads (one block at the end), then the stages from the last to the first, each from its last layer
+            S = int(self.desc._b_base_.nscales)
+            yield nt - 2 * S, 2 * S
+            for s in range(S - 1, -1, -1):
+                base = 0 if s == 0 else 2 * (hidden + 1) + 6 * (s - 1)
+                for l in range(hidden if s == 0 else 2, -1, -1):
+                    yield base + 2 * l, 2
+            return
         t0 = 0
         if self.desc.kind == _lib.KIND["bspline_mscale_HL"]:   # its frozen first stage (tensors 0, 1) comes last
             t0, hidden = 2, max(hidden - 1, 0)
@@ -226,9 +279,14 @@ class FusedTrainer:
         return out
 
     # ------------------------------------------------------------------ schedule
-    def current_lr(self) -> float:
+    def lr_factor(self) -> float:
         """LambdaLR(lambda x: gamma**min(x/niters, 1)) (wire_image_denoise.py:128)."""
-        return self.base_lr * self.gamma ** min(self.epoch / self.niters, 1)
+        return self.gamma ** min(self.epoch / self.niters, 1)
+
+    def current_lr(self):
+        """The rate of the next step (a list for the per-stage rates of bspline_mscale_hier)."""
+        f = self.lr_factor()
+        return [r * f for r in self.base_lr] if isinstance(self.base_lr, list) else self.base_lr * f
 
     def scheduler_step(self) -> None:
         self.epoch += 1
@@ -326,10 +384,7 @@ class FusedTrainer:
         for m in range(1, self.micro):
             gsum.add_(self.gbuf[m])
         self.t += 1
-        _lib.check(L.wire_adam_step_flat(stream, self.flat.data_ptr(), gsum.data_ptr(),
-                                         self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.count,
-                                         self.current_lr(), self.betas[0], self.betas[1], self.eps,
-                                         self.t), "adam")
+        self._adam(stream, gsum)
         self.loss = gsum[self.count:self.count + 1].clone()   # the buffer is reused next step
         if self.check_every and self.world > 1 and self.t % self.check_every == 0:
             if not replicas_identical(self.flat, self.group):
@@ -378,9 +433,7 @@ class FusedTrainer:
                                   self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
                                   self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
         self.t += 1
-        _lib.check(L.wire_adam_step_flat(stream, self.flat.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(),
-                                         self.exp_avg_sq.data_ptr(), self.count, self.current_lr(),
-                                         self.betas[0], self.betas[1], self.eps, self.t), "adam")
+        self._adam(stream, g)
         self.loss = g[self.count:self.count + 1].clone()
         return self.loss
 
@@ -425,9 +478,7 @@ class FusedTrainer:
                                   self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
                                   self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
         self.t += 1
-        _lib.check(L.wire_adam_step_flat(stream, self.flat.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(),
-                                         self.exp_avg_sq.data_ptr(), self.count, self.current_lr(),
-                                         self.betas[0], self.betas[1], self.eps, self.t), "adam")
+        self._adam(stream, g)
         self.loss = g[self.count:self.count + 1].clone()
         return self.loss
 
