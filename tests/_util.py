@@ -1,5 +1,6 @@
 """Shared helpers of the test-suite (fixture loading, model rebuild, metrics)."""
 import contextlib
+import ctypes as C
 import os
 import sys
 
@@ -239,3 +240,45 @@ def oracle_grads_chunked(kind, P, coords, target, L, om1, om, sc, double, nf=Non
 def wire_oracle_grads_chunked(P, coords, target, L, om1, om, sc, double, chunk=16384):
     """oracle_grads_chunked for the 1-D Gabor net (modules/wire.py:161-167)."""
     return oracle_grads_chunked("wire", P, coords, target, L, om1, om, sc, double, None, chunk)
+
+
+# ---------------------------------------------------------------------------
+# inputs and small helpers the GPU tests of the B-spline kinds share
+# ---------------------------------------------------------------------------
+def _coords(n, D=2, seed=1):
+    return np.random.default_rng(seed).uniform(-1, 1, (n, D)).astype(np.float32)
+
+
+def _target(n, O=3, seed=2):
+    return np.random.default_rng(seed).uniform(0, 1, (n, O)).astype(np.float32)
+
+
+def _grid_coords(H, W):
+    # the reference drivers' utils.get_coords: linspace(-1, 1) per axis, meshgrid 'xy', flat index = y W + x
+    X, Y = np.meshgrid(torch.linspace(-1, 1, W).numpy(), torch.linspace(-1, 1, H).numpy(), indexing="xy")
+    return np.stack([X.reshape(-1), Y.reshape(-1)], 1).astype(np.float32)
+
+
+def _sd(model):
+    return {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+
+
+def _errs(label, got, ref32, ref64):
+    within_ref(relmax(got, ref64), relmax(ref32, ref64), label)
+
+
+def _prof(fn):
+    """Launches per profiler class (wire_prof_read) of one call of fn."""
+    from wire_amd import _lib
+    L = _lib.lib()
+    torch.cuda.synchronize()
+    _lib.check(L.wire_prof_read((C.c_double * 4)(), (C.c_int64 * 4)(), (C.c_double * 4)()), "prof_read")
+    _lib.check(L.wire_prof_enable(1), "prof_enable")
+    try:
+        fn()
+        torch.cuda.synchronize()
+        ms, launches, fl = (C.c_double * 4)(), (C.c_int64 * 4)(), (C.c_double * 4)()
+        _lib.check(L.wire_prof_read(ms, launches, fl), "prof_read")
+    finally:
+        L.wire_prof_enable(0)
+    return list(launches)

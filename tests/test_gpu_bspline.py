@@ -4,7 +4,6 @@ Every comparison follows err_build <= 2 err_ref + 1e-6 (tests/_util.within_ref),
 arithmetic (lin / s, four squared relus, autograd of them) against fp64 on the same inputs.  Knob changes sit inside
 ``tune(...)``.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -12,7 +11,7 @@ import pytest
 import torch
 
 import bspline_ref as br
-from _util import GOLDEN, checksum, params_np, relmax, tune, within_ref
+from _util import GOLDEN, checksum, params_np, tune, within_ref, _coords, _errs, _grid_coords, _prof, _target
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -23,18 +22,6 @@ def _model(D, hf, L, O, s, seed=0, outermost_linear=True, kind="bspline_form"):
     torch.manual_seed(seed)
     return models.get_INR(nonlin=kind, in_features=D, out_features=O, hidden_features=hf, hidden_layers=L,
                           outermost_linear=outermost_linear, scale=s).to(DEV)
-
-
-def _coords(n, D, seed=1):
-    return np.random.default_rng(seed).uniform(-1, 1, (n, D)).astype(np.float32)
-
-
-def _target(n, O, seed=2):
-    return np.random.default_rng(seed).uniform(0, 1, (n, O)).astype(np.float32)
-
-
-def _errs(label, got, ref32, ref64):
-    within_ref(relmax(got, ref64), relmax(ref32, ref64), label)
 
 
 # ---- 1. one layer ---------------------------------------------------------------------------------------------------
@@ -84,22 +71,6 @@ def test_net_forward(L, K):
     _errs(f"bspline net fwd L={L} K={K} fused_fwd=0", y_l, y32, y64)
 
 
-def _prof(fn):
-    from wire_amd import _lib
-    L = _lib.lib()
-    torch.cuda.synchronize()
-    _lib.check(L.wire_prof_read((C.c_double * 4)(), (C.c_int64 * 4)(), (C.c_double * 4)()), "prof_read")
-    _lib.check(L.wire_prof_enable(1), "prof_enable")
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms, launches, fl = (C.c_double * 4)(), (C.c_int64 * 4)(), (C.c_double * 4)()
-        _lib.check(L.wire_prof_read(ms, launches, fl), "prof_read")
-    finally:
-        L.wire_prof_enable(0)
-    return list(launches)
-
-
 def test_inference_launch_counts_equal_gauss():
     x = torch.tensor(_coords(65536, 2), device=DEV)
     counts = {}
@@ -131,12 +102,6 @@ def _oracle_step(shape):
         r64 = br.loss_and_grads(sd, L, x.astype(np.float64), t.astype(np.float64), s, np.float64)
         _ORACLE[shape] = (x, t, r32, r64, (H, W))
     return _ORACLE[shape]
-
-
-def _grid_coords(H, W):
-    # the reference drivers' utils.get_coords: linspace(-1, 1) per axis, meshgrid 'xy', flat index = y W + x
-    X, Y = np.meshgrid(torch.linspace(-1, 1, W).numpy(), torch.linspace(-1, 1, H).numpy(), indexing="xy")
-    return np.stack([X.reshape(-1), Y.reshape(-1)], 1).astype(np.float32)
 
 
 @pytest.mark.parametrize("shape", list(SHAPES))

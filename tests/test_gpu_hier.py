@@ -13,7 +13,8 @@ import pytest
 import torch
 
 import hier_ref as hr
-from _util import GOLDEN, checksum, final_bias_within_ref, load_golden, relmax, tune, within_ref
+from _util import (GOLDEN, checksum, final_bias_within_ref, load_golden, relmax, tune, within_ref, _coords,
+                   _grid_coords, _prof, _sd, _target)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -29,28 +30,11 @@ def _model(st, K=256, hl=2, seed=0):
                           scale=0.0, scale_tensor=st).to(DEV)
 
 
-def _sd(model):
-    return {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
-
-
 def _heads(model):
     out = {}
     for s, lin in enumerate(model.linears):
         out[f"linears.{s}.weight"], out[f"linears.{s}.bias"] = lin.weight.detach().cpu().numpy(), lin.bias.detach().cpu().numpy()
     return out
-
-
-def _coords(n, seed=1):
-    return np.random.default_rng(seed).uniform(-1, 1, (n, 2)).astype(np.float32)
-
-
-def _target(n, seed=2):
-    return np.random.default_rng(seed).uniform(0, 1, (n, 3)).astype(np.float32)
-
-
-def _grid_coords(H, W):
-    X, Y = np.meshgrid(torch.linspace(-1, 1, W).numpy(), torch.linspace(-1, 1, H).numpy(), indexing="xy")
-    return np.stack([X.reshape(-1), Y.reshape(-1)], 1).astype(np.float32)
 
 
 def _both(model, L, x, t, st):
@@ -255,22 +239,6 @@ def test_step_radon_runs():
 
 
 # ---- 4. what runs -----------------------------------------------------------------------------------------------------
-def _prof(fn):
-    from wire_amd import _lib
-    L = _lib.lib()
-    torch.cuda.synchronize()
-    _lib.check(L.wire_prof_read((C.c_double * 4)(), (C.c_int64 * 4)(), (C.c_double * 4)()), "prof_read")
-    _lib.check(L.wire_prof_enable(1), "prof_enable")
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms, launches, fl = (C.c_double * 4)(), (C.c_int64 * 4)(), (C.c_double * 4)()
-        _lib.check(L.wire_prof_read(ms, launches, fl), "prof_read")
-    finally:
-        L.wire_prof_enable(0)
-    return list(launches)
-
-
 @pytest.mark.parametrize("hl", [2, 3])
 def test_launch_counts(hl):
     """Per step at S stages, L hidden layers: forward GEMMs L + 2 (S - 1) (the join is ONE GEMM over 2K), weight-gradient

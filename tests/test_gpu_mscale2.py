@@ -12,7 +12,8 @@ import pytest
 import torch
 
 import mscale2_ref as mr
-from _util import GOLDEN, checksum, final_bias_within_ref, load_golden, relmax, tune, within_ref
+from _util import (GOLDEN, checksum, final_bias_within_ref, load_golden, relmax, tune, within_ref, _coords,
+                   _grid_coords, _prof, _sd, _target)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -29,23 +30,6 @@ def _model(st, K=256, hl=2, seed=0):
     return models.get_INR(nonlin="bspline_mscale_2", in_features=2, out_features=3, hidden_features=K,
                           scaled_hidden_features=0, hidden_layers=hl, first_omega_0=-0.2, hidden_omega_0=-0.2,
                           scale=0.0, scale_tensor=torch.tensor(st).to(DEV)).to(DEV)
-
-
-def _sd(model):
-    return {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
-
-
-def _coords(n, seed=1):
-    return np.random.default_rng(seed).uniform(-1, 1, (n, 2)).astype(np.float32)
-
-
-def _target(n, seed=2):
-    return np.random.default_rng(seed).uniform(0, 1, (n, 3)).astype(np.float32)
-
-
-def _grid_coords(H, W):
-    X, Y = np.meshgrid(torch.linspace(-1, 1, W).numpy(), torch.linspace(-1, 1, H).numpy(), indexing="xy")
-    return np.stack([X.reshape(-1), Y.reshape(-1)], 1).astype(np.float32)
 
 
 def _check_grads(tag, got, r32, r64, n):
@@ -188,22 +172,6 @@ def test_trainer_render_and_hashed():
 
 
 # ---- 4. what runs ---------------------------------------------------------------------------------------------------
-def _prof(fn):
-    from wire_amd import _lib
-    L = _lib.lib()
-    torch.cuda.synchronize()
-    _lib.check(L.wire_prof_read((C.c_double * 4)(), (C.c_int64 * 4)(), (C.c_double * 4)()), "prof_read")
-    _lib.check(L.wire_prof_enable(1), "prof_enable")
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms, launches, fl = (C.c_double * 4)(), (C.c_int64 * 4)(), (C.c_double * 4)()
-        _lib.check(L.wire_prof_read(ms, launches, fl), "prof_read")
-    finally:
-        L.wire_prof_enable(0)
-    return list(launches)
-
-
 def _kernel_names(fn):
     from torch.profiler import ProfilerActivity, profile
     fn()

@@ -3,7 +3,6 @@
 Every comparison follows err_build <= 2 err_ref + 1e-6 (tests/_util.within_ref), err_ref being the reference's own fp32
 arithmetic (lin / s, four squared relus, autograd of them) against fp64 on the same inputs.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -11,7 +10,7 @@ import pytest
 import torch
 
 import mscale_ref as mr
-from _util import GOLDEN, checksum, relmax, within_ref
+from _util import GOLDEN, checksum, within_ref, _coords, _errs, _grid_coords, _prof, _sd, _target
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -26,28 +25,6 @@ def _model(shf, st, s, K=256, hl=2, seed=0):
     return models.get_INR(nonlin="bspline_mscale_HL", in_features=2, out_features=3, hidden_features=K,
                           scaled_hidden_features=shf, hidden_layers=hl, first_omega_0=-0.2, hidden_omega_0=-0.2,
                           scale=s, scale_tensor=torch.tensor(st).to(DEV)).to(DEV)
-
-
-def _sd(model):
-    return {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
-
-
-def _coords(n, D=2, seed=1):
-    return np.random.default_rng(seed).uniform(-1, 1, (n, D)).astype(np.float32)
-
-
-def _target(n, O=3, seed=2):
-    return np.random.default_rng(seed).uniform(0, 1, (n, O)).astype(np.float32)
-
-
-def _errs(label, got, ref32, ref64):
-    within_ref(relmax(got, ref64), relmax(ref32, ref64), label)
-
-
-def _grid_coords(H, W):
-    # the reference drivers' utils.get_coords: linspace(-1, 1) per axis, meshgrid 'xy', flat index = y W + x
-    X, Y = np.meshgrid(torch.linspace(-1, 1, W).numpy(), torch.linspace(-1, 1, H).numpy(), indexing="xy")
-    return np.stack([X.reshape(-1), Y.reshape(-1)], 1).astype(np.float32)
 
 
 # ---- 1. the first stage alone: every column, across the group boundaries ---------------------------------------------
@@ -132,22 +109,6 @@ def test_trainer_step(net):
 
 
 # ---- 3. what runs ---------------------------------------------------------------------------------------------------
-def _prof(fn):
-    from wire_amd import _lib
-    L = _lib.lib()
-    torch.cuda.synchronize()
-    _lib.check(L.wire_prof_read((C.c_double * 4)(), (C.c_int64 * 4)(), (C.c_double * 4)()), "prof_read")
-    _lib.check(L.wire_prof_enable(1), "prof_enable")
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms, launches, fl = (C.c_double * 4)(), (C.c_int64 * 4)(), (C.c_double * 4)()
-        _lib.check(L.wire_prof_read(ms, launches, fl), "prof_read")
-    finally:
-        L.wire_prof_enable(0)
-    return list(launches)
-
-
 @pytest.mark.parametrize("hl", [2, 3])
 def test_launch_counts(hl):
     """Forward GEMMs: SHF -> K and the hl - 1 hidden ones; data gradients: the hidden layers only (none for SHF -> K);

@@ -46,8 +46,8 @@ class NetDesc(C.Structure):
 
 
 class NetDescMS(C.Structure):
-    """struct wire_net_desc_ms: the multi-scale B-spline net's descriptor (kind 6).  The library takes a pointer to its
-    ``base`` member; ``make_desc_ms`` returns that member, which keeps this struct alive and lies at its start."""
+    """struct wire_net_desc_ms: the scaled B-spline nets' descriptor (kinds 6, 8, 9).  The library takes a pointer to its
+    ``base`` member; ``make_desc_scaled`` returns that member, which keeps this struct alive and lies at its start."""
     _fields_ = [("base", NetDesc), ("first_width", C.c_int32), ("nscales", C.c_int32),
                 ("scales", C.c_float * MS_MAX_SCALES)]
 
@@ -165,42 +165,50 @@ def make_desc(kind: str, in_features: int, width: int, hidden_layers: int, out_f
                    float(hidden_omega0), float(scale0))
 
 
+def make_desc_scaled(kind: str, in_features: int, width: int, hidden_layers: int, out_features: int,
+                     first_omega0: float, hidden_omega0: float, scale0: float, first_width: int, scales,
+                     min_scales: int) -> NetDesc:
+    """Descriptor of a scaled B-spline net: the ``base`` NetDesc of a NetDescMS (pass it wherever a NetDesc goes; it
+    keeps the struct alive and lies at its start), ``scales`` padded with zeros."""
+    scales = [float(v) for v in scales]
+    if not min_scales <= len(scales) <= MS_MAX_SCALES:
+        raise ValueError(f"{len(scales)} scales: the descriptor takes {min_scales}..{MS_MAX_SCALES}")
+    ms = NetDescMS(make_desc(kind, in_features, width, hidden_layers, out_features, first_omega0, hidden_omega0, scale0),
+                   int(first_width), len(scales),
+                   (C.c_float * MS_MAX_SCALES)(*(scales + [0.0] * (MS_MAX_SCALES - len(scales)))))
+    return ms.base
+
+
 def make_desc_ms(in_features: int, width: int, hidden_layers: int, out_features: int, first_omega0: float,
                  hidden_omega0: float, scale0: float, first_width: int, scales) -> NetDesc:
-    """Descriptor of a bspline_mscale_HL net: the ``base`` NetDesc of a NetDescMS (pass it wherever a NetDesc goes)."""
-    scales = [float(v) for v in scales]
-    if not 2 <= len(scales) <= MS_MAX_SCALES:
-        raise ValueError(f"{len(scales)} scales: the descriptor takes 2..{MS_MAX_SCALES}")
-    ms = NetDescMS(make_desc("bspline_mscale_HL", in_features, width, hidden_layers, out_features, first_omega0,
-                             hidden_omega0, scale0), int(first_width), len(scales),
-                   (C.c_float * MS_MAX_SCALES)(*scales))
-    return ms.base
+    """Descriptor of a bspline_mscale_HL net (kind 6): one scale per column group of its first stage."""
+    return make_desc_scaled("bspline_mscale_HL", in_features, width, hidden_layers, out_features, first_omega0,
+                            hidden_omega0, scale0, first_width, scales, 2)
 
 
 def make_desc_m2(in_features: int, width: int, hidden_layers: int, out_features: int, first_omega0: float,
                  hidden_omega0: float, scale0: float, scales) -> NetDesc:
-    """Descriptor of a bspline_mscale_2 net (kind 8): the ``base`` NetDesc of a NetDescMS with first_width = 0 and one
-    scale per trunk pass; ``scale0`` is carried and ignored."""
-    scales = [float(v) for v in scales]
-    if not 1 <= len(scales) <= MS_MAX_SCALES:
-        raise ValueError(f"{len(scales)} scales: the descriptor takes 1..{MS_MAX_SCALES}")
-    m2 = NetDescMS(make_desc("bspline_mscale_2", in_features, width, hidden_layers, out_features, first_omega0,
-                             hidden_omega0, scale0), 0, len(scales),
-                   (C.c_float * MS_MAX_SCALES)(*(scales + [0.0] * (MS_MAX_SCALES - len(scales)))))
-    return m2.base
+    """Descriptor of a bspline_mscale_2 net (kind 8): first_width = 0 and one scale per trunk pass; ``scale0`` is
+    carried and ignored."""
+    return make_desc_scaled("bspline_mscale_2", in_features, width, hidden_layers, out_features, first_omega0,
+                            hidden_omega0, scale0, 0, scales, 1)
 
 
 def make_desc_hier(in_features: int, width: int, hidden_layers: int, out_features: int, first_omega0: float,
                    hidden_omega0: float, scale0: float, scales) -> NetDesc:
-    """Descriptor of a bspline_mscale_hier net (kind 9): the ``base`` NetDesc of a NetDescMS with first_width = 0 and one
-    scale per stage; ``scale0`` is carried and ignored."""
-    scales = [float(v) for v in scales]
-    if not 1 <= len(scales) <= MS_MAX_SCALES:
-        raise ValueError(f"{len(scales)} scales: the descriptor takes 1..{MS_MAX_SCALES}")
-    h = NetDescMS(make_desc("bspline_mscale_hier", in_features, width, hidden_layers, out_features, first_omega0,
-                            hidden_omega0, scale0), 0, len(scales),
-                  (C.c_float * MS_MAX_SCALES)(*(scales + [0.0] * (MS_MAX_SCALES - len(scales)))))
-    return h.base
+    """Descriptor of a bspline_mscale_hier net (kind 9): first_width = 0 and one scale per stage; ``scale0`` is
+    carried and ignored."""
+    return make_desc_scaled("bspline_mscale_hier", in_features, width, hidden_layers, out_features, first_omega0,
+                            hidden_omega0, scale0, 0, scales, 1)
+
+
+def hier_tensor_map(hidden_layers: int, nscales: int):
+    """params[] of a bspline_mscale_hier net (csrc/wire_plan.h: hier_t, hier_th) as (first, last, head0): the first
+    tensor and the index of the last layer of every stage, and the first head's tensor.  Stage 0 holds hidden_layers + 1
+    (W, b) pairs, a later stage three; the heads' pairs follow the stages."""
+    L, S = int(hidden_layers), int(nscales)
+    start = lambda s: 0 if s == 0 else 2 * (L + 1) + 6 * (s - 1)
+    return [start(s) for s in range(S)], [L] + [2] * (S - 1), start(S)
 
 
 def ptr_array(ptrs):

@@ -10,21 +10,14 @@
 #include <algorithm>
 #include <cmath>
 
-#include "../../include/wire_hip.h"
-#include "wire_gemm.h"
-#include "wire_point.h"
+#include "wire_plan.h"
 
-extern int wire_fail_(int code, const char* msg);   // wire_api.hip
 // GEMM family the tuning flags select (wire_family_, wire_gemm.h): FAM_X3 = split-bf16 (wire_gemmx3.hip, every kind),
 // FAM_3M = 3-multiplication complex fp32 MFMA (wire_gemm3m.hip, ComplexGaborLayer only), FAM_4M = 4M fp32 MFMA.
 // The per-layer entry points run the SAME kernels as wire_mlp_fwd / wire_mlp_bwd, so the per-layer parity
 // tests (protocol step (i)) check the code the bench times.
-#ifndef WIRE_AMAX_SLOTS
-#define WIRE_AMAX_SLOTS 64
-#endif
 
 namespace {
-inline int rup(int v, int m) { return (v + m - 1) / m * m; }
 inline int64_t rup64(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 struct LayerWs {

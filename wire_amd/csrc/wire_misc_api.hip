@@ -1,0 +1,167 @@
+// wire_misc_api.hip -- the one-launch entry points of the C ABI (include/wire_hip.h): training glue, metrics, the
+// Radon transform, the combiner and first stage of the scaled B-spline nets as layer calls, layout helpers.
+#include <cmath>
+
+#include "wire_plan.h"
+
+// ---------------------------------------------------------------------------
+// training glue
+// ---------------------------------------------------------------------------
+extern "C" int wire_coords_from_index(void* stream, const int64_t* idx, int64_t first, int64_t n,
+                                      const float* tx, int W, const float* ty, int H,
+                                      const float* tz, int T, float* coords) {
+  if (n < 0 || !tx || !ty || !coords || W < 1 || H < 1 || (tz && T < 1))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_coords_from_index");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_coords((hipStream_t)stream, idx, first, n, tx, W, ty, H, tz, T, coords));
+  return WIRE_OK;
+}
+extern "C" int wire_perm_indices(void* stream, uint64_t seed, int64_t n_total, int64_t first, int64_t count,
+                                 int64_t* idx_out) {
+  if (n_total < 1 || first < 0 || count < 0 || first + count > n_total || (count > 0 && !idx_out))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_perm_indices");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_perm_indices((hipStream_t)stream, seed, n_total, first, count, idx_out));
+  return WIRE_OK;
+}
+extern "C" int wire_mse_grad(void* stream, const float* y, const float* target, const int64_t* idx,
+                             int64_t first, int64_t n, int O, float weight, float* g_y,
+                             float* loss_out, float* rec, float* partial) {
+  if (n < 0 || O < 1 || !y || !target || !g_y || !loss_out || !partial)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_mse_grad");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_mse_grad((hipStream_t)stream, y, target, idx, first, n, O, weight, g_y, loss_out,
+                         rec, partial));
+  return WIRE_OK;
+}
+extern "C" int wire_avgpool_mse_grad(void* stream, const float* y, int H, int W, int O, int scale,
+                                     const float* gt_lr, float* g_y, float* rec_lr, float* loss_out,
+                                     float* partial) {
+  if (H < 1 || W < 1 || O < 1 || scale < 1 || scale > H || scale > W || !y || !gt_lr || !g_y || !loss_out || !partial)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_avgpool_mse_grad");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_avgpool_mse_grad((hipStream_t)stream, y, H, W, O, scale, gt_lr, g_y, rec_lr, loss_out, partial));
+  return WIRE_OK;
+}
+extern "C" int wire_adam_step_flat(void* stream, float* param, const float* grad, float* exp_avg,
+                                   float* exp_avg_sq, int64_t count, float lr, float beta1,
+                                   float beta2, float eps, int64_t step) {
+  if (count < 0 || step < 1 || !param || !grad || !exp_avg || !exp_avg_sq)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_adam_step_flat");
+  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_adam((hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, count,
+                     (float)((double)lr / bc1), beta1, beta2, eps, (float)(1.0 / std::sqrt(bc2))));
+  return WIRE_OK;
+}
+
+extern "C" int wire_eval_metric(void* stream, int mode, const float* rec, const float* gt, int64_t count,
+                                float thres, float* out2, float* partial) {
+  if ((mode != 0 && mode != 1) || count < 1 || !rec || !gt || !out2 || !partial)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_eval_metric");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_metric((hipStream_t)stream, mode, rec, gt, count, thres, out2, partial));
+  return WIRE_OK;
+}
+
+extern "C" int wire_track_best(void* stream, const float* metric, float* best_metric, int force, const float* src,
+                               float* dst, int64_t count, int* updated) {
+  if (!metric || !best_metric || count < 0 || (count > 0 && (!src || !dst)))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_track_best");
+  if (count > 0 && (((uintptr_t)src | (uintptr_t)dst) & 15)) return fail(WIRE_ERR_ARG, "src / dst must be 16-byte aligned");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_track_best((hipStream_t)stream, metric, best_metric, force, src, dst, count, updated));
+  return WIRE_OK;
+}
+extern "C" int wire_radon_fwd(void* stream, const float* img, const float* angles_deg, int H, int W, int nangles,
+                              float* sino) {
+  if (H < 1 || W < 1 || nangles < 1 || !img || !angles_deg || !sino) return fail(WIRE_ERR_ARG, "bad argument to wire_radon_fwd");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_radon_fwd((hipStream_t)stream, img, angles_deg, H, W, nangles, sino));
+  return WIRE_OK;
+}
+extern "C" int wire_radon_bwd(void* stream, const float* g_sino, const float* angles_deg, int H, int W, int nangles,
+                              float* g_img) {
+  if (H < 1 || W < 1 || nangles < 1 || !g_sino || !angles_deg || !g_img) return fail(WIRE_ERR_ARG, "bad argument to wire_radon_bwd");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_radon_bwd((hipStream_t)stream, g_sino, angles_deg, H, W, nangles, g_img));
+  return WIRE_OK;
+}
+extern "C" int wire_mscale_first_fwd(void* stream, const float* x, const float* W, const float* b, int64_t n,
+                                     int in_features, int out_features, int nscales, const float* scales_host, float* out) {
+  if (n < 0 || in_features < 1 || in_features > 4 || (n > 0 && (!x || !W || !b || !out)) || !scales_host)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_mscale_first_fwd");
+  // the descriptor's checks of the first stage (make_plan), on a net around it
+  wire_net_desc_ms m{};
+  m.base.kind = WIRE_KIND_BSPLINE_MS; m.base.in_features = in_features; m.base.width = 1; m.base.out_features = 1;
+  m.base.scale0 = 1.f; m.first_width = out_features; m.nscales = nscales;
+  if (nscales >= 2 && nscales <= WIRE_MS_MAX_SCALES)
+    for (int g = 0; g < nscales; ++g) m.scales[g] = scales_host[g];
+  Plan p; if (int rc = make_plan(&m.base, p)) return rc;
+  MscaleC c{};
+  for (int g = 0; g < p.T; ++g) c.c[g] = p.sc_c[g];
+  HIPCHK(launch_mscale_first((hipStream_t)stream, x, n, in_features, W, b, p.SHF, c, p.ms_split, p.SHF, 0.f, nullptr, out));
+  return WIRE_OK;
+}
+static bool m2_shape_ok(int S, int O) { return S >= 1 && S <= WIRE_MS_MAX_SCALES && O >= 1 && O <= 8; }
+extern "C" int wire_m2_combine_fwd(void* stream, int nscales, int out_features, const float* W1, const float* b1,
+                                   const float* W2, const float* b2, const float* t, int64_t n, float* y) {
+  if (!m2_shape_ok(nscales, out_features) || n < 0 || !W1 || !b1 || !W2 || !b2 || (n > 0 && (!t || !y)))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_m2_combine_fwd");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_m2_comb_fwd((hipStream_t)stream, M2Comb{W1, b1, W2, b2}, nscales, out_features, t, n, y));
+  return WIRE_OK;
+}
+extern "C" int64_t wire_m2_combine_ws_bytes(int nscales, int out_features, int64_t n) {
+  if (!m2_shape_ok(nscales, out_features) || n < 0) return fail(WIRE_ERR_ARG, "bad argument to wire_m2_combine_ws_bytes");
+  return (int64_t)m2_comb_blocks(n) * m2_comb_grad_floats(nscales, out_features) * 4 + 256;
+}
+extern "C" int wire_m2_combine_bwd(void* stream, int nscales, int out_features, const float* W1, const float* b1,
+                                   const float* W2, const float* b2, const float* t, int64_t n, const float* g_y,
+                                   float* g_t, float* gW1, float* gb1, float* gW2, float* gb2, void* ws,
+                                   int64_t ws_bytes) {
+  if (!m2_shape_ok(nscales, out_features) || n < 1 || !W1 || !b1 || !W2 || !b2 || !t || !g_y || !g_t || !gW1 || !gb1 ||
+      !gW2 || !gb2 || !ws)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_m2_combine_bwd");
+  if (ws_bytes < wire_m2_combine_ws_bytes(nscales, out_features, n)) return fail(WIRE_ERR_SIZE, "ws too small");
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(s, 3, 0);
+  const M2Comb w{W1, b1, W2, b2};
+  HIPCHK(launch_m2_comb_bwd(s, w, nscales, out_features, t, n, M2Loss{}, g_y, g_t, (float*)ws, nullptr));
+  HIPCHK(launch_m2_comb_reduce(s, (const float*)ws, n, nscales, out_features, M2Grads{gW1, gb1, gW2, gb2}));
+  return WIRE_OK;
+}
+extern "C" int wire_posenc_fwd(void* stream, const float* coords, int64_t n, int D, int F, float* out) {
+  if (n < 0 || D < 1 || D > 4 || F < 0 || F > 30 || (n > 0 && (!coords || !out)))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_posenc_fwd");
+  HIPCHK(launch_posenc((hipStream_t)stream, coords, n, D, F, D + 2 * D * F, out));
+  return WIRE_OK;
+}
+extern "C" int wire_posenc_bwd(void* stream, const float* coords, int64_t n, int D, int F, const float* g_pe,
+                               float* g_coords) {
+  if (n < 0 || D < 1 || D > 4 || F < 0 || F > 30 || (n > 0 && (!coords || !g_pe || !g_coords)))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_posenc_bwd");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_posenc_bwd((hipStream_t)stream, coords, n, D, F, g_pe, D + 2 * D * F, g_coords));
+  return WIRE_OK;
+}
+extern "C" int wire_sigmoid_inplace(void* stream, float* x, int64_t count) {
+  if (count < 0 || (count > 0 && !x)) return fail(WIRE_ERR_ARG, "bad argument to wire_sigmoid_inplace");
+  HIPCHK(launch_sigmoid((hipStream_t)stream, x, count));
+  return WIRE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// layout helpers
+// ---------------------------------------------------------------------------
+extern "C" int wire_c64_to_blocked(void* stream, const void* src, int64_t n, int K, float* dst) {
+  if (n < 0 || K < 1 || !src || !dst) return fail(WIRE_ERR_ARG, "bad argument");
+  HIPCHK(launch_c64_to_blocked((hipStream_t)stream, (const float*)src, n, K, rup(2 * K, 64), dst));
+  return WIRE_OK;
+}
+extern "C" int wire_blocked_to_c64(void* stream, const float* src, int64_t n, int K, void* dst) {
+  if (n < 0 || K < 1 || !src || !dst) return fail(WIRE_ERR_ARG, "bad argument");
+  HIPCHK(launch_blocked_to_c64((hipStream_t)stream, src, n, K, rup(2 * K, 64), (float*)dst));
+  return WIRE_OK;
+}

@@ -10,6 +10,7 @@ attribute names and init order (same ``torch.manual_seed`` -> same
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional
 
 import torch
@@ -127,6 +128,22 @@ def _has_hparams(m: nn.Module) -> bool:
 
 def _scalar_param(value: float, trainable: bool) -> nn.Parameter:
     return nn.Parameter(float(value) * torch.ones(1), requires_grad=bool(trainable))
+
+
+def scale_list(x) -> List[float]:
+    """A scale_tensor / sigma0 argument (tensor or sequence) as a list of floats."""
+    if isinstance(x, torch.Tensor):
+        return [float(v) for v in x.detach().reshape(-1).cpu().tolist()]
+    return [float(v) for v in x]
+
+
+def check_scales(kind: str, scales: List[float], lo: Optional[int] = None) -> None:
+    """NotImplementedError for a zero or non-finite scale and, with ``lo``, for a count outside lo..MS_MAX_SCALES."""
+    if lo is not None and not lo <= len(scales) <= _lib.MS_MAX_SCALES:
+        raise NotImplementedError(f"{kind} needs {lo}..{_lib.MS_MAX_SCALES} scales, got {len(scales)}")
+    for v in scales:
+        if v == 0.0 or not math.isfinite(v):
+            raise NotImplementedError(f"{kind} scale {v} is zero or not finite")
 
 
 def _param_value(p) -> float:

@@ -19,30 +19,15 @@ eight, a zero or non-finite one, ``outermost_linear=False``, ``trainable=True`` 
 """
 from __future__ import annotations
 
-import math
 from typing import List
 
 import torch
 from torch import nn
 
 from .. import _lib, functional as Fh
-from ._base import ActivationLayer, FinalLinear, HipINR
+from ._base import ActivationLayer, FinalLinear, HipINR, check_scales, scale_list
 
 __all__ = ["Bsplines_form", "AdaptiveScaleCombiner", "INR"]
-
-
-def _scale_list(scale_tensor) -> List[float]:
-    if isinstance(scale_tensor, torch.Tensor):
-        return [float(v) for v in scale_tensor.detach().reshape(-1).cpu().tolist()]
-    return [float(v) for v in scale_tensor]
-
-
-def _check_scales(scales: List[float]) -> None:
-    if not 1 <= len(scales) <= _lib.MS_MAX_SCALES:
-        raise NotImplementedError(f"bspline_mscale_2 needs 1..{_lib.MS_MAX_SCALES} scales, got {len(scales)}")
-    for v in scales:
-        if v == 0.0 or not math.isfinite(v):
-            raise NotImplementedError(f"bspline_mscale_2 scale {v} is zero or not finite")
 
 
 class Bsplines_form(ActivationLayer):
@@ -71,7 +56,7 @@ class Bsplines_form(ActivationLayer):
 
     def forward(self, input, scale):
         s = float(scale)
-        _check_scales([s])
+        check_scales("bspline_mscale_2", [s], 1)
         return Fh.real_layer(self.kind, input, self.linear.weight, self._bias_or_zeros(self.linear),
                              float(self.omega_0), s)
 
@@ -107,8 +92,8 @@ class INR(HipINR):
         super().__init__()
         if not outermost_linear:
             raise NotImplementedError("bspline_mscale_2 with outermost_linear=False is not on the MI355X path")
-        scales = _scale_list(scale_tensor)
-        _check_scales(scales)
+        scales = scale_list(scale_tensor)
+        check_scales(self.kind, scales, 1)
         self.nonlin = Bsplines_form
         self.complex = False
         self.pos_encode = False

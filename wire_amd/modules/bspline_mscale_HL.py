@@ -19,23 +19,16 @@ non-finite scale) and ``outermost_linear=False`` raise NotImplementedError; a pl
 """
 from __future__ import annotations
 
-import math
 from typing import List
 
 import torch
 from torch import nn
 
 from .. import _lib
-from ._base import ActivationLayer, FinalLinear, HipINR, _param_value
+from ._base import ActivationLayer, FinalLinear, HipINR, check_scales, scale_list
 from .bspline_form import Bsplines_form
 
 __all__ = ["Bsplines_form", "Scaled_Bsplines_form", "INR", "column_groups"]
-
-
-def _scale_list(sigma0) -> List[float]:
-    if isinstance(sigma0, torch.Tensor):
-        return [float(v) for v in sigma0.detach().reshape(-1).cpu().tolist()]
-    return [float(v) for v in sigma0]
 
 
 def column_groups(out_features: int, nscales: int) -> List[int]:
@@ -54,12 +47,6 @@ def column_groups(out_features: int, nscales: int) -> List[int]:
     return [0] * 256 + [1 + (j - 256) // split for j in range(256, shf)]
 
 
-def _check_scales(scales: List[float]) -> None:
-    for v in scales:
-        if v == 0.0 or not math.isfinite(v):
-            raise NotImplementedError(f"bspline_mscale_HL scale {v} is zero or not finite")
-
-
 class Scaled_Bsplines_form(ActivationLayer):
     kind = "bspline_mscale_HL"
 
@@ -68,9 +55,9 @@ class Scaled_Bsplines_form(ActivationLayer):
         super().__init__()
         if trainable:
             raise NotImplementedError("Scaled_Bsplines_form(trainable=True): trainable scales are not on the MI355X path")
-        scales = _scale_list(sigma0)
+        scales = scale_list(sigma0)
         column_groups(out_features, len(scales))
-        _check_scales(scales)
+        check_scales(self.kind, scales)
         self.is_first = is_first
         self.in_features = in_features
         self.out_features = out_features
@@ -82,9 +69,9 @@ class Scaled_Bsplines_form(ActivationLayer):
         self._scales = scales
 
     def refresh_hparams(self):
-        scales = _scale_list(self.scale_0)
+        scales = scale_list(self.scale_0)
         column_groups(self.out_features, len(scales))
-        _check_scales(scales)
+        check_scales(self.kind, scales)
         self._scales = scales
         self._s = scales[0]
 
@@ -105,9 +92,9 @@ class INR(HipINR):
         super().__init__()
         if not outermost_linear:
             raise NotImplementedError("bspline_mscale_HL with outermost_linear=False is not on the MI355X path")
-        scales = _scale_list(scale_tensor)
+        scales = scale_list(scale_tensor)
         column_groups(scaled_hidden_features, len(scales))
-        _check_scales(scales + [float(scale)])
+        check_scales(self.kind, scales + [float(scale)])
         self.nonlin = Bsplines_form
         self.nonlin_first = Scaled_Bsplines_form
         self.scale_tensor = scale_tensor
@@ -132,7 +119,7 @@ class INR(HipINR):
             m.refresh_hparams()
         if len({m._s for m in rest}) > 1:
             raise NotImplementedError("per-layer scale_0 values differ; the fused path supports one hidden scale")
-        _check_scales([rest[0]._s])
+        check_scales(self.kind, [rest[0]._s])
         self._arch["scale0"] = rest[0]._s
 
     def net_desc(self) -> _lib.NetDesc:

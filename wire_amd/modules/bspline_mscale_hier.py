@@ -22,30 +22,15 @@ No scale (the default ``scale_tensor=[]``), more than eight, a zero or non-finit
 """
 from __future__ import annotations
 
-import math
 from typing import List
 
 import torch
 from torch import nn
 
 from .. import _lib, functional as Fh
-from ._base import ActivationLayer, HipINR, _param_value, _scalar_param
+from ._base import ActivationLayer, HipINR, _param_value, _scalar_param, check_scales, scale_list
 
 __all__ = ["Bsplines_form", "INR"]
-
-
-def _scale_list(scale_tensor) -> List[float]:
-    if isinstance(scale_tensor, torch.Tensor):
-        return [float(v) for v in scale_tensor.detach().reshape(-1).cpu().tolist()]
-    return [float(v) for v in scale_tensor]
-
-
-def _check_scales(scales: List[float]) -> None:
-    if not 1 <= len(scales) <= _lib.MS_MAX_SCALES:
-        raise NotImplementedError(f"bspline_mscale_hier needs 1..{_lib.MS_MAX_SCALES} scales, got {len(scales)}")
-    for v in scales:
-        if v == 0.0 or not math.isfinite(v):
-            raise NotImplementedError(f"bspline_mscale_hier scale {v} is zero or not finite")
 
 
 class Bsplines_form(ActivationLayer):
@@ -90,8 +75,8 @@ class INR(HipINR):
                  outermost_linear=True, first_omega_0=-0.2, hidden_omega_0=-0.2, scale=15.0, scale_tensor=[],
                  pos_encode=False, multiscale=True, sidelength=512, fn_samples=None, use_nyquist=True):
         super().__init__()
-        scales = _scale_list(scale_tensor)
-        _check_scales(scales)
+        scales = scale_list(scale_tensor)
+        check_scales(self.kind, scales, 1)
         hidden_layers = int(hidden_layers)
         if hidden_layers < 1:
             raise NotImplementedError(f"bspline_mscale_hier needs hidden_layers >= 1, got {hidden_layers}")
@@ -141,7 +126,7 @@ class INR(HipINR):
                 raise NotImplementedError(f"bspline_mscale_hier stage {s}: per-layer scale_0 values differ "
                                           f"({sorted(vals)}); the MI355X path takes one divisor per stage")
             scales.append(vals.pop())
-        _check_scales(scales)
+        check_scales(self.kind, scales, 1)
         self._scales = scales
 
     def net_desc(self) -> _lib.NetDesc:

@@ -176,8 +176,7 @@ class FusedTrainer:
             self._adam_slices = [(0, self.count, self.base_lr)]
             return
         S, L = int(self.desc._b_base_.nscales), int(self.desc.hidden_layers)
-        first = [0] + [2 * (L + 1) + 6 * (s - 1) for s in range(1, S)]       # first tensor of each stage
-        head0 = 2 * (L + 1) + 6 * (S - 1)
+        first, _, head0 = _lib.hier_tensor_map(L, S)                         # first tensor of each stage, of the heads
         lo = [self.offsets[t] for t in first] + [self.offsets[head0]]
         if rates is None:                                                    # the stages alone: the heads keep their bits
             self._adam_slices = [(0, lo[-1], self.base_lr)]
@@ -212,11 +211,11 @@ class FusedTrainer:
         if self.desc.kind == _lib.KIND["bspline_mscale_hier"]:
             # the heads (one block at the end), then the stages from the last to the first, each from its last layer
             S = int(self.desc._b_base_.nscales)
+            first, last, _ = _lib.hier_tensor_map(hidden, S)
             yield nt - 2 * S, 2 * S
             for s in range(S - 1, -1, -1):
-                base = 0 if s == 0 else 2 * (hidden + 1) + 6 * (s - 1)
-                for l in range(hidden if s == 0 else 2, -1, -1):
-                    yield base + 2 * l, 2
+                for l in range(last[s], -1, -1):
+                    yield first[s] + 2 * l, 2
             return
         t0 = 0
         if self.desc.kind == _lib.KIND["bspline_mscale_HL"]:   # its frozen first stage (tensors 0, 1) comes last
