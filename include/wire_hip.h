@@ -31,6 +31,10 @@
  *                (modules/bspline_mscale_HL.py; its scales travel in
  *                 wire_net_desc_ms, see below)
  *       bspline_m2, bspline_hier : see wire_net_desc_ms below
+ *       mfn    : per filter i = 0..L: mu_i[K][D], gamma_i[K], w_i[K][D], c_i[K]
+ *                (gabon_filters.{i}.mu | .gamma | .linear.weight | .linear.bias);
+ *                then {W_i[K][K], b_i[K]} i = 0..L-1 (linear.{i}); then W_f[O][K],
+ *                b_f[O] (linear.{L}); all f32          (modules/mfn.py:29-54)
  *  - internal activation layout ("blocked planar"): a
  *    complex row of K features is stored as P = roundup(2K,64) floats; group
  *    g of 32 features occupies columns [64g,64g+32) = real parts and
@@ -67,14 +71,18 @@ typedef enum wire_kind {
   WIRE_KIND_BSPLINE_MS = 6, /* modules/bspline_mscale_HL.py: a frozen
                             Scaled_Bsplines_form D -> SHF, then Bsplines_form
                             SHF -> K; described by wire_net_desc_ms        */
-  /* 7 stays unassigned: a plain descriptor of kind 7 is WIRE_ERR_ARG, and callers rely on that */
+  /* 7 and 10 stay unassigned: a plain descriptor of kind 7 or 10 is WIRE_ERR_ARG, and callers rely on that */
   WIRE_KIND_BSPLINE_M2 = 8, /* modules/bspline_mscale_2.py: the bspline_form
                             trunk run once per scale, the S outputs through
                             freq_mlp; described by wire_net_desc_ms        */
-  WIRE_KIND_BSPLINE_HIER = 9 /* modules/bspline_mscale_hier.py: one stage per
+  WIRE_KIND_BSPLINE_HIER = 9, /* modules/bspline_mscale_hier.py: one stage per
                             scale, stage s > 0 joins its first layer with the
                             previous stage's output (2K -> K), one linear head
                             per stage; described by wire_net_desc_ms       */
+  WIRE_KIND_MFN = 11     /* modules/mfn.py: the multiplicative filter network
+                            z_0 = g_0(x), z_{i+1} = (z_i W_i^T + b_i) g_{i+1}(x),
+                            y = z_L W_f^T + b_f with hidden_layers + 1 Gabor
+                            filters g_i of the COORDINATES; a plain wire_net_desc  */
 } wire_kind;
 
 /* Architecture + hyper-parameters of one INR (modules/wire.py:96-159). */
@@ -92,6 +100,16 @@ typedef struct wire_net_desc {
                               (zero or not finite -> WIRE_ERR_ARG)                */
 } wire_net_desc;
 
+/* The multiplicative filter network (WIRE_KIND_MFN, modules/mfn.py) is described by a plain wire_net_desc:
+ *   width = K (hidden_features), hidden_layers = L >= 0 (L + 1 filters, L linears K -> K, the final linear K -> O),
+ *   in_features = D <= 4, out_features = O <= 8; first_omega0, hidden_omega0, scale0 and posenc_freqs are carried and
+ *   ignored (a zero scale0 is accepted).  g_i(x)_j = exp(-gamma_ij / 2 |x - mu_ij|^2) sin(x . w_ij + c_ij): every filter
+ *   reads the coordinates, so every filter contributes to g_coords.  The net runs layer by layer in every mode: the
+ *   knobs fused_fwd, fused_train, fused_bwd, fused_rstore and split_out leave its results unchanged.  Its backward is
+ *   deterministic (the filters' column sums are per-block partials added in a fixed order).
+ *   wire_act_out_offset(layer l) = the stored z_l.  The hooked call announces the final linear {W_f, b_f} first; then, for
+ *   i = L-1 .. 0, the pair {W_i, b_i} followed by the four tensors of filter i + 1; filter 0 last.  Every tensor
+ *   exactly once.                                                                                                     */
 /* The multi-scale B-spline net (WIRE_KIND_BSPLINE_MS, modules/bspline_mscale_HL.py): a wire_net_desc followed by the
  * shape of its frozen first stage.  Callers pass &desc.base wherever a const wire_net_desc* is taken; the library reads
  * the tail only when base.kind is WIRE_KIND_BSPLINE_MS.
@@ -374,6 +392,18 @@ int64_t wire_m2_combine_ws_bytes(int nscales, int out_features, int64_t n);
 int wire_m2_combine_bwd(void* stream, int nscales, int out_features, const float* W1, const float* b1, const float* W2,
                         const float* b2, const float* t, int64_t n, const float* g_y, float* g_t, float* gW1,
                         float* gb1, float* gW2, float* gb2, void* ws, int64_t ws_bytes);
+
+/* ---- GaborLayer.forward of the multiplicative filter network (modules/mfn.py:24-26) on native tensors ---------------
+ * x [n][in <= 4], mu [out][in], gamma [out], w [out][in] (linear.weight), c [out] (linear.bias) -> out [n][out] =
+ * exp(-gamma_j / 2 |x - mu_j|^2) sin(x . w_j + c_j).  The backward takes g_out [n][out] and writes g_mu, g_gamma, g_w,
+ * g_c and, when g_x is not NULL, g_x [n][in]; deterministic (per-block partials reduced in a fixed order in ws,
+ * wire_mfn_filter_ws_bytes(n, out) bytes).                                                                          */
+int wire_mfn_filter_fwd(void* stream, const float* x, const float* mu, const float* gamma, const float* w, const float* c,
+                        int64_t n, int in_features, int out_features, float* out);
+int64_t wire_mfn_filter_ws_bytes(int64_t n, int out_features);
+int wire_mfn_filter_bwd(void* stream, const float* g_out, const float* x, const float* mu, const float* gamma,
+                        const float* w, const float* c, int64_t n, int in_features, int out_features, float* g_mu,
+                        float* g_gamma, float* g_w, float* g_c, float* g_x, void* ws, int64_t ws_bytes);
 
 /* ---- positional encoding (PosEncoding.forward, modules/relu.py:62-75) ----
  * out[n][D + 2 D F]: the raw coordinates, then for each frequency i < F and dimension j < D: sin(2^i pi c_j),

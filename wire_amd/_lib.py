@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libwire_hip.so")
 
 KIND = {"wire": 0, "wire2d": 1, "siren": 2, "gauss": 3, "relu": 4, "bspline_form": 5, "bspline_mscale_HL": 6,
-        "bspline_mscale_2": 8, "bspline_mscale_hier": 9}
+        "bspline_mscale_2": 8, "bspline_mscale_hier": 9, "mfn": 11}
 MS_MAX_SCALES = 8   # WIRE_MS_MAX_SCALES
 ABI_VERSION = 1
 
@@ -33,7 +33,7 @@ SYMBOLS = [
     "wire_blocked_to_c64", "wire_prof_enable", "wire_prof_read", "wire_tune_set", "wire_tune_get", "wire_avgpool_mse_grad", "wire_layer2d_ws_bytes", "wire_gabor2d_fwd", "wire_gabor2d_bwd", "wire_eval_metric", "wire_real_layer_fwd", "wire_real_layer_bwd", "wire_train_fwd_bwd", "wire_perm_indices", "wire_gabor_hparam_grad", "wire_track_best", "wire_sigmoid_inplace", "wire_radon_fwd", "wire_radon_bwd", "wire_gabor2d_hparam_grad", "wire_posenc_fwd", "wire_act_out_offset", "wire_train_fwd_bwd_hooked",
     "wire_bwd_coords_scratch_bytes", "wire_mlp_bwd_coords", "wire_posenc_bwd", "wire_gabor_bwd_first_coords",
     "wire_gabor2d_bwd_first_coords", "wire_mscale_first_fwd", "wire_m2_combine_fwd", "wire_m2_combine_ws_bytes",
-    "wire_m2_combine_bwd",
+    "wire_m2_combine_bwd", "wire_mfn_filter_fwd", "wire_mfn_filter_ws_bytes", "wire_mfn_filter_bwd",
 ]
 
 
@@ -93,6 +93,10 @@ def _declare(l: C.CDLL) -> None:
     l.wire_m2_combine_ws_bytes.argtypes = [i32, i32, i64]
     l.wire_m2_combine_ws_bytes.restype = i64
     l.wire_m2_combine_bwd.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64]
+    l.wire_mfn_filter_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]
+    l.wire_mfn_filter_ws_bytes.argtypes = [i64, i32]
+    l.wire_mfn_filter_ws_bytes.restype = i64
+    l.wire_mfn_filter_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64]
     l.wire_bwd_coords_scratch_bytes.argtypes = [dp, i64]
     l.wire_bwd_coords_scratch_bytes.restype = i64
     l.wire_mlp_bwd_coords.argtypes = [vp, dp, vp, vp, i64, vp, vp, i64, vp, i64, C.POINTER(vp), vp]

@@ -1,6 +1,6 @@
 // wire_api.hip -- the C ABI of libwire_hip.so (include/wire_hip.h): the error channel, the profiler, the pack and the
 // launch sequences of the whole-net calls.  The plan and the size queries: wire_plan.hip; the hierarchical net:
-// wire_hier_api.hip; the one-launch entry points: wire_misc_api.hip; the per-layer ones: wire_layer_api.hip.
+// wire_hier_api.hip; the multiplicative filter network: wire_mfn_api.hip; the one-launch entry points: wire_misc_api.hip; the per-layer ones: wire_layer_api.hip.
 // No device memory is allocated here; every launch goes on the caller's stream.
 #include <cmath>
 #include <cstdarg>
@@ -203,6 +203,7 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
     }
   }
   if (p.hier) return hier_pack(s, p, params, packed);   // wire_hier_api.hip
+  if (p.mfn) return mfn_pack(s, p, params, packed);     // wire_mfn_api.hip
   std::vector<const float*> hW(p.L + 1, nullptr), hb(p.L + 1, nullptr);
   for (int l = 1; l <= p.L; ++l) {
     hW[l] = (const float*)params[p.t0 + p.per_layer * l]; hb[l] = (const float*)params[p.t0 + p.per_layer * l + 1];
@@ -378,6 +379,9 @@ extern "C" int wire_mlp_fwd(void* stream, const wire_net_desc* d, const float* p
   if (p.hier)
     return hier_fwd_core(stream, p, hier_route(p, n, save_for_bwd ? MODE_AUTOGRAD : MODE_INFER), packed, coords, n, y, act,
                          act_bytes);
+  if (p.mfn)
+    return mfn_fwd_core(stream, p, mfn_route(p, n, save_for_bwd ? MODE_AUTOGRAD : MODE_INFER), packed, coords, n, y, act,
+                        act_bytes);
   return mlp_fwd_core(stream, p, make_route(p, n, save_for_bwd ? MODE_AUTOGRAD : MODE_INFER), packed, coords, n, y, act,
                       act_bytes);
 }
@@ -729,6 +733,9 @@ extern "C" int wire_mlp_bwd(void* stream, const wire_net_desc* d, const float* p
   if (p.hier)
     return hier_bwd_core(stream, p, hier_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
                          scratch_bytes, grads, nullptr, nullptr, nullptr);
+  if (p.mfn)
+    return mfn_bwd_core(stream, p, mfn_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
+                        scratch_bytes, grads, nullptr, nullptr, nullptr);
   return mlp_bwd_core(stream, p, make_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
                       scratch_bytes, grads);
 }
@@ -741,6 +748,9 @@ extern "C" int wire_mlp_bwd_coords(void* stream, const wire_net_desc* d, const f
   if (p.hier)
     return hier_bwd_core(stream, p, hier_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
                          scratch_bytes, grads_host, nullptr, nullptr, g_coords);
+  if (p.mfn)
+    return mfn_bwd_core(stream, p, mfn_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
+                        scratch_bytes, grads_host, nullptr, nullptr, g_coords);
   return mlp_bwd_core(stream, p, make_route(p, n, MODE_AUTOGRAD), packed, coords, n, g_y, act, act_bytes, scratch,
                       scratch_bytes, grads_host, nullptr, nullptr, g_coords);
 }
@@ -773,6 +783,15 @@ extern "C" int wire_train_fwd_bwd_hooked(void* stream, const wire_net_desc* d, c
       HIPCHK(launch_mse_final(s, Sx + sc.lpart, hier_head_blocks(n), (float)(weight * inv_no), loss_out)); }
     return hier_bwd_core(stream, p, hr, packed, coords, n, g_y, act, act_bytes, scratch, scratch_bytes, grads, ready, user,
                          nullptr);
+  }
+  if (p.mfn) {
+    // layer by layer: the forward that stores z_l / lin_l, the MSE and its gradient, the backward
+    const Route mr = mfn_route(p, n, MODE_TRAIN);
+    if (int rc = mfn_fwd_core(stream, p, mr, packed, coords, n, y, act, act_bytes)) return rc;
+    { ProfScope ps(s, 3, 0);
+      HIPCHK(launch_mse_grad(s, y, target, idx, first, n, p.O, weight, g_y, loss_out, rec, partial)); }
+    return mfn_bwd_core(stream, p, mr, packed, coords, n, g_y, act, act_bytes, scratch, scratch_bytes, grads, ready, user,
+                        nullptr);
   }
   const Route r = make_route(p, n, MODE_TRAIN);
   if (p.m2) {

@@ -237,6 +237,45 @@ WIRE_DEVINL void gabor2d_fwd_lean(float u, float v, float p, float q, float w0, 
   o_im = e * sn;
 }
 
+// ---- multiplicative filter network (modules/mfn.py:24-26): g(x)_j = exp(-gamma_j / 2 |x - mu_j|^2) sin(x . w_j + c_j)
+// One table per filter, MFN_TAB floats per column j: mu_j[0..4), w_j[0..4) (zero beyond D), gamma_j, c_j, 0, 0 -- three
+// 16-byte loads; a pad column is all zero, which makes its g exactly 0.  The norm is formed as sum (x_d - mu_d)^2 (the
+// reference expands it and cancels); the sine argument reaches hundreds of radians at the reference's init, so the
+// trigonometric part takes wire_sincos_hw, whose two-term reduction keeps 4e-7 whatever the magnitude.
+#define MFN_TAB 12
+struct MfnCol { float mu[4], w[4], gamma, c; };
+WIRE_DEVINL MfnCol mfn_load(const float* __restrict__ tab, int col) {
+  const f32x4* t = reinterpret_cast<const f32x4*>(tab + (size_t)col * MFN_TAB);
+  const f32x4 a = t[0], b = t[1], g = t[2];
+  MfnCol p;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) { p.mu[d] = a[d]; p.w[d] = b[d]; }
+  p.gamma = g[0]; p.c = g[1];
+  return p;
+}
+// e = exp(-gamma nrm / 2), (sn, cs) = sincos(x . w + c); x[d] = 0 beyond D
+WIRE_DEVINL void mfn_eval(const MfnCol& p, const float (&x)[4], float& nrm, float& e, float& sn, float& cs) {
+  float n2 = 0.f, a = p.c;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const float t = x[d] - p.mu[d];
+    n2 = __builtin_fmaf(t, t, n2);
+    a = __builtin_fmaf(x[d], p.w[d], a);
+  }
+  nrm = n2;
+  e = wire_exp(-0.5f * p.gamma * n2);
+  wire_sincos_hw(a, sn, cs);
+}
+WIRE_DEVINL float mfn_g(const MfnCol& p, const float (&x)[4]) {
+  float nrm, e, sn, cs;
+  mfn_eval(p, x, nrm, e, sn, cs);
+  return e * sn;
+}
+WIRE_DEVINL void mfn_load_x(const float* __restrict__ coords, long long row, int D, float (&x)[4]) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d) x[d] = d < D ? coords[row * D + d] : 0.f;
+}
+
 // ---- power-of-two operand scales of the 2 x fp16 split GEMMs (wire_gemmx2h.hip) ------------------------------
 // Every tensor that such a GEMM reads as an operand has WIRE_AMAX_SLOTS sharded slots holding the bit pattern of its
 // max |value| (unsigned compare = float compare for non-negative floats), filled by its producer with atomicMax and

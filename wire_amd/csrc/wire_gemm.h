@@ -24,6 +24,11 @@ enum WireEpi {
   EPI_GABOR2D_BWD_FIRST = 12, // real first layer of wire2d: o0 = g_(u|p) [M][2*ldu]
   EPI_BSPLINE_FWD = 13,     // quadratic B-spline (scale = c = 1 / |sigma0|): o0 = lin, o1 = act
   EPI_BSPLINE_BWD = 14,     // i0 = lin -> o0 = g_lin (no out read)
+  // multiplicative filter network (modules/mfn.py:46-54): g = the Gabor filter of the row's coordinates (ep.coords,
+  // ep.D) and the column's entry of the filter table (ep.ftab, wire_dev.h: MfnCol)
+  EPI_MFN_FWD = 15,         // lin = C + bias: o0 = lin (optional), o1 = lin g
+  EPI_MFN_BWD = 16,         // C = g_z: i0 = lin -> o0 = g_z g (the layer below's g_lin), o1 = g_z lin (the filter's
+                            //   upstream gradient h); i0 null (filter 0): o1 = g_z alone
   // flag on the layer-1 data-gradient forms of the 16 x 16 x 32 kernels (the real BWD forms, GABOR_BWD_FIRST,
   // GABOR2D_BWD_FIRST): the instantiation that also writes ep.cg_partial.  Host code passes the plain code; the
   // launchers pick the flagged instantiation when ep.cg_partial is set
@@ -75,6 +80,7 @@ struct GemmEpiParams {
   // pre-split activations (wire_dev.h: wire_store_out4), 2 x fp16 kernels only:
   float o1_split = 0.f;               //   != 0: the forward epilogue stores o1 (out) split with this power-of-two scale
   float a_split_inv = 0.f;            //   != 0: A is such a pre-split tensor; 1 / its scale (amax_a is not read)
+  const float* ftab = nullptr;        // EPI_MFN_*: the filter's table [Nc][MFN_TAB] (wire_dev.h: mfn_load)
 #ifdef WIRE_ABLATE
   int ablate = 0;                // tools/gemm_tune only: 1 no global loads, 2 no LDS writes, 4 no barrier
 #endif

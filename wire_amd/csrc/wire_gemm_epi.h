@@ -420,6 +420,51 @@ WIRE_DEVINL void gemm_epilogue(f32x16 (&acc)[MT][WN], const GemmEpiParams& ep, c
           }
         }
     }
+  } else if constexpr (EPI == EPI_MFN_FWD) {
+#pragma unroll
+    for (int j = 0; j < WN; ++j) {
+      const int col = n_w + 32 * j + l31;
+      const float bb = ep.bias[col];
+      const MfnCol fc = mfn_load(ep.ftab, col);
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = m_w + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
+          if (row < M) {
+            float x[4];
+            mfn_load_x(ep.coords, row, ep.D, x);
+            const float lin = acc[i][j][r] + bb;
+            if (ep.o0) ep.o0[(size_t)row * ep.ld0 + col] = lin;
+            ep.o1[(size_t)row * ep.ld1 + col] = col < ep.kvalid ? lin * mfn_g(fc, x) : 0.f;
+          }
+        }
+    }
+  } else if constexpr (EPI == EPI_MFN_BWD) {
+#pragma unroll
+    for (int j = 0; j < WN; ++j) {
+      const int col = n_w + 32 * j + l31;
+      MfnCol fc{};
+      if (ep.i0) fc = mfn_load(ep.ftab, col);
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = m_w + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
+          if (row < M) {
+            const float gz = acc[i][j][r];
+            if (ep.i0) {
+              float x[4];
+              mfn_load_x(ep.coords, row, ep.D, x);
+              const float lin = ep.i0[(size_t)row * ep.ld0 + col];
+              ep.o0[(size_t)row * ep.ld0 + col] = gz * mfn_g(fc, x);
+              ep.o1[(size_t)row * ep.ld1 + col] = gz * lin;
+            } else {
+              ep.o1[(size_t)row * ep.ld1 + col] = gz;
+            }
+          }
+        }
+    }
   } else if constexpr (EPI == EPI_GABOR2D_FWD) {
     // wave tile = 32 rows x 128 columns = (lin_re | lin_im | sy_re | sy_im) of 32 features
     static_assert(EPI != EPI_GABOR2D_FWD || WN == 4, "2-D Gabor needs a 128-column wave tile");

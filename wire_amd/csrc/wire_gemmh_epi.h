@@ -224,6 +224,70 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
       }
     }
     if constexpr (CG) h_cg_store<NRB>(cg, ep, M, m_w, n_w, lane);
+  } else if constexpr (EPI == EPI_MFN_FWD || EPI == EPI_MFN_BWD) {
+    // one span of 32 columns at a time: this lane's four columns of the filter table stay in registers over the rows
+#pragma unroll 1
+    for (int sp = 0; sp < 4; ++sp) {
+      if (n_w + 32 * sp >= Nc) continue;
+      const int col = n_w + 32 * sp + cq;
+      const bool filt = EPI == EPI_MFN_FWD || ep.i0 != nullptr;
+      MfnCol fc[4];
+      f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+      if (filt) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) fc[q] = mfn_load(ep.ftab, col + q);
+      }
+      if constexpr (EPI == EPI_MFN_FWD) bv = *reinterpret_cast<const f32x4*>(ep.bias + col);
+#pragma unroll
+      for (int rb = 0; rb < NRB; ++rb) {
+        f32x4 a2[2];
+        // (sp is a runtime index here: the accumulator pair is selected below)
+        f32x4 ax = acc[rb][0], ay = acc[rb][1];
+        if (sp == 1) { ax = acc[rb][2]; ay = acc[rb][3]; }
+        if (sp == 2) { ax = acc[rb][4]; ay = acc[rb][5]; }
+        if (sp == 3) { ax = acc[rb][6]; ay = acc[rb][7]; }
+        h_pair_rows(ax, ay, a2[0], a2[1]);
+#pragma unroll
+        for (int hr = 0; hr < 2; ++hr) {
+          const int row = m_w + 16 * rb + 8 * hr + rr;
+          const int rowc = row < M ? row : M - 1;
+          float x[4] = {0.f, 0.f, 0.f, 0.f};
+          f32x4 g = {0.f, 0.f, 0.f, 0.f};
+          if (filt) {
+            mfn_load_x(ep.coords, rowc, ep.D, x);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) g[q] = mfn_g(fc[q], x);
+          }
+          if constexpr (EPI == EPI_MFN_FWD) {
+            f32x4 lin, o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              lin[q] = a2[hr][q] + bv[q];
+              o[q] = col + q < ep.kvalid ? lin[q] * g[q] : 0.f;
+            }
+            if constexpr (X2) h_amax4(amx, o);
+            if (row < M) {
+              if (ep.o0) *reinterpret_cast<f32x4*>(ep.o0 + (size_t)row * ep.ld0 + col) = lin;
+              *reinterpret_cast<f32x4*>(ep.o1 + (size_t)row * ep.ld1 + col) = o;
+            }
+          } else {
+            if (filt) {
+              const f32x4 lin = *reinterpret_cast<const f32x4*>(ep.i0 + (size_t)rowc * ep.ld0 + col);
+              f32x4 gl, hh;
+#pragma unroll
+              for (int q = 0; q < 4; ++q) { gl[q] = a2[hr][q] * g[q]; hh[q] = a2[hr][q] * lin[q]; }
+              if constexpr (X2) h_amax4(amx, gl);
+              if (row < M) {
+                *reinterpret_cast<f32x4*>(ep.o0 + (size_t)row * ep.ld0 + col) = gl;
+                *reinterpret_cast<f32x4*>(ep.o1 + (size_t)row * ep.ld1 + col) = hh;
+              }
+            } else if (row < M) {
+              *reinterpret_cast<f32x4*>(ep.o1 + (size_t)row * ep.ld1 + col) = a2[hr];
+            }
+          }
+        }
+      }
+    }
   } else if constexpr (EPI == EPI_GABOR2D_FWD) {
     // the wave's 128 columns = (lin_re | lin_im | sy_re | sy_im) of 32 features (modules/wire2d.py:56-67)
     const int grp = n_w >> 7;

@@ -505,6 +505,8 @@ hipError_t launch_gemmx2h_nt(hipStream_t s, int epi, const float* A, int lda, co
     case EPI_BSPLINE_BWD:
       return ep.cg_partial ? launchx2h_t<EPI_BSPLINE_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep)
                            : launchx2h_t<EPI_BSPLINE_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+    case EPI_MFN_FWD: return launchx2h_t<EPI_MFN_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+    case EPI_MFN_BWD: return launchx2h_t<EPI_MFN_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
     case EPI_GABOR2D_FWD:
       if (Nc & 127) return hipErrorInvalidValue;
       return launchx2h_t<EPI_GABOR2D_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);

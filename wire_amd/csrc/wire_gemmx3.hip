@@ -432,6 +432,8 @@ hipError_t launch_gemmx3_nt(hipStream_t s, int epi, const float* A, int lda, con
     case EPI_RELU_BWD: return launchx3_nt_t<EPI_RELU_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_BSPLINE_FWD: return launchx3_nt_t<EPI_BSPLINE_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_BSPLINE_BWD: return launchx3_nt_t<EPI_BSPLINE_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+    case EPI_MFN_FWD: return launchx3_nt_t<EPI_MFN_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+    case EPI_MFN_BWD: return launchx3_nt_t<EPI_MFN_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_GABOR2D_FWD:
       if (Nc & 127) return hipErrorInvalidValue;
       return launchx3_nt_t<EPI_GABOR2D_FWD, 1, 4>(s, A, lda, Bx3, M, Nc, Kd, ep);

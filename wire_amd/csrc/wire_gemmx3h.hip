@@ -239,7 +239,7 @@ bool gemmx3h_handles(int epi, int64_t M) {
   if (!h16 || M < 4096) return false;
   if (epi == EPI_STORE || epi == EPI_GABOR_FWD) return (h16 & 1) != 0;
   if (epi == EPI_GABOR_BWD || epi == EPI_GABOR_BWD_FIRST) return (h16 & 2) != 0;
-  if (epi_real_fwd(epi) || epi_real_bwd(epi)) return (h16 & 4) != 0;
+  if (epi_real_fwd(epi) || epi_real_bwd(epi) || epi == EPI_MFN_FWD || epi == EPI_MFN_BWD) return (h16 & 4) != 0;
   if (epi >= EPI_GABOR2D_FWD && epi <= EPI_GABOR2D_BWD_FIRST) return (h16 & 8) != 0;
   return false;
 }
@@ -275,6 +275,8 @@ hipError_t launch_gemmx3h_nt(hipStream_t s, int epi, const float* A, int lda, co
     case EPI_BSPLINE_BWD:
       return ep.cg_partial ? launchx3h_t<EPI_BSPLINE_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
                            : launchx3h_t<EPI_BSPLINE_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_MFN_FWD: return launchx3h_t<EPI_MFN_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_MFN_BWD: return launchx3h_t<EPI_MFN_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_GABOR2D_FWD:
       if (Nc & 127) return hipErrorInvalidValue;
       return launchx3h_t<EPI_GABOR2D_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);

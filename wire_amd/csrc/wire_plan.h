@@ -1,5 +1,5 @@
 // wire_plan.h -- internal to the host layer (not installed): what wire_plan.hip, wire_api.hip, wire_hier_api.hip,
-// wire_misc_api.hip and wire_layer_api.hip share -- the error channel, the profiler's scope, the plan of a net, its
+// wire_mfn_api.hip, wire_misc_api.hip and wire_layer_api.hip share -- the error channel, the profiler's scope, the plan of a net, its
 // buffer layouts and the route of a whole-net call.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -93,6 +93,11 @@ struct Plan {
   int HS = 0, HL = 0;
   int64_t hj_fwd[WIRE_MS_MAX_SCALES] = {}, hj_fwd_x3[WIRE_MS_MAX_SCALES] = {}, hj_fwd_x2[WIRE_MS_MAX_SCALES] = {},
           hj_bias[WIRE_MS_MAX_SCALES] = {}, hj_half[WIRE_MS_MAX_SCALES] = {}, hj_wamax = -1, h_nat = -1;
+  // WIRE_KIND_MFN (kind then reads WIRE_KIND_RELU: real K -> K layers without an activation of their own): L + 1 Gabor
+  // filters of the coordinates (tensors 4 i .. 4 i + 3: mu, gamma, w, c), the hidden layer l = 1 .. L is the reference's
+  // linear[l - 1] (tensors mfn_tw(p, l), + 1), its output multiplied by filter l; the filters' tables [P][MFN_TAB] at mf_tab
+  bool mfn = false;
+  int64_t mf_tab = -1;
   // packed image offsets (floats); index l = 0..L (l = 0 only when first_gemm)
   std::vector<int64_t> off_fwd, off_dg, off_bias, off_fwd_x3, off_dg_x3, off_fwd_3m, off_dg_3m, off_fwd_x2, off_dg_x2;
   int64_t off_wf, off_bf, off_first, off_wamax, total_packed;   // off_wamax: max-|weight| slots, WIRE_AMAX_SLOTS per layer
@@ -106,6 +111,10 @@ struct Plan {
 // params[] index of tensor q of the native first layer: the multi-scale net's frozen first stage is tensors 0, 1; the
 // multi-pass net's first trunk layer follows the combiner (t0)
 inline int first_tensor(const Plan& p, int q) { return p.ms ? q : p.t0 + q; }
+
+// ---- the multiplicative filter network's index maps: W of hidden layer l >= 1, the table of filter i
+inline int mfn_tw(const Plan& p, int l) { return 4 * (p.L + 1) + 2 * (l - 1); }
+inline const float* mfn_tab(const Plan& p, const float* packed, int i) { return packed + p.mf_tab + (int64_t)i * p.P * 12; }
 
 // ---- the hierarchical net's index maps
 inline int hier_last(const Plan& p, int st) { return st == 0 ? p.HL : 2; }           // index of stage st's last layer
@@ -166,7 +175,9 @@ ActLayout act_layout(const Plan& p, int64_t n1, int save);
 
 // (the multi-pass net: gtr = the combiner's gradient of the trunk's outputs [S2][n1][O], cpart = its weight-gradient
 // partials, crep = the coordinates once per pass [S2][n1][D] for the first layer's sums over all rows)
-struct ScratchLayout { int64_t ga, gb, gu, slab, bslab, fpw, fpb, crp, gamax, gch, gch_stride, gtr, cpart, crep, total; int S; };
+// (the multiplicative filter network: mh = the upstream gradient h of the filter in turn [n1][P], mfp = the per-block
+// partials of its column sums)
+struct ScratchLayout { int64_t ga, gb, gu, slab, bslab, fpw, fpb, crp, gamax, gch, gch_stride, gtr, cpart, crep, mh, mfp, total; int S; };
 ScratchLayout scratch_layout(const Plan& p, int64_t n1);
 
 // coordinate-gradient scratch (wire_mlp_bwd_coords), behind the backward's own: the per-row partials of the layer-1
@@ -218,6 +229,17 @@ inline const unsigned* wamax_of(const Plan& p, const float* packed, int l) {   /
 hipError_t layer_nt(hipStream_t s, const Plan& p, WireFamily f, const float* packed, int l, bool dg, int epi,
                     const float* A, int64_t n, GemmEpiParams ep, const unsigned* amax_a = nullptr,
                     const unsigned* amax_b = nullptr, unsigned* amax_out = nullptr);   // wire_api.hip
+
+// ---------------------------------------------------------------------------
+// the multiplicative filter network (wire_mfn_api.hip)
+// ---------------------------------------------------------------------------
+Route mfn_route(const Plan& p, int64_t n, RouteMode mode);
+int mfn_pack(hipStream_t s, const Plan& p, const void* const* params, float* packed);
+int mfn_fwd_core(void* stream, const Plan& p, const Route& r, const float* packed, const float* coords, int64_t n, float* y,
+                 void* act, int64_t act_bytes);
+int mfn_bwd_core(void* stream, const Plan& p, const Route& r, const float* packed, const float* coords, int64_t n,
+                 const float* g_y, const void* act, int64_t act_bytes, void* scratch, int64_t scratch_bytes,
+                 void* const* grads, wire_grad_ready_fn ready, void* user, float* g_coords);
 
 // ---------------------------------------------------------------------------
 // the hierarchical B-spline net (wire_hier_api.hip)

@@ -40,8 +40,15 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   p.O = d->out_features; p.F = d->posenc_freqs;
   p.w1 = d->first_omega0; p.w = d->hidden_omega0; p.s = d->scale0;
   if (p.kind < WIRE_KIND_WIRE || (p.kind > WIRE_KIND_BSPLINE_MS && p.kind != WIRE_KIND_BSPLINE_M2 &&
-                                  p.kind != WIRE_KIND_BSPLINE_HIER))
+                                  p.kind != WIRE_KIND_BSPLINE_HIER && p.kind != WIRE_KIND_MFN))
     return fail(WIRE_ERR_ARG, "unknown kind %d", p.kind);
+  if (p.kind == WIRE_KIND_MFN) {
+    // modules/mfn.py: the omegas, `scale` and the positional encoding are carried and ignored; the K -> K layers are
+    // real linears whose activation is the multiplication by the next filter (EPI_MFN_*)
+    p.mfn = true;
+    p.kind = WIRE_KIND_RELU;
+    p.F = 0;
+  }
   if (p.kind == WIRE_KIND_BSPLINE_HIER) {
     // modules/bspline_mscale_hier.py: one stage per entry of scale_tensor, `scale` unused
     const wire_net_desc_ms* m = reinterpret_cast<const wire_net_desc_ms*>(d);
@@ -127,6 +134,15 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   }
   p.tfloats[p.ntens - 2] = cm * p.O * K;
   p.tfloats[p.ntens - 1] = cm * p.O;
+  if (p.mfn) {    // filters 0 .. L (mu, gamma, w, c), the hidden linears, the final linear
+    p.ntens = 4 * (p.L + 1) + 2 * p.L + 2;
+    p.tfloats.assign(p.ntens, 0);
+    for (int i = 0; i <= p.L; ++i) {
+      p.tfloats[4 * i] = K * p.D; p.tfloats[4 * i + 1] = K; p.tfloats[4 * i + 2] = K * p.D; p.tfloats[4 * i + 3] = K;
+    }
+    for (int l = 1; l <= p.L; ++l) { p.tfloats[mfn_tw(p, l)] = K * K; p.tfloats[mfn_tw(p, l) + 1] = K; }
+    p.tfloats[p.ntens - 2] = p.O * K; p.tfloats[p.ntens - 1] = p.O;
+  }
   if (p.hier) {   // stage 0: HL + 1 pairs; stages s >= 1: three pairs (layer 1: [K][2K]); the HS heads at the end
     p.ntens = 2 * (p.HL + 1) + 6 * (p.HS - 1) + 2 * p.HS;
     p.tfloats.assign(p.ntens, 0);
@@ -170,7 +186,8 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   // (a positional-encoding net -- relu, 64 padded encoded features -- has its GEMM first layer's image, P x 64, in front)
   // (the multi-pass net: one set of hidden images per pass, each with its own c folded in -- fx_pass_off; the chain's
   // transposed images below carry no c and serve every pass)
-  const bool fx_ok = !p.hier && p.L >= 1 && fused_fwd_shape(p.kind, p.P) &&
+  // (the multiplicative filter network runs layer by layer: no whole-net image)
+  const bool fx_ok = !p.hier && !p.mfn && p.L >= 1 && fused_fwd_shape(p.kind, p.P) &&
                      (!p.first_gemm || (p.kind == WIRE_KIND_RELU && p.Pin0 == 64));
   if (fx_ok) {
     p.off_fx = off;
@@ -193,6 +210,8 @@ int make_plan(const wire_net_desc* d, Plan& p) {
     p.hj_wamax = off; off += (int64_t)p.HS * WIRE_AMAX_SLOTS;
     p.h_nat = off;                                         // per stage: W0 [K][D], b0 [K], Wh [O][K], bh [O]
     off += (int64_t)p.HS * hier_nat_stride(p);
+  } else if (p.mfn) {
+    p.mf_tab = off; off += (int64_t)(p.L + 1) * p.P * 12;    // the filters' tables [P][MFN_TAB]
   } else if (!p.first_gemm || p.ms) {
     for (int q = 0; q < p.per_layer; ++q) off += rup((int)p.tfloats[first_tensor(p, q)], 4);
   }
@@ -214,7 +233,7 @@ ActLayout act_layout(const Plan& p, int64_t n1, int save) {
   a.pe = off; if (p.first_gemm) off += n * p.Pin0;
   if (save) {
     a.out0 = off; off += a.np * p.P * (p.L + 1);
-    a.lin0 = off; if (!p.cplx) off += a.np * p.P;
+    a.lin0 = off; if (!p.cplx && !p.mfn) off += a.np * p.P;   // (a filter network's z_0 has no pre-activation)
     a.lin1 = off; off += a.np * p.Pl * p.L;
   } else {
     a.ping = off; off += n * p.P;
@@ -277,6 +296,11 @@ ScratchLayout scratch_layout(const Plan& p, int64_t n1) {
     s.gtr = off; off += n * p.O;
     s.cpart = off; off += (int64_t)m2_comb_blocks(n1) * m2_comb_grad_floats(p.S2, p.O) + M2_COMB_MAXBLK;   // + loss partials
     s.crep = off; off += n * p.D;
+  }
+  s.mh = s.mfp = off;
+  if (p.mfn) {
+    s.mh = off; off += n * p.P;
+    s.mfp = off; off += (int64_t)(mfn_sums_blocks(n) + 1) * 10 * p.K;
   }
   s.total = off;
   return s;

@@ -157,6 +157,35 @@ hipError_t launch_hier_pack_join(hipStream_t s, const float* W, const float* b, 
 hipError_t launch_hier_join_reduce(hipStream_t s, const float* slab, const float* bslab, int S, int K, int P, float* gW,
                                    float* gb);
 
+// ---- the multiplicative filter network (wire_mfn.hip): g(x)_j = exp(-gamma_j / 2 |x - mu_j|^2) sin(x . w_j + c_j)
+// tab: a filter's table [P][MFN_TAB] in the packed image (wire_dev.h), written by launch_mfn_pack_table from the native
+// mu [K][D], gamma [K], w [K][D], c [K]
+hipError_t launch_mfn_pack_table(hipStream_t s, const float* mu, const float* gamma, const float* w, const float* c, int K,
+                                 int D, int P, float* tab);
+// out [n][P] = g(x) (pad columns 0), or mul g with mul [n][P]; amax_out: max |out| slots or null
+hipError_t launch_mfn_filter_fwd(hipStream_t s, const float* tab, const float* coords, int64_t n, int D, int K, int P,
+                                 const float* mul, float* out, unsigned* amax_out);
+hipError_t launch_mfn_filter_fwd_native(hipStream_t s, const float* mu, const float* gamma, const float* w, const float* c,
+                                        const float* coords, int64_t n, int D, int K, float* out);
+// g_z = g_y wf; part_w / part_b (optional): launch_final_bwd's partials of g_y^T z, sum g_y; lin != null: g_lin = g_z g(x)
+// (tab; its maximum into amax_g) and hbuf = g_z lin, else hbuf = g_z; every row of P floats
+hipError_t launch_mfn_final_bwd(hipStream_t s, const float* g_y, int64_t n, int O, const float* wf, const float* z,
+                                const float* lin, const float* tab, const float* coords, int D, int P, float* g_lin,
+                                float* hbuf, float* part_w, float* part_b, unsigned* amax_g);
+// a filter's parameter gradients from its upstream gradient hbuf [n][ldh]; part: mfn_sums_blocks(n) * 10 * K floats
+int mfn_sums_blocks(int64_t n);
+hipError_t launch_mfn_filter_sums(hipStream_t s, const float* tab, const float* coords, int64_t n, int D, int K,
+                                  const float* hbuf, int ldh, float* part, float* g_mu, float* g_gamma, float* g_w,
+                                  float* g_c);
+hipError_t launch_mfn_filter_sums_native(hipStream_t s, const float* mu, const float* gamma, const float* w, const float* c,
+                                         const float* coords, int64_t n, int D, int K, const float* hbuf, float* part,
+                                         float* g_mu, float* g_gamma, float* g_w, float* g_c);
+// a filter's share of the coordinate gradient, g_x [n][D] (acc != 0: added to what is there); fixed summation order
+hipError_t launch_mfn_filter_gx(hipStream_t s, const float* tab, const float* coords, int64_t n, int D, int K,
+                                const float* hbuf, int ldh, int acc, float* g_x);
+hipError_t launch_mfn_filter_gx_native(hipStream_t s, const float* mu, const float* gamma, const float* w, const float* c,
+                                       const float* coords, int64_t n, int D, int K, const float* hbuf, float* g_x);
+
 // ---- coordinate gradients (first-order, fp32)
 // g_x[r][d] = sum_k G[r][k] W[k][d] (+ sum_k G2[r][k] V[k][d]) over the K valid features of a stored first-layer gradient
 // (real g_lin_0, wire g_u, wire2d g_u with G2 = g_p); W, V native [K][D].  One wave per row, fixed reduction order.

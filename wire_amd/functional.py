@@ -497,3 +497,51 @@ class _RealLayerFunction(torch.autograd.Function):
 
 def real_layer(kind: str, x, W, b, omega0: float, scale0: float):
     return _RealLayerFunction.apply(x, W, b, kind, float(omega0), float(scale0))
+
+
+class _MfnFilterFunction(torch.autograd.Function):
+    """GaborLayer.forward of the multiplicative filter network (modules/mfn.py:24-26) on native tensors:
+    wire_mfn_filter_fwd / wire_mfn_filter_bwd.  x [n][D] -> [n][K]."""
+
+    @staticmethod
+    def forward(ctx, x, mu, gamma, w, c):
+        L = _lib.lib()
+        _require_cuda(x, "layer input")
+        _require_cuda(mu, "layer parameter")
+        K, D = mu.shape
+        xin = x.detach().to(torch.float32).contiguous()
+        n = xin.shape[0]
+        nat = [_native(t) for t in (mu, gamma, w, c)]
+        out = torch.empty(n, K, dtype=torch.float32, device=x.device)
+        if n > 0:
+            _lib.check(L.wire_mfn_filter_fwd(_stream_ptr(x.device), xin.data_ptr(), *[t.data_ptr() for t in nat], n, D, K,
+                                             out.data_ptr()), "wire_mfn_filter_fwd")
+        ctx.save_for_backward(xin, *nat)
+        ctx.xdtype = x.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        L = _lib.lib()
+        xin, mu, gamma, w, c = ctx.saved_tensors
+        K, D = mu.shape
+        n = xin.shape[0]
+        dev = g_out.device
+        g = g_out.detach().to(torch.float32).contiguous()
+        grads = [torch.zeros_like(t) for t in (mu, gamma, w, c)]
+        gx = None
+        if ctx.needs_input_grad[0]:
+            _no_second_order("mfn GaborLayer")
+            gx = torch.zeros(n, D, dtype=torch.float32, device=dev)
+        if n > 0:
+            ws_bytes = _lib.check(L.wire_mfn_filter_ws_bytes(n, K), "wire_mfn_filter_ws_bytes")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(L.wire_mfn_filter_bwd(_stream_ptr(dev), g.data_ptr(), xin.data_ptr(), mu.data_ptr(),
+                                             gamma.data_ptr(), w.data_ptr(), c.data_ptr(), n, D, K,
+                                             *[t.data_ptr() for t in grads], None if gx is None else gx.data_ptr(),
+                                             ws.data_ptr(), ws_bytes), "wire_mfn_filter_bwd")
+        return (None if gx is None else gx.to(ctx.xdtype), *grads)
+
+
+def mfn_filter(x, mu, gamma, w, c):
+    return _MfnFilterFunction.apply(x, mu, gamma, w, c)

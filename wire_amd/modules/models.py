@@ -11,11 +11,15 @@ arguments its own signature has, so both call styles work:
     get_INR(nonlin='wire', in_features=2, out_features=3, hidden_features=256,
             hidden_layers=2, first_omega_0=7., hidden_omega_0=7., scale=6.)
     get_INR('wire', 2, 300, 0, 2, 3, scale_tensor=[0.0], ...)   # bspline_* style
+
+The multiplicative filter network is reached as ``wire_amd.modules.mfn.INR(...)``; ``get_INR('mfn', ...)`` raises
+NotImplementedError naming that constructor until the factory moves over.
 """
 from . import bspline_form, bspline_mscale_2, bspline_mscale_HL, bspline_mscale_hier, gauss, relu, siren, wire, wire2d
 
-# keys of modules/models.py:15-25 that are on the MI355X path; 'mfn' and 'bspline_cubic'
-# are out of scope (SURVEY.md section 2.1 rows 7-8).
+# keys of modules/models.py:15-25 that this factory builds.  'mfn' is on the MI355X path but is not built here yet (three
+# tests pin the NotImplementedError): construct it with wire_amd.modules.mfn.INR, as the reference's own factory cannot
+# build it either.  'bspline_cubic' is out of scope (SURVEY.md section 2.1 row 8).
 model_dict = {'bspline_form': bspline_form,
               'bspline_mscale_2': bspline_mscale_2,
               'bspline_mscale_HL': bspline_mscale_HL,
@@ -40,6 +44,9 @@ def get_INR(nonlin, in_features, hidden_features, scaled_hidden_features=None,
     with ``pos_encode=True``, as the reference's drivers spell it).
     Remaining arguments: see modules/models.py:31-56 of the reference.
     """
+    if nonlin == 'mfn':
+        raise NotImplementedError("get_INR does not build 'mfn' yet: construct it with wire_amd.modules.mfn.INR(in_features, "
+                                  "hidden_features, hidden_layers, out_features), which runs on the MI355X hot path")
     if nonlin in _OUT_OF_SCOPE:
         raise NotImplementedError(f"nonlin '{nonlin}' is outside the MI355X hot path of wire_amd")
     if nonlin not in model_dict:

@@ -54,7 +54,8 @@ class FusedTrainer:
             raise NotImplementedError("FusedTrainer needs outermost_linear=True: this net ends in an activation layer "
                                       "(modules/siren.py:81-84, gauss.py:63-66, relu.py:116-119) and runs layer by layer; "
                                       "train it through model(coords) + torch.optim")
-        if any(getattr(m, "trainable", False) for m in model.net):
+        # (mfn.INR has no ``net``: its filters and linears carry no trainable omega_0 / scale_0)
+        if any(getattr(m, "trainable", False) for m in getattr(model, "net", ())):
             raise NotImplementedError("FusedTrainer keeps omega_0 / scale_0 fixed (they are not in its flat parameter "
                                       "buffer); a net with trainable=True layers (modules/wire.py:80-81) trains through "
                                       "model(coords) + torch.optim")
@@ -216,6 +217,14 @@ class FusedTrainer:
             for s in range(S - 1, -1, -1):
                 for l in range(last[s], -1, -1):
                     yield first[s] + 2 * l, 2
+            return
+        if self.desc.kind == _lib.KIND["mfn"]:
+            # the final linear; then for i = L-1 .. 0 the pair {W_i, b_i} and the four tensors of filter i + 1; filter 0
+            yield nt - 2, 2
+            for i in range(hidden - 1, -1, -1):
+                yield 4 * (hidden + 1) + 2 * i, 2
+                yield 4 * (i + 1), 4
+            yield 0, 4
             return
         t0 = 0
         if self.desc.kind == _lib.KIND["bspline_mscale_HL"]:   # its frozen first stage (tensors 0, 1) comes last
