@@ -505,7 +505,7 @@ def _splitmix64(z: int) -> int:
 
 def hash_perm(n_total: int, seed: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
     """pi_seed(first .. first+count) of the keyed bijection of [0, n_total) that libwire_hip's
-    perm_indices_kernel evaluates (wire_point.hip): four rounds of x = (x*M_r + K_r) mod 2^b, x ^= x >> s on
+    perm_indices_kernel evaluates (wire_train.hip): four rounds of x = (x*M_r + K_r) mod 2^b, x ^= x >> s on
     the smallest power-of-two domain, cycle-walking back into [0, n_total).  Test infrastructure."""
     count = n_total - first if count is None else count
     b = 0

@@ -636,7 +636,7 @@ KIND_CASES = {
 @pytest.mark.parametrize("case", list(KIND_CASES))
 def test_fused_step_equals_autograd_path_every_kind(case):
     """FusedTrainer.step (wire_train_fwd_bwd: forward, the FUSED final stage -- final linear + MSE + final backward +
-    activation gradient of the last hidden layer in one pass, wire_point.hip final_fused_kernel, every net kind --
+    activation gradient of the last hidden layer in one pass, wire_final.hip final_fused_kernel, every net kind --
     and the backward) against the autograd path of the same module on the same batch: ``model(coords)`` ->
     ``((pix - gt)**2).mean()`` -> ``backward()`` (wire_image_denoise.py:146-156), which runs the unfused kernels
     (wire_mlp_fwd / wire_mlp_bwd).  Output, loss and every parameter gradient, scale-relative 2e-5."""

@@ -4,7 +4,7 @@
 // with WIRE_ABLATE so single costs (global loads, LDS writes, barriers) can be
 // switched off (results are then wrong; only the timing matters).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -c tools/gemm_tune.hip -o build/gemm_tune.o
-//   hipcc --offload-arch=gfx950 build/gemm_tune.o build/csrc/wire_point.o -o build/gemm_tune
+//   hipcc --offload-arch=gfx950 build/gemm_tune.o build/csrc/wire_knobs.o build/csrc/wire_gemmx3h.o -o build/gemm_tune
 //   ./build/gemm_tune [N] [P] [rounds]
 #include <hip/hip_runtime.h>
 

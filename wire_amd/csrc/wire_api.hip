@@ -410,7 +410,7 @@ struct Bwd {
   const unsigned* oslots(int l) const { return reinterpret_cast<const unsigned*>(A + a.amax) + l * WIRE_AMAX_SLOTS; }
   float* grad(int t) const { return grads ? (float*)grads[t] : nullptr; }
   void done(int t, int count) const { if (ready) ready(user, t, count); }
-  int64_t crp_set() const { return (int64_t)(colreduce_blocks(n) + 32) * p.ldu * 5; }   // wire2d: the second set of sums
+  int64_t crp_set() const { return (int64_t)prereduce_room(colreduce_blocks(n)) * p.ldu * 5; }   // wire2d: the second set of sums
   // the stages, in launch order
   int final_stage();
   int first_point();

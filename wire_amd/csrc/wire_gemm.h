@@ -200,7 +200,7 @@ struct FusedFwdParams {
   // the final stage inside the training forward (real nets; target != null): from the accumulators of layer L the wave forms
   // y = h_L W_f^T + b_f, the MSE terms against target[src] (src = idx ? idx[row] : first + row), dL/dy = gscale (y - t),
   // g_lin_L = (dL/dy W_f) act'(lin_L) -- stored, its maximum published -- and per workgroup the sums dL/dy^T h_L, sum dL/dy,
-  // sum (y - t)^2 (what final_fused_kernel of wire_point.hip does from the stored lin_L / out_L, which are then not written)
+  // sum (y - t)^2 (what final_fused_kernel of wire_final.hip does from the stored lin_L / out_L, which are then not written)
   const float* target = nullptr; const int64_t* idx = nullptr; long long first = 0; float gscale = 0.f;
   float* rec = nullptr;                                   // optional scatter of y to rec[src]
   float* g_lin = nullptr;                                 // g_lin_L rows of P floats (padded to 128 rows)

@@ -14,7 +14,7 @@
 //
 //  gemm_tn_kernel : slab[s] = G[rows_s]^T * Z[rows_s]    (weight gradient,
 //      reduction over the sample axis split across workgroups; partial slabs
-//      are summed deterministically by reduce kernels in wire_point.hip).
+//      are summed deterministically by reduce kernels in wire_reduce.hip).
 //
 // Tiling (both): 128x128 output tile per 256-thread workgroup, 4 waves, each
 // wave a 64x64 (or 32x128) block of v_mfma_f32_32x32x2_f32 tiles, BK = 16 (40 KB

@@ -14,11 +14,7 @@
 #include "wire_dev.h"
 #include "wire_point.h"
 
-#define HIER_MAXO 8
-#define HIER_ROWS 256                  // rows of one head-backward block (FB_ROWS of wire_point.hip: the same partial layout)
 #define HIER_FIRST_ROWS 64
-
-static inline unsigned hcdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
 // ---- first layer of a stage: one thread per feature, 64 rows per block; pad features are written as 0
 __global__ void hier_first_fwd_kernel(const float* __restrict__ coords, long long n, int D, const float* __restrict__ W0,
@@ -52,7 +48,7 @@ hipError_t launch_hier_first_fwd(hipStream_t s, const float* coords, int64_t n, 
   if (n <= 0) return hipSuccess;
   if (D < 1 || D > 4 || ldo < P) return hipErrorInvalidValue;
   const int bx = P >= 256 ? 256 : P;   // P is a multiple of 64
-  hipLaunchKernelGGL(hier_first_fwd_kernel, dim3(hcdiv(n, HIER_FIRST_ROWS), hcdiv(P, bx)), dim3(bx), 0, s, coords,
+  hipLaunchKernelGGL(hier_first_fwd_kernel, dim3(cdiv(n, HIER_FIRST_ROWS), cdiv(P, bx)), dim3(bx), 0, s, coords,
                      (long long)n, D, W0, b0, K, P, c, lin, out, ldo, amax_out);
   return hipGetLastError();
 }
@@ -76,21 +72,21 @@ __global__ __launch_bounds__(256) void hier_head_fwd_kernel(const float* __restr
   const long long wstride = (long long)gridDim.x * 4;
   float lacc = 0.f;
   for (long long row = (long long)blockIdx.x * 4 + wave; row < n; row += wstride) {
-    float a[HIER_MAXO];
+    float a[WIRE_MAXO];
 #pragma unroll
-    for (int o = 0; o < HIER_MAXO; ++o) a[o] = 0.f;
+    for (int o = 0; o < WIRE_MAXO; ++o) a[o] = 0.f;
     const float* xr = x + row * (long long)ldx;
     for (int c = lane * 4; c < P; c += 256) {
       const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + c);
 #pragma unroll
-      for (int o = 0; o < HIER_MAXO; ++o)
+      for (int o = 0; o < WIRE_MAXO; ++o)
         if (o < O) {
           const f32x4 wv = *reinterpret_cast<const f32x4*>(&sw[o * P + c]);
           a[o] += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
         }
     }
 #pragma unroll
-    for (int o = 0; o < HIER_MAXO; ++o)
+    for (int o = 0; o < WIRE_MAXO; ++o)
       if (o < O) {
         float v = a[o];
 #pragma unroll
@@ -125,13 +121,13 @@ int hier_head_blocks(int64_t n) {
 hipError_t launch_hier_head_fwd(hipStream_t s, const float* x, int ldx, const float* Wh, const float* bh, int64_t n, int K,
                                 int P, int O, int acc, float* y, const M2Loss& ls, float* loss_part) {
   if (n <= 0) return hipSuccess;
-  if (O < 1 || O > HIER_MAXO || (P & 3) || (ldx & 3) || (size_t)O * P * sizeof(float) > 65536) return hipErrorInvalidValue;
+  if (O < 1 || O > WIRE_MAXO || (P & 3) || (ldx & 3) || (size_t)O * P * sizeof(float) > 65536) return hipErrorInvalidValue;
   hipLaunchKernelGGL(hier_head_fwd_kernel, dim3(hier_head_blocks(n)), dim3(256), (size_t)O * P * sizeof(float), s, x, ldx,
                      Wh, bh, (long long)n, K, P, O, acc, y, ls, loss_part);
   return hipGetLastError();
 }
 
-// ---- backward of one head: blocks of HIER_ROWS rows, one thread per feature.
+// ---- backward of one head: blocks of WIRE_FB_ROWS rows, one thread per feature.
 //   part_w != null: the block's partial of gWh = g_y^T x (part_w[block][O][P]) and of gbh (part_b[block][O])
 //   g_lin != null:  g_lin[row][f] = (sum_o g_y[row][o] Wh[o][f]) c B'(c lin[row][f]) + (add ? add[row][f] : 0), 0 in the
 //                   pad features, and its max |value|
@@ -141,9 +137,9 @@ __global__ __launch_bounds__(256) void hier_head_bwd_kernel(const float* __restr
                                                             const float* __restrict__ add, int K, int P, float c,
                                                             float* __restrict__ g_lin, float* __restrict__ part_w,
                                                             float* __restrict__ part_b, unsigned* __restrict__ amax_g) {
-  __shared__ float sgy[HIER_ROWS * HIER_MAXO];
-  const long long r0 = (long long)blockIdx.x * HIER_ROWS;
-  long long r1 = r0 + HIER_ROWS;
+  __shared__ float sgy[WIRE_FB_ROWS * WIRE_MAXO];
+  const long long r0 = (long long)blockIdx.x * WIRE_FB_ROWS;
+  long long r1 = r0 + WIRE_FB_ROWS;
   if (r1 > n) r1 = n;
   const int nr = (int)(r1 - r0);
   for (int i = threadIdx.x; i < nr * O; i += blockDim.x) sgy[i] = g_y[r0 * O + i];
@@ -152,9 +148,9 @@ __global__ __launch_bounds__(256) void hier_head_bwd_kernel(const float* __restr
   float amx = 0.f;
   if (f < P) {
     const bool valid = f < K;
-    float w[HIER_MAXO], a[HIER_MAXO];
+    float w[WIRE_MAXO], a[WIRE_MAXO];
 #pragma unroll
-    for (int o = 0; o < HIER_MAXO; ++o) {
+    for (int o = 0; o < WIRE_MAXO; ++o) {
       a[o] = 0.f;
       w[o] = (o < O && valid) ? Wh[(size_t)o * K + f] : 0.f;
     }
@@ -176,7 +172,7 @@ __global__ __launch_bounds__(256) void hier_head_bwd_kernel(const float* __restr
         if (r < nr) {
           float gr = 0.f;
 #pragma unroll
-          for (int o = 0; o < HIER_MAXO; ++o)
+          for (int o = 0; o < WIRE_MAXO; ++o)
             if (o < O) {
               const float g = sgy[r * O + o];
               gr = __builtin_fmaf(g, w[o], gr);
@@ -194,7 +190,7 @@ __global__ __launch_bounds__(256) void hier_head_bwd_kernel(const float* __restr
     if (part_w) {
       float* pw = part_w + (size_t)blockIdx.x * O * P;
 #pragma unroll
-      for (int o = 0; o < HIER_MAXO; ++o)
+      for (int o = 0; o < WIRE_MAXO; ++o)
         if (o < O) pw[(size_t)o * P + f] = a[o];
     }
   }
@@ -210,9 +206,9 @@ hipError_t launch_hier_head_bwd(hipStream_t s, const float* g_y, int64_t n, int 
                                 const float* lin, const float* add, int K, int P, float c, float* g_lin, float* part_w,
                                 float* part_b, unsigned* amax_g) {
   if (n <= 0) return hipSuccess;
-  if (O < 1 || O > HIER_MAXO || (!g_lin && !part_w) || (g_lin && !lin) || (part_w && (!x || !part_b)))
+  if (O < 1 || O > WIRE_MAXO || (!g_lin && !part_w) || (g_lin && !lin) || (part_w && (!x || !part_b)))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(hier_head_bwd_kernel, dim3((unsigned)final_bwd_blocks(n), hcdiv(P, 256)), dim3(256), 0, s, g_y,
+  hipLaunchKernelGGL(hier_head_bwd_kernel, dim3((unsigned)final_bwd_blocks(n), cdiv(P, 256)), dim3(256), 0, s, g_y,
                      (long long)n, O, Wh, x, ldx, lin, add, K, P, c, g_lin, part_w, part_b, amax_g);
   return hipGetLastError();
 }
@@ -237,7 +233,7 @@ __global__ void hier_pack_join_kernel(const float* __restrict__ W, const float* 
 }
 hipError_t launch_hier_pack_join(hipStream_t s, const float* W, const float* b, int K, int P, float* fwd, float* bias,
                                  float* Wa, float* Wb) {
-  hipLaunchKernelGGL(hier_pack_join_kernel, dim3(hcdiv(2 * P, 128), (unsigned)P), dim3(128), 0, s, W, b, K, P, fwd, bias, Wa,
+  hipLaunchKernelGGL(hier_pack_join_kernel, dim3(cdiv(2 * P, 128), (unsigned)P), dim3(128), 0, s, W, b, K, P, fwd, bias, Wa,
                      Wb);
   return hipGetLastError();
 }
@@ -265,7 +261,7 @@ __global__ __launch_bounds__(256) void hier_join_reduce_kernel(const float* __re
 }
 hipError_t launch_hier_join_reduce(hipStream_t s, const float* slab, const float* bslab, int S, int K, int P, float* gW,
                                    float* gb) {
-  hipLaunchKernelGGL(hier_join_reduce_kernel, dim3(hcdiv(2 * K, 256), (unsigned)K), dim3(256), 0, s, slab, bslab, S, K, P,
+  hipLaunchKernelGGL(hier_join_reduce_kernel, dim3(cdiv(2 * K, 256), (unsigned)K), dim3(256), 0, s, slab, bslab, S, K, P,
                      gW, gb);
   return hipGetLastError();
 }

@@ -59,10 +59,10 @@ HierScratch hier_scratch(const Plan& p, int64_t n) {
   s.S = mx(p.x3 ? s_x3 : s_4m, 1);
   s.slab = off; off += (int64_t)s_max * p.P * pn;
   s.bslab = off; off += (int64_t)s_max * p.P;
-  const int nbf = final_bwd_blocks(n) + 32;
+  const int nbf = prereduce_room(final_bwd_blocks(n));
   s.fpw = off; off += (int64_t)nbf * p.O * p.P;
   s.fpb = off; off += (int64_t)nbf * p.O + 64;
-  s.crp = off; off += (int64_t)(colreduce_blocks(n) + 32) * p.P * 5;
+  s.crp = off; off += (int64_t)prereduce_room(colreduce_blocks(n)) * p.P * 5;
   s.lpart = off; off += HIER_HEAD_MAXBLK;
   s.total = off;
   off = (off + 63) / 64 * 64;

@@ -72,9 +72,9 @@ LayerWs layer_ws(int64_t n, int in, int out) {
   w.bias = take(w.Pout);
   w.slab = take(slab_f);
   w.bslab = take(bslab_f);
-  w.fpw = take((int64_t)(final_bwd_blocks(n) + 32) * 8 * Pmax);
-  w.fpb = take((int64_t)(final_bwd_blocks(n) + 32) * 8);
-  w.crp = take((int64_t)(colreduce_blocks(n) + 32) * (w.Pout / 2) * 5);
+  w.fpw = take((int64_t)prereduce_room(final_bwd_blocks(n)) * 8 * Pmax);
+  w.fpb = take((int64_t)prereduce_room(final_bwd_blocks(n)) * 8);
+  w.crp = take((int64_t)prereduce_room(colreduce_blocks(n)) * (w.Pout / 2) * 5);
   w.wf = take((int64_t)8 * Pmax);
   w.bfr = take(64);
   w.btf_x3 = take(gemmx3_b_image_floats(w.Pout, w.Pin));
@@ -452,7 +452,7 @@ Layer2dWs layer2d_ws(int64_t n, int in, int out) {
   w.bias = take(2 * w.Pout);
   w.slab = take(s_max * 2 * w.Pout * w.Pin);
   w.bslab = take(s_max * 2 * w.Pout);
-  w.crp = take((int64_t)(colreduce_blocks(n) + 32) * w.ldu * 5);
+  w.crp = take((int64_t)prereduce_room(colreduce_blocks(n)) * w.ldu * 5);
   w.btf_x3 = take(gemmx3_b_image_floats(2 * w.Pout, w.Pin));
   w.btd_x3 = take(gemmx3_b_image_floats(w.Pin, 2 * w.Pout));
   w.x2 = take(x2_region_floats(2 * w.Pout, w.Pin));

@@ -13,8 +13,6 @@
 #define M2_MAXSO (M2_MAX_SCALES * 8)   // S.O <= 8 x 8
 #define M2_ROWS 16                     // rows of one backward tile
 
-static inline unsigned cdiv_(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
-
 int m2_comb_blocks(int64_t n) {
   const int64_t t = (n + M2_ROWS - 1) / M2_ROWS;
   return (int)(t < M2_COMB_MAXBLK ? (t < 1 ? 1 : t) : M2_COMB_MAXBLK);
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(256) void m2_comb_fwd_kernel(M2Comb w, int S, int O
 hipError_t launch_m2_comb_fwd(hipStream_t s, const M2Comb& w, int S, int O, const float* t, int64_t n, float* y) {
   if (n <= 0) return hipSuccess;
   if (S < 1 || S > M2_MAX_SCALES || O < 1 || O > 8) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(m2_comb_fwd_kernel, dim3(cdiv_(n, 256)), dim3(256), 0, s, w, S, O, t, (long long)n, y);
+  hipLaunchKernelGGL(m2_comb_fwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, w, S, O, t, (long long)n, y);
   return hipGetLastError();
 }
 
@@ -231,7 +229,7 @@ hipError_t launch_m2_comb_bwd(hipStream_t s, const M2Comb& w, int S, int O, cons
 hipError_t launch_m2_comb_reduce(hipStream_t s, const float* part, int64_t n, int S, int O, const M2Grads& g) {
   if (n <= 0) return hipSuccess;
   const int G = m2_comb_grad_floats(S, O);
-  hipLaunchKernelGGL(m2_comb_reduce_kernel, dim3(cdiv_(G, 256)), dim3(256), 0, s, part, m2_comb_blocks(n), S, O, g);
+  hipLaunchKernelGGL(m2_comb_reduce_kernel, dim3(cdiv(G, 256)), dim3(256), 0, s, part, m2_comb_blocks(n), S, O, g);
   return hipGetLastError();
 }
 
@@ -247,6 +245,6 @@ __global__ __launch_bounds__(256) void m2_sum_passes_kernel(const float* __restr
 hipError_t launch_m2_sum_passes(hipStream_t s, const float* g, int S, int64_t n, int D, float* out) {
   const int64_t nd = n * D;
   if (nd <= 0) return hipSuccess;
-  hipLaunchKernelGGL(m2_sum_passes_kernel, dim3(cdiv_(nd, 256)), dim3(256), 0, s, g, S, (long long)nd, out);
+  hipLaunchKernelGGL(m2_sum_passes_kernel, dim3(cdiv(nd, 256)), dim3(256), 0, s, g, S, (long long)nd, out);
   return hipGetLastError();
 }

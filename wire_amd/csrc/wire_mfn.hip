@@ -5,9 +5,6 @@
 #include "wire_dev.h"
 #include "wire_point.h"
 
-#define MAXO 8
-static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
-
 // a filter's parameters: its table in the packed image (whole-net calls), or the native tensors (per-layer calls)
 struct MfnSrc { const float* tab; const float* mu; const float* gamma; const float* w; const float* c; int D; int K; };
 WIRE_DEVINL MfnCol mfn_src_load(const MfnSrc& s, int col) {
@@ -96,11 +93,10 @@ hipError_t launch_mfn_filter_fwd_native(hipStream_t s, const float* mu, const fl
 
 // ---------------------------------------------------------------------------
 // final linear backward fused with the last multiplicative stage: g_z = g_y wf (wf [O][P]); partials of g_y^T z and of
-// the column sums of g_y in launch_final_bwd's layout (256 rows per block, launch_final_reduce adds them up); then
+// the column sums of g_y in launch_final_bwd's layout (WIRE_FB_ROWS rows per block, launch_final_reduce adds them up); then
 //   lin != null: g_lin = g_z g(x) (the layer below's; its maximum into amax_g) and h = g_z lin (the filter's upstream)
 //   lin == null (no hidden layer): h = g_z
 // ---------------------------------------------------------------------------
-#define MFB_ROWS 256   // = FB_ROWS of wire_point.hip (final_bwd_blocks)
 __global__ __launch_bounds__(256) void mfn_final_bwd_kernel(const float* __restrict__ g_y, long long n, int O,
                                                             const float* __restrict__ wf, const float* __restrict__ z,
                                                             const float* __restrict__ lin, const float* __restrict__ tab,
@@ -108,10 +104,10 @@ __global__ __launch_bounds__(256) void mfn_final_bwd_kernel(const float* __restr
                                                             float* __restrict__ g_lin, float* __restrict__ hbuf,
                                                             float* __restrict__ part_w, float* __restrict__ part_b,
                                                             unsigned* __restrict__ amax_g) {
-  __shared__ float sgy[MFB_ROWS * MAXO];
-  __shared__ float sx[MFB_ROWS * 4];
-  const long long r0 = (long long)blockIdx.x * MFB_ROWS;
-  long long r1 = r0 + MFB_ROWS;
+  __shared__ float sgy[WIRE_FB_ROWS * WIRE_MAXO];
+  __shared__ float sx[WIRE_FB_ROWS * 4];
+  const long long r0 = (long long)blockIdx.x * WIRE_FB_ROWS;
+  long long r1 = r0 + WIRE_FB_ROWS;
   if (r1 > n) r1 = n;
   const int nr = (int)(r1 - r0);
   for (int i = threadIdx.x; i < nr * O; i += blockDim.x) sgy[i] = g_y[r0 * O + i];
@@ -123,9 +119,9 @@ __global__ __launch_bounds__(256) void mfn_final_bwd_kernel(const float* __restr
   const int col = blockIdx.y * blockDim.x + threadIdx.x;
   float amx = 0.f;
   if (col < P) {
-    float w[MAXO], a[MAXO];
+    float w[WIRE_MAXO], a[WIRE_MAXO];
 #pragma unroll
-    for (int o = 0; o < MAXO; ++o) { a[o] = 0.f; w[o] = o < O ? wf[(size_t)o * P + col] : 0.f; }
+    for (int o = 0; o < WIRE_MAXO; ++o) { a[o] = 0.f; w[o] = o < O ? wf[(size_t)o * P + col] : 0.f; }
     MfnCol fc{};
     if (lin) fc = mfn_load(tab, col);
     for (int r = 0; r < nr; ++r) {
@@ -133,7 +129,7 @@ __global__ __launch_bounds__(256) void mfn_final_bwd_kernel(const float* __restr
       const float zv = part_w ? z[row * P + col] : 0.f;
       float gz = 0.f;
 #pragma unroll
-      for (int o = 0; o < MAXO; ++o)
+      for (int o = 0; o < WIRE_MAXO; ++o)
         if (o < O) {
           const float g = sgy[r * O + o];
           gz = __builtin_fmaf(g, w[o], gz);
@@ -152,7 +148,7 @@ __global__ __launch_bounds__(256) void mfn_final_bwd_kernel(const float* __restr
     if (part_w) {
       float* pw = part_w + (size_t)blockIdx.x * O * P;
 #pragma unroll
-      for (int o = 0; o < MAXO; ++o)
+      for (int o = 0; o < WIRE_MAXO; ++o)
         if (o < O) pw[(size_t)o * P + col] = a[o];
     }
   }
@@ -167,8 +163,8 @@ hipError_t launch_mfn_final_bwd(hipStream_t s, const float* g_y, int64_t n, int 
                                 const float* lin, const float* tab, const float* coords, int D, int P, float* g_lin,
                                 float* hbuf, float* part_w, float* part_b, unsigned* amax_g) {
   if (n <= 0) return hipSuccess;
-  if (O > MAXO || D < 1 || D > 4) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mfn_final_bwd_kernel, dim3(cdiv(n, MFB_ROWS), cdiv(P, 256)), dim3(256), 0, s, g_y, (long long)n, O,
+  if (O > WIRE_MAXO || D < 1 || D > 4) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mfn_final_bwd_kernel, dim3(cdiv(n, WIRE_FB_ROWS), cdiv(P, 256)), dim3(256), 0, s, g_y, (long long)n, O,
                      wf, z, lin, tab, coords, D, P, g_lin, hbuf, part_w, part_b, amax_g);
   return hipGetLastError();
 }

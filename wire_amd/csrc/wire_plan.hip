@@ -284,12 +284,12 @@ ScratchLayout scratch_layout(const Plan& p, int64_t n1) {
   }
   // + pre-reduction scratch; the training forward with the final stage inside writes one block per 128-row workgroup
   // (the multi-pass net: one set of blocks per pass)
-  const int nbf = (p.off_fx >= 0 && !p.cplx ? 2 : 1) * p.S2 * final_bwd_blocks(n1) + 32;
+  const int nbf = prereduce_room((p.off_fx >= 0 && !p.cplx ? 2 : 1) * p.S2 * final_bwd_blocks(n1));
   s.fpw = off; off += (int64_t)nbf * p.O * p.P;
   s.fpb = off; off += (int64_t)nbf * p.O + 64;
   // (wire2d: two sets, one per Linear of the first layer, when the data-gradient epilogue forms the sums itself)
   // (the data-gradient chain writes one block of first-layer sums per 64- or 128-row workgroup: 4 x the 256-row blocks)
-  s.crp = off; off += (int64_t)((p.off_fxd >= 0 ? 4 : 1) * colreduce_blocks(n) + 32) * (p.cplx ? p.ldu : p.P) * 5 *
+  s.crp = off; off += (int64_t)prereduce_room((p.off_fxd >= 0 ? 4 : 1) * colreduce_blocks(n)) * (p.cplx ? p.ldu : p.P) * 5 *
                       (p.kind == WIRE_KIND_WIRE2D ? 2 : 1);
   s.gtr = s.cpart = s.crep = off;
   if (p.m2) {

@@ -1,11 +1,28 @@
-// wire_point.h -- launchers of the bandwidth-bound kernels around the GEMMs.
+// wire_point.h -- launchers of the bandwidth/VALU-bound kernels around the MFMA GEMMs, one group per source file.
+//
+// All of them move each activation byte at most once and keep 128-byte (32 lanes x 4 B) or 16-byte-per-lane accesses;
+// none needs MFMA.  What several of the files must agree on (the row-block size of the final linear's partial sums, the
+// output limit, the pre-reduction slack) is defined here, once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 enum { NK_WIRE = 0, NK_WIRE2D = 1, NK_SIREN = 2, NK_GAUSS = 3, NK_RELU = 4, NK_BSPLINE = 5 };
 
-// ---- weight packing (native nn.Parameter layout -> padded real-expanded image)
+#define WIRE_MAXO 8        // outputs of the final linear (the point kernels keep one accumulator per output in registers)
+// rows of one block of the final linear's backward: every kernel that writes part_w / part_b for launch_final_reduce
+// (final_bwd, final_fused, hier_head_bwd, mfn_final_bwd) uses this layout, final_bwd_blocks(n) blocks of it
+#define WIRE_FB_ROWS 256
+static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
+// the two-stage reductions of wire_reduce.hip first sum a long list of per-block partials into at most PRE_CHUNKS chunks,
+// written behind the blocks: a partial buffer of nblk blocks needs room for prereduce_room(nblk) of them
+#define PRE_CHUNKS 32
+static inline int prereduce_room(int nblk) { return nblk + PRE_CHUNKS; }
+
+// ===========================================================================
+// wire_pack.hip -- weight packing
+// ===========================================================================
+// ---- native nn.Parameter layout -> padded real-expanded image
 hipError_t launch_pack_hidden(hipStream_t s, int kind, const float* W, const float* b,
                               const float* V, const float* c, int K, int Kin, int P, int Pin,
                               float* Bt_fwd, float* Bt_dgrad, float* bias);
@@ -20,7 +37,13 @@ hipError_t launch_pack_hidden_batch(hipStream_t s, int kind, const PackBatch& pb
 hipError_t launch_pack3m_batch(hipStream_t s, const PackBatch& pb, int nb, int K, int Kin, int Kp, int Kpin);
 hipError_t launch_pack_final(hipStream_t s, int kind, const float* Wf, const float* bf, int K,
                              int P, int O, float* wf, float* bfr);
+// ---- 3M complex path: blocked-planar complex weight matrices
+hipError_t launch_pack3m(hipStream_t s, const float* W, const float* b, int K, int Kin, int Kp, int Kpin,
+                         float* Wb_fwd, float* Wb_dg, float* bias);
 
+// ===========================================================================
+// wire_first.hip -- the first stages, and the way back to the coordinates
+// ===========================================================================
 // ---- first layer (D <= 4 inputs): elementwise, VALU/HBM-write bound
 // out [n][P] blocked; lin (optional): real nets [n][P]; wire: real u [n][P/2] (per-layer API)
 hipError_t launch_first_fwd(hipStream_t s, int kind, const float* coords, int64_t n, int D,
@@ -28,6 +51,34 @@ hipError_t launch_first_fwd(hipStream_t s, int kind, const float* coords, int64_
                             int K, int P, float omega, float scale, float* lin, float* out,
                             unsigned* amax_out = nullptr);   // amax_out: max |out| slots (wire_dev.h) or null
 
+// ---- positional encoding (modules/relu.py:62-75) into a [n][Pin] padded row
+hipError_t launch_posenc(hipStream_t s, const float* coords, int64_t n, int D, int F, int Pin,
+                         float* dst);
+
+// ---- the frozen first stage of the multi-scale B-spline net (modules/bspline_mscale_HL.py: Scaled_Bsplines_form)
+// dst[r][j] = B(c[g(j)] (x_r . W0[j] + b0[j])) for j < SHF, 0 for SHF <= j < ld; g(j) = 0 below 256, else
+// 1 + (j - 256) / split.  split_scale != 0 (ld % 4 == 0, 16-byte aligned rows): stored pre-split as wire_store_out4 does
+// (B <= 0.75); else fp32, and amax (optional) receives max |value| for the 2 x fp16 GEMM that reads it.
+struct MscaleC { float c[8]; };
+hipError_t launch_mscale_first(hipStream_t s, const float* coords, int64_t n, int D, const float* W0, const float* b0,
+                               int SHF, const MscaleC& c, int split, int ld, float split_scale, unsigned* amax,
+                               float* dst);
+
+// ---- coordinate gradients (first-order, fp32)
+// g_x[r][d] = sum_k G[r][k] W[k][d] (+ sum_k G2[r][k] V[k][d]) over the K valid features of a stored first-layer gradient
+// (real g_lin_0, wire g_u, wire2d g_u with G2 = g_p); W, V native [K][D].  One wave per row, fixed reduction order.
+hipError_t launch_coordgrad_rows(hipStream_t s, const float* G, int ldg, const float* G2, const float* W, const float* V,
+                                 int K, int D, int64_t n, float* g_x);
+// g_x[r][d] = sum_t partial[t][r][d], t = 0 .. ntiles - 1 in that order (the data-gradient epilogue's per-column-tile
+// partials, GemmEpiParams::cg_partial)
+hipError_t launch_coordgrad_reduce(hipStream_t s, const float* partial, int ntiles, int64_t n, int D, float* g_x);
+// modules/relu.py:62-75 backward: g_pe [n][ldpe] in posenc_kernel's feature order -> g_x [n][D]
+hipError_t launch_posenc_bwd(hipStream_t s, const float* coords, int64_t n, int D, int F, const float* g_pe, int ldpe,
+                             float* g_x);
+
+// ===========================================================================
+// wire_final.hip -- the final linear
+// ===========================================================================
 // ---- final linear: y[n][O] = z[n][P] . wf[O][P] + bf
 hipError_t launch_final_fwd(hipStream_t s, const float* z, int64_t n, int P, int O,
                             const float* wf, const float* bfr, float* y);
@@ -41,19 +92,24 @@ hipError_t launch_final_bwd(hipStream_t s, int kind, int raw, const float* g_y, 
                             const float* wf, const float* lin, const float* out, int K, int P,
                             float omega, float scale, float* g_lin, float* part_w,
                             float* part_b, unsigned* amax_g = nullptr);   // amax_g: max |g_lin| slots or null
-// part_w / part_b must have room for final_bwd_blocks(n) + 32 blocks (pre-reduction scratch)
-hipError_t launch_final_reduce(hipStream_t s, int kind, float* part_w, float* part_b,
-                               int nblk, int O, int K, int P, float* gWf, float* gbf);
 
 // ---- fused final stage of a training step (wire, O <= 4): y = Re(z Wf^T + bf), MSE loss + dL/dy,
 // rec scatter, g_out = g_y conj(Wf), Gabor gradient of layer L, and the per-block partials of g_Wf /
-// g_bf in the SAME layout launch_final_bwd produces (FB_ROWS rows per block) for launch_final_reduce.
+// g_bf in the SAME layout launch_final_bwd produces (WIRE_FB_ROWS rows per block) for launch_final_reduce.
 bool final_fused_supported(int P, int O);
 hipError_t launch_final_fused(hipStream_t s, int kind, const float* out, const float* lin, int64_t n, int P, int O,
                               int kvalid, const float* wf, const float* bfr, const float* target, const int64_t* idx,
                               int64_t first, float weight, float omega, float scale, float* y, float* rec,
                               float* g_lin, float* part_w, float* part_b, float* loss_partial,
                               float* loss_out, unsigned* amax_g = nullptr);   // amax_g: max |g_lin| slots or null
+
+// ===========================================================================
+// wire_reduce.hip -- deterministic two-stage reductions
+// ===========================================================================
+// ---- the final linear's weight gradient from the per-block partials of launch_final_bwd and its kin:
+// part_w / part_b must have room for prereduce_room(final_bwd_blocks(n)) blocks (pre-reduction scratch)
+hipError_t launch_final_reduce(hipStream_t s, int kind, float* part_w, float* part_b,
+                               int nblk, int O, int K, int P, float* gWf, float* gbf);
 
 // ---- weight-gradient slab reduction: slab[S][Pm][Pn] (+ bslab[S][Pm]) -> native grads
 hipError_t launch_wgrad_reduce(hipStream_t s, int kind, const float* slab, const float* bslab,
@@ -62,12 +118,19 @@ hipError_t launch_wgrad_reduce(hipStream_t s, int kind, const float* slab, const
 
 // ---- first-layer weight gradient: g_W0[c][d] = sum_n G[n][c] x[n][d], g_b0[c] = sum_n G[n][c]
 int colreduce_blocks(int64_t n);
-// partial must have room for (colreduce_blocks(n) + 32) * C * 5 floats
+// partial must have room for prereduce_room(colreduce_blocks(n)) * C * 5 floats
 hipError_t launch_colreduce_final(hipStream_t s, int C, int D, int64_t n, float* partial, float* gW0, float* gb0);
 hipError_t launch_colreduce_final_blocks(hipStream_t s, int C, int D, int nblk, float* partial, float* gW0, float* gb0);
 hipError_t launch_colreduce(hipStream_t s, const float* G, int ldg, int C, const float* x, int D,
                             int64_t n, float* partial, float* gW0, float* gb0);
 
+// ---- 3M complex path: slab reduction
+hipError_t launch_wgrad3m_reduce(hipStream_t s, const float* slab, const float* bslab, int S, int K, int Kin,
+                                 int Kp_o, int Kp_i, float* gW, float* gb);
+
+// ===========================================================================
+// wire_layer_point.hip -- what only the per-layer API uses
+// ===========================================================================
 // ---- layout conversion for the per-layer API
 hipError_t launch_c64_to_blocked(hipStream_t s, const float* src, int64_t n, int K, int P, float* dst);
 hipError_t launch_blocked_to_c64(hipStream_t s, const float* src, int64_t n, int K, int P, float* dst);
@@ -95,19 +158,53 @@ hipError_t launch_real_act_bwd_point(hipStream_t s, int kind, const float* g, co
                                      const float* out, int64_t n, int P, float omega, float scale,
                                      float* g_lin);
 
-// ---- positional encoding (modules/relu.py:62-75) into a [n][Pin] padded row
-hipError_t launch_posenc(hipStream_t s, const float* coords, int64_t n, int D, int F, int Pin,
-                         float* dst);
+// ---- trainable omega_0 / scale_0 (ComplexGaborLayer(trainable=True), modules/wire.py:80-81):
+// out2 = { dL/d omega_0, dL/d scale_0 }; partial: 2 * hparam_blocks(n) floats
+int hparam_blocks(int64_t n);
+hipError_t launch_gabor_hparam_grad(hipStream_t s, const float* g, const float* lin, const float* out, int64_t n,
+                                    int K, int P, int is_first, float scale, float* partial, float* out2);
+hipError_t launch_gabor2d_hparam_grad(hipStream_t s, const float* g, const float* linsy, const float* out, int64_t n,
+                                      int K, int P, int is_first, float scale, float* partial, float* out2);
 
-// ---- the frozen first stage of the multi-scale B-spline net (modules/bspline_mscale_HL.py: Scaled_Bsplines_form)
-// dst[r][j] = B(c[g(j)] (x_r . W0[j] + b0[j])) for j < SHF, 0 for SHF <= j < ld; g(j) = 0 below 256, else
-// 1 + (j - 256) / split.  split_scale != 0 (ld % 4 == 0, 16-byte aligned rows): stored pre-split as wire_store_out4 does
-// (B <= 0.75); else fp32, and amax (optional) receives max |value| for the 2 x fp16 GEMM that reads it.
-struct MscaleC { float c[8]; };
-hipError_t launch_mscale_first(hipStream_t s, const float* coords, int64_t n, int D, const float* W0, const float* b0,
-                               int SHF, const MscaleC& c, int split, int ld, float split_scale, unsigned* amax,
-                               float* dst);
+// ===========================================================================
+// wire_train.hip -- the glue of a training run
+// ===========================================================================
+// ---- training glue
+// idx_out[r] = pi_seed(first + r), r < count: a keyed bijection pi_seed of [0, n_total) (the epoch's shuffle)
+hipError_t launch_perm_indices(hipStream_t s, uint64_t seed, int64_t n_total, int64_t first, int64_t count,
+                               int64_t* idx_out);
+hipError_t launch_coords(hipStream_t s, const int64_t* idx, int64_t first, int64_t n,
+                         const float* tx, int W, const float* ty, int H, const float* tz, int T,
+                         float* coords);
+hipError_t launch_mse_final(hipStream_t s, const float* partial, int nb, float lscale, float* loss_out);
+hipError_t launch_mse_grad(hipStream_t s, const float* y, const float* target, const int64_t* idx,
+                           int64_t first, int64_t n, int O, float weight, float* g_y,
+                           float* loss_out, float* rec, float* partial);
+// super-resolution loss: AvgPool2d(scale) of the [H W][O] reconstruction against gt_lr [H2 W2][O]
+// (wire_SISR.py:151-161): loss, dL/dy (g_y [H W][O]), optionally the pooled image; partial >= 1024 floats
+hipError_t launch_avgpool_mse_grad(hipStream_t s, const float* y, int H, int W, int O, int scale,
+                                   const float* gt_lr, float* g_y, float* rec_lr, float* loss_out,
+                                   float* partial);
+hipError_t launch_adam(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t count,
+                       float step_size, float beta1, float beta2, float eps, float inv_sqrt_bc2);
 
+// ---- evaluation metrics: mode 0 -> {sum sq err, max gt}; mode 1 -> {intersection, union}
+hipError_t launch_metric(hipStream_t s, int mode, const float* rec, const float* gt, int64_t count, float thres,
+                         float* out, float* partial);
+
+// ---- best-so-far tracking on the device and the sigmoid of the mesh-export query
+hipError_t launch_track_best(hipStream_t s, const float* metric, float* best, int force, const float* src,
+                             float* dst, int64_t count, int* updated);
+hipError_t launch_sigmoid(hipStream_t s, float* x, int64_t count);
+
+// ---- CT forward operator: rotate-and-sum Radon transform (modules/lin_inverse.py:19-40) and its adjoint
+hipError_t launch_radon_fwd(hipStream_t s, const float* img, const float* angles, int H, int W, int A, float* sino);
+hipError_t launch_radon_bwd(hipStream_t s, const float* g_sino, const float* angles, int H, int W, int A,
+                            float* g_img);
+
+// ===========================================================================
+// wire_m2.hip, wire_hier.hip, wire_mfn.hip -- the point kernels of the newer net kinds
+// ===========================================================================
 // ---- the scale combiner of the multi-pass B-spline net (wire_m2.hip): t [S][n][O] (the trunk's outputs, pass-major)
 // -> y [n][O] = W2 relu(W1 [t_0 | .. | t_{S-1}] + b1) + b2, W1 [128][S O], W2 [O][128]; S <= 8, O <= 8
 #define M2_MAX_SCALES 8
@@ -185,62 +282,3 @@ hipError_t launch_mfn_filter_gx(hipStream_t s, const float* tab, const float* co
                                 const float* hbuf, int ldh, int acc, float* g_x);
 hipError_t launch_mfn_filter_gx_native(hipStream_t s, const float* mu, const float* gamma, const float* w, const float* c,
                                        const float* coords, int64_t n, int D, int K, const float* hbuf, float* g_x);
-
-// ---- coordinate gradients (first-order, fp32)
-// g_x[r][d] = sum_k G[r][k] W[k][d] (+ sum_k G2[r][k] V[k][d]) over the K valid features of a stored first-layer gradient
-// (real g_lin_0, wire g_u, wire2d g_u with G2 = g_p); W, V native [K][D].  One wave per row, fixed reduction order.
-hipError_t launch_coordgrad_rows(hipStream_t s, const float* G, int ldg, const float* G2, const float* W, const float* V,
-                                 int K, int D, int64_t n, float* g_x);
-// g_x[r][d] = sum_t partial[t][r][d], t = 0 .. ntiles - 1 in that order (the data-gradient epilogue's per-column-tile
-// partials, GemmEpiParams::cg_partial)
-hipError_t launch_coordgrad_reduce(hipStream_t s, const float* partial, int ntiles, int64_t n, int D, float* g_x);
-// modules/relu.py:62-75 backward: g_pe [n][ldpe] in posenc_kernel's feature order -> g_x [n][D]
-hipError_t launch_posenc_bwd(hipStream_t s, const float* coords, int64_t n, int D, int F, const float* g_pe, int ldpe,
-                             float* g_x);
-
-// ---- training glue
-// idx_out[r] = pi_seed(first + r), r < count: a keyed bijection pi_seed of [0, n_total) (the epoch's shuffle)
-hipError_t launch_perm_indices(hipStream_t s, uint64_t seed, int64_t n_total, int64_t first, int64_t count,
-                               int64_t* idx_out);
-hipError_t launch_coords(hipStream_t s, const int64_t* idx, int64_t first, int64_t n,
-                         const float* tx, int W, const float* ty, int H, const float* tz, int T,
-                         float* coords);
-hipError_t launch_mse_final(hipStream_t s, const float* partial, int nb, float lscale, float* loss_out);
-hipError_t launch_mse_grad(hipStream_t s, const float* y, const float* target, const int64_t* idx,
-                           int64_t first, int64_t n, int O, float weight, float* g_y,
-                           float* loss_out, float* rec, float* partial);
-// super-resolution loss: AvgPool2d(scale) of the [H W][O] reconstruction against gt_lr [H2 W2][O]
-// (wire_SISR.py:151-161): loss, dL/dy (g_y [H W][O]), optionally the pooled image; partial >= 1024 floats
-hipError_t launch_avgpool_mse_grad(hipStream_t s, const float* y, int H, int W, int O, int scale,
-                                   const float* gt_lr, float* g_y, float* rec_lr, float* loss_out,
-                                   float* partial);
-hipError_t launch_adam(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t count,
-                       float step_size, float beta1, float beta2, float eps, float inv_sqrt_bc2);
-
-// ---- evaluation metrics: mode 0 -> {sum sq err, max gt}; mode 1 -> {intersection, union}
-hipError_t launch_metric(hipStream_t s, int mode, const float* rec, const float* gt, int64_t count, float thres,
-                         float* out, float* partial);
-
-// ---- 3M complex path: blocked-planar complex weight matrices + slab reduction
-hipError_t launch_pack3m(hipStream_t s, const float* W, const float* b, int K, int Kin, int Kp, int Kpin,
-                         float* Wb_fwd, float* Wb_dg, float* bias);
-hipError_t launch_wgrad3m_reduce(hipStream_t s, const float* slab, const float* bslab, int S, int K, int Kin,
-                                 int Kp_o, int Kp_i, float* gW, float* gb);
-
-// ---- trainable omega_0 / scale_0 (ComplexGaborLayer(trainable=True), modules/wire.py:80-81):
-// out2 = { dL/d omega_0, dL/d scale_0 }; partial: 2 * hparam_blocks(n) floats
-int hparam_blocks(int64_t n);
-hipError_t launch_gabor_hparam_grad(hipStream_t s, const float* g, const float* lin, const float* out, int64_t n,
-                                    int K, int P, int is_first, float scale, float* partial, float* out2);
-hipError_t launch_gabor2d_hparam_grad(hipStream_t s, const float* g, const float* linsy, const float* out, int64_t n,
-                                      int K, int P, int is_first, float scale, float* partial, float* out2);
-
-// ---- best-so-far tracking on the device and the sigmoid of the mesh-export query
-hipError_t launch_track_best(hipStream_t s, const float* metric, float* best, int force, const float* src,
-                             float* dst, int64_t count, int* updated);
-hipError_t launch_sigmoid(hipStream_t s, float* x, int64_t count);
-
-// ---- CT forward operator: rotate-and-sum Radon transform (modules/lin_inverse.py:19-40) and its adjoint
-hipError_t launch_radon_fwd(hipStream_t s, const float* img, const float* angles, int H, int W, int A, float* sino);
-hipError_t launch_radon_bwd(hipStream_t s, const float* g_sino, const float* angles, int H, int W, int A,
-                            float* g_img);

@@ -1,0 +1,420 @@
+// wire_train.hip -- the glue of a training run around the net: the epoch's shuffle, coordinate generation, the MSE and
+// super-resolution losses with their gradients, flat Adam, evaluation metrics, best-so-far tracking, the sigmoid of the
+// mesh export, and the CT forward operator (Radon transform) with its adjoint.
+#include "wire_dev.h"
+#include "wire_point.h"
+
+// ===========================================================================
+// training glue
+// ===========================================================================
+// Keyed bijection of [0, n): the per-epoch shuffle of wire_image_denoise.py:142 / wire_occupancy.py:137
+// (torch.randperm) as a function of the POSITION, so that a rank generates exactly the slice of the epoch's
+// permutation it trains on -- O(shard) work and memory per rank whatever the world size and the grid size
+// (randperm sorts all n keys on every rank: 0.57 ms at n = 262 144, 1 GB of int64 at 512^3).
+// b = bits of the smallest power of two >= n; four rounds of  x = (x * M_r + K_r) mod 2^b; x ^= x >> s  (each
+// invertible mod 2^b), then cycle-walking: re-apply while x >= n (2^b < 2 n, so < 2 applications on average;
+// it terminates because the walk stays on the cycle of a permutation of [0, 2^b) that contains the start).
+// (tests/test_shuffle.py holds the bit-exact numpy twin.)
+__device__ __host__ inline unsigned long long perm_splitmix(unsigned long long z) {
+  z += 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+struct PermKeys { unsigned long long m[4], k[4]; };
+__device__ inline unsigned long long perm_apply(unsigned long long x, unsigned long long n, int b, int sh,
+                                                const PermKeys& K) {
+  const unsigned long long mask = (b >= 64) ? ~0ull : ((1ull << b) - 1ull);
+  do {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      x = (x * K.m[r] + K.k[r]) & mask;
+      x ^= x >> sh;
+    }
+  } while (x >= n);
+  return x;
+}
+__global__ void perm_indices_kernel(PermKeys K, long long n_total, int b, int sh, long long first, long long count,
+                                    int64_t* __restrict__ idx_out) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= count) return;
+  idx_out[r] = (int64_t)perm_apply((unsigned long long)(first + r), (unsigned long long)n_total, b, sh, K);
+}
+hipError_t launch_perm_indices(hipStream_t s, uint64_t seed, int64_t n_total, int64_t first, int64_t count,
+                               int64_t* idx_out) {
+  if (count <= 0) return hipSuccess;
+  if (n_total < 1 || first < 0 || first + count > n_total) return hipErrorInvalidValue;
+  int b = 0;
+  while (b < 63 && (1ull << b) < (unsigned long long)n_total) ++b;
+  if (b == 0) b = 1;                       // n = 1: domain {0, 1}, cycle-walking maps 0 -> 0
+  const int sh = b / 2 > 0 ? b / 2 : 1;
+  PermKeys K;
+  for (int r = 0; r < 4; ++r) {
+    K.m[r] = perm_splitmix(seed * 8 + r) | 1ull;          // odd multiplier: a bijection mod 2^b
+    K.k[r] = perm_splitmix(seed * 8 + 4 + r);
+  }
+  hipLaunchKernelGGL(perm_indices_kernel, dim3(cdiv(count, 256)), dim3(256), 0, s, K, (long long)n_total, b, sh,
+                     (long long)first, (long long)count, idx_out);
+  return hipGetLastError();
+}
+
+__global__ void coords_kernel(const int64_t* __restrict__ idx, long long first, long long n,
+                              const float* __restrict__ tx, int W, const float* __restrict__ ty,
+                              int H, const float* __restrict__ tz, int T,
+                              float* __restrict__ coords) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  long long id = idx ? idx[r] : first + r;
+  if (tz) {
+    const long long k = id % T;
+    id /= T;
+    const long long j = id % W, i = id / W;
+    coords[r * 3 + 0] = tx[j];
+    coords[r * 3 + 1] = ty[i];
+    coords[r * 3 + 2] = tz[k];
+  } else {
+    const long long j = id % W, i = id / W;
+    coords[r * 2 + 0] = tx[j];
+    coords[r * 2 + 1] = ty[i];
+  }
+}
+hipError_t launch_coords(hipStream_t s, const int64_t* idx, int64_t first, int64_t n,
+                         const float* tx, int W, const float* ty, int H, const float* tz, int T,
+                         float* coords) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(coords_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, idx, (long long)first,
+                     (long long)n, tx, W, ty, H, tz, T, coords);
+  return hipGetLastError();
+}
+
+#define MSE_BLOCKS 1024
+__global__ __launch_bounds__(256) void mse_grad_kernel(const float* __restrict__ y,
+                                                       const float* __restrict__ target,
+                                                       const int64_t* __restrict__ idx,
+                                                       long long first, long long n, int O,
+                                                       float gscale, float* __restrict__ g_y,
+                                                       float* __restrict__ rec,
+                                                       float* __restrict__ partial) {
+  __shared__ float red[256];
+  const long long total = n * O;
+  float acc = 0.f;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (long long)gridDim.x * blockDim.x) {
+    const long long r = e / O;
+    const int o = (int)(e - r * O);
+    const long long src = idx ? idx[r] : first + r;
+    const float yy = y[e];
+    const float d = yy - target[src * O + o];
+    g_y[e] = gscale * d;
+    if (rec) rec[src * O + o] = yy;
+    acc = __builtin_fmaf(d, d, acc);
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+__global__ void mse_final_kernel(const float* __restrict__ partial, int nb, float lscale,
+                                 float* __restrict__ loss_out) {
+  __shared__ float red[256];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) acc += partial[i];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss_out[0] = red[0] * lscale;
+}
+// loss_out[0] = lscale * sum of nb partial sums (one block)
+hipError_t launch_mse_final(hipStream_t s, const float* partial, int nb, float lscale, float* loss_out) {
+  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, nb, lscale, loss_out);
+  return hipGetLastError();
+}
+hipError_t launch_mse_grad(hipStream_t s, const float* y, const float* target, const int64_t* idx,
+                           int64_t first, int64_t n, int O, float weight, float* g_y,
+                           float* loss_out, float* rec, float* partial) {
+  if (n <= 0) return hipSuccess;
+  unsigned nb = cdiv(n * O, 256);
+  if (nb > MSE_BLOCKS) nb = MSE_BLOCKS;
+  const float inv = (float)(1.0 / ((double)n * (double)O));
+  hipLaunchKernelGGL(mse_grad_kernel, dim3(nb), dim3(256), 0, s, y, target, idx, (long long)first,
+                     (long long)n, O, weight * 2.f * inv, g_y, rec, partial);
+  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, weight * inv,
+                     loss_out);
+  return hipGetLastError();
+}
+
+// ===========================================================================
+// super-resolution loss (wire_SISR.py:151-161): rec = AvgPool2d(scale)(rec_hr as [O][H][W]),
+// loss = mean((gt_lr - rec)^2) over H2 W2 O, H2 = H / scale, W2 = W / scale (floor: AvgPool2d's default
+// ceil_mode = False drops ragged borders).  One thread per pooled element; it also scatters
+// dL/d rec_hr = 2 (rec - gt_lr) / (H2 W2 O scale^2) to its scale x scale window.  y, g_y: [H W][O].
+// ===========================================================================
+__global__ __launch_bounds__(256) void avgpool_mse_grad_kernel(const float* __restrict__ y, int H, int W, int O,
+                                                               int sc, int H2, int W2,
+                                                               const float* __restrict__ gt_lr, float gscale,
+                                                               float* __restrict__ g_y,
+                                                               float* __restrict__ rec_lr,
+                                                               float* __restrict__ partial) {
+  __shared__ float red[256];
+  const long long total = (long long)H2 * W2 * O;
+  const float inv = 1.f / (float)(sc * sc);
+  float acc = 0.f;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (long long)gridDim.x * blockDim.x) {
+    const long long pix = e / O;
+    const int o = (int)(e - pix * O);
+    const int pi = (int)(pix / W2), pj = (int)(pix - (long long)pi * W2);
+    const float* src = y + ((size_t)(pi * sc) * W + (size_t)pj * sc) * O + o;
+    float sum = 0.f;
+    for (int a = 0; a < sc; ++a)
+      for (int b = 0; b < sc; ++b) sum += src[((size_t)a * W + b) * O];
+    const float pool = sum * inv;
+    const float d = pool - gt_lr[e];
+    if (rec_lr) rec_lr[e] = pool;
+    const float g = gscale * d;
+    float* dst = g_y + ((size_t)(pi * sc) * W + (size_t)pj * sc) * O + o;
+    for (int a = 0; a < sc; ++a)
+      for (int b = 0; b < sc; ++b) dst[((size_t)a * W + b) * O] = g;
+    acc = __builtin_fmaf(d, d, acc);
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+hipError_t launch_avgpool_mse_grad(hipStream_t s, const float* y, int H, int W, int O, int scale,
+                                   const float* gt_lr, float* g_y, float* rec_lr, float* loss_out,
+                                   float* partial) {
+  const int H2 = H / scale, W2 = W / scale;
+  if (H2 < 1 || W2 < 1) return hipErrorInvalidValue;
+  // ragged borders receive no gradient
+  if (H2 * scale != H || W2 * scale != W) {
+    hipError_t e = hipMemsetAsync(g_y, 0, (size_t)H * W * O * sizeof(float), s);
+    if (e != hipSuccess) return e;
+  }
+  const long long total = (long long)H2 * W2 * O;
+  unsigned nb = cdiv(total, 256);
+  if (nb > MSE_BLOCKS) nb = MSE_BLOCKS;
+  const double invn = 1.0 / (double)total;
+  hipLaunchKernelGGL(avgpool_mse_grad_kernel, dim3(nb), dim3(256), 0, s, y, H, W, O, scale, H2, W2, gt_lr,
+                     (float)(2.0 * invn / ((double)scale * scale)), g_y, rec_lr, partial);
+  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, (float)invn, loss_out);
+  return hipGetLastError();
+}
+
+// torch.optim.Adam (_single_tensor_adam): m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
+// denom = sqrt(v)/sqrt(bc2) + eps; p -= (lr/bc1) m/denom
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                            float* __restrict__ m, float* __restrict__ v, long long count,
+                            float step_size, float beta1, float beta2, float eps,
+                            float inv_sqrt_bc2) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const float gg = g[i];
+  const float mm = __builtin_fmaf(beta1, m[i], (1.f - beta1) * gg);
+  const float vv = __builtin_fmaf(beta2, v[i], (1.f - beta2) * gg * gg);
+  m[i] = mm;
+  v[i] = vv;
+  const float denom = __builtin_fmaf(__builtin_sqrtf(vv), inv_sqrt_bc2, eps);
+  p[i] = p[i] - step_size * (mm / denom);
+}
+hipError_t launch_adam(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t count,
+                       float step_size, float beta1, float beta2, float eps, float inv_sqrt_bc2) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(adam_kernel, dim3(cdiv(count, 256)), dim3(256), 0, s, p, g, m, v,
+                     (long long)count, step_size, beta1, beta2, eps, inv_sqrt_bc2);
+  return hipGetLastError();
+}
+
+// ===========================================================================
+// evaluation metrics on device (wire_image_denoise.py:161-178, wire_occupancy.py:160-162):
+//   mode 0: out = { sum (gt - rec)^2, max gt }            -> PSNR = 10 log10(max(x) / mse)
+//   mode 1: out = { |pred>=thres AND gt!=0|, |pred>=thres OR gt!=0| }   -> IoU
+// two-level deterministic reduction (block partials, then one block)
+// ===========================================================================
+#define MET_BLOCKS 1024
+__global__ __launch_bounds__(256) void metric_kernel(int mode, const float* __restrict__ rec,
+                                                     const float* __restrict__ gt, long long count,
+                                                     float thres, float* __restrict__ partial) {
+  __shared__ float r0[256], r1[256];
+  float a = 0.f, b = mode == 0 ? -3.4e38f : 0.f;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < count; e += (long long)gridDim.x * 256) {
+    const float x = gt[e], y = rec[e];
+    if (mode == 0) {
+      const float d = x - y;
+      a = __builtin_fmaf(d, d, a);
+      b = x > b ? x : b;
+    } else {
+      const bool p = y >= thres, q = x != 0.f;
+      a += (p && q) ? 1.f : 0.f;
+      b += (p || q) ? 1.f : 0.f;
+    }
+  }
+  r0[threadIdx.x] = a; r1[threadIdx.x] = b;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (threadIdx.x < sft) {
+      r0[threadIdx.x] += r0[threadIdx.x + sft];
+      r1[threadIdx.x] = mode == 0 ? (r1[threadIdx.x] > r1[threadIdx.x + sft] ? r1[threadIdx.x] : r1[threadIdx.x + sft])
+                                  : r1[threadIdx.x] + r1[threadIdx.x + sft];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = r0[0]; partial[2 * blockIdx.x + 1] = r1[0]; }
+}
+__global__ void metric_final_kernel(int mode, const float* __restrict__ partial, int nb, float* __restrict__ out) {
+  __shared__ float r0[256], r1[256];
+  float a = 0.f, b = mode == 0 ? -3.4e38f : 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) {
+    a += partial[2 * i];
+    const float v = partial[2 * i + 1];
+    b = mode == 0 ? (v > b ? v : b) : b + v;
+  }
+  r0[threadIdx.x] = a; r1[threadIdx.x] = b;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (threadIdx.x < sft) {
+      r0[threadIdx.x] += r0[threadIdx.x + sft];
+      r1[threadIdx.x] = mode == 0 ? (r1[threadIdx.x] > r1[threadIdx.x + sft] ? r1[threadIdx.x] : r1[threadIdx.x + sft])
+                                  : r1[threadIdx.x] + r1[threadIdx.x + sft];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] = r0[0]; out[1] = r1[0]; }
+}
+hipError_t launch_metric(hipStream_t s, int mode, const float* rec, const float* gt, int64_t count, float thres,
+                         float* out, float* partial) {
+  if (count <= 0) return hipErrorInvalidValue;
+  unsigned nb = cdiv(count, 256);
+  if (nb > MET_BLOCKS) nb = MET_BLOCKS;
+  hipLaunchKernelGGL(metric_kernel, dim3(nb), dim3(256), 0, s, mode, rec, gt, (long long)count, thres, partial);
+  hipLaunchKernelGGL(metric_final_kernel, dim3(1), dim3(256), 0, s, mode, partial, (int)nb, out);
+  return hipGetLastError();
+}
+
+// ===========================================================================
+// best-reconstruction tracking without a host round trip (wire_image_denoise.py:176-178:
+//   if (mse_array[epoch] < best_mse) or (epoch == 0): best_mse = ...; best_img = imrec
+// wire_occupancy.py:170-172: if lossval < best_mse: ...; best_img = copy.deepcopy(im_estim)).
+// Every thread reads the two scalars; the scalar itself is updated by a second one-thread launch.
+// ===========================================================================
+__global__ void best_copy_kernel(const float* __restrict__ metric, const float* __restrict__ best, int force,
+                                 const float* __restrict__ src, float* __restrict__ dst, long long count) {
+  if (!(force || metric[0] < best[0])) return;
+  const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i + 3 < count) {
+    *reinterpret_cast<f32x4*>(dst + i) = *reinterpret_cast<const f32x4*>(src + i);
+  } else {
+    for (long long j = i; j < count; ++j) dst[j] = src[j];
+  }
+}
+__global__ void best_scalar_kernel(const float* __restrict__ metric, float* __restrict__ best, int force,
+                                   int* __restrict__ updated) {
+  const bool take = force || metric[0] < best[0];
+  if (take) best[0] = metric[0];
+  if (updated) updated[0] = take ? 1 : 0;
+}
+hipError_t launch_track_best(hipStream_t s, const float* metric, float* best, int force, const float* src,
+                             float* dst, int64_t count, int* updated) {
+  if (count > 0)
+    hipLaunchKernelGGL(best_copy_kernel, dim3(cdiv(count, 1024)), dim3(256), 0, s, metric, best, force, src, dst,
+                       (long long)count);
+  hipLaunchKernelGGL(best_scalar_kernel, dim3(1), dim3(1), 0, s, metric, best, force, updated);
+  return hipGetLastError();
+}
+
+// torch.sigmoid of the dense occupancy query before the cube is written out (modules/volutils.py:128-131)
+__global__ void sigmoid_kernel(float* __restrict__ x, long long count) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) x[i] = 1.f / (1.f + wire_exp(-x[i]));
+}
+hipError_t launch_sigmoid(hipStream_t s, float* x, int64_t count) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(sigmoid_kernel, dim3(cdiv(count, 256)), dim3(256), 0, s, x, (long long)count);
+  return hipGetLastError();
+}
+
+// ===========================================================================
+// CT forward operator (modules/lin_inverse.py:19-40, wire_ct.py:128-133): the parallel-beam Radon transform the
+// reference builds from kornia.geometry.rotate (kornia 0.6.5: get_rotation_matrix2d about ((W-1)/2, (H-1)/2),
+// positive angle = counter-clockwise, warp_affine -> affine_grid + grid_sample, bilinear, zero padding,
+// align_corners = True) followed by a sum over the rows:
+//     sino[a][j] = sum_i  bilinear(img, x = c (j - cx) - s (i - cy) + cx,  y = s (j - cx) + c (i - cy) + cy)
+// with c = cos(theta_a), s = sin(theta_a).  Samples within one pixel outside the image interpolate against zero.
+// Pinned by the gt -> sinogram pair the reference stores (multiscale_results/ct/.../info.mat).
+// Forward: one thread per (angle, column), rows in the loop -> reads of a row walk a straight line of the image.
+// Backward (the adjoint, for dL/dimg): same traversal, four atomic adds per sample.
+// ===========================================================================
+template <bool BWD>
+__global__ __launch_bounds__(256) void radon_kernel(const float* __restrict__ img, const float* __restrict__ angles,
+                                                    int H, int W, int A, float* __restrict__ sino,
+                                                    const float* __restrict__ g_sino, float* __restrict__ g_img) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  const int a = blockIdx.y;
+  if (j >= W) return;
+  const float th = angles[a] * 0.017453292519943295f;
+  float sn, cs;
+  wire_sincos(th, sn, cs);
+  const float cx = 0.5f * (float)(W - 1), cy = 0.5f * (float)(H - 1);
+  const float xj = (float)j - cx;
+  const float g = BWD ? g_sino[(size_t)a * W + j] : 0.f;
+  float acc = 0.f;
+  for (int i = 0; i < H; ++i) {
+    const float yi = (float)i - cy;
+    const float x = __builtin_fmaf(cs, xj, -(sn * yi)) + cx;
+    const float y = __builtin_fmaf(sn, xj, cs * yi) + cy;
+    const float xf = floorf(x), yf = floorf(y);
+    const int x0 = (int)xf, y0 = (int)yf;
+    if (x0 < -1 || x0 >= W || y0 < -1 || y0 >= H) continue;
+    const float wx1 = x - xf, wy1 = y - yf, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+    const bool vx0 = x0 >= 0, vx1 = x0 + 1 < W, vy0 = y0 >= 0, vy1 = y0 + 1 < H;
+    if (!BWD) {
+      float v = 0.f;
+      if (vy0) {
+        const float* r = img + (size_t)y0 * W;
+        if (vx0) v += wy0 * wx0 * r[x0];
+        if (vx1) v += wy0 * wx1 * r[x0 + 1];
+      }
+      if (vy1) {
+        const float* r = img + (size_t)(y0 + 1) * W;
+        if (vx0) v += wy1 * wx0 * r[x0];
+        if (vx1) v += wy1 * wx1 * r[x0 + 1];
+      }
+      acc += v;
+    } else {
+      if (vy0) {
+        float* r = g_img + (size_t)y0 * W;
+        if (vx0) atomicAdd(r + x0, g * wy0 * wx0);
+        if (vx1) atomicAdd(r + x0 + 1, g * wy0 * wx1);
+      }
+      if (vy1) {
+        float* r = g_img + (size_t)(y0 + 1) * W;
+        if (vx0) atomicAdd(r + x0, g * wy1 * wx0);
+        if (vx1) atomicAdd(r + x0 + 1, g * wy1 * wx1);
+      }
+    }
+  }
+  if (!BWD) sino[(size_t)a * W + j] = acc;
+}
+hipError_t launch_radon_fwd(hipStream_t s, const float* img, const float* angles, int H, int W, int A, float* sino) {
+  dim3 grid(cdiv(W, 256), (unsigned)A);
+  hipLaunchKernelGGL(radon_kernel<false>, grid, dim3(256), 0, s, img, angles, H, W, A, sino, nullptr, nullptr);
+  return hipGetLastError();
+}
+hipError_t launch_radon_bwd(hipStream_t s, const float* g_sino, const float* angles, int H, int W, int A,
+                            float* g_img) {
+  hipError_t e = hipMemsetAsync(g_img, 0, (size_t)H * W * sizeof(float), s);
+  if (e != hipSuccess) return e;
+  dim3 grid(cdiv(W, 256), (unsigned)A);
+  hipLaunchKernelGGL(radon_kernel<true>, grid, dim3(256), 0, s, nullptr, angles, H, W, A, nullptr, g_sino, g_img);
+  return hipGetLastError();
+}
