@@ -312,6 +312,24 @@ int wire_avgpool_mse_grad(void* stream, const float* y, int H, int W, int O, int
                           const float* gt_lr, float* g_y, float* rec_lr, float* loss_out,
                           float* partial);
 
+/* Multi-image super-resolution loss of wire_multi_sr.py:190-208: B frames y [B][H*W][O] (row i*W + j inside a
+ * frame), each pooled on its own by torch.nn.AvgPool2d(scale) to rec [B][H2*W2][O] (H2 = H/scale, W2 = W/scale,
+ * floor), loss = MSELoss()(rec*mask, gt_lr*mask) = sum (rec m - gt m)^2 / (B H2 W2 O) -- the mean runs over every
+ * element, masked ones included.  mask [B][H2*W2][O] may hold any values (dL/drec = 2 (rec m - gt m) m / count);
+ * NULL = all ones.  Writes loss_out[0], EVERY element of g_y [B][H*W][O] (ragged borders exactly 0) and, if
+ * rec_lr != NULL, the unmasked pooled frames.  No atomics: the same call gives the same bits.
+ * partial: >= 1024 floats of scratch.  B, O or scale < 1, scale > min(H, W), or a NULL pointer other than mask /
+ * rec_lr: WIRE_ERR_ARG before any HIP call.                                                             */
+int wire_avgpool_mse_grad_frames(void* stream, const float* y, int B, int H, int W, int O, int scale,
+                                 const float* gt_lr, const float* mask, float* g_y, float* rec_lr,
+                                 float* loss_out, float* partial);
+/* The frames' coordinates of that loop on the device -- motion.get_imstack's Xstack / Ystack at scale = 1
+ * (modules/motion.py:284-318 as wire_multi_sr.py:74-78 calls it; ImageSRDataset stacks them, motion.py:66-69):
+ * mats: DEVICE fp64 [B][2][3]; for frame f, row i, column j, in fp64
+ *   Xn = m00 j + m01 i + m02,  Yn = m10 j + m11 i + m12,  coords[f][i*W + j] = (float(2 Xn / W - 1), float(2 Yn / H - 1)).
+ * coords: [B][H*W][2].  B, H or W < 1 or a NULL pointer: WIRE_ERR_ARG before any HIP call.               */
+int wire_affine_coords(void* stream, const double* mats, int B, int H, int W, float* coords);
+
 /* torch.optim.Adam single step over a flat fp32 buffer (complex tensors as
  * real pairs; wire_image_denoise.py:123-125).  step is 1-based.            */
 int wire_adam_step_flat(void* stream, float* param, const float* grad,

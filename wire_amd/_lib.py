@@ -34,6 +34,7 @@ SYMBOLS = [
     "wire_bwd_coords_scratch_bytes", "wire_mlp_bwd_coords", "wire_posenc_bwd", "wire_gabor_bwd_first_coords",
     "wire_gabor2d_bwd_first_coords", "wire_mscale_first_fwd", "wire_m2_combine_fwd", "wire_m2_combine_ws_bytes",
     "wire_m2_combine_bwd", "wire_mfn_filter_fwd", "wire_mfn_filter_ws_bytes", "wire_mfn_filter_bwd",
+    "wire_avgpool_mse_grad_frames", "wire_affine_coords",
 ]
 
 
@@ -126,6 +127,8 @@ def _declare(l: C.CDLL) -> None:
                                    vp, i64]
     l.wire_gabor2d_hparam_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, f32, f32, i64, i32, i32, i32, vp, vp, i64]
     l.wire_avgpool_mse_grad.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    l.wire_avgpool_mse_grad_frames.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    l.wire_affine_coords.argtypes = [vp, vp, i32, i32, i32, vp]
     l.wire_train_fwd_bwd.argtypes = [vp, dp, vp, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp, vp, i64, vp, i64,
                                      C.POINTER(vp)]
     l.wire_train_fwd_bwd_hooked.argtypes = [vp, dp, vp, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp, vp, i64, vp, i64,

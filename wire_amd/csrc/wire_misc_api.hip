@@ -43,6 +43,23 @@ extern "C" int wire_avgpool_mse_grad(void* stream, const float* y, int H, int W,
   HIPCHK(launch_avgpool_mse_grad((hipStream_t)stream, y, H, W, O, scale, gt_lr, g_y, rec_lr, loss_out, partial));
   return WIRE_OK;
 }
+extern "C" int wire_avgpool_mse_grad_frames(void* stream, const float* y, int B, int H, int W, int O, int scale,
+                                            const float* gt_lr, const float* mask, float* g_y, float* rec_lr,
+                                            float* loss_out, float* partial) {
+  if (B < 1 || H < 1 || W < 1 || O < 1 || scale < 1 || scale > H || scale > W || !y || !gt_lr || !g_y || !loss_out ||
+      !partial)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_avgpool_mse_grad_frames");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_avgpool_mse_grad_frames((hipStream_t)stream, y, B, H, W, O, scale, gt_lr, mask, g_y, rec_lr, loss_out,
+                                        partial));
+  return WIRE_OK;
+}
+extern "C" int wire_affine_coords(void* stream, const double* mats, int B, int H, int W, float* coords) {
+  if (B < 1 || H < 1 || W < 1 || !mats || !coords) return fail(WIRE_ERR_ARG, "bad argument to wire_affine_coords");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_affine_coords((hipStream_t)stream, mats, B, H, W, coords));
+  return WIRE_OK;
+}
 extern "C" int wire_adam_step_flat(void* stream, float* param, const float* grad, float* exp_avg,
                                    float* exp_avg_sq, int64_t count, float lr, float beta1,
                                    float beta2, float eps, int64_t step) {

@@ -185,6 +185,15 @@ hipError_t launch_mse_grad(hipStream_t s, const float* y, const float* target, c
 hipError_t launch_avgpool_mse_grad(hipStream_t s, const float* y, int H, int W, int O, int scale,
                                    const float* gt_lr, float* g_y, float* rec_lr, float* loss_out,
                                    float* partial);
+// multi-image super-resolution loss (wire_multi_sr.py:190-208): y, g_y [B][H W][O], gt_lr / mask (null: ones) / rec_lr
+// (optional) [B][H2 W2][O]; loss = mean((rec m - gt m)^2) over all B H2 W2 O elements; every element of g_y is written;
+// partial >= 1024 floats
+hipError_t launch_avgpool_mse_grad_frames(hipStream_t s, const float* y, int B, int H, int W, int O, int scale,
+                                          const float* gt_lr, const float* mask, float* g_y, float* rec_lr,
+                                          float* loss_out, float* partial);
+// coords [B][H W][2] = the grid moved by frame f's 2 x 3 matrix mats[f] (device, fp64), normalised as 2 X / W - 1
+// (modules/motion.py:284-318 at scale = 1)
+hipError_t launch_affine_coords(hipStream_t s, const double* mats, int B, int H, int W, float* coords);
 hipError_t launch_adam(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t count,
                        float step_size, float beta1, float beta2, float eps, float inv_sqrt_bc2);
 

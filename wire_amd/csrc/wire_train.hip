@@ -1,6 +1,7 @@
-// wire_train.hip -- the glue of a training run around the net: the epoch's shuffle, coordinate generation, the MSE and
-// super-resolution losses with their gradients, flat Adam, evaluation metrics, best-so-far tracking, the sigmoid of the
-// mesh export, and the CT forward operator (Radon transform) with its adjoint.
+// wire_train.hip -- the glue of a training run around the net: the epoch's shuffle, coordinate generation (grid tables
+// and per-frame rigid motion), the MSE, super-resolution and multi-image super-resolution losses with their gradients,
+// flat Adam, evaluation metrics, best-so-far tracking, the sigmoid of the mesh export, and the CT forward operator
+// (Radon transform) with its adjoint.
 #include "wire_dev.h"
 #include "wire_point.h"
 
@@ -208,6 +209,181 @@ hipError_t launch_avgpool_mse_grad(hipStream_t s, const float* y, int H, int W, 
   hipLaunchKernelGGL(avgpool_mse_grad_kernel, dim3(nb), dim3(256), 0, s, y, H, W, O, scale, H2, W2, gt_lr,
                      (float)(2.0 * invn / ((double)scale * scale)), g_y, rec_lr, partial);
   hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, (float)invn, loss_out);
+  return hipGetLastError();
+}
+
+// ===========================================================================
+// multi-image super-resolution loss (wire_multi_sr.py:190-208): B frames of [H W][O], each pooled on its own --
+//   rec = AvgPool2d(scale)(frame), d = rec * m - gt * m, loss = mean(d^2) over all B H2 W2 O elements (masked ones
+//   included, as MSELoss does), dL/drec = 2 d m / (B H2 W2 O), spread over the window as dL/drec / scale^2.
+// A block takes one strip (frame, pooled row, tile of pooled columns): `scale` HR rows of a contiguous run of floats.
+// Lanes read CONSECUTIVE floats of an HR row and add the strip's rows in a register (column sums), the column sums
+// meet in LDS, one thread per pooled element adds its `scale` columns in a fixed order, and the gradient goes back
+// out of LDS with lanes writing consecutive floats again.  Every element of g_y is written exactly once: the ragged
+// right border by the last tile of a strip, the ragged bottom rows by the strips of the last pooled row (zeros).
+// No atomics: per-block loss partials in a grid that depends on the shape alone, summed by mse_final_kernel.
+// A window row wider than the LDS tile (scale * O > APF_CAP floats) takes the direct kernel below instead.
+// ===========================================================================
+#define APF_CAP 1024
+__global__ __launch_bounds__(256) void avgpool_frames_kernel(const float* __restrict__ y, int B, int H, int W, int O,
+                                                             int sc, int H2, int W2, int TP, int ntile,
+                                                             const float* __restrict__ gt_lr,
+                                                             const float* __restrict__ mask, float gscale,
+                                                             float* __restrict__ g_y, float* __restrict__ rec_lr,
+                                                             float* __restrict__ partial) {
+  __shared__ float colsum[APF_CAP], gpool[APF_CAP], red[256];
+  const long long rowf = (long long)W * O;                    // floats of an HR row
+  const int pf = sc * O;                                       // floats of a window row (<= APF_CAP)
+  const float inv = 1.f / ((float)sc * (float)sc);
+  const long long njobs = (long long)B * H2 * ntile;
+  const int tid = threadIdx.x;
+  float acc = 0.f;
+  for (long long job = blockIdx.x; job < njobs; job += gridDim.x) {
+    const int t = (int)(job % ntile);
+    const long long fr = job / ntile;
+    const int pi = (int)(fr % H2);
+    const long long f = fr / H2;
+    const int p0 = t * TP;
+    const int np = W2 - p0 < TP ? W2 - p0 : TP;
+    const int nx = np * pf;                                    // floats of the tile in one HR row (<= APF_CAP)
+    const long long x0 = (long long)p0 * pf;
+    const long long hr0 = (f * H + (long long)pi * sc) * rowf + x0;
+    for (int x = tid; x < nx; x += 256) {
+      const float* src = y + hr0 + x;
+      float s = 0.f;
+      for (int a = 0; a < sc; ++a) s += src[a * rowf];
+      colsum[x] = s;
+    }
+    __syncthreads();
+    const long long pbase = ((f * H2 + pi) * W2 + p0) * O;
+    for (int e = tid; e < np * O; e += 256) {
+      const int pl = e / O, o = e - pl * O;
+      const float* cs = colsum + pl * pf + o;
+      float s = 0.f;
+      for (int b = 0; b < sc; ++b) s += cs[b * O];
+      const float pool = s * inv;
+      const float m = mask ? mask[pbase + e] : 1.f;
+      const float d = __fmul_rn(pool, m) - __fmul_rn(gt_lr[pbase + e], m);
+      if (rec_lr) rec_lr[pbase + e] = pool;
+      gpool[e] = gscale * (d * m);
+      acc = __builtin_fmaf(d, d, acc);
+    }
+    __syncthreads();
+    // (the next strip's colsum is written behind this barrier and its gpool behind the next one: no third barrier)
+    const int nxw = t == ntile - 1 ? (int)(rowf - x0) : nx;     // the last tile also owns the ragged right border
+    for (int a = 0; a < sc; ++a) {
+      float* dst = g_y + hr0 + a * rowf;
+      for (int x = tid; x < nxw; x += 256) {
+        const int pl = x / pf;
+        dst[x] = x < nx ? gpool[pl * O + (x - pl * pf) % O] : 0.f;
+      }
+    }
+    if (pi == H2 - 1)
+      for (int i = H2 * sc; i < H; ++i) {
+        float* dst = g_y + (f * H + i) * rowf + x0;
+        for (int x = tid; x < nxw; x += 256) dst[x] = 0.f;
+      }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (tid < sft) red[tid] += red[tid + sft];
+    __syncthreads();
+  }
+  if (tid == 0) partial[blockIdx.x] = red[0];
+}
+// scale * O > APF_CAP: one thread per pooled element reads and writes its own window (g_y's ragged borders are zeroed
+// by the launcher)
+__global__ __launch_bounds__(256) void avgpool_frames_direct_kernel(const float* __restrict__ y, int B, int H, int W,
+                                                                    int O, int sc, int H2, int W2,
+                                                                    const float* __restrict__ gt_lr,
+                                                                    const float* __restrict__ mask, float gscale,
+                                                                    float* __restrict__ g_y,
+                                                                    float* __restrict__ rec_lr,
+                                                                    float* __restrict__ partial) {
+  __shared__ float red[256];
+  const long long total = (long long)B * H2 * W2 * O;
+  const long long rowf = (long long)W * O;
+  const float inv = 1.f / ((float)sc * (float)sc);
+  float acc = 0.f;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (long long)gridDim.x * blockDim.x) {
+    const long long pix = e / O;
+    const int o = (int)(e - pix * O);
+    const int pj = (int)(pix % W2);
+    const long long fr = pix / W2;
+    const int pi = (int)(fr % H2);
+    const long long f = fr / H2;
+    const long long off = (f * H + (long long)pi * sc) * rowf + (long long)pj * sc * O + o;
+    float sum = 0.f;
+    for (int a = 0; a < sc; ++a)
+      for (int b = 0; b < sc; ++b) sum += y[off + a * rowf + (long long)b * O];
+    const float pool = sum * inv;
+    const float m = mask ? mask[e] : 1.f;
+    const float d = __fmul_rn(pool, m) - __fmul_rn(gt_lr[e], m);
+    if (rec_lr) rec_lr[e] = pool;
+    const float g = gscale * (d * m);
+    for (int a = 0; a < sc; ++a)
+      for (int b = 0; b < sc; ++b) g_y[off + a * rowf + (long long)b * O] = g;
+    acc = __builtin_fmaf(d, d, acc);
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+hipError_t launch_avgpool_mse_grad_frames(hipStream_t s, const float* y, int B, int H, int W, int O, int scale,
+                                          const float* gt_lr, const float* mask, float* g_y, float* rec_lr,
+                                          float* loss_out, float* partial) {
+  const int H2 = H / scale, W2 = W / scale;
+  if (B < 1 || O < 1 || H2 < 1 || W2 < 1) return hipErrorInvalidValue;
+  const double total = (double)B * H2 * W2 * O;
+  const float gscale = (float)(2.0 / total / ((double)scale * scale));
+  unsigned nb;
+  if ((long long)scale * O <= APF_CAP) {
+    const int cap = APF_CAP / (scale * O);
+    const int TP = W2 < cap ? W2 : cap;
+    const int ntile = (W2 + TP - 1) / TP;
+    const long long njobs = (long long)B * H2 * ntile;
+    nb = njobs < MSE_BLOCKS ? (unsigned)njobs : MSE_BLOCKS;
+    hipLaunchKernelGGL(avgpool_frames_kernel, dim3(nb), dim3(256), 0, s, y, B, H, W, O, scale, H2, W2, TP, ntile,
+                       gt_lr, mask, gscale, g_y, rec_lr, partial);
+  } else {
+    if (H2 * scale != H || W2 * scale != W) {
+      hipError_t e = hipMemsetAsync(g_y, 0, (size_t)B * H * W * O * sizeof(float), s);
+      if (e != hipSuccess) return e;
+    }
+    const long long n = (long long)total;
+    nb = n < (long long)MSE_BLOCKS * 256 ? cdiv(n, 256) : MSE_BLOCKS;
+    hipLaunchKernelGGL(avgpool_frames_direct_kernel, dim3(nb), dim3(256), 0, s, y, B, H, W, O, scale, H2, W2, gt_lr,
+                       mask, gscale, g_y, rec_lr, partial);
+  }
+  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, (float)(1.0 / total), loss_out);
+  return hipGetLastError();
+}
+
+// The coordinate stack of motion.get_imstack at scale = 1 (modules/motion.py:284-318 as wire_multi_sr.py:74-78 calls
+// it): frame f's pixel (i, j) moved by its 2 x 3 matrix, then normalised -- all in fp64, rounded to fp32 once.
+__global__ void affine_coords_kernel(const double* __restrict__ mats, long long n, int H, int W,
+                                     float* __restrict__ coords) {
+#pragma clang fp contract(off)
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const long long hw = (long long)H * W;
+  const long long f = r / hw, p = r - f * hw;
+  const double i = (double)(p / W), j = (double)(p % W);
+  const double* m = mats + f * 6;
+  const double xn = m[0] * j + m[1] * i + m[2];
+  const double yn = m[3] * j + m[4] * i + m[5];
+  coords[r * 2 + 0] = (float)(2.0 * xn / (double)W - 1.0);
+  coords[r * 2 + 1] = (float)(2.0 * yn / (double)H - 1.0);
+}
+hipError_t launch_affine_coords(hipStream_t s, const double* mats, int B, int H, int W, float* coords) {
+  const long long n = (long long)B * H * W;
+  hipLaunchKernelGGL(affine_coords_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, mats, n, H, W, coords);
   return hipGetLastError();
 }
 

@@ -40,10 +40,14 @@ class FusedTrainer:
     loops of the reference's bspline_*.py drivers: a number steps the stages' tensors only -- the heads are not in
     ``model.parameters()`` there and keep their initial values, though their gradients are computed and present in
     ``flat_grad`` -- and a sequence steps stage s and head s with ``lr[s]`` (times the schedule's factor).  A sequence
-    for any other kind, or of the wrong length, is a ValueError.  ``step_downsampled`` and ``step_radon`` work for
-    bspline_mscale_hier as for the other kinds."""
+    for any other kind, or of the wrong length, is a ValueError.  ``step_downsampled``, ``step_radon`` and
+    ``step_frames`` work for bspline_mscale_hier as for the other kinds.
 
-    def __init__(self, model: HipINR, grid: Sequence[int], target: torch.Tensor, lr: float = 5e-3,
+    ``target`` is the [npoints, O] signal of ``step`` / ``step_hashed`` and the default ``gt`` of the metrics.  The
+    operator steps bring their own data, so a trainer that only runs those may pass ``target=None``; ``step``,
+    ``step_hashed`` and a metric called without ``gt`` then raise ValueError."""
+
+    def __init__(self, model: HipINR, grid: Sequence[int], target: Optional[torch.Tensor], lr: float = 5e-3,
                  betas=(0.9, 0.999), eps: float = 1e-8, gamma: float = 0.1, niters: int = 2000,
                  coords_style: str = "torch", keep_rec: bool = False, micro_shards: int = 1,
                  group: Optional[dist.ProcessGroup] = None):
@@ -75,8 +79,9 @@ class FusedTrainer:
         self.tz = tz.to(self.dev) if tz is not None else None
         self.npoints = H * W * (T or 1)
         self.O = self.desc.out_features
-        self.target = target.to(self.dev, torch.float32).reshape(self.npoints, self.O).contiguous()
-        self.rec = torch.zeros_like(self.target) if keep_rec else None
+        self.target = None if target is None else \
+            target.to(self.dev, torch.float32).reshape(self.npoints, self.O).contiguous()
+        self.rec = torch.zeros(self.npoints, self.O, dtype=torch.float32, device=self.dev) if keep_rec else None
 
         # ---- flat parameter / gradient / Adam-state buffers; parameters become views
         tensors = model.param_tensors()
@@ -299,12 +304,17 @@ class FusedTrainer:
     def scheduler_step(self) -> None:
         self.epoch += 1
 
+    def _need_target(self, what: str) -> None:
+        if self.target is None:
+            raise ValueError(f"{what} needs the trainer's target; this trainer was built with target=None")
+
     # ------------------------------------------------------------------ one step
     def step(self, indices: Optional[torch.Tensor] = None, first: int = 0,
              count: Optional[int] = None) -> torch.Tensor:
         """One optimizer step on a global batch: rows ``indices`` (contiguous int64 device
         tensor of flat grid indices, every rank passes the same one) or the range
         [first, first+count).  Returns the (device-resident, all-reduced) batch loss; no host sync."""
+        self._need_target("step")
         if indices is not None:
             if indices.dtype != torch.int64 or not indices.is_cuda or indices.dim() != 1:
                 raise ValueError("indices must be a 1-D CUDA int64 tensor")
@@ -333,6 +343,7 @@ class FusedTrainer:
         the device (wire_perm_indices): this rank generates only ITS shard of the batch, so the cost of the
         shuffle does not grow with the world size or with the grid (512^3: no 1 GB index vector).  ``seed`` is
         the epoch counter; every rank passes the same (seed, first, count).  No host sync."""
+        self._need_target("step_hashed")
         B = int(count if count is not None else self.npoints - first)
         if first < 0 or first + B > self.npoints:
             raise ValueError(f"positions [{first}, {first + B}) outside the epoch of {self.npoints} points")
@@ -445,6 +456,83 @@ class FusedTrainer:
         self.loss = g[self.count:self.count + 1].clone()
         return self.loss
 
+    # ------------------------------------------------------------------ multi-image super-resolution step
+    def affine_coords(self, mats) -> torch.Tensor:
+        """The coordinates of B frames of the trainer's grid, each moved by its 2 x 3 matrix -- ``motion.get_imstack``'s
+        ``Xstack`` / ``Ystack`` at scale 1 (modules/motion.py:284-318, wire_multi_sr.py:74-78) as ``ImageSRDataset``
+        stacks them -- computed on the device in fp64 (wire_affine_coords): the 2 x 3 matrices are all that crosses the
+        bus.  ``mats``: [B, 2, 3] array or tensor.  Returns the contiguous float32 device tensor [B, H*W, 2]."""
+        if self.tz is not None or len(self.grid) != 2:
+            raise ValueError("affine_coords needs a 2-D grid")
+        m = torch.as_tensor(mats).detach().to(self.dev, torch.float64)
+        if m.dim() != 3 or tuple(m.shape[1:]) != (2, 3) or m.shape[0] < 1:
+            raise ValueError("mats must be [B, 2, 3] with B >= 1")
+        m = m.contiguous()
+        H, W = int(self.grid[0]), int(self.grid[1])
+        out = torch.empty(m.shape[0], H * W, 2, dtype=torch.float32, device=self.dev)
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        _lib.check(self.L.wire_affine_coords(stream, m.data_ptr(), m.shape[0], H, W, out.data_ptr()), "affine_coords")
+        return out
+
+    def step_frames(self, coords: torch.Tensor, gt_lr: torch.Tensor, scale: int, mask: Optional[torch.Tensor] = None,
+                    rec_lr: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One optimizer step of the multi-image super-resolution loop (wire_multi_sr.py:190-208) on a batch of B frames:
+        ``coords`` [B, H*W, 2] (contiguous device float32; frame f's rows are the trainer's grid moved by that frame's
+        motion -- ``affine_coords`` makes them) go through the model in ONE forward of B*H*W rows,
+        ``torch.nn.AvgPool2d(scale)`` brings every frame to the resolution of ``gt_lr`` ([B, H//scale * W//scale, O]),
+        loss = ``MSELoss()(output*mask, gt_lr*mask)`` (``mask`` shaped like ``gt_lr``, any values; None = ones); backward
+        through the pooling and the network, Adam.  ``rec_lr`` (optional, shaped like ``gt_lr``) receives the unmasked
+        pooled frames, and the high-resolution frames of this step stay in ``self.y`` ([B*H*W, O]).  B is read from
+        ``coords`` and may change from call to call (a last, smaller batch).  2-D grids, single process."""
+        if self.tz is not None or len(self.grid) != 2:
+            raise ValueError("step_frames needs a 2-D grid")
+        if self.world != 1:
+            raise NotImplementedError("step_frames is single-process")
+        H, W = int(self.grid[0]), int(self.grid[1])
+        scale = int(scale)
+        if scale < 1 or scale > min(H, W):
+            raise ValueError(f"scale {scale} outside 1..min(H, W)")
+        H2, W2 = H // scale, W // scale
+        if not isinstance(coords, torch.Tensor) or not coords.is_cuda or coords.dtype != torch.float32 \
+                or coords.dim() != 3 or coords.shape[0] < 1 or tuple(coords.shape[1:]) != (H * W, 2) \
+                or not coords.is_contiguous():
+            raise ValueError(f"coords must be a contiguous CUDA float32 tensor [B, {H * W}, 2]")
+        xy = coords.detach()
+        B = int(xy.shape[0])
+        gt = gt_lr.detach()
+        if not gt.is_cuda or gt.dtype != torch.float32 or gt.numel() != B * H2 * W2 * self.O:
+            raise ValueError(f"gt_lr must be a CUDA float32 tensor of {B} x {H2 * W2} x {self.O} elements")
+        gt = gt.contiguous()
+        mk = None
+        if mask is not None:
+            mk = mask.detach()
+            if not mk.is_cuda or mk.dtype != torch.float32 or mk.numel() != gt.numel():
+                raise ValueError(f"mask must be a CUDA float32 tensor of {B} x {H2 * W2} x {self.O} elements")
+            mk = mk.contiguous()
+        if rec_lr is not None and (not rec_lr.is_cuda or rec_lr.dtype != torch.float32
+                                   or rec_lr.numel() != gt.numel() or not rec_lr.is_contiguous()):
+            raise ValueError("rec_lr must be a contiguous CUDA float32 tensor shaped like gt_lr")
+        L, d = self.L, C.byref(self.desc)
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        n = B * H * W
+        self._reserve(n)
+        g = self.gbuf[0]
+        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
+        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), xy.data_ptr(), n,
+                                  self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
+        _lib.check(L.wire_avgpool_mse_grad_frames(stream, self.y.data_ptr(), B, H, W, self.O, scale, gt.data_ptr(),
+                                                  mk.data_ptr() if mk is not None else None, self.gy.data_ptr(),
+                                                  rec_lr.data_ptr() if rec_lr is not None else None,
+                                                  g.data_ptr() + 4 * self.count, self.partial.data_ptr()),
+                   "avgpool_mse_grad_frames")
+        _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), xy.data_ptr(), n,
+                                  self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
+                                  self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
+        self.t += 1
+        self._adam(stream, g)
+        self.loss = g[self.count:self.count + 1].clone()
+        return self.loss
+
     # ------------------------------------------------------------------ CT step
     def step_radon(self, sinogram: torch.Tensor, thetas: torch.Tensor) -> torch.Tensor:
         """One optimizer step of the CT loop (wire_ct.py:128-139): the model is evaluated on the WHOLE grid in raster
@@ -498,12 +586,16 @@ class FusedTrainer:
     def psnr(self, rec: torch.Tensor, gt: Optional[torch.Tensor] = None) -> torch.Tensor:
         """utils.psnr(gt, rec) = 10 log10(max(gt) / mse) (modules/utils.py:67-82) computed on the
         device; returns a 0-dim device tensor (no host sync, no image copy)."""
+        if gt is None:
+            self._need_target("psnr without gt")
         out = self._metric(0, rec, self.target if gt is None else gt, 0.0)
         return 10.0 * torch.log10(out[1] / (out[0] / rec.numel()))
 
     def iou(self, pred: torch.Tensor, gt: Optional[torch.Tensor] = None, thres: float = 0.5) -> torch.Tensor:
         """volutils.get_IoU(pred, gt, thres) (modules/volutils.py:74-91) on the device; ``pred`` is
         left untouched (the reference binarises it in place)."""
+        if gt is None:
+            self._need_target("iou without gt")
         out = self._metric(1, pred, self.target if gt is None else gt, thres)
         return out[0] / out[1]
 
