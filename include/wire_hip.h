@@ -348,6 +348,30 @@ int wire_adam_step_flat(void* stream, float* param, const float* grad,
 int wire_eval_metric(void* stream, int mode, const float* rec, const float* gt,
                      int64_t count, float thres, float* out2, float* partial);
 
+/* Structural similarity (SSIM) of two channel-last images x, y [H][W][O] without a device->host copy or a transposed
+ * copy: the windowed moments m(x), m(y), m(x^2), m(y^2), m(xy) under a separable window of `taps` weights
+ * (window_host, HOST memory, applied along both axes) over the valid region [H-taps+1][W-taps+1], and per pixel and
+ * channel
+ *   vx = cov_norm (m(x^2) - m(x)^2),  vy = cov_norm (m(y^2) - m(y)^2),  vxy = cov_norm (m(xy) - m(x) m(y)),
+ *   S  = (2 m(x) m(y) + c1) (2 vxy + c2) / ((m(x)^2 + m(y)^2 + c1) (vx + vy + c2)).
+ * out1[0] = the mean of S over all pixels and channels; map (optional, NULL for none) receives S itself,
+ * [H-taps+1][W-taps+1][O].  Two definitions are in use in the reference's drivers, both with c1 = (0.01 L)^2,
+ * c2 = (0.03 L)^2, L = the data range:
+ *   - pytorch_msssim.ssim(im_gt, im_rec, data_range=1, size_average=True), every epoch of the super-resolution loops
+ *     (wire_SISR.py:169, bspline_SISR.py:192): 11 taps g[i] = exp(-(i-5)^2 / (2 1.5^2)) normalised to sum 1 in fp32,
+ *     cov_norm = 1;
+ *   - skimage.metrics.structural_similarity(..., multichannel=True) with its defaults, the final report of wire_ct.py,
+ *     bspline_ct.py, wire_multi_sr.py, both SISR drivers and modules/volutils.py: 7 taps of 1/7 (a uniform filter,
+ *     then 3 pixels cropped at each side = the valid region), cov_norm = 49/48 (sample covariance); the mean over
+ *     channels of per-channel means is the same number as the mean over everything.
+ * taps odd in 3..11, O in 1..8, H, W >= taps, cov_norm / c1 / c2 finite, every pointer but map non-NULL: anything else
+ * is WIRE_ERR_ARG before any HIP call; ws_bytes < wire_ssim_ws_bytes(H, W, O, taps) is WIRE_ERR_SIZE.  fp32; per-tile
+ * partial sums reduced in a fixed order in ws (no atomics: the same call gives the same bits).  x, y, out1, map, ws:
+ * device.                                                                                                         */
+int64_t wire_ssim_ws_bytes(int H, int W, int O, int taps);
+int wire_ssim(void* stream, const float* x, const float* y, int H, int W, int O, int taps, const float* window_host,
+              float cov_norm, float c1, float c2, float* out1, float* map, void* ws, int64_t ws_bytes);
+
 /* Best-reconstruction tracking of the drivers without a device->host copy per epoch
  * (wire_image_denoise.py:176-178: `if (mse_array[epoch] < best_mse) or (epoch == 0): best_mse = ...; best_img = imrec`;
  * wire_occupancy.py:170-172 with lossval): if force != 0 or metric[0] < best_metric[0], copy src[0..count) to dst

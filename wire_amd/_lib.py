@@ -34,7 +34,7 @@ SYMBOLS = [
     "wire_bwd_coords_scratch_bytes", "wire_mlp_bwd_coords", "wire_posenc_bwd", "wire_gabor_bwd_first_coords",
     "wire_gabor2d_bwd_first_coords", "wire_mscale_first_fwd", "wire_m2_combine_fwd", "wire_m2_combine_ws_bytes",
     "wire_m2_combine_bwd", "wire_mfn_filter_fwd", "wire_mfn_filter_ws_bytes", "wire_mfn_filter_bwd",
-    "wire_avgpool_mse_grad_frames", "wire_affine_coords",
+    "wire_avgpool_mse_grad_frames", "wire_affine_coords", "wire_ssim_ws_bytes", "wire_ssim",
 ]
 
 
@@ -136,6 +136,9 @@ def _declare(l: C.CDLL) -> None:
     l.wire_real_layer_fwd.argtypes = [vp, i32, vp, vp, vp, f32, f32, i64, i32, i32, vp, vp, i64]
     l.wire_real_layer_bwd.argtypes = [vp, i32, vp, vp, vp, vp, f32, f32, i64, i32, i32, vp, vp, vp, vp, i64]
     l.wire_eval_metric.argtypes = [vp, i32, vp, vp, i64, f32, vp, vp]
+    l.wire_ssim_ws_bytes.argtypes = [i32, i32, i32, i32]
+    l.wire_ssim_ws_bytes.restype = i64
+    l.wire_ssim.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(C.c_float), f32, f32, f32, vp, vp, vp, i64]
     l.wire_prof_enable.argtypes = [i32]
     l.wire_prof_read.argtypes = [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double)]
 

@@ -82,6 +82,28 @@ extern "C" int wire_eval_metric(void* stream, int mode, const float* rec, const 
   return WIRE_OK;
 }
 
+static bool ssim_shape_ok(int H, int W, int O, int taps) {
+  return taps >= 3 && taps <= SSIM_MAX_TAPS && (taps & 1) && H >= taps && W >= taps && O >= 1 && O <= WIRE_MAXO &&
+         ssim_tiles(H, W, taps) <= 0x7fffffff;
+}
+extern "C" int64_t wire_ssim_ws_bytes(int H, int W, int O, int taps) {
+  if (!ssim_shape_ok(H, W, O, taps)) return fail(WIRE_ERR_ARG, "bad argument to wire_ssim_ws_bytes");
+  return ssim_tiles(H, W, taps) * 4 + 256;
+}
+extern "C" int wire_ssim(void* stream, const float* x, const float* y, int H, int W, int O, int taps,
+                         const float* window_host, float cov_norm, float c1, float c2, float* out1, float* map, void* ws,
+                         int64_t ws_bytes) {
+  if (!ssim_shape_ok(H, W, O, taps) || !x || !y || !window_host || !out1 || !ws || !std::isfinite(cov_norm) ||
+      !std::isfinite(c1) || !std::isfinite(c2))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_ssim");
+  if (ws_bytes < wire_ssim_ws_bytes(H, W, O, taps)) return fail(WIRE_ERR_SIZE, "ws too small");
+  SsimWin win{};
+  for (int t = 0; t < taps; ++t) win.w[t] = window_host[t];
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_ssim((hipStream_t)stream, x, y, H, W, O, taps, win, cov_norm, c1, c2, out1, map, (float*)ws));
+  return WIRE_OK;
+}
+
 extern "C" int wire_track_best(void* stream, const float* metric, float* best_metric, int force, const float* src,
                                float* dst, int64_t count, int* updated) {
   if (!metric || !best_metric || count < 0 || (count > 0 && (!src || !dst)))

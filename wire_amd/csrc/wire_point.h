@@ -167,7 +167,7 @@ hipError_t launch_gabor2d_hparam_grad(hipStream_t s, const float* g, const float
                                       int K, int P, int is_first, float scale, float* partial, float* out2);
 
 // ===========================================================================
-// wire_train.hip -- the glue of a training run
+// wire_train.hip -- the glue of a training run (and wire_ssim.hip, the one metric with a kernel file of its own)
 // ===========================================================================
 // ---- training glue
 // idx_out[r] = pi_seed(first + r), r < count: a keyed bijection pi_seed of [0, n_total) (the epoch's shuffle)
@@ -200,6 +200,14 @@ hipError_t launch_adam(hipStream_t s, float* p, const float* g, float* m, float*
 // ---- evaluation metrics: mode 0 -> {sum sq err, max gt}; mode 1 -> {intersection, union}
 hipError_t launch_metric(hipStream_t s, int mode, const float* rec, const float* gt, int64_t count, float thres,
                          float* out, float* partial);
+// ---- structural similarity (wire_ssim.hip): x, y [H][W][O] channel last, a separable window of `taps` (odd, 3 ..
+// SSIM_MAX_TAPS) floats over the valid region; out1[0] = the mean of the index, map (optional) [H-taps+1][W-taps+1][O];
+// partial: ssim_tiles(H, W, taps) floats
+#define SSIM_MAX_TAPS 11
+struct SsimWin { float w[SSIM_MAX_TAPS]; };
+int64_t ssim_tiles(int H, int W, int taps);
+hipError_t launch_ssim(hipStream_t s, const float* x, const float* y, int H, int W, int O, int taps, const SsimWin& win,
+                       float cov, float c1, float c2, float* out1, float* map, float* partial);
 
 // ---- best-so-far tracking on the device and the sigmoid of the mesh-export query
 hipError_t launch_track_best(hipStream_t s, const float* metric, float* best, int force, const float* src,

@@ -545,3 +545,92 @@ class _MfnFilterFunction(torch.autograd.Function):
 
 def mfn_filter(x, mu, gamma, w, c):
     return _MfnFilterFunction.apply(x, mu, gamma, w, c)
+
+
+# ---------------------------------------------------------------------------
+# structural similarity on the device (wire_ssim)
+# ---------------------------------------------------------------------------
+_SSIM_WINDOWS = {}
+
+
+def _ssim_window(window):
+    """(taps, fp32 weights as a ctypes array, cov_norm) of a window spec: "gaussian" = (11, 1.5), "uniform" = (7, None),
+    or a (taps, sigma_or_None) tuple -- a Gaussian of that sigma, or ``taps`` equal weights with the sample covariance."""
+    key = {"gaussian": (11, 1.5), "uniform": (7, None)}.get(window, window) if isinstance(window, str) else window
+    if not (isinstance(key, tuple) and len(key) == 2 and isinstance(key[0], int)):
+        raise ValueError(f"window must be 'gaussian', 'uniform' or a (taps, sigma_or_None) tuple, not {window!r}")
+    taps, sigma = key
+    if taps < 3 or taps > 11 or taps % 2 == 0:
+        raise ValueError(f"a window has an odd number of taps in 3..11, not {taps}")
+    if key not in _SSIM_WINDOWS:
+        if sigma is None:
+            w = torch.full((taps,), 1.0 / taps, dtype=torch.float32)
+            cov = taps * taps / (taps * taps - 1.0)
+        else:
+            # pytorch_msssim's _fspecial_gauss_1d, in fp32 throughout
+            coords = torch.arange(taps, dtype=torch.float32) - (taps // 2)
+            w = torch.exp(-(coords ** 2) / (2 * float(sigma) ** 2))
+            w = w / w.sum()
+            cov = 1.0
+        _SSIM_WINDOWS[key] = (taps, (C.c_float * taps)(*w.tolist()), cov)
+    return _SSIM_WINDOWS[key]
+
+
+def _ssim(rec, gt, H, W, window, data_range, full, ws=None):
+    """ssim() with a workspace the caller may keep between calls; returns (result, workspace)."""
+    taps, win, cov = _ssim_window(window)
+    uniform = window == "uniform" or (isinstance(window, tuple) and window[1] is None)
+    if data_range is None:
+        if uniform:
+            raise ValueError("window='uniform' (skimage.metrics.structural_similarity) needs data_range: skimage derives "
+                             "it from the dtype, 2.0 for float images in the release the drivers were written against")
+        data_range = 1.0
+    H, W = int(H), int(W)
+    if H < taps or W < taps:
+        raise ValueError(f"a {H} x {W} image is smaller than the {taps}-tap window")
+    if rec.numel() != gt.numel() or rec.numel() % (H * W) != 0:
+        raise ValueError(f"rec ({rec.numel()}) and gt ({gt.numel()}) must both hold H*W*O = {H * W}*O elements")
+    O = rec.numel() // (H * W)
+    if not 1 <= O <= 8:
+        raise ValueError(f"{O} channels: the library takes 1..8")
+    for t in (rec, gt):
+        if tuple(t.shape) not in ((H * W, O), (1, H * W, O), (H, W, O)):
+            raise ValueError(f"shape {tuple(t.shape)} is none of [H*W, O], [1, H*W, O], [H, W, O]")
+    _require_cuda(rec, "rec")
+    _require_cuda(gt, "gt")
+    if rec.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise ValueError("rec and gt must be float32")
+    L = _lib.lib()
+    dev = rec.device
+    x, y = gt.detach().contiguous(), rec.detach().contiguous()
+    ws_bytes = _lib.check(L.wire_ssim_ws_bytes(H, W, O, taps), "wire_ssim_ws_bytes")
+    if ws is None or ws.numel() < ws_bytes or ws.device != dev:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    smap = torch.empty(H - taps + 1, W - taps + 1, O, dtype=torch.float32, device=dev) if full else None
+    c1, c2 = (0.01 * float(data_range)) ** 2, (0.03 * float(data_range)) ** 2
+    _lib.check(L.wire_ssim(_stream_ptr(dev), x.data_ptr(), y.data_ptr(), H, W, O, taps, win, cov, c1, c2, out.data_ptr(),
+                           None if smap is None else smap.data_ptr(), ws.data_ptr(), ws.numel()), "wire_ssim")
+    return ((out, smap) if full else out), ws
+
+
+def ssim(rec: torch.Tensor, gt: torch.Tensor, H: int, W: int, window="gaussian", data_range=None, full: bool = False):
+    """Structural similarity of two images on the device (wire_ssim): no copy to the host, no transposed copy, no sync.
+
+    ``rec`` and ``gt`` are CUDA float32 tensors of H*W*O elements in the trainer's layout -- [H*W, O], [1, H*W, O] or
+    [H, W, O], channel last, O <= 8.  Returns a 0-dim device tensor, or ``(ssim, map)`` with ``full=True``, the map
+    [H - taps + 1, W - taps + 1, O] over the valid region.
+
+    ``window="gaussian"``: ``pytorch_msssim.ssim(gt, rec, data_range=1, size_average=True)`` as the super-resolution
+    drivers call it every epoch -- 11 taps, sigma 1.5, normalised in fp32, population covariance; ``data_range``
+    defaults to 1.0, what the drivers pass.
+    ``window="uniform"``: ``skimage.metrics.structural_similarity(gt, rec, multichannel=True)`` with its defaults, the
+    drivers' final report -- a 7 x 7 uniform filter, sample covariance (49/48), the border of 3 cropped.  ``data_range``
+    must be given (ValueError otherwise): skimage derives it from the dtype, and 2.0 is what the release the drivers
+    were written against (the one that still takes ``multichannel=``) derives for float images.
+    A ``(taps, sigma_or_None)`` tuple selects another odd size in 3..11: a Gaussian, or equal weights with the sample
+    covariance.
+
+    CPU tensors raise WireHipError.  An image smaller than the window raises ValueError; this is stricter than
+    pytorch_msssim, which warns and skips the smoothing along that axis."""
+    return _ssim(rec, gt, H, W, window, data_range, full)[0]

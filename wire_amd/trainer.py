@@ -29,7 +29,7 @@ from typing import List, Optional, Sequence
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, functional
 from .modules._base import HipINR
 from .modules.utils import axis_tables
 from .parallel import FlatGradAllReducer, replicas_identical, shard_bounds
@@ -598,6 +598,24 @@ class FusedTrainer:
             self._need_target("iou without gt")
         out = self._metric(1, pred, self.target if gt is None else gt, thres)
         return out[0] / out[1]
+
+    def ssim(self, rec: torch.Tensor, gt: Optional[torch.Tensor] = None, window="gaussian", data_range=None,
+             full: bool = False):
+        """functional.ssim(rec, gt, H, W, ...) on the trainer's (H, W) grid (a 3-D grid is a ValueError): the
+        structural similarity the super-resolution drivers log every epoch (``window="gaussian"``,
+        wire_SISR.py:169) and every driver reports at the end (``window="uniform"``, which needs ``data_range``),
+        computed on the device from the channel-last ``render()`` / ``rec`` as it is.  ``gt=None`` compares against the
+        trainer's target.  Returns a 0-dim device tensor (no host sync), or ``(ssim, map)`` with ``full=True``; the
+        workspace is kept between calls.  ``update_best`` keeps the SMALLEST metric, so a caller that tracks the best
+        image by SSIM passes ``-ssim``."""
+        if len(self.grid) != 2:
+            raise ValueError("ssim compares 2-D images; this trainer's grid is 3-D")
+        if gt is None:
+            self._need_target("ssim without gt")
+            gt = self.target
+        res, self._ssim_ws = functional._ssim(rec, gt, self.grid[0], self.grid[1], window, data_range, full,
+                                              getattr(self, "_ssim_ws", None))
+        return res
 
     def _metric(self, mode: int, rec: torch.Tensor, gt: torch.Tensor, thres: float) -> torch.Tensor:
         rec = rec.detach().to(torch.float32).contiguous()
