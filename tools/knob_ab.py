@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Interleaved A/B of one tuning knob on the headline training step (and the forward-only render) in ONE process on one
 box: blocks of timed steps alternate between the two settings, so clock / temperature drift hits both alike.
-    python3 tools/knob_ab.py split_out [hidden_features] [nonlin] [values, e.g. 2,1]"""
+    python3 tools/knob_ab.py split_out [hidden_features] [nonlin] [values, e.g. 2,1]
+Several knobs switched together: their keys joined by "+", e.g. first_dn+bwd_lookahead."""
 import os
 import sys
 import time
@@ -15,6 +16,7 @@ from wire_amd.modules import models
 from wire_amd.trainer import FusedTrainer
 
 knob = sys.argv[1].encode() if len(sys.argv) > 1 else b"split_out"
+keys = knob.split(b"+")
 hf = int(sys.argv[2]) if len(sys.argv) > 2 else 363
 nonlin = sys.argv[3] if len(sys.argv) > 3 else "wire"
 vals = tuple(int(v) for v in sys.argv[4].split(",")) if len(sys.argv) > 4 else (1, 0)
@@ -27,10 +29,11 @@ tr = FusedTrainer(model, (512, 512), torch.rand(512 * 512, 3), lr=5e-3, niters=2
 L = _lib.lib()
 tot = {v: [] for v in vals}
 rnd = {v: [] for v in vals}
-default = L.wire_tune_get(knob)
+default = [L.wire_tune_get(k) for k in keys]
 for rep in range(6):
     for v in vals:
-        _lib.check(L.wire_tune_set(knob, v))
+        for k in keys:
+            _lib.check(L.wire_tune_set(k, v))
         for i in range(3):
             tr.step_hashed(rep * 100 + i)
         torch.cuda.synchronize()
@@ -47,7 +50,8 @@ for rep in range(6):
             tr.render()
         torch.cuda.synchronize()
         rnd[v].append((time.perf_counter() - t0) / 5 * 1e3)
-_lib.check(L.wire_tune_set(knob, default))
+for k, dv in zip(keys, default):
+    _lib.check(L.wire_tune_set(k, dv))
 for v in vals:
     print(f"{knob.decode()} = {v} ({nonlin}, hidden_features {hf}): step mean {sum(tot[v]) / len(tot[v]):.3f} ms  min {min(tot[v]):.3f} ms"
           f"   |  render mean {sum(rnd[v]) / len(rnd[v]):.3f} ms  min {min(rnd[v]):.3f} ms   "

@@ -566,6 +566,7 @@ int Bwd::layers() {
       ep.omega = (l - 1 == 0) ? p.w1 : p.w;
       ep.i0 = lin_l(l - 1); ep.o0 = gnext; ep.ld0 = p.Pl;
       ep.recompute_out = r.recompute_out && l >= 2;
+      ep.lookahead = r.bwd_lookahead && ep.recompute_out;             // (lin_{l-1}: the activation buffer; g_lin_{l-1}: the scratch)
       // (real nets: the layer-1 epilogue sums g_lin_0 [x | 1] itself)
       if (l == 1 && first_sums) { ep.coords = coords; ep.D = p.D; ep.cr_partial = Sx + sc.crp; ep.cr_C = p.K; }
     } else {
@@ -575,6 +576,7 @@ int Bwd::layers() {
       // (wire, wire2d: g_u [x | 1] per 256-row tile instead of storing g_u for a separate pass)
       if (first_sums) { ep.cr_partial = Sx + sc.crp; ep.cr_C = p.K; ep.cr_set = crp_set(); }
       ep.recompute_out = r.recompute_out0;
+      ep.first_dn = r.first_dn;
       ep.W0 = first(0); ep.b0 = first(1);
       if (pl == 4) { ep.W0b = first(2); ep.b0b = first(3); }
     }

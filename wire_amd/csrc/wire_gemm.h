@@ -32,8 +32,16 @@ enum WireEpi {
   // flag on the layer-1 data-gradient forms of the 16 x 16 x 32 kernels (the real BWD forms, GABOR_BWD_FIRST,
   // GABOR2D_BWD_FIRST): the instantiation that also writes ep.cg_partial.  Host code passes the plain code; the
   // launchers pick the flagged instantiation when ep.cg_partial is set
-  EPI_CG = 64
+  EPI_CG = 64,
+  // flags on GABOR_BWD_FIRST / GABOR2D_BWD_FIRST of the 16 x 16 x 32 kernels: the instantiations whose input width D is a
+  // compile-time 2 or 3 (wire_gemmh_epi.h: h_gabor_bwd_first_dn, h_gabor2d_bwd_first_dn).  The launchers pick them when
+  // ep.first_dn is set and ep.D is 2 or 3; every other D keeps the plain form
+  EPI_D2 = 128, EPI_D3 = 256,
+  // flag on GABOR_BWD of the 16 x 16 x 32 kernels: the edition whose epilogue loads the next row block's lin ahead of
+  // the current block's arithmetic and stores (wire_gemmh_epi.h: h_gabor_bwd_la); picked when ep.lookahead is set
+  EPI_LA = 512
 };
+constexpr int EPI_FLAGS = EPI_CG | EPI_D2 | EPI_D3 | EPI_LA;
 
 // the real-valued activation epilogues (siren / gauss / relu / B-spline) and their ACT_* code (wire_dev.h)
 constexpr bool epi_real_fwd(int e) {
@@ -72,6 +80,8 @@ struct GemmEpiParams {
                                  //   coordinate-gradient partials [column tile][M][D] of g_lin_0 W0 (real nets; W0 native
                                  //   [K][D]), g_u W0 (wire), g_u W0 + g_p W0b (wire2d); the stores are unchanged
   int recompute_out = 0;         // EPI_GABOR_BWD of wire_gemmx3h.hip: out = act(lin) again instead of reading i1
+  int lookahead = 0;             // EPI_GABOR_BWD of the 16 x 16 x 32 kernels: the look-ahead edition (EPI_LA); needs recompute_out; i0 and o0 must not overlap
+  int first_dn = 0;              // the *_BWD_FIRST forms of the 16 x 16 x 32 kernels: D = 2, 3 as compile-time editions (EPI_D2, EPI_D3)
   int stagger = 0, stagger_lo = 0, stagger_hi = 0;   // wire_gemmx3g.hip: late start (100 MHz ticks) of blocks [lo, hi)
   // 2 x fp16 split GEMM (wire_gemmx2h.hip): sharded max-|value| slots (WIRE_AMAX_SLOTS unsigned each, wire_dev.h)
   const unsigned* amax_a = nullptr;   //   of the activation operand A (filled by A's producer)

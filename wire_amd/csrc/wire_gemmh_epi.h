@@ -61,16 +61,379 @@ WIRE_DEVINL void h_cg_store(const float (&cg)[4], const GemmEpiParams& ep, const
   for (int d = 0; d < ep.D; ++d) dst[d] = cg[d];
 }
 
+// ---------------------------------------------------------------------------
+// The layer-1 data-gradient forms of the complex nets with the input width a compile-time constant DN = 2, 3 (EPI_D2,
+// EPI_D3; knob "first_dn").  Same values as the plain forms in h_epilogue below, which run every chain over four terms with
+// x[d] = w[d] = +0 for d >= D: fmaf(+0, +0, u) = u for every u but -0 (which it turns into +0: the plain form departs
+// from first_fwd_kernel's u there, this one does not), and a sum that starts at +0 and only ever adds g * (+0) stays +0
+// for finite g -- written out as the constant below, so cr_partial keeps its [.][5] layout.  What else differs is WHEN
+// things are loaded: the coordinates of the lane's 2 NRB rows once per tile instead of once per row and column group, the
+// first layer's parameters of both column groups ahead of the first group's arithmetic.  Loads of rows >= M read row
+// M - 1 and are not used.  The order of every surviving fmaf chain and of the reductions is that of the plain forms.
+// ---------------------------------------------------------------------------
+template <int DN>
+WIRE_DEVINL void h_cg_add_dn(float (&cg)[4], const float (&t)[DN], const int e, const int lane) {
+#pragma unroll
+  for (int d = 0; d < DN; ++d) {
+    float v = t[d];
+    v += __shfl_xor(v, 8); v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+    cg[d] += (lane >> 3) == e ? v : 0.f;
+  }
+}
+template <int DN, int NRB>
+WIRE_DEVINL void h_load_rows_dn(float (&xs)[2 * NRB][DN], const GemmEpiParams& ep, const int M, const int m_w, const int rr) {
+#pragma unroll
+  for (int e = 0; e < 2 * NRB; ++e) {
+    int row = m_w + 8 * e + rr;                                   // = m_w + 16 rb + 8 hr + rr, e = 2 rb + hr
+    row = row < M ? row : M - 1;
+#pragma unroll
+    for (int d = 0; d < DN; ++d) xs[e][d] = ep.coords[(size_t)row * DN + d];
+  }
+}
+// sums over the 8 row lanes of each 16-lane row, then into this wave's [64 features][5] of LDS
+template <int DN>
+WIRE_DEVINL void h_crs_to_lds_dn(const float (&crs)[4][DN + 1], float* red, const int rr) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int d = 0; d <= DN; ++d) {
+      float v = crs[q][d];
+      v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
+      o[d < DN ? d : 4] = v;
+    }
+    if (rr == 0) {
+#pragma unroll
+      for (int d = 0; d < 5; ++d) red[q * 5 + d] = o[d];
+    }
+  }
+}
+
+template <bool CG, int DN, int NRB>
+WIRE_DEVINL void h_gabor_bwd_first_dn(const f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const int M, const int m_w,
+                                      const int n_w, const int Nc, const int lane, unsigned char* lds, const int wave,
+                                      const int rt) {
+  const int rr = lane & 7, cq = 16 * ((lane >> 3) & 1) + 4 * (lane >> 4);
+  const float w0 = ep.omega, m2s2 = -2.f * ep.scale * ep.scale;
+  float xs[2 * NRB][DN];
+  h_load_rows_dn<DN, NRB>(xs, ep, M, m_w, rr);
+  float w[2][4][DN], bb[2][4];
+#pragma unroll
+  for (int G = 0; G < 2; ++G) {
+    const int c0 = n_w + 64 * G + cq;
+    const int f0 = ((c0 >> 6) << 5) + (c0 & 31);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool valid = f0 + q < ep.kvalid;
+      bb[G][q] = valid ? ep.b0[f0 + q] : 0.f;
+#pragma unroll
+      for (int d = 0; d < DN; ++d) w[G][q][d] = valid ? ep.W0[(f0 + q) * DN + d] : 0.f;
+    }
+  }
+  float cg[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int G = 0; G < 2; ++G) {
+    if (n_w + 64 * G >= Nc) continue;
+    const int c0 = n_w + 64 * G + cq;                             // this lane's first re column; im = + 32
+    const int f0 = ((c0 >> 6) << 5) + (c0 & 31);                  // ... = features f0 .. f0 + 3
+    float crs[4][DN + 1];                                         // sums of g_u [x | 1]
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int d = 0; d <= DN; ++d) crs[q][d] = 0.f;
+#pragma unroll
+    for (int rb = 0; rb < NRB; ++rb) {
+      f32x4 are[2], aim[2];
+      h_pair_rows(acc[rb][4 * G], acc[rb][4 * G + 1], are[0], are[1]);
+      h_pair_rows(acc[rb][4 * G + 2], acc[rb][4 * G + 3], aim[0], aim[1]);
+#pragma unroll
+      for (int hr = 0; hr < 2; ++hr) {
+        const int e = 2 * rb + hr;
+        const int row = m_w + 8 * e + rr;
+        float t[DN];
+#pragma unroll
+        for (int d = 0; d < DN; ++d) t[d] = 0.f;
+        if (row < M) {
+          f32x4 pr = {0.f, 0.f, 0.f, 0.f}, pi = pr;
+          if (!ep.recompute_out) {
+            const float* Op = ep.i1 + (size_t)row * ep.ld1 + c0;
+            pr = *reinterpret_cast<const f32x4*>(Op);
+            pi = *reinterpret_cast<const f32x4*>(Op + 32);
+          }
+          f32x4 gu;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            float u = bb[G][q];
+#pragma unroll
+            for (int d = 0; d < DN; ++d) u = __builtin_fmaf(xs[e][d], w[G][q][d], u);
+            if (ep.recompute_out) {
+              float a, b;
+              gabor_fwd_real(u, w0, ep.scale, a, b);
+              pr[q] = a; pi[q] = b;
+            }
+            const float v = gabor_bwd_real(are[hr][q], aim[hr][q], u, pr[q], pi[q], w0, m2s2);
+            gu[q] = f0 + q < ep.kvalid ? v : 0.f;
+          }
+          if constexpr (CG) {                                     // (w is 0 for pad features)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+              for (int d = 0; d < DN; ++d) t[d] = __builtin_fmaf(gu[q], w[G][q][d], t[d]);
+          }
+          if (ep.cr_partial) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+#pragma unroll
+              for (int d = 0; d < DN; ++d) crs[q][d] = __builtin_fmaf(gu[q], xs[e][d], crs[q][d]);
+              crs[q][DN] += gu[q];
+            }
+          } else {
+            *reinterpret_cast<f32x4*>(ep.o0 + (size_t)row * ep.ldu + f0) = gu;
+          }
+        }
+        if constexpr (CG) h_cg_add_dn<DN>(cg, t, e, lane);
+      }
+    }
+    if (ep.cr_partial)   // (the main loop is over: every wave has passed its last barrier, the stage buffers are free)
+      h_crs_to_lds_dn<DN>(crs, reinterpret_cast<float*>(lds) + (wave * 64 + 32 * G + cq) * 5, rr);
+  }
+  if (ep.cr_partial) {                                            // the four waves: (w0 + w1) + (w2 + w3)
+    __syncthreads();
+    const float* red = reinterpret_cast<const float*>(lds);       // [4 waves][64 features][5]
+    const int fbase = (n_w >> 6) << 5;                            // first complex feature of this 128-column tile
+    for (int e = threadIdx.x; e < 64 * 5; e += 256) {
+      const int f = e / 5, d = e - 5 * f;
+      const float v = (red[e] + red[64 * 5 + e]) + (red[2 * 64 * 5 + e] + red[3 * 64 * 5 + e]);
+      if (fbase + f < ep.cr_C) ep.cr_partial[((size_t)rt * ep.cr_C + fbase + f) * 5 + d] = v;
+    }
+  }
+  if constexpr (CG) h_cg_store<NRB>(cg, ep, M, m_w, n_w, lane);
+}
+
+template <bool CG, int DN, int NRB>
+WIRE_DEVINL void h_gabor2d_bwd_first_dn(const f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const int M, const int m_w,
+                                        const int n_w, const int Nc, const int lane, unsigned char* lds, const int wave,
+                                        const int rt) {
+  const int rr = lane & 7, cq = 16 * ((lane >> 3) & 1) + 4 * (lane >> 4);
+  const float m2s2 = -2.f * ep.scale * ep.scale, w0 = ep.omega;
+  float xs[2 * NRB][DN];
+  h_load_rows_dn<DN, NRB>(xs, ep, M, m_w, rr);
+  float w[2][4][DN], wv[2][4][DN], bb[2][4], bv2[2][4];
+#pragma unroll
+  for (int G = 0; G < 2; ++G) {
+    const int c0 = n_w + 64 * G + cq;
+    const int f0 = ((c0 >> 6) << 5) + (c0 & 31);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool valid = f0 + q < ep.kvalid;
+      bb[G][q] = valid ? ep.b0[f0 + q] : 0.f;
+      bv2[G][q] = valid ? ep.b0b[f0 + q] : 0.f;
+#pragma unroll
+      for (int d = 0; d < DN; ++d) {
+        w[G][q][d] = valid ? ep.W0[(f0 + q) * DN + d] : 0.f;
+        wv[G][q][d] = valid ? ep.W0b[(f0 + q) * DN + d] : 0.f;
+      }
+    }
+  }
+  float cg[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int G = 0; G < 2; ++G) {
+    if (n_w + 64 * G >= Nc) continue;
+    const int c0 = n_w + 64 * G + cq;                             // re column of g_out / out; im = + 32
+    const int f0 = ((c0 >> 6) << 5) + (c0 & 31);
+    float cru[4][DN + 1], crp2[4][DN + 1];                        // sums of g_u [x | 1], g_p [x | 1]
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int d = 0; d <= DN; ++d) { cru[q][d] = 0.f; crp2[q][d] = 0.f; }
+#pragma unroll
+    for (int rb = 0; rb < NRB; ++rb) {
+      f32x4 are[2], aim[2];
+      h_pair_rows(acc[rb][4 * G], acc[rb][4 * G + 1], are[0], are[1]);
+      h_pair_rows(acc[rb][4 * G + 2], acc[rb][4 * G + 3], aim[0], aim[1]);
+      f32x4 pr[2], pi[2];
+#pragma unroll
+      for (int hr = 0; hr < 2; ++hr) {
+        int row = m_w + 16 * rb + 8 * hr + rr;
+        row = row < M ? row : M - 1;
+        const float* Op = ep.i1 + (size_t)row * ep.ld1 + c0;
+        pr[hr] = *reinterpret_cast<const f32x4*>(Op);
+        pi[hr] = *reinterpret_cast<const f32x4*>(Op + 32);
+      }
+#pragma unroll
+      for (int hr = 0; hr < 2; ++hr) {
+        const int e = 2 * rb + hr;
+        const int row = m_w + 8 * e + rr;
+        f32x4 g0, g2;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float uu = bb[G][q], p2 = bv2[G][q];
+#pragma unroll
+          for (int d = 0; d < DN; ++d) {
+            uu = __builtin_fmaf(xs[e][d], w[G][q][d], uu);
+            p2 = __builtin_fmaf(xs[e][d], wv[G][q][d], p2);
+          }
+          const float gr = are[hr][q], gi = aim[hr][q];
+          const float c_r = __builtin_fmaf(pr[hr][q], gr, pi[hr][q] * gi);
+          const float c_i = __builtin_fmaf(pr[hr][q], gi, -(pi[hr][q] * gr));
+          const float tt = m2s2 * c_r;
+          g0[q] = __builtin_fmaf(tt, uu, w0 * c_i);
+          g2[q] = tt * p2;
+        }
+        if constexpr (CG) {                                       // (w, wv are 0 for pad features)
+          float t[DN];
+#pragma unroll
+          for (int d = 0; d < DN; ++d) t[d] = 0.f;
+          if (row < M) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+              for (int d = 0; d < DN; ++d)
+                t[d] = __builtin_fmaf(g2[q], wv[G][q][d], __builtin_fmaf(g0[q], w[G][q][d], t[d]));
+          }
+          h_cg_add_dn<DN>(cg, t, e, lane);
+        }
+        if (row < M) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (!(f0 + q < ep.kvalid)) { g0[q] = 0.f; g2[q] = 0.f; }
+          if (ep.cr_partial) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+#pragma unroll
+              for (int d = 0; d < DN; ++d) {
+                cru[q][d] = __builtin_fmaf(g0[q], xs[e][d], cru[q][d]);
+                crp2[q][d] = __builtin_fmaf(g2[q], xs[e][d], crp2[q][d]);
+              }
+              cru[q][DN] += g0[q];
+              crp2[q][DN] += g2[q];
+            }
+          } else {
+            float* Gp = ep.o0 + (size_t)row * (2 * ep.ldu);
+            *reinterpret_cast<f32x4*>(Gp + f0) = g0;
+            *reinterpret_cast<f32x4*>(Gp + ep.ldu + f0) = g2;
+          }
+        }
+      }
+    }
+    if (ep.cr_partial) {                                          // [2 sets][4 waves][64 features][5]
+      float* red = reinterpret_cast<float*>(lds) + (wave * 64 + 32 * G + cq) * 5;
+      h_crs_to_lds_dn<DN>(cru, red, rr);
+      h_crs_to_lds_dn<DN>(crp2, red + 4 * 64 * 5, rr);
+    }
+  }
+  if (ep.cr_partial) {
+    __syncthreads();
+    const float* red = reinterpret_cast<const float*>(lds);
+    const int fbase = (n_w >> 6) << 5;                            // first feature of this 128-column tile
+    for (int e = threadIdx.x; e < 2 * 64 * 5; e += 256) {
+      const int set = e / (64 * 5), r = e - set * (64 * 5);
+      const int f = r / 5, d = r - 5 * f;
+      const float* rs = red + set * (4 * 64 * 5);
+      const float v = (rs[r] + rs[64 * 5 + r]) + (rs[2 * 64 * 5 + r] + rs[3 * 64 * 5 + r]);
+      if (fbase + f < ep.cr_C)
+        ep.cr_partial[(size_t)set * ep.cr_set + ((size_t)rt * ep.cr_C + fbase + f) * 5 + d] = v;
+    }
+  }
+  if constexpr (CG) h_cg_store<NRB>(cg, ep, M, m_w, n_w, lane);
+}
+
+// ---------------------------------------------------------------------------
+// EPI_GABOR_BWD with one row block of look-ahead (EPI_LA; knob "bwd_lookahead").  The plain form in h_epilogue loads lin
+// of a 16-row block, computes, stores g_lin and only then loads the next block: nothing tells the compiler that ep.i0 and
+// ep.o0 are different buffers, so it may not move a load above the stores before it -- eight serialised round trips to
+// memory per wave and tile.  Here the loads of block i + 1 (the next 16 rows, then the second 64-column group) are
+// issued in program order BEFORE the arithmetic and stores of block i, into registers of their own (16; the accumulators
+// of finished blocks are dead by then).  Same arithmetic on the same values: the caller guarantees that lin and g_lin do
+// not overlap (the whole-net calls: activation buffer and scratch).  This edition always evaluates out = act(lin) again
+// (ep.recompute_out, the default): with the branch that reads out instead in the same code, the wait counts at the point
+// where the two paths meet are those of the reading path, and the look-ahead loads are waited for right after their issue.
+// (Tried and dropped: a second copy of the loop with unconditional stores for waves whose rows all lie inside the matrix,
+// so that the waits need not allow for a store that was branched over -- the freer schedule spills, 64 - 104 bytes.)
+// ---------------------------------------------------------------------------
+template <bool X2, int NRB>
+WIRE_DEVINL void h_gabor_bwd_la(const f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const int M, const int m_w,
+                                const int n_w, const int Nc, const int lane, float& amx) {
+  const int rr = lane & 7, cq = 16 * ((lane >> 3) & 1) + 4 * (lane >> 4);
+  const float w0 = ep.omega, w0l2e = ep.omega * 1.44269502f, ns2l2e = -(ep.scale * ep.scale) * 1.44269502f;
+  const float m2s2 = -2.f * ep.scale * ep.scale;
+  const int ngrp = n_w + 64 >= Nc ? 1 : 2;                        // 64-column groups of this tile inside the matrix
+  auto load_lin = [&](const int i, f32x4 (&u)[2], f32x4 (&v)[2]) {
+    const int G = i / NRB, rb = i % NRB;
+#pragma unroll
+    for (int hr = 0; hr < 2; ++hr) {
+      int row = m_w + 16 * rb + 8 * hr + rr;
+      row = row < M ? row : M - 1;
+      const float* Lp = ep.i0 + (size_t)row * ep.ld0 + n_w + 64 * G + cq;
+      u[hr] = *reinterpret_cast<const f32x4*>(Lp);
+      v[hr] = *reinterpret_cast<const f32x4*>(Lp + 32);
+    }
+  };
+  f32x4 lu[2], lv[2];
+  load_lin(0, lu, lv);
+#pragma unroll
+  for (int i = 0; i < 2 * NRB; ++i) {
+    const int G = i / NRB, rb = i % NRB;
+    if (G >= ngrp) break;
+    const int c0 = n_w + 64 * G + cq;                             // this lane's first re column; im = + 32
+    const int f0 = ((c0 >> 6) << 5) + (c0 & 31);                  // ... = features f0 .. f0 + 3
+    f32x4 nu[2] = {lu[0], lu[1]}, nv[2] = {lv[0], lv[1]};
+    const bool more = i + 1 < 2 * NRB && (i + 1) / NRB < ngrp;
+    if (more) load_lin(i + 1, nu, nv);
+    f32x4 are[2], aim[2], pr[2], pi[2];
+    h_pair_rows(acc[rb][4 * G], acc[rb][4 * G + 1], are[0], are[1]);
+    h_pair_rows(acc[rb][4 * G + 2], acc[rb][4 * G + 3], aim[0], aim[1]);
+#pragma unroll
+    for (int hr = 0; hr < 2; ++hr)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float a, b;
+        gabor_fwd_lean(lu[hr][q], lv[hr][q], w0, w0l2e, ns2l2e, a, b);
+        const bool valid = f0 + q < ep.kvalid;
+        pr[hr][q] = valid ? a : 0.f;
+        pi[hr][q] = valid ? b : 0.f;
+      }
+#pragma unroll
+    for (int hr = 0; hr < 2; ++hr) {
+      const int row = m_w + 16 * rb + 8 * hr + rr;
+      f32x4 gl_re, gl_im;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float gr = are[hr][q], gi = aim[hr][q];
+        const float c_r = __builtin_fmaf(pr[hr][q], gr, pi[hr][q] * gi);
+        const float c_i = __builtin_fmaf(pr[hr][q], gi, -(pi[hr][q] * gr));
+        const float tt = m2s2 * c_r;
+        gl_re[q] = __builtin_fmaf(tt, lu[hr][q], w0 * c_i);
+        gl_im[q] = __builtin_fmaf(tt, lv[hr][q], -(w0 * c_r));
+      }
+      if constexpr (X2) { h_amax4(amx, gl_re); h_amax4(amx, gl_im); }
+      if (row < M) {
+        float* Gp = ep.o0 + (size_t)row * ep.ld0 + c0;
+        *reinterpret_cast<f32x4*>(Gp) = gl_re;
+        *reinterpret_cast<f32x4*>(Gp + 32) = gl_im;
+      }
+    }
+#pragma unroll
+    for (int hr = 0; hr < 2; ++hr) { lu[hr] = nu[hr]; lv[hr] = nv[hr]; }
+  }
+}
+
 // NRB = 16-row blocks of the wave's tile (4: 64 rows per wave, 256-row workgroup tiles; 2: 32 rows per wave, 128-row tiles
 // -- not with the first-layer sums (cr_partial), whose per-tile layout is that of the 256-row tile)
 // EPIX = an EPI_* code, | EPI_CG for the layer-1 data-gradient forms that also write coordinate-gradient partials
-// (ep.cg_partial): a separate instantiation, so the forms without it keep their registers
+// (ep.cg_partial): a separate instantiation, so the forms without it keep their registers; | EPI_D2 or EPI_D3 for the
+// compile-time-width editions of the *_BWD_FIRST forms above; | EPI_LA for the look-ahead edition of GABOR_BWD
 template <int EPIX, bool X2 = false, int NRB = 4>
 WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const int M, const int m_w, const int n_w,
                             const int Nc, const int lane, unsigned char* lds, const int wave, const int rt,
                             const float acc_scale = 1.f) {
-  constexpr int EPI = EPIX & ~EPI_CG;
+  constexpr int EPI = EPIX & ~EPI_FLAGS;
   constexpr bool CG = (EPIX & EPI_CG) != 0;
+  constexpr int DN = (EPIX & EPI_D2) ? 2 : (EPIX & EPI_D3) ? 3 : 0;   // compile-time input width of the *_BWD_FIRST forms
+  constexpr bool LA = (EPIX & EPI_LA) != 0;
+  static_assert(!LA || EPI == EPI_GABOR_BWD, "EPI_LA: the hidden-layer data gradient of the 1-D Gabor net");
+  static_assert(DN == 0 || ((EPI == EPI_GABOR_BWD_FIRST || EPI == EPI_GABOR2D_BWD_FIRST) && NRB == 4),
+                "EPI_D2 / EPI_D3: the layer-1 forms of the complex nets on the 256-row tile");
   const int rr = lane & 7, ch = (lane >> 3) & 1, g = lane >> 4;
   float amx = 0.f;
   if constexpr (X2) {
@@ -338,6 +701,12 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
         }
       }
     }
+  } else if constexpr (EPI == EPI_GABOR_BWD && LA) {
+    h_gabor_bwd_la<X2, NRB>(acc, ep, M, m_w, n_w, Nc, lane, amx);
+  } else if constexpr (EPI == EPI_GABOR_BWD_FIRST && DN != 0) {
+    h_gabor_bwd_first_dn<CG, DN, NRB>(acc, ep, M, m_w, n_w, Nc, lane, lds, wave, rt);
+  } else if constexpr (EPI == EPI_GABOR2D_BWD_FIRST && DN != 0) {
+    h_gabor2d_bwd_first_dn<CG, DN, NRB>(acc, ep, M, m_w, n_w, Nc, lane, lds, wave, rt);
   } else if constexpr (EPI == EPI_GABOR2D_BWD || EPI == EPI_GABOR2D_BWD_FIRST) {
     // C = g_out (re | im pairs, P wide); writes g_(lin | sy) into the 2P-wide row (or the real g_(u | p) of layer 0)
     const float m2s2 = -2.f * ep.scale * ep.scale, w0 = ep.omega;

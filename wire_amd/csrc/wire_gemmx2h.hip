@@ -464,13 +464,33 @@ static hipError_t launchx2h_t(hipStream_t s, const float* A, int lda, const unsi
       return hipErrorInvalidValue;
     }
   }
+  // (the compile-time-width editions of the layer-1 forms and the look-ahead edition of GABOR_BWD exist for the default A
+  //  mode only: the same values either way)
+  constexpr int EPI0 = EPI & ~(EPI_D2 | EPI_D3 | EPI_LA);
   if (knob(K_X2_AMODE) == 2)
     hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 2, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
   else if (knob(K_X2_AMODE) == 1)
-    hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 1, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
+    hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI0, 1, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
   else
-    hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 0, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
+    hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI0, 0, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
   return hipGetLastError();
+}
+// the layer-1 forms of the complex nets: | EPI_CG when the call wants the coordinate-gradient partials, | EPI_D2 / EPI_D3
+// when the route asks for the compile-time input width (ep.first_dn) and D is 2 or 3
+template <int EPI>
+static hipError_t launchx2h_first(hipStream_t s, const float* A, int lda, const unsigned short* Bx2, int64_t M, int Nc,
+                                  int Kd, const GemmEpiParams& ep) {
+  // (wire2d at D = 3: both Linears' parameters of both column groups and 24 coordinates spill 150 - 260 bytes where the
+  //  plain form spills 16 - 124 -- no such edition; its D = 2 edition spills less than the plain form)
+  constexpr int E3 = EPI == EPI_GABOR2D_BWD_FIRST ? 0 : EPI_D3;
+  const int dn = ep.first_dn && ep.coords && (ep.D == 2 || (ep.D == 3 && E3)) ? ep.D : 0;
+  if (ep.cg_partial)
+    return dn == 2 ? launchx2h_t<EPI | EPI_CG | EPI_D2>(s, A, lda, Bx2, M, Nc, Kd, ep)
+         : dn == 3 ? launchx2h_t<EPI | EPI_CG | E3>(s, A, lda, Bx2, M, Nc, Kd, ep)
+                   : launchx2h_t<EPI | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep);
+  return dn == 2 ? launchx2h_t<EPI | EPI_D2>(s, A, lda, Bx2, M, Nc, Kd, ep)
+       : dn == 3 ? launchx2h_t<EPI | E3>(s, A, lda, Bx2, M, Nc, Kd, ep)
+                 : launchx2h_t<EPI>(s, A, lda, Bx2, M, Nc, Kd, ep);
 }
 
 // Bx2: the image of launch_x2_split_b_batch; ep.amax_a / ep.amax_b: the operands' maximum slots
@@ -485,10 +505,10 @@ hipError_t launch_gemmx2h_nt(hipStream_t s, int epi, const float* A, int lda, co
   switch (epi) {
     case EPI_STORE: return launchx2h_t<EPI_STORE>(s, A, lda, Bx2, M, Nc, Kd, ep);
     case EPI_GABOR_FWD: return launchx2h_t<EPI_GABOR_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD: return launchx2h_t<EPI_GABOR_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD_FIRST:
-      return ep.cg_partial ? launchx2h_t<EPI_GABOR_BWD_FIRST | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep)
-                           : launchx2h_t<EPI_GABOR_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep);
+    case EPI_GABOR_BWD:
+      return ep.lookahead && ep.recompute_out ? launchx2h_t<EPI_GABOR_BWD | EPI_LA>(s, A, lda, Bx2, M, Nc, Kd, ep)
+                          : launchx2h_t<EPI_GABOR_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+    case EPI_GABOR_BWD_FIRST: return launchx2h_first<EPI_GABOR_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep);
     case EPI_SIREN_FWD: return launchx2h_t<EPI_SIREN_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
     case EPI_GAUSS_FWD: return launchx2h_t<EPI_GAUSS_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
     case EPI_RELU_FWD: return launchx2h_t<EPI_RELU_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
@@ -511,9 +531,7 @@ hipError_t launch_gemmx2h_nt(hipStream_t s, int epi, const float* A, int lda, co
       if (Nc & 127) return hipErrorInvalidValue;
       return launchx2h_t<EPI_GABOR2D_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
     case EPI_GABOR2D_BWD: return launchx2h_t<EPI_GABOR2D_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD_FIRST:
-      return ep.cg_partial ? launchx2h_t<EPI_GABOR2D_BWD_FIRST | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep)
-                           : launchx2h_t<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep);
+    case EPI_GABOR2D_BWD_FIRST: return launchx2h_first<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep);
     default: return hipErrorInvalidValue;
   }
 }

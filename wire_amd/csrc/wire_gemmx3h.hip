@@ -234,6 +234,24 @@ static hipError_t launchx3h_t(hipStream_t s, const float* A, int lda, const unsi
   return hipGetLastError();
 }
 
+// the layer-1 forms of the complex nets: | EPI_CG when the call wants the coordinate-gradient partials, | EPI_D2 / EPI_D3
+// when the route asks for the compile-time input width (ep.first_dn) and D is 2 or 3
+template <int EPI>
+static hipError_t launchx3h_first(hipStream_t s, const float* A, int lda, const unsigned short* Bu, int64_t M, int Nc,
+                                  int Kd, const GemmEpiParams& ep) {
+  // (wire2d at D = 3: both Linears' parameters of both column groups and 24 coordinates spill 150 - 260 bytes where the
+  //  plain form spills 16 - 124 -- no such edition; its D = 2 edition spills less than the plain form)
+  constexpr int E3 = EPI == EPI_GABOR2D_BWD_FIRST ? 0 : EPI_D3;
+  const int dn = ep.first_dn && ep.coords && (ep.D == 2 || (ep.D == 3 && E3)) ? ep.D : 0;
+  if (ep.cg_partial)
+    return dn == 2 ? launchx3h_t<EPI | EPI_CG | EPI_D2>(s, A, lda, Bu, M, Nc, Kd, ep)
+         : dn == 3 ? launchx3h_t<EPI | EPI_CG | E3>(s, A, lda, Bu, M, Nc, Kd, ep)
+                   : launchx3h_t<EPI | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep);
+  return dn == 2 ? launchx3h_t<EPI | EPI_D2>(s, A, lda, Bu, M, Nc, Kd, ep)
+       : dn == 3 ? launchx3h_t<EPI | E3>(s, A, lda, Bu, M, Nc, Kd, ep)
+                 : launchx3h_t<EPI>(s, A, lda, Bu, M, Nc, Kd, ep);
+}
+
 bool gemmx3h_handles(int epi, int64_t M) {
   const int h16 = knob(K_X3_H16);
   if (!h16 || M < 4096) return false;
@@ -255,10 +273,10 @@ hipError_t launch_gemmx3h_nt(hipStream_t s, int epi, const float* A, int lda, co
   switch (epi) {
     case EPI_STORE: return launchx3h_t<EPI_STORE>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_GABOR_FWD: return launchx3h_t<EPI_GABOR_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD: return launchx3h_t<EPI_GABOR_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD_FIRST:
-      return ep.cg_partial ? launchx3h_t<EPI_GABOR_BWD_FIRST | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
-                           : launchx3h_t<EPI_GABOR_BWD_FIRST>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_GABOR_BWD:
+      return ep.lookahead && ep.recompute_out ? launchx3h_t<EPI_GABOR_BWD | EPI_LA>(s, A, lda, Bu, M, Nc, Kd, ep)
+                          : launchx3h_t<EPI_GABOR_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_GABOR_BWD_FIRST: return launchx3h_first<EPI_GABOR_BWD_FIRST>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_SIREN_FWD: return launchx3h_t<EPI_SIREN_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_GAUSS_FWD: return launchx3h_t<EPI_GAUSS_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_RELU_FWD: return launchx3h_t<EPI_RELU_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
@@ -281,9 +299,7 @@ hipError_t launch_gemmx3h_nt(hipStream_t s, int epi, const float* A, int lda, co
       if (Nc & 127) return hipErrorInvalidValue;
       return launchx3h_t<EPI_GABOR2D_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_GABOR2D_BWD: return launchx3h_t<EPI_GABOR2D_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD_FIRST:
-      return ep.cg_partial ? launchx3h_t<EPI_GABOR2D_BWD_FIRST | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
-                           : launchx3h_t<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_GABOR2D_BWD_FIRST: return launchx3h_first<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bu, M, Nc, Kd, ep);
     default: return hipErrorInvalidValue;
   }
 }

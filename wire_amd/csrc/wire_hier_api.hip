@@ -273,7 +273,7 @@ int hier_bwd_core(void* stream, const Plan& p, const Route& r, const float* pack
 Route hier_route(const Plan& p, int64_t n, RouteMode mode) {
   Route r = make_route(p, n, mode);
   r.fused_fwd = r.fuse = r.fused_train = r.fused_final = r.chain = r.rstore = r.skip_out_L = false;
-  r.first_sums = r.cg_epi = false;
+  r.first_sums = r.cg_epi = r.first_dn = r.bwd_lookahead = false;
   r.wb_l0 = p.L + 1; r.wb_n = 0;
   for (float& v : r.out_scale) v = 0.f;
   return r;

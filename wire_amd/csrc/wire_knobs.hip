@@ -57,6 +57,17 @@ constexpr KnobDef kKnobs[] = {
     // on the 16 x 16 x 32 kernels the last data-gradient GEMM's epilogue forms the first layer's gradient sums itself
     // instead of storing g_u for a separate reduction pass
     flag_knob(K_FIRST_SUMS, "first_sums", "WIRE_FIRST_SUMS", 1),
+    // wire / wire2d, that epilogue at D = 2 or 3: the edition with D a compile-time constant (no zero terms in the chains
+    // over the input width), the tile's coordinates loaded once per wave and the first layer's parameters of both column
+    // groups loaded ahead of the arithmetic (wire_gemmh_epi.h: h_gabor_bwd_first_dn).  0 = the plain edition; same bits.
+    // Headline step, one process, alternating blocks (profiles/r05_dgrad_events_ab.txt): the four data-gradient launches
+    // 1.829 -> 1.772 ms by events
+    flag_knob(K_FIRST_DN, "first_dn", "WIRE_FIRST_DN", 1),
+    // wire, the hidden layers' data-gradient epilogue on the 16 x 16 x 32 kernels: lin of the next 16-row block is loaded
+    // ahead of the current block's arithmetic and stores (wire_gemmh_epi.h: h_gabor_bwd_la).  0 = load, compute, store per
+    // block; same bits.  The four data-gradient launches 1.848 -> 1.787 ms by events; both knobs: step 5.585 -> 5.503 ms
+    // (profiles/r05_dgrad_events_ab.txt, r05_knob_ab.txt)
+    flag_knob(K_BWD_LOOKAHEAD, "bwd_lookahead", "WIRE_BWD_LOOKAHEAD", 1),
     // with the fused training forward + data-gradient chain of a sine / Gaussian net: store r = c lin and no out_l
     flag_knob(K_FUSED_RSTORE, "fused_rstore", "WIRE_FUSED_RSTORE", 1),
     // behind the data-gradient chain: the weight gradients of layers 2 .. L as one launch

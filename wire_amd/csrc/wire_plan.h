@@ -102,7 +102,7 @@ struct Plan {
   std::vector<int64_t> off_fwd, off_dg, off_bias, off_fwd_x3, off_dg_x3, off_fwd_3m, off_dg_3m, off_fwd_x2, off_dg_x2;
   int64_t off_wf, off_bf, off_first, off_wamax, total_packed;   // off_wamax: max-|weight| slots, WIRE_AMAX_SLOTS per layer
   int64_t off_fx;    // k-permuted 2 x fp16 images of the hidden layers for the fused forward (wire_fused.hip), -1 = no such shape
-  bool k_split_out, k_recompute_out, k_first_sums, k_rstore, k_wgrad_batch, k_fused_fwd, k_fused_train, k_fused_bwd, k_fused_final,
+  bool k_split_out, k_recompute_out, k_first_sums, k_first_dn, k_bwd_lookahead, k_rstore, k_wgrad_batch, k_fused_fwd, k_fused_train, k_fused_bwd, k_fused_final,
        k_fused_train_p384;
   int64_t off_fxd;   // the same of the TRANSPOSED weights of layers L .. 1 (in that order) for the data-gradient chain, -1 = none
   std::vector<int64_t> tfloats;
@@ -215,6 +215,8 @@ struct Route {
   bool recompute_out0;    //   ... and wire's first-layer epilogue out_0 (first_fwd_kernel's own form, the same bits)
   bool first_sums;        // the layer-1 data-gradient epilogue sums the first layer's weight / bias gradient itself
   bool cg_epi;            //   ... and can form the per-row coordinate-gradient partials
+  bool bwd_lookahead;     // wire: the data-gradient epilogue of layers l >= 2 in its look-ahead edition ("bwd_lookahead")
+  bool first_dn;          // wire / wire2d: that epilogue in its compile-time-width edition where D is 2 or 3 ("first_dn")
   int wb_l0, wb_n, wb_S;  // weight-gradient batch: layers wb_l0 .. L, wb_n members of wb_S splits (wb_l0 = L + 1: none)
   float act_scale;        // split scale of the fused forward's activations, 0 = none known
   float out_scale[65];    // pre-split scale of out_l, l = 0 .. L (L <= 64); 0 = plain fp32

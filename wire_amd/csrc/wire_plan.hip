@@ -109,7 +109,8 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   // wire_tune_set from another thread in the middle of wire_train_fwd_bwd must not split a call between two formats
   // (the forward and the backward of the autograd path are separate calls: knobs must not change between them)
   p.k_split_out = knob(K_SPLIT_OUT) != 0; p.k_recompute_out = knob(K_RECOMPUTE_OUT) != 0;
-  p.k_first_sums = knob(K_FIRST_SUMS) != 0; p.k_rstore = knob(K_FUSED_RSTORE) != 0; p.k_wgrad_batch = knob(K_WGRAD_BATCH) != 0;
+  p.k_first_sums = knob(K_FIRST_SUMS) != 0; p.k_first_dn = knob(K_FIRST_DN) != 0;
+  p.k_bwd_lookahead = knob(K_BWD_LOOKAHEAD) != 0; p.k_rstore = knob(K_FUSED_RSTORE) != 0; p.k_wgrad_batch = knob(K_WGRAD_BATCH) != 0;
   p.k_fused_fwd = knob(K_FUSED_FWD) != 0; p.k_fused_train = p.k_fused_fwd && knob(K_FUSED_TRAIN);
   p.k_fused_train_p384 = knob(K_FUSED_TRAIN_P384) != 0;
   p.k_fused_bwd = p.k_fused_train && knob(K_FUSED_BWD); p.k_fused_final = p.k_fused_train && knob(K_FUSED_FINAL);
@@ -424,6 +425,8 @@ Route make_route(const Plan& p, int64_t n, RouteMode mode) {
   // (the multi-pass net: its layer-1 data gradient runs once per pass, its first-layer sums over all passes at once)
   r.cg_epi = h16_1 && !p.first_gemm && p.L >= 1 && !p.m2;
   r.first_sums = r.cg_epi && p.k_first_sums;
+  r.first_dn = h16_1 && p.cplx && p.k_first_dn;
+  r.bwd_lookahead = p.kind == WIRE_KIND_WIRE && p.x3 && gemmx3_nt_is_h16(EPI_GABOR_BWD, n) && p.k_bwd_lookahead;
   r.recompute_out0 = h16_1 && p.kind == WIRE_KIND_WIRE && p.k_recompute_out;
   // behind the chain every g_lin_l exists before the first weight gradient starts: those of layers 2 .. L (same shape,
   // operands a fixed step apart) run as ONE launch, each member accumulating L - 1 times the rows into a third of the
