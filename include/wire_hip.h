@@ -88,11 +88,16 @@ typedef enum wire_kind {
 /* Architecture + hyper-parameters of one INR (modules/wire.py:96-159). */
 typedef struct wire_net_desc {
   int32_t kind;            /* wire_kind                                           */
-  int32_t in_features;     /* D: coordinate dims (2 or 3)                         */
+  int32_t in_features;     /* D: coordinate dims, 1..4                            */
   int32_t width;           /* K: features per hidden layer AFTER the reference's
                               own rescale (int(h/sqrt2) wire, int(h/2) wire2d)   */
   int32_t hidden_layers;   /* L                                                   */
-  int32_t out_features;    /* O (<= 8)                                            */
+  int32_t out_features;    /* O, 1..8, and O x P <= 16384 with P the padded row
+                              width (roundup(2K, 64) wire / wire2d, roundup(K, 64)
+                              otherwise): the final linear's forward keeps W_f
+                              [O][P] in the 64 KB of LDS a launch gets.  A wider
+                              net is WIRE_ERR_ARG from every call that takes the
+                              descriptor, the size queries included            */
   int32_t posenc_freqs;    /* relu only: PosEncoding.num_frequencies, 0 = off     */
   float first_omega0;      /* omega of net[0] (bspline: carried, unused)          */
   float hidden_omega0;     /* omega of net[1..L] (bspline: carried, unused)       */
@@ -197,7 +202,10 @@ int wire_mlp_bwd(void* stream, const wire_net_desc* d, const float* packed,
  * linear backward and the last layer's activation gradient are ONE kernel (a single pass
  * over out_L / lin_L, final_fused_kernel); nets without a hidden layer or with O > 4 run
  * wire_mlp_fwd + wire_mse_grad + wire_mlp_bwd internally.
- * y [n][O] and g_y [n][O] are outputs; partial >= 4096 floats.                 */
+ * y [n][O] is an output; g_y [n][O] is caller scratch that receives dL/dy on the
+ * unfused sequence and for the kinds whose loss is not in final_fused_kernel
+ * (bspline_m2, bspline_hier, mfn) -- the fused final stage keeps dL/dy in registers
+ * and leaves g_y untouched; partial >= 4096 floats.                              */
 int wire_train_fwd_bwd(void* stream, const wire_net_desc* d, const float* packed,
                        const float* coords, int64_t n, const float* target,
                        const int64_t* idx, int64_t first, float weight, float* y,
@@ -256,7 +264,9 @@ int wire_gabor_bwd(void* stream, const void* g_act, const void* x,
 int wire_gabor_hparam_grad(void* stream, const void* g_act, const void* x, const void* W, const void* b,
                            float omega0, float scale0, int64_t n, int in_features, int out_features,
                            int is_first, float* out2, void* ws, int64_t ws_bytes);
-/* final nn.Linear(K,O,cfloat) + .real (modules/wire.py:156-157,164-165)    */
+/* final nn.Linear(K,O,cfloat) + .real (modules/wire.py:156-157,164-165);
+ * wire_final_fwd: out_features x roundup(2 in_features, 64) <= 16384, as for a
+ * descriptor (WIRE_ERR_ARG before any HIP call otherwise)                   */
 int wire_final_fwd(void* stream, const void* z, const void* Wf, const void* bf,
                    int64_t n, int in_features, int out_features, float* y,
                    void* ws, int64_t ws_bytes);

@@ -267,6 +267,55 @@ def _errs(label, got, ref32, ref64):
     within_ref(relmax(got, ref64), relmax(ref32, ref64), label)
 
 
+def abi_names(model):
+    """state_dict key of every tensor of model.param_tensors(), in the ABI's order (the heads of a hierarchical net, which
+    are in no state_dict, as "linears.{s}.weight" / "linears.{s}.bias")."""
+    by_id = {id(p): k for k, p in model.named_parameters()}
+    for s, lin in enumerate(getattr(model, "linears", [])):
+        by_id[id(lin.weight)], by_id[id(lin.bias)] = f"linears.{s}.weight", f"linears.{s}.bias"
+    return [by_id[id(t)] for t in model.param_tensors()]
+
+
+def abi_train_step(model, coords, table, idx=None, first=0, weight=1.0):
+    """wire_train_fwd_bwd through ctypes on explicit coordinates (FusedTrainer builds 2- and 3-axis grids only; modelled on
+    test_gpu_coords_grad._abi_forward).  coords [n][D]; ``table`` [T][O] holds the targets: row r trains against
+    table[idx[r]], or table[first + r] when idx is None.  Every output buffer is prefilled with NaN.  Returns a dict: y and
+    g_y [n][O], loss, rec [T][O] (NaN where the scatter wrote nothing), grads = {state_dict key: float64 array in the
+    native layout, complex as (re, im) pairs} and act / desc / lib for wire_act_out_offset."""
+    from wire_amd import _lib
+    L = _lib.lib()
+    dev = next(model.parameters()).device
+    desc = model.net_desc()
+    dp = C.byref(desc)
+    f32 = dict(dtype=torch.float32, device=dev)
+    x = torch.as_tensor(coords).to(**f32).contiguous()
+    tab = torch.as_tensor(table).to(**f32).contiguous()
+    n, O = x.shape[0], desc.out_features
+    assert x.shape[1] == desc.in_features and tab.shape[1] == O
+    ix = None if idx is None else torch.as_tensor(idx).to(device=dev, dtype=torch.int64).contiguous()
+    assert (int(ix.max()) if ix is not None else first + n - 1) < tab.shape[0] and first >= 0
+    names = abi_names(model)
+    nat = [p.detach().contiguous() for p in model.param_tensors()]
+    s = torch.cuda.current_stream(dev).cuda_stream
+    packed = torch.empty(L.wire_packed_floats(dp), **f32)
+    _lib.check(L.wire_pack_params(s, dp, _lib.ptr_array([p.data_ptr() for p in nat]), packed.data_ptr()), "pack")
+    ab = _lib.check(L.wire_act_bytes(dp, n, 1), "wire_act_bytes")
+    sb = _lib.check(L.wire_bwd_scratch_bytes(dp, n), "wire_bwd_scratch_bytes")
+    act = torch.empty(ab, dtype=torch.uint8, device=dev)
+    scr = torch.empty(sb, dtype=torch.uint8, device=dev)
+    nan = float("nan")
+    y, gy, rec = torch.full((n, O), nan, **f32), torch.full((n, O), nan, **f32), torch.full_like(tab, nan)
+    loss, part = torch.full((1,), nan, **f32), torch.empty(4096, **f32)
+    grads = [torch.full_like(torch.view_as_real(p) if p.is_complex() else p, nan) for p in nat]
+    _lib.check(L.wire_train_fwd_bwd(s, dp, packed.data_ptr(), x.data_ptr(), n, tab.data_ptr(),
+                                    None if ix is None else ix.data_ptr(), int(first), float(weight), y.data_ptr(),
+                                    gy.data_ptr(), loss.data_ptr(), rec.data_ptr(), part.data_ptr(), act.data_ptr(), ab,
+                                    scr.data_ptr(), sb, _lib.ptr_array([g.data_ptr() for g in grads])), "train_fwd_bwd")
+    torch.cuda.synchronize()
+    return dict(y=y.cpu().numpy(), gy=gy.cpu().numpy(), loss=float(loss.item()), rec=rec.cpu().numpy(),
+                grads={k: g.cpu().numpy().astype(np.float64) for k, g in zip(names, grads)}, act=act, desc=desc, lib=L)
+
+
 def _prof(fn):
     """Launches per profiler class (wire_prof_read) of one call of fn."""
     from wire_amd import _lib

@@ -136,10 +136,10 @@ def _layerwise_relu_masks(model, coords):
     return out
 
 
-def check_case(label, kind, D, hf, L, n, kw, pos_encode=False, outermost_linear=True, seed=0):
-    model = _model(kind, D, hf, L, seed=seed, pos_encode=pos_encode, outermost_linear=outermost_linear, **kw)
+def check_case(label, kind, D, hf, L, n, kw, pos_encode=False, outermost_linear=True, seed=0, O=3):
+    model = _model(kind, D, hf, L, O=O, seed=seed, pos_encode=pos_encode, outermost_linear=outermost_linear, **kw)
     nf = model.positional_encoding.num_frequencies if pos_encode else None
-    coords, w = _coords(n, D), _weights(n, 3)
+    coords, w = _coords(n, D), _weights(n, O)
     g = build_coords_grad(model, coords, w)
     masks = None
     if kind == "relu":

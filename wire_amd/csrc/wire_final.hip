@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void final_fwd_kernel(const float* __restrict_
 hipError_t launch_final_fwd(hipStream_t s, const float* z, int64_t n, int P, int O,
                             const float* wf, const float* bfr, float* y) {
   if (n <= 0) return hipSuccess;
-  if (O > WIRE_MAXO || (P & 3)) return hipErrorInvalidValue;
+  if (O > WIRE_MAXO || (P & 3) || (int64_t)O * P > WIRE_FINAL_MAX_OP) return hipErrorInvalidValue;
   unsigned grid = cdiv(n, 4);
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(final_fwd_kernel, dim3(grid), dim3(256), (size_t)O * P * sizeof(float), s, z,

@@ -310,6 +310,10 @@ extern "C" int wire_final_fwd(void* stream, const void* z, const void* Wf, const
                               int64_t ws_bytes) {
   if (n < 0 || in_features < 1 || out_features < 1 || out_features > 8 || !z || !Wf || !bf || !y || !ws)
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_final_fwd");
+  // final_fwd_kernel stages W_f [O][P] in the 64 KB of dynamic LDS a launch gets (make_plan refuses the same nets)
+  if ((int64_t)out_features * rup64(2 * (int64_t)in_features, 64) > WIRE_FINAL_MAX_OP)
+    return fail(WIRE_ERR_ARG, "out_features %d x padded row width %lld > %d (the final layer's weights in 64 KB)",
+                out_features, (long long)rup64(2 * (int64_t)in_features, 64), WIRE_FINAL_MAX_OP);
   if (n == 0) return WIRE_OK;
   const LayerWs w = layer_ws(n, in_features, out_features);
   if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");

@@ -59,9 +59,6 @@ int make_plan(const wire_net_desc* d, Plan& p) {
                                            (int)WIRE_KIND_BSPLINE_HIER);
     if (p.HL == 1 && p.HS > 1)
       return fail(WIRE_ERR_ARG, "hidden_layers 1 with %d scales: a later stage runs its layers 0, 1 and 2", p.HS);
-    if (p.O >= 1 && p.O <= 8 && p.K >= 1 && p.K <= 4096 && (int64_t)p.O * rup(p.K, 64) > 16384)
-      return fail(WIRE_ERR_ARG, "out_features %d x padded width %d > 16384 (kind %d)", p.O, rup(p.K, 64),
-                  (int)WIRE_KIND_BSPLINE_HIER);
     p.hier = true;
     p.kind = WIRE_KIND_BSPLINE;
     p.s = m->scales[0];
@@ -99,6 +96,10 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   if (p.F < 0 || (p.F > 0 && p.kind != WIRE_KIND_RELU)) return fail(WIRE_ERR_ARG, "posenc only with relu");
   p.cplx = (p.kind == WIRE_KIND_WIRE || p.kind == WIRE_KIND_WIRE2D);
   p.P = p.cplx ? rup(2 * p.K, 64) : rup(p.K, 64);
+  // final_fwd_kernel (wire_final.hip) stages W_f as [O][P] floats in the 64 KB of dynamic LDS a launch gets
+  if ((int64_t)p.O * p.P > WIRE_FINAL_MAX_OP)
+    return fail(WIRE_ERR_ARG, "out_features %d x padded row width %d > %d (the final layer's weights in 64 KB)", p.O, p.P,
+                WIRE_FINAL_MAX_OP);
   p.Pl = (p.kind == WIRE_KIND_WIRE2D) ? 2 * p.P : p.P;
   p.ldu = p.P / 2;
   p.Kp = p.P / 2;

@@ -10,6 +10,9 @@
 enum { NK_WIRE = 0, NK_WIRE2D = 1, NK_SIREN = 2, NK_GAUSS = 3, NK_RELU = 4, NK_BSPLINE = 5 };
 
 #define WIRE_MAXO 8        // outputs of the final linear (the point kernels keep one accumulator per output in registers)
+// final_fwd_kernel keeps W_f [O][P] in dynamic LDS and a launch gets 64 KB of it without an opt-in: O x P floats at most.
+// make_plan and wire_final_fwd refuse a wider net (WIRE_ERR_ARG) before anything is launched.
+#define WIRE_FINAL_MAX_OP 16384
 // rows of one block of the final linear's backward: every kernel that writes part_w / part_b for launch_final_reduce
 // (final_bwd, final_fused, hier_head_bwd, mfn_final_bwd) uses this layout, final_bwd_blocks(n) blocks of it
 #define WIRE_FB_ROWS 256
