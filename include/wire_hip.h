@@ -340,6 +340,38 @@ int wire_avgpool_mse_grad_frames(void* stream, const float* y, int B, int H, int
  * coords: [B][H*W][2].  B, H or W < 1 or a NULL pointer: WIRE_ERR_ARG before any HIP call.               */
 int wire_affine_coords(void* stream, const double* mats, int B, int H, int W, float* coords);
 
+/* Video compressive sensing (per-pixel coded exposure, modules/lin_inverse.py:42-95): the loss of a video estimate
+ * against a coded video, fused with its backward.  The T frames of pixel p are multiplied by that pixel's mask and
+ * summed in groups of nframes (lin_inverse.py:79-84) into C = ceil(T / nframes) coded frames; nframes > T gives one.
+ * dup_last = 1 keeps a property of the reference: its trailing `if idx < video_ten.shape[1]` (lin_inverse.py:86-91) is
+ * always true, so the last group is appended a second time, the coded video has C + 1 frames with frame C equal to
+ * frame C - 1, and an MSE against it weights the last group twice.  dup_last = 0 is the plain operator.  With
+ * C' = C + dup_last and count = C' NP O:
+ *   est[c][p][o] = sum_{k in group c} mask[p][k] y[p T + k][o]          (est[C] = est[C-1] when dup_last)
+ *   d = est - gt;   loss = sum d^2 / count
+ *   g_y[p T + k][o] = mask[p][k] 2 / count (d[c(k)][p][o] + (dup_last and c(k) == C - 1 ? d[C][p][o] : 0))
+ * Layout: the row order of the 3-D grid (row (i W + j) T + k), so a pixel's T frames are T O consecutive floats.
+ * y / g_y are LOCAL to the slab of pixels [p0, p0 + n_pix): [n_pix T][O].  mask [NP][T] (any float values, shared by
+ * the channels; this is the (H, W, totalframes) array of get_video_coding_frames as it lies in memory, NP = H W),
+ * gt [C'][NP][O] and est [C'][NP][O] (optional, NULL = not wanted) are whole-video arrays indexed by the global pixel.
+ * loss_out[0] is overwritten with THIS SLAB's sum d^2 / count (the global count): the losses of slabs that cover the
+ * video add up to the loss.  Every element of g_y is written exactly once.  No atomics, every sum in a fixed order:
+ * the same call gives the same bits.  partial: >= 1024 floats of scratch.
+ * T, O, nframes, n_pix or NP < 1, p0 < 0, p0 + n_pix > NP, dup_last not 0 / 1, or a NULL pointer other than est:
+ * WIRE_ERR_ARG before any HIP call.                                                                          */
+int wire_coded_mse_grad(void* stream, const float* y, int64_t p0, int64_t n_pix, int64_t NP, int T, int O,
+                        int nframes, int dup_last, const float* mask, const float* gt, float* g_y,
+                        float* est, float* loss_out, float* partial);
+/* The same operator in the reference's own layout, video2codedvideo of modules/lin_inverse.py:65-95 on one
+ * (T, H, W) video: video [T][NP], masks [T][NP] -> coded [C'][NP], and its adjoint
+ *   g_video[t][p] = masks[t][p] (g_coded[c(t)][p] + (dup_last and c(t) == C - 1 ? g_coded[C][p] : 0)).
+ * T, NP or nframes < 1, dup_last not 0 / 1, a NULL pointer, or more than 2^31 - 1 blocks of 256 values:
+ * WIRE_ERR_ARG before any HIP call.                                                                          */
+int wire_coded_fwd(void* stream, const float* video, const float* masks, int T, int64_t NP, int nframes,
+                   int dup_last, float* coded);
+int wire_coded_bwd(void* stream, const float* g_coded, const float* masks, int T, int64_t NP, int nframes,
+                   int dup_last, float* g_video);
+
 /* torch.optim.Adam single step over a flat fp32 buffer (complex tensors as
  * real pairs; wire_image_denoise.py:123-125).  step is 1-based.            */
 int wire_adam_step_flat(void* stream, float* param, const float* grad,

@@ -54,6 +54,38 @@ extern "C" int wire_avgpool_mse_grad_frames(void* stream, const float* y, int B,
                                         partial));
   return WIRE_OK;
 }
+extern "C" int wire_coded_mse_grad(void* stream, const float* y, int64_t p0, int64_t n_pix, int64_t NP, int T, int O,
+                                   int nframes, int dup_last, const float* mask, const float* gt, float* g_y,
+                                   float* est, float* loss_out, float* partial) {
+  if (T < 1 || O < 1 || nframes < 1 || n_pix < 1 || NP < 1 || p0 < 0 || n_pix > NP || p0 > NP - n_pix ||
+      (dup_last != 0 && dup_last != 1) || !y || !mask || !gt || !g_y || !loss_out || !partial)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_coded_mse_grad");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_coded_mse_grad((hipStream_t)stream, y, p0, n_pix, NP, T, O, nframes, dup_last, mask, gt, g_y, est,
+                               loss_out, partial));
+  return WIRE_OK;
+}
+// (one thread per value in a 1-D grid of 256-thread blocks)
+static bool coded_shape_ok(int T, int64_t NP, int nframes, int dup_last) {
+  return T >= 1 && NP >= 1 && nframes >= 1 && (dup_last == 0 || dup_last == 1) &&
+         NP <= ((int64_t)0x7fffffff * 256) / ((int64_t)T + 1);
+}
+extern "C" int wire_coded_fwd(void* stream, const float* video, const float* masks, int T, int64_t NP, int nframes,
+                              int dup_last, float* coded) {
+  if (!coded_shape_ok(T, NP, nframes, dup_last) || !video || !masks || !coded)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_coded_fwd");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_coded_fwd((hipStream_t)stream, video, masks, T, NP, nframes, dup_last, coded));
+  return WIRE_OK;
+}
+extern "C" int wire_coded_bwd(void* stream, const float* g_coded, const float* masks, int T, int64_t NP, int nframes,
+                              int dup_last, float* g_video) {
+  if (!coded_shape_ok(T, NP, nframes, dup_last) || !g_coded || !masks || !g_video)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_coded_bwd");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_coded_bwd((hipStream_t)stream, g_coded, masks, T, NP, nframes, dup_last, g_video));
+  return WIRE_OK;
+}
 extern "C" int wire_affine_coords(void* stream, const double* mats, int B, int H, int W, float* coords) {
   if (B < 1 || H < 1 || W < 1 || !mats || !coords) return fail(WIRE_ERR_ARG, "bad argument to wire_affine_coords");
   ProfScope ps((hipStream_t)stream, 3, 0);

@@ -194,6 +194,17 @@ hipError_t launch_avgpool_mse_grad(hipStream_t s, const float* y, int H, int W, 
 hipError_t launch_avgpool_mse_grad_frames(hipStream_t s, const float* y, int B, int H, int W, int O, int scale,
                                           const float* gt_lr, const float* mask, float* g_y, float* rec_lr,
                                           float* loss_out, float* partial);
+// video compressive sensing loss (modules/lin_inverse.py:42-95): y, g_y [n_pix T][O], the rows of pixels p0 .. p0 + n_pix
+// of NP; mask [NP][T], gt / est (optional) [C'][NP][O], C' = ceil(T / nframes) + dup_last; loss_out = this slab's
+// sum d^2 / (C' NP O); every element of g_y is written; partial >= 1024 floats
+hipError_t launch_coded_mse_grad(hipStream_t s, const float* y, int64_t p0, int64_t n_pix, int64_t NP, int T, int O,
+                                 int nframes, int dup_last, const float* mask, const float* gt, float* g_y, float* est,
+                                 float* loss_out, float* partial);
+// the same operator and its adjoint on frame-major tensors: video / masks / g_video [T][NP], coded / g_coded [C'][NP]
+hipError_t launch_coded_fwd(hipStream_t s, const float* video, const float* masks, int T, int64_t NP, int nframes,
+                            int dup_last, float* coded);
+hipError_t launch_coded_bwd(hipStream_t s, const float* g_coded, const float* masks, int T, int64_t NP, int nframes,
+                            int dup_last, float* g_video);
 // coords [B][H W][2] = the grid moved by frame f's 2 x 3 matrix mats[f] (device, fp64), normalised as 2 X / W - 1
 // (modules/motion.py:284-318 at scale = 1)
 hipError_t launch_affine_coords(hipStream_t s, const double* mats, int B, int H, int W, float* coords);

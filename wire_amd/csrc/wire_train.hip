@@ -365,6 +365,201 @@ hipError_t launch_avgpool_mse_grad_frames(hipStream_t s, const float* y, int B, 
   return hipGetLastError();
 }
 
+// ===========================================================================
+// video compressive sensing (modules/lin_inverse.py:42-95, the coded exposure of Hitomi et al.): the T frames of a
+// pixel are multiplied by the pixel's mask and summed in groups of `nframes` into C = ceil(T / nframes) coded frames;
+// with dup_last the last group is stored a second time (frame C == frame C - 1, as the reference's trailing
+// `if idx < video_ten.shape[1]` does), so an MSE over the C' = C + dup_last frames weights it twice:
+//   est[c][p][o] = sum_{k in chunk c} m[p][k] y[p T + k][o],   d = est - gt,   loss = sum d^2 / (C' NP O)
+//   dL/dy[p T + k][o] = m[p][k] 2 / (C' NP O) (d[c(k)][p][o] + (dup_last and c(k) == C - 1 ? d[C][p][o] : 0))
+// In the row order of the 3-D grid (idx = (i W + j) T + k) a pixel's T rows are T O consecutive floats of y and its T
+// mask values are consecutive too.  A block takes a tile of whole pixels, a contiguous run of y: lanes read CONSECUTIVE
+// floats, the masked products meet in LDS (pixel stride padded to an odd number of floats, so that the lanes of the
+// chunk sums, one pixel apart, fall into different banks), one thread per (chunk, pixel, channel) adds its frames in
+// order -- for a fixed chunk consecutive threads touch consecutive floats of gt / est -- and the gradient leaves LDS
+// with lanes writing consecutive floats again.  y / g_y are local to the slab of pixels [p0, p0 + n_pix); mask, gt and
+// est are indexed by the global pixel.  Every element of g_y is written exactly once.  No atomics: per-block loss
+// partials in a grid that depends on the shape alone, summed by mse_final_kernel.  A pixel span wider than the LDS
+// tile (T O > CV_CAP floats) takes the direct kernel below instead.
+// ===========================================================================
+#define CV_CAP 1024
+__global__ __launch_bounds__(256) void coded_mse_grad_kernel(const float* __restrict__ y, long long p0,
+                                                             long long n_pix, long long NP, int T, int O, int nf,
+                                                             int C, int dup, int TP, int PS,
+                                                             const float* __restrict__ mask,
+                                                             const float* __restrict__ gt, float gscale,
+                                                             float* __restrict__ g_y, float* __restrict__ est,
+                                                             float* __restrict__ partial) {
+  __shared__ float ym[CV_CAP], ms[CV_CAP], gd[CV_CAP], red[256];
+  const int pf = T * O;                                        // floats of a pixel (PS = pf or pf + 1, odd)
+  const long long njobs = (n_pix + TP - 1) / TP;
+  const long long cstride = NP * O;                            // floats of a coded frame
+  const int tid = threadIdx.x;
+  float acc = 0.f;
+  for (long long job = blockIdx.x; job < njobs; job += gridDim.x) {
+    const long long l0 = job * TP;                             // first pixel of the tile, slab-local
+    const int np = n_pix - l0 < TP ? (int)(n_pix - l0) : TP;
+    const int nx = np * pf;                                    // floats of the tile (np * PS <= CV_CAP)
+    const long long base = l0 * pf;
+    const float* mrow = mask + (p0 + l0) * T;
+    for (int x = tid; x < nx; x += 256) {
+      const int pl = x / pf, r = x - pl * pf;
+      const float m = mrow[pl * T + r / O];
+      ms[pl * PS + r] = m;
+      ym[pl * PS + r] = m * y[base + x];
+    }
+    __syncthreads();
+    const int ne = np * O;                                     // coded values of the tile in one coded frame
+    const long long cbase = (p0 + l0) * O;
+    for (int e = tid; e < C * ne; e += 256) {
+      const int c = e / ne, r = e - c * ne;
+      const int pl = r / O, o = r - pl * O;
+      const int k0 = c * nf, k1 = k0 + nf < T ? k0 + nf : T;
+      const float* src = ym + pl * PS + o;
+      float s = 0.f;
+      for (int k = k0; k < k1; ++k) s += src[k * O];
+      const long long ci = c * cstride + cbase + r;
+      float d = s - gt[ci];
+      if (est) est[ci] = s;
+      acc = __builtin_fmaf(d, d, acc);
+      if (dup && c == C - 1) {
+        const float d2 = s - gt[ci + cstride];
+        if (est) est[ci + cstride] = s;
+        acc = __builtin_fmaf(d2, d2, acc);
+        d += d2;
+      }
+      gd[e] = gscale * d;
+    }
+    __syncthreads();
+    for (int x = tid; x < nx; x += 256) {
+      const int pl = x / pf, r = x - pl * pf;
+      const int k = r / O, o = r - k * O;
+      g_y[base + x] = ms[pl * PS + r] * gd[(k / nf) * ne + pl * O + o];
+    }
+    __syncthreads();                                           // the next tile overwrites ms
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (tid < sft) red[tid] += red[tid + sft];
+    __syncthreads();
+  }
+  if (tid == 0) partial[blockIdx.x] = red[0];
+}
+// T * O > CV_CAP: one thread per (pixel, channel) walks its own frames, chunk by chunk
+__global__ __launch_bounds__(256) void coded_mse_grad_direct_kernel(const float* __restrict__ y, long long p0,
+                                                                    long long n_pix, long long NP, int T, int O,
+                                                                    int nf, int C, int dup,
+                                                                    const float* __restrict__ mask,
+                                                                    const float* __restrict__ gt, float gscale,
+                                                                    float* __restrict__ g_y, float* __restrict__ est,
+                                                                    float* __restrict__ partial) {
+  __shared__ float red[256];
+  const long long total = n_pix * O;
+  const long long cstride = NP * O;
+  float acc = 0.f;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (long long)gridDim.x * blockDim.x) {
+    const long long pl = e / O;
+    const int o = (int)(e - pl * O);
+    const float* yp = y + pl * T * O + o;
+    float* gp = g_y + pl * T * O + o;
+    const float* mp = mask + (p0 + pl) * T;
+    for (int c = 0; c < C; ++c) {
+      const int k0 = c * nf, k1 = k0 + nf < T ? k0 + nf : T;
+      float s = 0.f;
+      for (int k = k0; k < k1; ++k) s += mp[k] * yp[(long long)k * O];
+      const long long ci = c * cstride + (p0 + pl) * O + o;
+      float d = s - gt[ci];
+      if (est) est[ci] = s;
+      acc = __builtin_fmaf(d, d, acc);
+      if (dup && c == C - 1) {
+        const float d2 = s - gt[ci + cstride];
+        if (est) est[ci + cstride] = s;
+        acc = __builtin_fmaf(d2, d2, acc);
+        d += d2;
+      }
+      const float g = gscale * d;
+      for (int k = k0; k < k1; ++k) gp[(long long)k * O] = mp[k] * g;
+    }
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+hipError_t launch_coded_mse_grad(hipStream_t s, const float* y, int64_t p0, int64_t n_pix, int64_t NP, int T, int O,
+                                 int nframes, int dup_last, const float* mask, const float* gt, float* g_y, float* est,
+                                 float* loss_out, float* partial) {
+  if (T < 1 || O < 1 || nframes < 1 || n_pix < 1 || NP < 1) return hipErrorInvalidValue;
+  const int C = (int)(((long long)T + nframes - 1) / nframes);
+  const double count = (double)(C + dup_last) * (double)NP * O;
+  const float gscale = (float)(2.0 / count);
+  const long long pf = (long long)T * O;
+  const long long PS = pf | 1;                                 // odd pixel stride in LDS
+  unsigned nb;
+  if (PS <= CV_CAP) {
+    const long long cap = CV_CAP / PS;
+    const int TP = (int)(n_pix < cap ? n_pix : cap);
+    const long long njobs = (n_pix + TP - 1) / TP;
+    nb = njobs < MSE_BLOCKS ? (unsigned)njobs : MSE_BLOCKS;
+    hipLaunchKernelGGL(coded_mse_grad_kernel, dim3(nb), dim3(256), 0, s, y, (long long)p0, (long long)n_pix,
+                       (long long)NP, T, O, nframes, C, dup_last, TP, (int)PS, mask, gt, gscale, g_y, est, partial);
+  } else {
+    const long long n = (long long)n_pix * O;
+    nb = n < (long long)MSE_BLOCKS * 256 ? cdiv(n, 256) : MSE_BLOCKS;
+    hipLaunchKernelGGL(coded_mse_grad_direct_kernel, dim3(nb), dim3(256), 0, s, y, (long long)p0, (long long)n_pix,
+                       (long long)NP, T, O, nframes, C, dup_last, mask, gt, gscale, g_y, est, partial);
+  }
+  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, (float)(1.0 / count), loss_out);
+  return hipGetLastError();
+}
+
+// The same operator on the reference's frame-major tensors (video, masks [T][NP], coded [C'][NP]) and its adjoint:
+// one thread per coded value (forward) / per video value (backward), lanes on consecutive pixels of a frame.
+__global__ __launch_bounds__(256) void coded_fwd_kernel(const float* __restrict__ video, const float* __restrict__ masks,
+                                                        int T, long long NP, int nf, int C, int dup,
+                                                        float* __restrict__ coded) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= C * NP) return;
+  const int c = (int)(e / NP);
+  const long long p = e - c * NP;
+  const int k0 = c * nf, k1 = k0 + nf < T ? k0 + nf : T;
+  float s = 0.f;
+  for (int k = k0; k < k1; ++k) s += video[k * NP + p] * masks[k * NP + p];
+  coded[e] = s;
+  if (dup && c == C - 1) coded[e + NP] = s;
+}
+__global__ __launch_bounds__(256) void coded_bwd_kernel(const float* __restrict__ g_coded,
+                                                        const float* __restrict__ masks, int T, long long NP, int nf,
+                                                        int C, int dup, float* __restrict__ g_video) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= T * NP) return;
+  const int k = (int)(e / NP);
+  const long long p = e - k * NP;
+  const int c = k / nf;
+  float g = g_coded[c * NP + p];
+  if (dup && c == C - 1) g += g_coded[C * NP + p];
+  g_video[e] = masks[e] * g;
+}
+hipError_t launch_coded_fwd(hipStream_t s, const float* video, const float* masks, int T, int64_t NP, int nframes,
+                            int dup_last, float* coded) {
+  const int C = (int)(((long long)T + nframes - 1) / nframes);
+  hipLaunchKernelGGL(coded_fwd_kernel, dim3(cdiv((long long)C * NP, 256)), dim3(256), 0, s, video, masks, T,
+                     (long long)NP, nframes, C, dup_last, coded);
+  return hipGetLastError();
+}
+hipError_t launch_coded_bwd(hipStream_t s, const float* g_coded, const float* masks, int T, int64_t NP, int nframes,
+                            int dup_last, float* g_video) {
+  const int C = (int)(((long long)T + nframes - 1) / nframes);
+  hipLaunchKernelGGL(coded_bwd_kernel, dim3(cdiv((long long)T * NP, 256)), dim3(256), 0, s, g_coded, masks, T,
+                     (long long)NP, nframes, C, dup_last, g_video);
+  return hipGetLastError();
+}
+
 // The coordinate stack of motion.get_imstack at scale = 1 (modules/motion.py:284-318 as wire_multi_sr.py:74-78 calls
 // it): frame f's pixel (i, j) moved by its 2 x 3 matrix, then normalised -- all in fp64, rounded to fp32 once.
 __global__ void affine_coords_kernel(const double* __restrict__ mats, long long n, int H, int W,

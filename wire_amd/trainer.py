@@ -26,6 +26,7 @@ import ctypes as C
 import os
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -40,8 +41,8 @@ class FusedTrainer:
     loops of the reference's bspline_*.py drivers: a number steps the stages' tensors only -- the heads are not in
     ``model.parameters()`` there and keep their initial values, though their gradients are computed and present in
     ``flat_grad`` -- and a sequence steps stage s and head s with ``lr[s]`` (times the schedule's factor).  A sequence
-    for any other kind, or of the wrong length, is a ValueError.  ``step_downsampled``, ``step_radon`` and
-    ``step_frames`` work for bspline_mscale_hier as for the other kinds.
+    for any other kind, or of the wrong length, is a ValueError.  ``step_downsampled``, ``step_radon``,
+    ``step_frames`` and ``step_coded`` work for bspline_mscale_hier as for the other kinds.
 
     ``target`` is the [npoints, O] signal of ``step`` / ``step_hashed`` and the default ``gt`` of the metrics.  The
     operator steps bring their own data, so a trainer that only runs those may pass ``target=None``; ``step``,
@@ -573,6 +574,98 @@ class FusedTrainer:
         _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
                                   self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
                                   self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
+        self.t += 1
+        self._adam(stream, g)
+        self.loss = g[self.count:self.count + 1].clone()
+        return self.loss
+
+    # ------------------------------------------------------------------ video compressive-sensing step
+    def step_coded(self, coded: torch.Tensor, masks, nframes: int, dup_last: bool = True,
+                   slab: Optional[int] = None, est: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One optimizer step of video compressive sensing (the coded exposure of modules/lin_inverse.py:42-95): the
+        model is evaluated on the WHOLE (H, W, T) grid in row order (row (i*W + j)*T + k), every pixel's T frames are
+        multiplied by its mask and summed in groups of ``nframes`` -- ``lin_inverse.video2codedvideo`` -- and the loss
+        is the mean squared error against ``coded``; backward through the coding and the network, Adam.  In this row
+        order the operator is one pass over contiguous memory (wire_coded_mse_grad): the driver's
+        ``reshape(H, W, T).permute(2, 0, 1)`` into the reference's (1, T, H, W) is not made.
+
+        ``coded``: CUDA float32 of C' * H*W * O elements, frame-major ([C'][H*W][O]; for O = 1 exactly the reference's
+        (1, C', H, W)), C' = ceil(T / nframes) + dup_last.  ``dup_last=True`` is the reference's coded video, whose last
+        group comes twice; False the plain C frames.  ``masks``: H*W*T elements in (H, W, T) order, shared by the
+        channels -- the numpy array of ``lin_inverse.get_video_coding_frames`` (uploaded once and kept while the same
+        array object is passed; change the masks by passing a new array) or a CUDA float32 tensor.  ``est`` (optional,
+        shaped like ``coded``) receives the coded estimate.
+
+        ``slab=None``: one pass, and the video estimate of the step stays in ``self.y`` ([H*W*T, O]).  ``slab`` = a
+        number of pixels: the step walks the pixel ranges [p0, p0 + slab), each a contiguous row range of whole pixels,
+        sums their gradients and losses and runs Adam once, so the activations hold ``slab * T`` rows instead of
+        ``H*W*T``; ``self.y`` then holds the last slab only -- ``render()`` gives the whole video.  ``slab >= H*W`` is
+        the one-pass path.  3-D grids, single process."""
+        if self.tz is None or len(self.grid) != 3:
+            raise ValueError("step_coded needs a 3-D grid (H, W, T)")
+        if self.world != 1:
+            raise NotImplementedError("step_coded is single-process")
+        H, W, T = (int(v) for v in self.grid)
+        NP = H * W
+        nframes = int(nframes)
+        if nframes < 1:
+            raise ValueError(f"nframes {nframes} must be >= 1")
+        dup = int(bool(dup_last))
+        Cp = (T + nframes - 1) // nframes + dup
+        if not isinstance(coded, torch.Tensor) or not coded.is_cuda or coded.dtype != torch.float32 \
+                or coded.numel() != Cp * NP * self.O:
+            raise ValueError(f"coded must be a CUDA float32 tensor of {Cp} x {NP} x {self.O} elements")
+        gt = coded.detach().contiguous()
+        if isinstance(masks, torch.Tensor):
+            mk = masks.detach()
+            if not mk.is_cuda or mk.dtype != torch.float32 or mk.numel() != NP * T:
+                raise ValueError(f"masks must be a numpy array or a CUDA float32 tensor of {NP} x {T} elements")
+            mk = mk.contiguous()
+        else:
+            if getattr(self, "_coded_masks_src", None) is not masks:
+                arr = np.asarray(masks)
+                if arr.size != NP * T:
+                    raise ValueError(f"masks must be a numpy array or a CUDA float32 tensor of {NP} x {T} elements")
+                self._coded_masks_dev = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)) \
+                    .to(self.dev)
+                self._coded_masks_src = masks
+            mk = self._coded_masks_dev
+        if est is not None and (not est.is_cuda or est.dtype != torch.float32 or est.numel() != gt.numel()
+                                or not est.is_contiguous()):
+            raise ValueError("est must be a contiguous CUDA float32 tensor shaped like coded")
+        per = NP if slab is None else int(slab)
+        if per < 1:
+            raise ValueError(f"slab {per} must be >= 1 pixel")
+        per = min(per, NP)
+        L, d = self.L, C.byref(self.desc)
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        self._reserve(per * T)
+        g = self.gbuf[0]
+        gp = self.grad_ptrs[0]
+        if per < NP and getattr(self, "_gslab", None) is None:
+            # wire_mlp_bwd overwrites its gradients: the slabs after the first write here and are added to gbuf[0]
+            self._gslab = torch.zeros(self.count + 1, dtype=torch.float32, device=self.dev)
+            self._gslab_ptrs = _lib.ptr_array([self._gslab.data_ptr() + 4 * o for o in self.offsets])
+        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
+        for p0 in range(0, NP, per):
+            npix = min(per, NP - p0)
+            n = npix * T
+            if p0 > 0:
+                g, gp = self._gslab, self._gslab_ptrs
+            _lib.check(L.wire_coords_from_index(stream, None, p0 * T, n, self.tx.data_ptr(), W, self.ty.data_ptr(), H,
+                                                self.tz.data_ptr(), T, self.coords.data_ptr()), "coords")
+            _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
+                                      self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
+            _lib.check(L.wire_coded_mse_grad(stream, self.y.data_ptr(), p0, npix, NP, T, self.O, nframes, dup,
+                                             mk.data_ptr(), gt.data_ptr(), self.gy.data_ptr(),
+                                             est.data_ptr() if est is not None else None,
+                                             g.data_ptr() + 4 * self.count, self.partial.data_ptr()), "coded_mse_grad")
+            _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
+                                      self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
+                                      self.scratch.data_ptr(), self.scr_bytes, gp), "bwd")
+            if p0 > 0:
+                self.gbuf[0].add_(g)
+        g = self.gbuf[0]
         self.t += 1
         self._adam(stream, g)
         self.loss = g[self.count:self.count + 1].clone()
