@@ -26,6 +26,8 @@
  *                (modules/siren.py:64-88, gauss.py:44-67, relu.py:99-120,
  *                 bspline_form.py:73-110; its scale_0 buffers are not
  *                 trainable and travel in wire_net_desc.scale0)
+ *       bspline_cubic : the same list (modules/bspline_cubic.py:86-117; each
+ *                layer's scale_0, not trainable, travels in scale0)
  *       bspline_ms : W0[SHF][D], b0[SHF] (the frozen first stage), W1[K][SHF],
  *                b1[K], {W_l[K][K], b_l[K]} l=2..max(L,1), W_f, b_f, all f32
  *                (modules/bspline_mscale_HL.py; its scales travel in
@@ -79,10 +81,13 @@ typedef enum wire_kind {
                             scale, stage s > 0 joins its first layer with the
                             previous stage's output (2K -> K), one linear head
                             per stage; described by wire_net_desc_ms       */
-  WIRE_KIND_MFN = 11     /* modules/mfn.py: the multiplicative filter network
+  WIRE_KIND_MFN = 11,    /* modules/mfn.py: the multiplicative filter network
                             z_0 = g_0(x), z_{i+1} = (z_i W_i^T + b_i) g_{i+1}(x),
                             y = z_L W_f^T + b_f with hidden_layers + 1 Gabor
                             filters g_i of the COORDINATES; a plain wire_net_desc  */
+  WIRE_KIND_BSPLINE_CUBIC = 12 /* modules/bspline_cubic.py Bsplines_cubic: the
+                            cubic B-spline of lin = scale0 (x W^T) + b; a plain
+                            wire_net_desc                                        */
 } wire_kind;
 
 /* Architecture + hyper-parameters of one INR (modules/wire.py:96-159). */
@@ -102,7 +107,16 @@ typedef struct wire_net_desc {
   float first_omega0;      /* omega of net[0] (bspline: carried, unused)          */
   float hidden_omega0;     /* omega of net[1..L] (bspline: carried, unused)       */
   float scale0;            /* Gaussian scale s0; bspline: the divisor sigma0
-                              (zero or not finite -> WIRE_ERR_ARG)                */
+                              (zero or not finite -> WIRE_ERR_ARG); bspline_cubic:
+                              the multiplier s of every activation layer's INPUT,
+                              lin = s (x W^T) + b -- the bias is not scaled and
+                              the sign of s matters.  wire_pack_params folds it
+                              into the packed weights (s W in every image, so the
+                              data and coordinate gradients carry it), the
+                              weight gradients come out as dL/dW = s g_lin^T x,
+                              params / grads hold the unscaled W; both omegas are
+                              carried and unused; zero or not finite ->
+                              WIRE_ERR_ARG                                        */
 } wire_net_desc;
 
 /* The multiplicative filter network (WIRE_KIND_MFN, modules/mfn.py) is described by a plain wire_net_desc:
@@ -278,7 +292,9 @@ int wire_final_bwd(void* stream, const float* g_y, const void* z,
 /* SineLayer / GaussLayer / ReLULayer / Bsplines_form .forward (modules/siren.py:48-49,
  * gauss.py:27-28, relu.py:28-29, bspline_form.py:38-49) and their backward on native f32 tensors:
  * x [n][in], W [out][in], b [out] -> act [n][out].  kind = WIRE_KIND_SIREN /
- * _GAUSS / _RELU / _BSPLINE (scale0 = sigma0, the divisor; zero or not finite -> WIRE_ERR_ARG);
+ * _GAUSS / _RELU / _BSPLINE (scale0 = sigma0, the divisor; zero or not finite -> WIRE_ERR_ARG) /
+ * _BSPLINE_CUBIC (modules/bspline_cubic.py:44-52; scale0 multiplies x: lin = scale0 (x W^T) + b, g_x and g_W carry it,
+ * g_b does not; zero or not finite -> WIRE_ERR_ARG);
  * ws as for wire_gabor_fwd.                                                   */
 int wire_real_layer_fwd(void* stream, int kind, const float* x, const float* W,
                         const float* b, float omega0, float scale0, int64_t n,

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libwire_hip.so")
 
 KIND = {"wire": 0, "wire2d": 1, "siren": 2, "gauss": 3, "relu": 4, "bspline_form": 5, "bspline_mscale_HL": 6,
-        "bspline_mscale_2": 8, "bspline_mscale_hier": 9, "mfn": 11}
+        "bspline_mscale_2": 8, "bspline_mscale_hier": 9, "mfn": 11, "bspline_cubic": 12}
 MS_MAX_SCALES = 8   # WIRE_MS_MAX_SCALES
 ABI_VERSION = 1
 

@@ -116,7 +116,7 @@ int pack_hidden(hipStream_t s, const Plan& p, const void* const* params, float* 
         p3.fwd[i] = packed + p.off_fwd_3m[l]; p3.dg[i] = packed + p.off_dg_3m[l]; p3.bias[i] = packed + p.off_bias[l];
       }
     }
-    HIPCHK(launch_pack_hidden_batch(s, p.kind, pb, nb, p.K, p.K, p.P, p.P));
+    HIPCHK(launch_pack_hidden_batch(s, p.kind, pb, nb, p.K, p.K, p.P, p.P, p.ws));   // (everything below reads these images)
     if (p.Pl == p.P) {                                   // forward and transposed images have one shape: one launch
       for (int i = 0; i < nb; ++i) { sf.src[nb + i] = sd.src[i]; sf.dst[nb + i] = sd.dst[i]; }
       HIPCHK(launch_x3_split_b_batch(s, sf, 2 * nb, p.P, p.Pl, p.P));
@@ -213,9 +213,15 @@ extern "C" int wire_pack_params(void* stream, const wire_net_desc* d, const void
                            (const float*)params[p.ntens - 1], p.K, p.P, p.O, packed + p.off_wf,
                            packed + p.off_bf));
   if (!p.first_gemm || p.ms)   // (the multi-scale net: its first stage, read by mscale_first_kernel)
-    for (int q = 0; q < p.per_layer; ++q)
+    for (int q = 0; q < p.per_layer; ++q) {
+      if (q == 0 && p.ws != 1.f) {   // the cubic B-spline net: ws W0, as the hidden images (b0 stays as it is)
+        HIPCHK(launch_scale_copy(s, (const float*)params[first_tensor(p, 0)], p.tfloats[first_tensor(p, 0)], p.ws,
+                                 packed + first_native_off(p, 0)));
+        continue;
+      }
       HIPCHK(hipMemcpyAsync(packed + first_native_off(p, q), params[first_tensor(p, q)], p.tfloats[first_tensor(p, q)] * 4,
                             hipMemcpyDeviceToDevice, s));
+    }
   if (p.m2) {                  // the combiner, read by the m2_comb kernels
     const M2Comb w = comb_of(p, packed);
     const float* dst[4] = {w.W1, w.b1, w.W2, w.b2};
@@ -499,8 +505,11 @@ int Bwd::chain() {
   return WIRE_OK;
 }
 
-// the weight-gradient loader's form of Z = act(r) under rstore (launch_gemmx2_tn, z_act): sine 2, Gaussian 3, B-spline 4
-static int rstore_zmode(int kind) { return kind == WIRE_KIND_SIREN ? 2 : kind == WIRE_KIND_GAUSS ? 3 : 4; }
+// the weight-gradient loader's form of Z = act(r) under rstore (launch_gemmx2_tn, z_act): sine 2, Gaussian 3, B-spline 4,
+// cubic B-spline 5
+static int rstore_zmode(int kind) {
+  return kind == WIRE_KIND_SIREN ? 2 : kind == WIRE_KIND_GAUSS ? 3 : kind == WIRE_KIND_BSPLINE_CUBIC ? 5 : 4;
+}
 
 // 4. the weight-gradient batch of layers wb_l0 .. L (make_route), behind the chain
 int Bwd::wgrad_batch() {
@@ -553,7 +562,7 @@ int Bwd::layers() {
       if (r.tn_fam == FAM_3M)
         HIPCHK(launch_wgrad3m_reduce(s, slab, bslab, S, p.K, p.K, p.Kp, p.Kp, g(0), g(1)));
       else
-        HIPCHK(launch_wgrad_reduce(s, p.kind, slab, bslab, S, p.K, p.K, p.Pl, p.P, g(0), g(1), g(2), g(3)));
+        HIPCHK(launch_wgrad_reduce(s, p.kind, slab, bslab, S, p.K, p.K, p.Pl, p.P, g(0), g(1), g(2), g(3), p.ws));
       done(p.t0 + pl * l, pl);
     }
     if (r.chain) continue;                                  // g_lin_{l-1} (l = 1: the first layer's sums) is already there
@@ -645,11 +654,11 @@ int Bwd::first_params() {
   } else if (!p.first_gemm && r.chain) {
     // (the multi-pass net: S2 sets of blocks, one per pass)
     HIPCHK(launch_colreduce_final_blocks(s, p.K, p.D, p.S2 * (int)((n1 + chain_rows - 1) / chain_rows), crp, grad(p.t0),
-                                         grad(p.t0 + 1)));
+                                         grad(p.t0 + 1), p.ws));
   } else if (!p.first_gemm && r.first_sums) {
-    HIPCHK(launch_colreduce_final(s, p.K, p.D, n, crp, grad(0), grad(1)));
+    HIPCHK(launch_colreduce_final(s, p.K, p.D, n, crp, grad(0), grad(1), p.ws));
   } else if (!p.first_gemm) {   // (the multi-pass net: coords = the per-pass copies, n = all passes' rows)
-    HIPCHK(launch_colreduce(s, gcur, p.P, p.K, coords, p.D, n, crp, grad(p.t0), grad(p.t0 + 1)));   // gcur: g_lin_0 [n][P]
+    HIPCHK(launch_colreduce(s, gcur, p.P, p.K, coords, p.D, n, crp, grad(p.t0), grad(p.t0 + 1), p.ws));   // gcur: g_lin_0 [n][P]
   } else if (r.tn0 == FAM_X2) {                             // the multi-scale net: g_lin_0^T [pe | 1], pe pre-split
     const int S = gemmx2_tn_splits(n, p.P, p.Pin0, sc.S);
     HIPCHK(launch_gemmx2_tn(s, gcur, p.P, A + a.pe, p.Pin0, n, p.P, p.Pin0, S, Sx + sc.slab, Sx + sc.bslab, gslots(0),

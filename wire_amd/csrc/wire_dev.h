@@ -142,8 +142,9 @@ WIRE_DEVINL void gabor2d_fwd(float u, float v, float p, float q, float w0, float
 }
 
 // real sweep activations (config 5) and the quadratic B-spline (modules/bspline_form.py)
-enum { ACT_SIREN = 0, ACT_GAUSS = 1, ACT_RELU = 2, ACT_BSPLINE = 3 };
-// whether act'(lin) reads the stored activation out (gauss: -2 s^2 lin out; relu: [out > 0]); siren and the B-spline
+// and the cubic B-spline (modules/bspline_cubic.py)
+enum { ACT_SIREN = 0, ACT_GAUSS = 1, ACT_RELU = 2, ACT_BSPLINE = 3, ACT_BSPLINE3 = 4 };
+// whether act'(lin) reads the stored activation out (gauss: -2 s^2 lin out; relu: [out > 0]); siren and the B-splines
 // need lin alone
 constexpr bool act_bwd_reads_out(int act) { return act == ACT_GAUSS || act == ACT_RELU; }
 
@@ -163,6 +164,23 @@ WIRE_DEVINL float bspline2_d(float r) {
   const float t = __builtin_fmaxf(1.5f - a, 0.f);
   return a <= 0.5f ? -2.f * r : __builtin_copysignf(t, -r);
 }
+// Centred cubic B-spline of lin (modules/bspline_cubic.py:44-52 computes it as (1/6) relu(l+2)^3 - (2/3) relu(l+1)^3 +
+// relu(l)^3 - (2/3) relu(l-1)^3 + (1/6) relu(l-2)^3, whose terms cancel from |l|^3 once |l| > 2: at the class's scale
+// of 15 that form is wrong in the third digit in fp32).  Evaluated piecewise: exactly 0 outside |l| < 2.  The layer's
+// scale_0 multiplies the layer's INPUT, not lin: it sits in the packed weights (wire_pack.hip), so nothing here reads
+// s0.  No transcendental: the precise and the lean forms are one.
+//   B(l)  = 2/3 - l^2 + |l|^3 / 2 (|l| < 1),  (2 - |l|)^3 / 6 (1 <= |l| < 2),        0 otherwise
+//   B'(l) = l (3/2 |l| - 2),                  -sign(l) (2 - |l|)^2 / 2,              0
+WIRE_DEVINL float bspline3(float l) {
+  const float a = __builtin_fabsf(l);
+  const float t = __builtin_fmaxf(2.f - a, 0.f);
+  return a < 1.f ? __builtin_fmaf(a * a, __builtin_fmaf(0.5f, a, -1.f), 0.666666667f) : (t * t) * (t * 0.166666667f);
+}
+WIRE_DEVINL float bspline3_d(float l) {
+  const float a = __builtin_fabsf(l);
+  const float t = __builtin_fmaxf(2.f - a, 0.f);
+  return a < 1.f ? l * __builtin_fmaf(1.5f, a, -2.f) : __builtin_copysignf(0.5f * (t * t), -l);
+}
 template <int ACT>
 WIRE_DEVINL float real_act_fwd(float lin, float w0, float s0) {
   if (ACT == ACT_SIREN) {            // modules/siren.py:48-49
@@ -174,6 +192,8 @@ WIRE_DEVINL float real_act_fwd(float lin, float w0, float s0) {
     return wire_exp(-(t * t));
   } else if (ACT == ACT_BSPLINE) {   // s0 = c = 1 / |sigma0|
     return bspline2(s0 * lin);
+  } else if (ACT == ACT_BSPLINE3) {  // scale_0 is in the weights
+    return bspline3(lin);
   } else {                           // modules/relu.py:28-29
     return lin > 0.f ? lin : 0.f;
   }
@@ -188,6 +208,8 @@ WIRE_DEVINL float real_act_bwd(float g, float lin, float out, float w0, float s0
     return g * out * (-2.f * s0 * s0) * lin;
   } else if (ACT == ACT_BSPLINE) {     // dL/dlin = g B'(c lin) c
     return g * s0 * bspline2_d(s0 * lin);
+  } else if (ACT == ACT_BSPLINE3) {
+    return g * bspline3_d(lin);
   } else {
     return out > 0.f ? g : 0.f;        // out = max(lin, 0): out > 0 <=> lin > 0, so relu never needs lin stored
   }
@@ -206,6 +228,8 @@ WIRE_DEVINL float real_act_fwd_lean(float lin, float w0, float s0) {
     return __builtin_amdgcn_exp2f(-(t * t) * 1.44269502f);
   } else if (ACT == ACT_BSPLINE) {
     return bspline2(s0 * lin);
+  } else if (ACT == ACT_BSPLINE3) {  // scale_0 is in the weights
+    return bspline3(lin);
   } else {
     return lin > 0.f ? lin : 0.f;
   }
@@ -220,6 +244,8 @@ WIRE_DEVINL float real_act_bwd_lean(float g, float lin, float out, float w0, flo
     return g * out * (-2.f * s0 * s0) * lin;
   } else if (ACT == ACT_BSPLINE) {
     return g * s0 * bspline2_d(s0 * lin);
+  } else if (ACT == ACT_BSPLINE3) {
+    return g * bspline3_d(lin);
   } else {
     return out > 0.f ? g : 0.f;
   }

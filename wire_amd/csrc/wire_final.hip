@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void final_bwd_kernel(
             amx = __builtin_fmaxf(amx, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(g0), __builtin_fabsf(g1)),
                                                        __builtin_fmaxf(__builtin_fabsf(g2), __builtin_fabsf(g3))));
           } else {
-            constexpr int ACT = (KIND - NK_SIREN) < 0 ? 0 : (KIND - NK_SIREN);
+            constexpr int ACT = nk_real_act(KIND);
             const float gl = real_act_bwd<ACT>(gr, l0[q], pr[q], omega, scale);
             g_lin[row * P + c0] = gl;
             amx = __builtin_fmaxf(amx, __builtin_fabsf(gl));
@@ -194,6 +194,7 @@ hipError_t launch_final_bwd(hipStream_t s, int kind, int raw, const float* g_y, 
       case NK_GAUSS: FB_LAUNCH(NK_GAUSS, false); break;
       case NK_RELU: FB_LAUNCH(NK_RELU, false); break;
       case NK_BSPLINE: FB_LAUNCH(NK_BSPLINE, false); break;
+      case NK_BSPLINE3: FB_LAUNCH(NK_BSPLINE3, false); break;
       default: return hipErrorInvalidValue;
     }
   }
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(256) void final_fused_kernel(
         }
       }
     } else if (RECOMP) {                                           // siren / gauss: 8 real features per lane and pass
-      constexpr int ACT = (KIND - NK_SIREN) < 0 ? 0 : (KIND - NK_SIREN);
+      constexpr int ACT = nk_real_act(KIND);
 #pragma unroll
       for (int ps = 0; ps < NPASS; ++ps)
 #pragma unroll
@@ -437,7 +438,7 @@ __global__ __launch_bounds__(256) void final_fused_kernel(
         ff_amax4(amx, g0); ff_amax4(amx, g1); ff_amax4(amx, g2); ff_amax4(amx, g3);
       } else {
         // the same forms final_bwd_kernel uses (sin'= w0 cos, gauss' = -2 s^2 lin out, relu' = [out > 0])
-        constexpr int ACT = (KIND - NK_SIREN) < 0 ? 0 : (KIND - NK_SIREN);
+        constexpr int ACT = nk_real_act(KIND);
         f32x4 glr, gli;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -572,6 +573,9 @@ hipError_t launch_final_fused(hipStream_t s, int kind, const float* out, const f
     case NK_RELU: FF_LAUNCH_O(NP, RW, NK_RELU, false); break;                                                \
     case NK_BSPLINE:                                                                                         \
       if (out) { FF_LAUNCH_O(NP, RW, NK_BSPLINE, false); } else { FF_LAUNCH_O(NP, RW, NK_BSPLINE, true); }   \
+      break;                                                                                                 \
+    case NK_BSPLINE3:                                                                                        \
+      if (out) { FF_LAUNCH_O(NP, RW, NK_BSPLINE3, false); } else { FF_LAUNCH_O(NP, RW, NK_BSPLINE3, true); } \
       break;                                                                                                 \
     default: return hipErrorInvalidValue;                                                                    \
   }

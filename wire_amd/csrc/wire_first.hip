@@ -66,8 +66,7 @@ __global__ void first_fwd_kernel(const float* __restrict__ coords, long long n, 
         }
       }
     } else {
-      constexpr int ACT = KIND - NK_SIREN;
-      float o = real_act_fwd<ACT < 0 ? 0 : ACT>(u, omega, scale);
+      float o = real_act_fwd<nk_real_act(KIND)>(u, omega, scale);
       o = valid ? o : 0.f;
       amx = __builtin_fmaxf(amx, __builtin_fabsf(o));
       if (live) {
@@ -99,6 +98,7 @@ hipError_t launch_first_fwd(hipStream_t s, int kind, const float* coords, int64_
     case NK_GAUSS: FIRST_LAUNCH(NK_GAUSS); break;
     case NK_RELU: FIRST_LAUNCH(NK_RELU); break;
     case NK_BSPLINE: FIRST_LAUNCH(NK_BSPLINE); break;
+    case NK_BSPLINE3: FIRST_LAUNCH(NK_BSPLINE3); break;
     default: return hipErrorInvalidValue;
   }
 #undef FIRST_LAUNCH

@@ -75,7 +75,7 @@ WIRE_DEVINL void fx_dma16(const void* gsrc, unsigned char* lds_piece) {
 //   * the constant that the activation multiplies its argument with is folded into the weights and the bias when the
 //     image is packed: r = c lin with c = omega0 / 2 pi (sine, Gabor: v_sin / v_cos take revolutions), c = sigma0
 //     sqrt(log2 e) (Gaussian: exp(-(s lin)^2) = exp2(-r^2)), c = 1 / |sigma0| (B-spline: B(lin / sigma0) = B(r), B even),
-//     c = 1 (relu).  The accumulation error of r is the same
+//     c = 1 (relu; the cubic B-spline, whose scale_0 multiplies the layer's input and sits in the weights alone).  The accumulation error of r is the same
 //     RELATIVE error as that of lin (same products, same sums, scaled by c), i.e. the same absolute error in the argument of
 //     the sine as the layer-by-layer path's fl(omega0 lin) carries;
 //   * activations bounded by 16 (everything but relu) are split into (h, l) WITHOUT a power-of-two scale: h = fp16(x),
@@ -87,6 +87,7 @@ WIRE_DEVINL float fx_act(float r) {
   if (ACT == ACT_SIREN) return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(r));
   if (ACT == ACT_GAUSS) return __builtin_amdgcn_exp2f(-(r * r));
   if (ACT == ACT_BSPLINE) return bspline2(r);
+  if (ACT == ACT_BSPLINE3) return bspline3(r);
   return r > 0.f ? r : 0.f;
 }
 // Gabor exp(j w u - w v - s^2 (u^2 + v^2)) from (u', v') = c (u, v), c = w / 2 pi:  k1 = 2 pi log2 e, k2 = s^2 log2 e / c^2
@@ -159,7 +160,8 @@ hipError_t launch_fx_split_b_batch(hipStream_t s, const FxSplitBatch& sb, int nb
 template <int KIND>
 struct FxKind {
   static constexpr bool CPLX = KIND == NK_WIRE;
-  static constexpr int ACT = KIND == NK_SIREN ? ACT_SIREN : KIND == NK_GAUSS ? ACT_GAUSS : KIND == NK_BSPLINE ? ACT_BSPLINE : ACT_RELU;
+  static constexpr int ACT = KIND == NK_SIREN ? ACT_SIREN : KIND == NK_GAUSS ? ACT_GAUSS : KIND == NK_BSPLINE ? ACT_BSPLINE
+                             : KIND == NK_BSPLINE3 ? ACT_BSPLINE3 : ACT_RELU;
   static constexpr int U = CPLX ? 4 : 2;          // column blocks of one epilogue unit (complex: re | im of 32 features)
 };
 
@@ -686,6 +688,7 @@ WIRE_DEVINL void fx_tail_loss(const FusedFwdParams& fp, FxCtx& c, const f32x4 (&
       if (ACT == ACT_SIREN) v = go[e] * dk * __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(r));   // omega cos(omega lin)
       else if (ACT == ACT_GAUSS) v = go[e] * oo[cb][e] * dk * r;                                   // -2 s^2 lin out
       else if (ACT == ACT_BSPLINE) v = go[e] * fp.s * bspline2_d(r);                               // c B'(c lin)
+      else if (ACT == ACT_BSPLINE3) v = go[e] * bspline3_d(r);                                     // r = lin
       else v = r > 0.f ? go[e] : 0.f;
       gl[e] = v;
       amx = __builtin_fmaxf(amx, __builtin_fabsf(v));
@@ -1085,6 +1088,9 @@ __global__ __launch_bounds__(64 * W, 8 / W) void fused_bwd_kernel(const FusedBwd
         } else if (rstore && ACT == ACT_BSPLINE) {
           // aux = r = lin / |sigma0| (every layer: the first has the same c): d B(r) / d lin = c B'(r), c = fp.s
           v = go * fp.s * bspline2_d(aux[cb][e]);
+        } else if (rstore && ACT == ACT_BSPLINE3) {
+          // aux = r = lin (c = 1: the layer's scale_0 sits in the weights)
+          v = go * bspline3_d(aux[cb][e]);
         } else {
           float out = 0.f;
           if (ACT == ACT_GAUSS) out = real_act_fwd_lean<ACT_GAUSS>(aux[cb][e], om, fp.s);
@@ -1161,7 +1167,7 @@ __global__ __launch_bounds__(64 * W, 8 / W) void fused_bwd_kernel(const FusedBwd
 // shapes with a kernel: the 256-feature real nets (BASELINE.json configs[4]) and `wire` at padded widths 192 / 256 / 384
 // (config 1's K = 90, K <= 128, hidden_features = 256 -> K = 181)
 bool fused_fwd_shape(int kind, int P) {
-  if (kind == NK_SIREN || kind == NK_GAUSS || kind == NK_RELU || kind == NK_BSPLINE) return P == 256;
+  if (kind == NK_SIREN || kind == NK_GAUSS || kind == NK_RELU || kind == NK_BSPLINE || kind == NK_BSPLINE3) return P == 256;
   if (kind == NK_WIRE) return P == 192 || P == 256 || P == 384;
   return false;
 }
@@ -1169,6 +1175,7 @@ float fused_pre_scale(int kind, float omega0, float scale0) {
   if (kind == NK_SIREN || kind == NK_WIRE) return (float)((double)omega0 / 6.283185307179586);
   if (kind == NK_GAUSS) return (float)((double)scale0 * 1.2011224087864498);      // sqrt(log2 e)
   if (kind == NK_BSPLINE) return scale0;                                           // the plan's c = 1 / |sigma0|
+  // (NK_BSPLINE3: 1 -- its scale_0 multiplies W alone, never the bias: wire_pack_params wrote s W into every image)
   return 1.f;
 }
 
@@ -1179,7 +1186,7 @@ static hipError_t fx_launch_t(hipStream_t s, const FusedFwdParams& fp) {
   const unsigned grid = (unsigned)((fp.n + FX_ROWS - 1) / FX_ROWS);
   if (fp.out != nullptr) {                               // training forward: stores what the backward reads
     if constexpr (ABL == 0) {
-      if constexpr (KIND == NK_SIREN || KIND == NK_GAUSS || KIND == NK_BSPLINE) {
+      if constexpr (KIND == NK_SIREN || KIND == NK_GAUSS || KIND == NK_BSPLINE || KIND == NK_BSPLINE3) {
         if (fp.rstore) {
           const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_fwd_kernel<KIND, NB, RING, 0, 2>),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
@@ -1233,7 +1240,7 @@ hipError_t launch_fused_fwd(hipStream_t s, int kind, int P, const FusedFwdParams
   if (!(fp.c_first > 0.f) || !(fp.c_hidden > 0.f)) return hipErrorInvalidValue;
   if (fp.pe_F > 0 && (kind != NK_RELU || !fp.bias0 || !fp.wamax0 || fp.D + 2 * fp.D * fp.pe_F > 64)) return hipErrorInvalidValue;
   if (fp.pe_F == 0 && (!fp.W0 || !fp.b0)) return hipErrorInvalidValue;
-  if (fp.out != nullptr && ((kind != NK_RELU && !fp.lin) || ((kind == NK_SIREN || kind == NK_GAUSS || kind == NK_BSPLINE) && !fp.lin0) || !fp.amax_out))
+  if (fp.out != nullptr && ((kind != NK_RELU && !fp.lin) || ((kind == NK_SIREN || kind == NK_GAUSS || kind == NK_BSPLINE || kind == NK_BSPLINE3) && !fp.lin0) || !fp.amax_out))
     return hipErrorInvalidValue;
   if (fp.target != nullptr && (kind == NK_WIRE || !fp.out || !fp.wf || !fp.bfr || !fp.y || !fp.g_lin || !fp.part_w || !fp.part_b ||
                                !fp.loss_partial || !fp.amax_g))
@@ -1256,6 +1263,7 @@ hipError_t launch_fused_fwd(hipStream_t s, int kind, int P, const FusedFwdParams
     case NK_SIREN: return fx_launch_t<NK_SIREN, 16, 3>(s, fp);
     case NK_GAUSS: return fx_launch_t<NK_GAUSS, 16, 3>(s, fp);
     case NK_BSPLINE: return fx_launch_t<NK_BSPLINE, 16, 3>(s, fp);
+    case NK_BSPLINE3: return fx_launch_t<NK_BSPLINE3, 16, 3>(s, fp);
     case NK_RELU: return fx_launch_t<NK_RELU, 16, 3>(s, fp);
     case NK_WIRE:
       if (P == 192) return fx_launch_t<NK_WIRE, 12, 3>(s, fp);
@@ -1271,7 +1279,7 @@ template __global__ void fused_fwd_kernel<NK_SIREN, 16, 3, FX_PROBE_ABL>(const F
 
 // ---- the data-gradient chain (real nets, P = 256)
 bool fused_bwd_shape(int kind, int P) {
-  return (kind == NK_SIREN || kind == NK_GAUSS || kind == NK_RELU || kind == NK_BSPLINE) && P == 256;
+  return (kind == NK_SIREN || kind == NK_GAUSS || kind == NK_RELU || kind == NK_BSPLINE || kind == NK_BSPLINE3) && P == 256;
 }
 // W = waves per workgroup (the "fused_bwd_w" knob, wire_knobs.hip: 8 or 4)
 template <int KIND, int W, int ABL = 0>
@@ -1322,6 +1330,7 @@ hipError_t launch_fused_bwd(hipStream_t s, int kind, int P, const FusedBwdParams
     case NK_SIREN: return fxb_launch_t<NK_SIREN>(s, fp, W);
     case NK_GAUSS: return fxb_launch_t<NK_GAUSS>(s, fp, W);
     case NK_BSPLINE: return fxb_launch_t<NK_BSPLINE>(s, fp, W);
+    case NK_BSPLINE3: return fxb_launch_t<NK_BSPLINE3>(s, fp, W);
     case NK_RELU: return fxb_launch_t<NK_RELU>(s, fp, W);
     default: return hipErrorInvalidValue;
   }

@@ -29,6 +29,8 @@ enum WireEpi {
   EPI_MFN_FWD = 15,         // lin = C + bias: o0 = lin (optional), o1 = lin g
   EPI_MFN_BWD = 16,         // C = g_z: i0 = lin -> o0 = g_z g (the layer below's g_lin), o1 = g_z lin (the filter's
                             //   upstream gradient h); i0 null (filter 0): o1 = g_z alone
+  EPI_BSPLINE3_FWD = 17,    // cubic B-spline of lin (scale_0 sits in the packed weights): o0 = lin, o1 = act
+  EPI_BSPLINE3_BWD = 18,    // i0 = lin -> o0 = g_lin (no out read)
   // flag on the layer-1 data-gradient forms of the 16 x 16 x 32 kernels (the real BWD forms, GABOR_BWD_FIRST,
   // GABOR2D_BWD_FIRST): the instantiation that also writes ep.cg_partial.  Host code passes the plain code; the
   // launchers pick the flagged instantiation when ep.cg_partial is set
@@ -43,15 +45,16 @@ enum WireEpi {
 };
 constexpr int EPI_FLAGS = EPI_CG | EPI_D2 | EPI_D3 | EPI_LA;
 
-// the real-valued activation epilogues (siren / gauss / relu / B-spline) and their ACT_* code (wire_dev.h)
+// the real-valued activation epilogues (siren / gauss / relu / the B-splines) and their ACT_* code (wire_dev.h)
 constexpr bool epi_real_fwd(int e) {
-  return e == EPI_SIREN_FWD || e == EPI_GAUSS_FWD || e == EPI_RELU_FWD || e == EPI_BSPLINE_FWD;
+  return e == EPI_SIREN_FWD || e == EPI_GAUSS_FWD || e == EPI_RELU_FWD || e == EPI_BSPLINE_FWD || e == EPI_BSPLINE3_FWD;
 }
 constexpr bool epi_real_bwd(int e) {
-  return e == EPI_SIREN_BWD || e == EPI_GAUSS_BWD || e == EPI_RELU_BWD || e == EPI_BSPLINE_BWD;
+  return e == EPI_SIREN_BWD || e == EPI_GAUSS_BWD || e == EPI_RELU_BWD || e == EPI_BSPLINE_BWD || e == EPI_BSPLINE3_BWD;
 }
 constexpr int epi_real_act(int e) {
-  return (e == EPI_BSPLINE_FWD || e == EPI_BSPLINE_BWD) ? 3 : epi_real_fwd(e) ? e - EPI_SIREN_FWD : e - EPI_SIREN_BWD;
+  return (e == EPI_BSPLINE3_FWD || e == EPI_BSPLINE3_BWD) ? 4
+       : (e == EPI_BSPLINE_FWD || e == EPI_BSPLINE_BWD) ? 3 : epi_real_fwd(e) ? e - EPI_SIREN_FWD : e - EPI_SIREN_BWD;
 }
 
 struct GemmEpiParams {

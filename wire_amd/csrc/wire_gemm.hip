@@ -220,6 +220,8 @@ hipError_t launch_gemm_nt(hipStream_t s, int epi, const float* A, int lda, const
     case EPI_RELU_BWD: return launch_nt_t<EPI_RELU_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
     case EPI_BSPLINE_FWD: return launch_nt_t<EPI_BSPLINE_FWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
     case EPI_BSPLINE_BWD: return launch_nt_t<EPI_BSPLINE_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
+    case EPI_BSPLINE3_FWD: return launch_nt_t<EPI_BSPLINE3_FWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
+    case EPI_BSPLINE3_BWD: return launch_nt_t<EPI_BSPLINE3_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
     case EPI_MFN_FWD: return launch_nt_t<EPI_MFN_FWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
     case EPI_MFN_BWD: return launch_nt_t<EPI_MFN_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
     case EPI_GABOR2D_FWD:

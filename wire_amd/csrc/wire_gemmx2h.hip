@@ -452,7 +452,7 @@ static hipError_t launchx2h_t(hipStream_t s, const float* A, int lda, const unsi
   if (ep.a_split_inv != 0.f) {
     // (only the forward forms read an activation; the data gradients read g_lin, which has no a-priori bound)
     if constexpr (EPI == EPI_STORE || EPI == EPI_GABOR_FWD || EPI == EPI_GABOR2D_FWD || EPI == EPI_SIREN_FWD ||
-                  EPI == EPI_GAUSS_FWD || EPI == EPI_BSPLINE_FWD) {
+                  EPI == EPI_GAUSS_FWD || EPI == EPI_BSPLINE_FWD || EPI == EPI_BSPLINE3_FWD) {
       if (knob(K_X2_AMODE) == 2)
         hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 2, 4, 1, true>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m,
                            tiles_n, ep);
@@ -525,6 +525,10 @@ hipError_t launch_gemmx2h_nt(hipStream_t s, int epi, const float* A, int lda, co
     case EPI_BSPLINE_BWD:
       return ep.cg_partial ? launchx2h_t<EPI_BSPLINE_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep)
                            : launchx2h_t<EPI_BSPLINE_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+    case EPI_BSPLINE3_FWD: return launchx2h_t<EPI_BSPLINE3_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+    case EPI_BSPLINE3_BWD:
+      return ep.cg_partial ? launchx2h_t<EPI_BSPLINE3_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep)
+                           : launchx2h_t<EPI_BSPLINE3_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
     case EPI_MFN_FWD: return launchx2h_t<EPI_MFN_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
     case EPI_MFN_BWD: return launchx2h_t<EPI_MFN_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
     case EPI_GABOR2D_FWD:
@@ -572,7 +576,8 @@ WIRE_DEVINL x2s16x4 x2_lds_tr16(const unsigned char* p) {
 // wire_store_out4; 1 / scale from the host); 2 / 3 (round 4, the fused training forward of siren / gauss nets stores no out_l at
 // all): the pre-activation r = c lin the forward's activation was evaluated on -- the loader evaluates sin(2 pi r) (2) or
 // exp2(-r^2) (3) again, the very instructions of wire_fused.hip's producer, and splits with the fixed scale 1 / z_pre_inv; 4: the
-// same for the quadratic B-spline of a bspline_form net (wire_dev.h: bspline2(r), r = lin / |sigma0|).
+// same for the quadratic B-spline of a bspline_form net (wire_dev.h: bspline2(r), r = lin / |sigma0|); 5: for the cubic B-spline
+// of a bspline_cubic net (bspline3(r), r = lin: its scale sits in the weights).
 // RB = 16-feature blocks of G per wave (4: a wave owns 64 x 128 of the tile).  RB = 3 with (WM, WN) = (8, 1) is the P = 384
 // shape of round 4 (hidden_features = 256 through the reference's API, K = 181): 8 waves x 48 features = 384 x 128 -- the
 // (6, 1) shape's 6 waves leave two SIMDs of a CU with one wave and two with two, so the workgroup runs at the pace of 8 waves'
@@ -746,6 +751,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemmx2_tn16_kernel(
           if constexpr (ZMODE == 4) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) zz[e] = bspline2(zv[e]);
+          }
+          if constexpr (ZMODE == 5) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) zz[e] = bspline3(zv[e]);
           }
           x2_split2(zz[0], zz[1], s_z, h0, l0);
           x2_split2(zz[2], zz[3], s_z, h1, l1);
@@ -957,6 +966,7 @@ static hipError_t launch_x2_tn_t(hipStream_t s, dim3 grid, const float* G, int l
     if (z_act == 2) return X2_TN_Z(2);
     if (z_act == 3) return X2_TN_Z(3);
     if (z_act == 4) return X2_TN_Z(4);
+    if (z_act == 5) return X2_TN_Z(5);
   }
   if (z_act >= 2) return hipErrorInvalidValue;
   return z_pre_inv != 0.f ? X2_TN_Z(1) : X2_TN_Z(0);
@@ -965,7 +975,7 @@ static hipError_t launch_x2_tn_t(hipStream_t s, dim3 grid, const float* G, int l
 
 // `splits` from gemmx2_tn_splits; slabs [splits][Pm][Pn] (+ bslab [splits][Pm]) as launch_gemmx3_tn writes them.
 // z_pre_inv != 0: Z is a pre-split activation (wire_dev.h: wire_store_out4), 1 / its scale; amax_z is not read.
-// z_act = 2 / 3 / 4: Z holds the pre-activation r of a sine / Gaussian / B-spline layer as wire_fused.hip stored it; the loader evaluates the
+// z_act = 2 / 3 / 4 / 5: Z holds the pre-activation r of a sine / Gaussian / quadratic / cubic B-spline layer as wire_fused.hip stored it; the loader evaluates the
 // activation again and splits with scale 1 / z_pre_inv (which must be given).
 // batch > 1: `batch` weight gradients of the same shape in one launch -- member j reads G + j g_step, Z + j z_step and the
 // maximum slots amax_g + j amax_step (amax_z likewise) and writes the slabs [j][splits][Pm][Pn] (+ bslab [j][splits][Pm]).
@@ -975,7 +985,7 @@ hipError_t launch_gemmx2_tn(hipStream_t s, const float* G, int ldg, const float*
                             long long z_step, int amax_step) {
   const int shp = x2_tn_shape(Pm, Pn);
   if (!shp || (ldg & 3) || (ldz & 3) || splits < 1 || n < 1 || !amax_g || (!amax_z && z_pre_inv == 0.f) ||
-      (z_act != 0 && (z_act < 2 || z_act > 4 || z_pre_inv == 0.f)) || batch < 1 || batch > 8)
+      (z_act != 0 && (z_act < 2 || z_act > 5 || z_pre_inv == 0.f)) || batch < 1 || batch > 8)
     return hipErrorInvalidValue;
   const int TMf = x2_tn_tm(shp), TNf = x2_tn_tn(shp);
   const int tiles_m = Pm / TMf, tiles_n = (Pn + TNf - 1) / TNf;

@@ -407,6 +407,8 @@ hipError_t launch_gemmx3_nt(hipStream_t s, int epi, const float* A, int lda, con
       case EPI_RELU_BWD: return launchx3_nt_t<EPI_RELU_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
       case EPI_BSPLINE_FWD: return launchx3_nt_t<EPI_BSPLINE_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
       case EPI_BSPLINE_BWD: return launchx3_nt_t<EPI_BSPLINE_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+      case EPI_BSPLINE3_FWD: return launchx3_nt_t<EPI_BSPLINE3_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+      case EPI_BSPLINE3_BWD: return launchx3_nt_t<EPI_BSPLINE3_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
       default: break;
     }
   }
@@ -432,6 +434,8 @@ hipError_t launch_gemmx3_nt(hipStream_t s, int epi, const float* A, int lda, con
     case EPI_RELU_BWD: return launchx3_nt_t<EPI_RELU_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_BSPLINE_FWD: return launchx3_nt_t<EPI_BSPLINE_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_BSPLINE_BWD: return launchx3_nt_t<EPI_BSPLINE_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+    case EPI_BSPLINE3_FWD: return launchx3_nt_t<EPI_BSPLINE3_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+    case EPI_BSPLINE3_BWD: return launchx3_nt_t<EPI_BSPLINE3_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_MFN_FWD: return launchx3_nt_t<EPI_MFN_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_MFN_BWD: return launchx3_nt_t<EPI_MFN_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     case EPI_GABOR2D_FWD:

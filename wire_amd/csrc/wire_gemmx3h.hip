@@ -293,6 +293,10 @@ hipError_t launch_gemmx3h_nt(hipStream_t s, int epi, const float* A, int lda, co
     case EPI_BSPLINE_BWD:
       return ep.cg_partial ? launchx3h_t<EPI_BSPLINE_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
                            : launchx3h_t<EPI_BSPLINE_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_BSPLINE3_FWD: return launchx3h_t<EPI_BSPLINE3_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
+    case EPI_BSPLINE3_BWD:
+      return ep.cg_partial ? launchx3h_t<EPI_BSPLINE3_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
+                           : launchx3h_t<EPI_BSPLINE3_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_MFN_FWD: return launchx3h_t<EPI_MFN_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_MFN_BWD: return launchx3h_t<EPI_MFN_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
     case EPI_GABOR2D_FWD:

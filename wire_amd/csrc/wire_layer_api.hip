@@ -96,10 +96,10 @@ struct LayerGemm {
   // weights: W_ + btf / btd hold the fp32 images of the family, btf_x3 / btd_x3 the split images
   hipError_t pack(hipStream_t s, int kind, const float* W, const float* b, const float* V, const float* c, int out,
                   int in, int Pout_g, int Pin, float* btf, float* btd, float* bias, float* btf_x3,
-                  float* btd_x3) const {
+                  float* btd_x3, float wscale = 1.f) const {
     if (fam == FAM_3M) return launch_pack3m(s, W, b, out, in, Pout_g / 2, Pin / 2, btf, btd, bias);
     hipError_t e = launch_pack_hidden(s, kind, W, b, V, c, out, in, kind == NK_WIRE2D ? Pout_g / 2 : Pout_g, Pin,
-                                      btf, btd, bias);
+                                      btf, btd, bias, wscale);
     if (e != hipSuccess || fam != FAM_X3) return e;
     e = launch_x3_split_b(s, btf, Pin, Pout_g, Pin, btf_x3);
     if (e != hipSuccess) return e;
@@ -141,7 +141,8 @@ struct LayerGemm {
     return launch_gemm_nt(s, epi, A, Kd, dgrad ? btd : btf, Kd, n, Nc, Kd, ep);
   }
   hipError_t tn_reduce(hipStream_t s, int kind, const float* G, const float* Z, int64_t n, int Pm, int Pn, int out,
-                       int in, float* slab, float* bslab, float* gW, float* gb, float* gV, float* gc) const {
+                       int in, float* slab, float* bslab, float* gW, float* gb, float* gV, float* gc,
+                       float wscale = 1.f) const {
     hipError_t e;
     if (use_x2(EPI_STORE, n) && gemmx2_tn_applies(Pm, Pn)) {
       const int S2 = gemmx2_tn_splits(n, Pm, Pn, 256);
@@ -153,7 +154,7 @@ struct LayerGemm {
       if (e != hipSuccess) return e;
       e = launch_gemmx2_tn(s, G, Pm, Z, Pn, n, Pm, Pn, S2, slab, bslab, slots(2), slots(3));
       if (e != hipSuccess) return e;
-      return launch_wgrad_reduce(s, kind, slab, bslab, S2, out, in, Pm, Pn, gW, gb, gV, gc);
+      return launch_wgrad_reduce(s, kind, slab, bslab, S2, out, in, Pm, Pn, gW, gb, gV, gc, wscale);
     }
     const int S = layer_splits(fam, n, Pm, Pn);
     if (fam == FAM_3M) {
@@ -164,7 +165,7 @@ struct LayerGemm {
     e = fam == FAM_X3 ? launch_gemmx3_tn(s, G, Pm, Z, Pn, n, Pm, Pn, S, slab, bslab)
                       : launch_gemm_tn(s, G, Pm, Z, Pn, n, Pm, Pn, S, slab, bslab);
     if (e != hipSuccess) return e;
-    return launch_wgrad_reduce(s, kind, slab, bslab, S, out, in, Pm, Pn, gW, gb, gV, gc);
+    return launch_wgrad_reduce(s, kind, slab, bslab, S, out, in, Pm, Pn, gW, gb, gV, gc, wscale);
   }
 };
 }  // namespace
@@ -349,28 +350,41 @@ extern "C" int wire_final_bwd(void* stream, const float* g_y, const void* z, con
 }
 
 // ---------------------------------------------------------------------------
-// real-valued layers: SineLayer / GaussLayer / ReLULayer / Bsplines_form .forward
-// (modules/siren.py:48-49, gauss.py:27-28, relu.py:28-29, bspline_form.py:38-49) on native [n][in] f32 tensors.
+// real-valued layers: SineLayer / GaussLayer / ReLULayer / Bsplines_form / Bsplines_cubic .forward
+// (modules/siren.py:48-49, gauss.py:27-28, relu.py:28-29, bspline_form.py:38-49, bspline_cubic.py:44-52) on native
+// [n][in] f32 tensors.
 // ---------------------------------------------------------------------------
 static int real_epi_fwd(int kind) {
   return kind == WIRE_KIND_SIREN ? EPI_SIREN_FWD : kind == WIRE_KIND_GAUSS ? EPI_GAUSS_FWD
-       : kind == WIRE_KIND_BSPLINE ? EPI_BSPLINE_FWD : EPI_RELU_FWD;
+       : kind == WIRE_KIND_BSPLINE ? EPI_BSPLINE_FWD : kind == WIRE_KIND_BSPLINE_CUBIC ? EPI_BSPLINE3_FWD : EPI_RELU_FWD;
 }
+static bool real_kind(int kind) { return (kind >= WIRE_KIND_SIREN && kind <= WIRE_KIND_BSPLINE) || kind == WIRE_KIND_BSPLINE_CUBIC; }
 // the kernels' scale of a real layer: the B-spline's sigma0 is a divisor, passed on as c = 1 / |sigma0| (B is even); false:
-// sigma0 is zero or not finite
-static bool real_scale(int kind, float& scale0) {
-  if (kind != WIRE_KIND_BSPLINE) return true;
+// sigma0 is zero or not finite.  The cubic B-spline's scale_0 multiplies the layer's input: it goes into the packed weights
+// (wscale: s W in both images, the bias as it is; g_W is multiplied by it on the way out) and the kernels' scale is 1
+static bool real_scale(int kind, float& scale0, float& wscale) {
+  wscale = 1.f;
+  if (kind != WIRE_KIND_BSPLINE && kind != WIRE_KIND_BSPLINE_CUBIC) return true;
   if (!(std::isfinite(scale0) && scale0 != 0.f)) return false;
-  scale0 = (float)(1.0 / fabs((double)scale0));
+  if (kind == WIRE_KIND_BSPLINE_CUBIC) { wscale = scale0; scale0 = 1.f; }
+  else scale0 = (float)(1.0 / fabs((double)scale0));
   return true;
 }
+// the 2 x fp16 region of a real layer's workspace, or null: a cubic B-spline layer of at most 64 inputs stays on the
+// 3 x bf16 kernels at every row count.  The 2 x fp16 split drops the l l product (2^-22 of each product); the 2 to 64
+// products of such a row do not average that out, and the layer's scale_0 sits in the operand (|s W| is 15 times the
+// other kinds' at the class default): measured 3.5 times the fp32 error on lin at 2 -> 256, s = 15, 8229 rows, where the
+// whole-net path's first layer is an fp32 FMA chain.  3 x bf16 carries 24 bits per operand.
+static float* real_x2_region(int kind, int Pin, float* x2) {
+  return kind == WIRE_KIND_BSPLINE_CUBIC && Pin <= 64 ? nullptr : x2;
+}
 static int real_forward_ws(hipStream_t s, const LayerWs& w, float* W_, int kind, const void* x, const void* Wt,
-                           const void* b, float omega0, float scale0, int64_t n, int in, int out, int Pin,
+                           const void* b, float omega0, float scale0, float wscale, int64_t n, int in, int out, int Pin,
                            int Pout) {
-  const LayerGemm g{wire_family_(kind), W_ + w.x2};
+  const LayerGemm g{wire_family_(kind), real_x2_region(kind, Pin, W_ + w.x2)};
   LCHK(launch_pad_rows(s, (const float*)x, n, in, Pin, W_ + w.xb));
   LCHK(g.pack(s, kind, (const float*)Wt, (const float*)b, nullptr, nullptr, out, in, Pout, Pin, W_ + w.btf,
-              W_ + w.btd, W_ + w.bias, W_ + w.btf_x3, W_ + w.btd_x3));
+              W_ + w.btd, W_ + w.bias, W_ + w.btf_x3, W_ + w.btd_x3, wscale));
   GemmEpiParams ep;
   ep.bias = W_ + w.bias; ep.o0 = W_ + w.lin; ep.o1 = W_ + w.out; ep.ld0 = Pout; ep.ld1 = Pout;
   ep.omega = omega0; ep.scale = scale0; ep.kvalid = out;
@@ -382,8 +396,9 @@ static int real_forward_ws(hipStream_t s, const LayerWs& w, float* W_, int kind,
 extern "C" int wire_real_layer_fwd(void* stream, int kind, const float* x, const float* W, const float* b,
                                    float omega0, float scale0, int64_t n, int in_features, int out_features,
                                    float* act_out, void* ws, int64_t ws_bytes) {
-  if (kind < WIRE_KIND_SIREN || kind > WIRE_KIND_BSPLINE || n < 0 || in_features < 1 || out_features < 1 || !x ||
-      !W || !b || !act_out || !ws || !real_scale(kind, scale0))
+  float wscale;
+  if (!real_kind(kind) || n < 0 || in_features < 1 || out_features < 1 || !x ||
+      !W || !b || !act_out || !ws || !real_scale(kind, scale0, wscale))
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_real_layer_fwd");
   if (n == 0) return WIRE_OK;
   const LayerWs w = layer_ws(n, in_features, out_features);   // complex sizing is an upper bound
@@ -391,7 +406,7 @@ extern "C" int wire_real_layer_fwd(void* stream, int kind, const float* x, const
   const int Pin = rup(in_features, 64), Pout = rup(out_features, 64);
   hipStream_t s = (hipStream_t)stream;
   float* W_ = (float*)ws;
-  if (int rc = real_forward_ws(s, w, W_, kind, x, W, b, omega0, scale0, n, in_features, out_features, Pin, Pout))
+  if (int rc = real_forward_ws(s, w, W_, kind, x, W, b, omega0, scale0, wscale, n, in_features, out_features, Pin, Pout))
     return rc;
   LCHK(launch_unpad_rows(s, W_ + w.out, n, out_features, Pout, act_out));
   return WIRE_OK;
@@ -401,20 +416,21 @@ extern "C" int wire_real_layer_bwd(void* stream, int kind, const float* g_act, c
                                    const float* b, float omega0, float scale0, int64_t n, int in_features,
                                    int out_features, float* g_x, float* g_W, float* g_b, void* ws,
                                    int64_t ws_bytes) {
-  if (kind < WIRE_KIND_SIREN || kind > WIRE_KIND_BSPLINE || n <= 0 || in_features < 1 || out_features < 1 ||
-      !g_act || !x || !W || !b || !g_W || !g_b || !ws || !real_scale(kind, scale0))
+  float wscale;
+  if (!real_kind(kind) || n <= 0 || in_features < 1 || out_features < 1 ||
+      !g_act || !x || !W || !b || !g_W || !g_b || !ws || !real_scale(kind, scale0, wscale))
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_real_layer_bwd");
   const LayerWs w = layer_ws(n, in_features, out_features);
   if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
   const int Pin = rup(in_features, 64), Pout = rup(out_features, 64);
   hipStream_t s = (hipStream_t)stream;
   float* W_ = (float*)ws;
-  if (int rc = real_forward_ws(s, w, W_, kind, x, W, b, omega0, scale0, n, in_features, out_features, Pin, Pout))
+  if (int rc = real_forward_ws(s, w, W_, kind, x, W, b, omega0, scale0, wscale, n, in_features, out_features, Pin, Pout))
     return rc;
   LCHK(launch_pad_rows(s, g_act, n, out_features, Pout, W_ + w.gact));
   LCHK(launch_real_act_bwd_point(s, kind, W_ + w.gact, W_ + w.lin, W_ + w.out, n, Pout, omega0, scale0,
                                  W_ + w.glin));
-  const LayerGemm g{wire_family_(kind), W_ + w.x2};
+  const LayerGemm g{wire_family_(kind), real_x2_region(kind, Pin, W_ + w.x2)};
   if (g_x) {
     GemmEpiParams ep; ep.o0 = W_ + w.gxb; ep.ld0 = Pin; ep.ld1 = Pin;
     LCHK(g.nt(s, EPI_STORE, W_ + w.glin, n, Pin, Pout, true, W_ + w.btf, W_ + w.btd, W_ + w.btf_x3, W_ + w.btd_x3,
@@ -422,7 +438,7 @@ extern "C" int wire_real_layer_bwd(void* stream, int kind, const float* g_act, c
     LCHK(launch_unpad_rows(s, W_ + w.gxb, n, in_features, Pin, g_x));
   }
   LCHK(g.tn_reduce(s, kind, W_ + w.glin, W_ + w.xb, n, Pout, Pin, out_features, in_features, W_ + w.slab,
-                   W_ + w.bslab, g_W, g_b, nullptr, nullptr));
+                   W_ + w.bslab, g_W, g_b, nullptr, nullptr, wscale));
   return WIRE_OK;
 }
 

@@ -178,6 +178,7 @@ hipError_t launch_real_act_bwd_point(hipStream_t s, int kind, const float* g, co
     case NK_GAUSS: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_GAUSS>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
     case NK_RELU: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_RELU>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
     case NK_BSPLINE: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_BSPLINE>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
+    case NK_BSPLINE3: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_BSPLINE3>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

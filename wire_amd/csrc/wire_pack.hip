@@ -12,10 +12,12 @@
 //     [ (o,re),(i,re) ] =  W_re   [ (o,re),(i,im) ] = -W_im
 //     [ (o,im),(i,re) ] =  W_im   [ (o,im),(i,im) ] =  W_re
 // The data-gradient GEMM g_z = g_lin conj(W) uses exactly the transposed image.
+// WS: the real kinds' W is multiplied by ws on the way in (launch_pack_hidden: wscale), the bias is not
+template <bool WS>
 WIRE_DEVINL void pack_hidden_body(int kind, const float* __restrict__ W, const float* __restrict__ b,
                                   const float* __restrict__ V, const float* __restrict__ c, int K,
                                   int Kin, int P, int Pin, int Nc, float* __restrict__ Bt_fwd,
-                                  float* __restrict__ Bt_dgrad, float* __restrict__ bias) {
+                                  float* __restrict__ Bt_dgrad, float* __restrict__ bias, float ws) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;   // input (reduction) index
   const int j = blockIdx.y;                              // GEMM output column
   if (k >= Pin) return;
@@ -45,41 +47,62 @@ WIRE_DEVINL void pack_hidden_body(int kind, const float* __restrict__ W, const f
   } else {
     if (j < K) {
       bv = b[j];
-      if (k < Kin) val = W[(size_t)j * Kin + k];
+      if (k < Kin) val = WS ? ws * W[(size_t)j * Kin + k] : W[(size_t)j * Kin + k];
     }
   }
   Bt_fwd[(size_t)j * Pin + k] = val;
   Bt_dgrad[(size_t)k * Nc + j] = val;
   if (k == 0) bias[j] = bv;
 }
+template <bool WS>
 __global__ void pack_hidden_kernel(int kind, const float* __restrict__ W, const float* __restrict__ b,
                                    const float* __restrict__ V, const float* __restrict__ c, int K,
                                    int Kin, int P, int Pin, int Nc, float* __restrict__ Bt_fwd,
-                                   float* __restrict__ Bt_dgrad, float* __restrict__ bias) {
-  pack_hidden_body(kind, W, b, V, c, K, Kin, P, Pin, Nc, Bt_fwd, Bt_dgrad, bias);
+                                   float* __restrict__ Bt_dgrad, float* __restrict__ bias, float ws) {
+  pack_hidden_body<WS>(kind, W, b, V, c, K, Kin, P, Pin, Nc, Bt_fwd, Bt_dgrad, bias, ws);
 }
 // the same for up to PACK_MAXB layers of one shape in one launch (blockIdx.z = layer): wire_pack_params runs once per
 // optimizer step, and a chain of ~5 us launches per layer costs more in launch gaps than in work
-__global__ void pack_hidden_batch_kernel(int kind, PackBatch pb, int K, int Kin, int P, int Pin, int Nc) {
+template <bool WS>
+__global__ void pack_hidden_batch_kernel(int kind, PackBatch pb, int K, int Kin, int P, int Pin, int Nc, float ws) {
   const int z = blockIdx.z;
-  pack_hidden_body(kind, pb.W[z], pb.b[z], pb.V[z], pb.c[z], K, Kin, P, Pin, Nc, pb.fwd[z], pb.dg[z], pb.bias[z]);
+  pack_hidden_body<WS>(kind, pb.W[z], pb.b[z], pb.V[z], pb.c[z], K, Kin, P, Pin, Nc, pb.fwd[z], pb.dg[z], pb.bias[z], ws);
 }
 hipError_t launch_pack_hidden_batch(hipStream_t s, int kind, const PackBatch& pb, int nb, int K, int Kin, int P,
-                                    int Pin) {
+                                    int Pin, float wscale) {
   if (nb < 1 || nb > PACK_MAXB) return hipErrorInvalidValue;
   const int Nc = (kind == NK_WIRE2D) ? 2 * P : P;
   dim3 grid(cdiv(Pin, 128), (unsigned)Nc, (unsigned)nb);
-  hipLaunchKernelGGL(pack_hidden_batch_kernel, grid, dim3(128), 0, s, kind, pb, K, Kin, P, Pin, Nc);
+  if (wscale != 1.f)
+    hipLaunchKernelGGL(pack_hidden_batch_kernel<true>, grid, dim3(128), 0, s, kind, pb, K, Kin, P, Pin, Nc, wscale);
+  else
+    hipLaunchKernelGGL(pack_hidden_batch_kernel<false>, grid, dim3(128), 0, s, kind, pb, K, Kin, P, Pin, Nc, 1.f);
   return hipGetLastError();
 }
 
 hipError_t launch_pack_hidden(hipStream_t s, int kind, const float* W, const float* b,
                               const float* V, const float* c, int K, int Kin, int P, int Pin,
-                              float* Bt_fwd, float* Bt_dgrad, float* bias) {
+                              float* Bt_fwd, float* Bt_dgrad, float* bias, float wscale) {
   const int Nc = (kind == NK_WIRE2D) ? 2 * P : P;
   dim3 grid(cdiv(Pin, 128), (unsigned)Nc);
-  hipLaunchKernelGGL(pack_hidden_kernel, grid, dim3(128), 0, s, kind, W, b, V, c, K, Kin, P, Pin,
-                     Nc, Bt_fwd, Bt_dgrad, bias);
+  if (wscale != 1.f)
+    hipLaunchKernelGGL(pack_hidden_kernel<true>, grid, dim3(128), 0, s, kind, W, b, V, c, K, Kin, P, Pin,
+                       Nc, Bt_fwd, Bt_dgrad, bias, wscale);
+  else
+    hipLaunchKernelGGL(pack_hidden_kernel<false>, grid, dim3(128), 0, s, kind, W, b, V, c, K, Kin, P, Pin,
+                       Nc, Bt_fwd, Bt_dgrad, bias, 1.f);
+  return hipGetLastError();
+}
+
+// dst = c src: the native copy of the cubic B-spline net's first-layer weights (c = its scale_0), read by the first-layer
+// kernels and the coordinate gradient
+__global__ void scale_copy_kernel(const float* __restrict__ src, long long n, float c, float* __restrict__ dst) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = c * src[i];
+}
+hipError_t launch_scale_copy(hipStream_t s, const float* src, int64_t n, float c, float* dst) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(scale_copy_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, src, (long long)n, c, dst);
   return hipGetLastError();
 }
 

@@ -69,6 +69,12 @@ inline int rup(int v, int m) { return (v + m - 1) / m * m; }
 struct Plan {
   int kind, D, K, L, O, F;
   float w1, w, s;
+  // WIRE_KIND_BSPLINE_CUBIC: scale0 multiplies every activation layer's INPUT (lin = ws x W^T + b).  It lives in the packed
+  // weights alone: wire_pack_params writes ws W into every image of the hidden layers and into the first layer's native
+  // copy (forward, data gradient and coordinate gradient read ws W; the maxima the split GEMMs scale by are taken of
+  // ws W), the bias stays as it is, the weight-gradient reductions multiply g_W by ws on the way out, and the kernels'
+  // own scale s is 1.  Every other kind: ws = 1, nothing is multiplied
+  float ws = 1.f;
   bool cplx, first_gemm, m3, x3, x2;
   int P, Pl, Din, Pin0, ldu, ntens, per_layer, Kp;
   // the three scaled kinds (wire_net_desc_ms): c_k = 1 / |scales[k]|, k < nsc -- per column group (T), pass (S2) or stage (HS)

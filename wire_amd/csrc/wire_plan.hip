@@ -39,8 +39,10 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   p.kind = d->kind; p.D = d->in_features; p.K = d->width; p.L = d->hidden_layers;
   p.O = d->out_features; p.F = d->posenc_freqs;
   p.w1 = d->first_omega0; p.w = d->hidden_omega0; p.s = d->scale0;
+  p.ws = 1.f;
   if (p.kind < WIRE_KIND_WIRE || (p.kind > WIRE_KIND_BSPLINE_MS && p.kind != WIRE_KIND_BSPLINE_M2 &&
-                                  p.kind != WIRE_KIND_BSPLINE_HIER && p.kind != WIRE_KIND_MFN))
+                                  p.kind != WIRE_KIND_BSPLINE_HIER && p.kind != WIRE_KIND_MFN &&
+                                  p.kind != WIRE_KIND_BSPLINE_CUBIC))
     return fail(WIRE_ERR_ARG, "unknown kind %d", p.kind);
   if (p.kind == WIRE_KIND_MFN) {
     // modules/mfn.py: the omegas, `scale` and the positional encoding are carried and ignored; the K -> K layers are
@@ -88,6 +90,13 @@ int make_plan(const wire_net_desc* d, Plan& p) {
     // sigma0 divides lin (modules/bspline_form.py:44); B is even, so every kernel multiplies by c = 1 / |sigma0| instead
     if (!(std::isfinite(p.s) && p.s != 0.f)) return fail(WIRE_ERR_ARG, "bspline scale0 %g is zero or not finite", (double)p.s);
     p.s = (float)(1.0 / fabs((double)p.s));
+  }
+  if (p.kind == WIRE_KIND_BSPLINE_CUBIC) {
+    // scale_0 multiplies the layer's input (modules/bspline_cubic.py:45), sign included: into the weights (Plan::ws); the
+    // activation is B(lin) itself, so the kernels' scale is 1 (the whole-net kernels fold c = 1, the chain reads fp.s = 1)
+    if (!(std::isfinite(p.s) && p.s != 0.f)) return fail(WIRE_ERR_ARG, "bspline_cubic scale0 %g is zero or not finite", (double)p.s);
+    p.ws = p.s;
+    p.s = 1.f;
   }
   if (p.D < 1 || p.D > 4) return fail(WIRE_ERR_ARG, "in_features %d outside 1..4", p.D);
   if (p.K < 1 || p.K > 4096) return fail(WIRE_ERR_ARG, "width %d outside 1..4096", p.K);
@@ -326,6 +335,7 @@ int epi_fwd(int kind) {
     case WIRE_KIND_SIREN: return EPI_SIREN_FWD;
     case WIRE_KIND_GAUSS: return EPI_GAUSS_FWD;
     case WIRE_KIND_BSPLINE: return EPI_BSPLINE_FWD;
+    case WIRE_KIND_BSPLINE_CUBIC: return EPI_BSPLINE3_FWD;
     default: return EPI_RELU_FWD;
   }
 }
@@ -336,6 +346,7 @@ int epi_bwd(int kind) {
     case WIRE_KIND_SIREN: return EPI_SIREN_BWD;
     case WIRE_KIND_GAUSS: return EPI_GAUSS_BWD;
     case WIRE_KIND_BSPLINE: return EPI_BSPLINE_BWD;
+    case WIRE_KIND_BSPLINE_CUBIC: return EPI_BSPLINE3_BWD;
     default: return EPI_RELU_BWD;
   }
 }
@@ -344,7 +355,7 @@ int epi_bwd(int kind) {
 // route: what one whole-net call runs, decided once from (plan, n, entry point)
 // ---------------------------------------------------------------------------
 // Power-of-two split scale of activations with an a-priori bound (bound < 2^e -> 2^(15 - e): |out| scale < 2^15): sine
-// and Gaussian <= 1; Gabor |exp(j w lin - s^2 |lin|^2)| = exp(-w v - s^2 (u^2 + v^2)) <= exp((w / 2s)^2), attained at
+// and Gaussian <= 1, the B-splines <= 3/4 and 2/3; Gabor |exp(j w lin - s^2 |lin|^2)| = exp(-w v - s^2 (u^2 + v^2)) <= exp((w / 2s)^2), attained at
 // lin = -j w / 2 s^2 -- accepted up to 16 (w / s <= 3.33: every configuration of the reference's scripts); 0 beyond it
 static float act_bound_scale(const Plan& p) {
   double bound = 1.0;
@@ -409,14 +420,16 @@ Route make_route(const Plan& p, int64_t n, RouteMode mode) {
   r.chain = (r.fused_train || m2_chain) && p.k_fused_bwd && p.off_fxd >= 0;
   r.fused_final = r.chain && r.fused_train && !p.cplx && p.k_fused_final;
   r.rstore = r.chain && r.fused_train && p.k_rstore &&
-             (p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_GAUSS || p.kind == WIRE_KIND_BSPLINE);   // 1.3 GB per step less
+             (p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_GAUSS || p.kind == WIRE_KIND_BSPLINE ||
+              p.kind == WIRE_KIND_BSPLINE_CUBIC);                                                       // 1.3 GB per step less
   // out_l is stored pre-split (wire_dev.h: wire_store_out4) when the call runs the 2 x fp16 kernels and every reader of
   // out_l understands the format: the forward GEMM of layer l + 1 (pre-split A edition), the weight-gradient GEMM of layer
   // l + 1 (gemmx2_tn16, pre-split Z) and NOTHING else -- the data-gradient epilogue of layer l + 1 must evaluate
   // act(lin_l) again rather than read out_l (recompute_out; sine and B-spline need no out), out_0 comes from first_fwd_kernel, out_L
   // feeds the final linear layer in fp32, relu's out carries its backward's sign decisions
   const bool split = x2tn && p.k_split_out && p.kind != WIRE_KIND_RELU &&
-                     (p.k_recompute_out || p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_BSPLINE);
+                     (p.k_recompute_out || p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_BSPLINE ||
+                      p.kind == WIRE_KIND_BSPLINE_CUBIC);
   for (int l = 1; l < p.L; ++l) r.out_scale[l] = !split ? 0.f : ftrain ? 1.f : act_bound_scale(p);
   // the layer-1 data gradient of a native first layer on the 16 x 16 x 32 kernel: its epilogue can sum g_lin_0 (wire:
   // g_u) [x | 1] per tile itself instead of storing it for a separate pass, and form the coordinate-gradient partials

@@ -7,7 +7,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-enum { NK_WIRE = 0, NK_WIRE2D = 1, NK_SIREN = 2, NK_GAUSS = 3, NK_RELU = 4, NK_BSPLINE = 5 };
+// (the values of wire_kind, include/wire_hip.h: a plan's kind is handed to the launchers as it is)
+enum { NK_WIRE = 0, NK_WIRE2D = 1, NK_SIREN = 2, NK_GAUSS = 3, NK_RELU = 4, NK_BSPLINE = 5, NK_BSPLINE3 = 12 };
+// the ACT_* code (wire_dev.h) of a real kind: siren 0 .. bspline 3 in the order of the NK_* values, the cubic B-spline 4;
+// 0 for the complex kinds, whose kernels never evaluate it
+constexpr int nk_real_act(int kind) { return kind == NK_BSPLINE3 ? 4 : kind < NK_SIREN ? 0 : kind - NK_SIREN; }
 
 #define WIRE_MAXO 8        // outputs of the final linear (the point kernels keep one accumulator per output in registers)
 // final_fwd_kernel keeps W_f [O][P] in dynamic LDS and a launch gets 64 KB of it without an opt-in: O x P floats at most.
@@ -28,7 +32,9 @@ static inline int prereduce_room(int nblk) { return nblk + PRE_CHUNKS; }
 // ---- native nn.Parameter layout -> padded real-expanded image
 hipError_t launch_pack_hidden(hipStream_t s, int kind, const float* W, const float* b,
                               const float* V, const float* c, int K, int Kin, int P, int Pin,
-                              float* Bt_fwd, float* Bt_dgrad, float* bias);
+                              float* Bt_fwd, float* Bt_dgrad, float* bias, float wscale = 1.f);
+// (wscale != 1, real kinds: the images hold wscale W, the bias stays as it is -- the cubic B-spline layer's scale_0, which
+// multiplies the layer's input: s (x W^T) + b = x (s W)^T + b)
 // several layers of one shape per launch (grid.z = layer)
 #define PACK_MAXB 16
 struct PackBatch {
@@ -36,7 +42,8 @@ struct PackBatch {
   float* fwd[PACK_MAXB]; float* dg[PACK_MAXB]; float* bias[PACK_MAXB];
 };
 hipError_t launch_pack_hidden_batch(hipStream_t s, int kind, const PackBatch& pb, int nb, int K, int Kin, int P,
-                                    int Pin);
+                                    int Pin, float wscale = 1.f);
+hipError_t launch_scale_copy(hipStream_t s, const float* src, int64_t n, float c, float* dst);   // dst = c src
 hipError_t launch_pack3m_batch(hipStream_t s, const PackBatch& pb, int nb, int K, int Kin, int Kp, int Kpin);
 hipError_t launch_pack_final(hipStream_t s, int kind, const float* Wf, const float* bf, int K,
                              int P, int O, float* wf, float* bfr);
@@ -117,15 +124,19 @@ hipError_t launch_final_reduce(hipStream_t s, int kind, float* part_w, float* pa
 // ---- weight-gradient slab reduction: slab[S][Pm][Pn] (+ bslab[S][Pm]) -> native grads
 hipError_t launch_wgrad_reduce(hipStream_t s, int kind, const float* slab, const float* bslab,
                                int S, int K, int Kin, int Pm, int Pn, float* gW, float* gb,
-                               float* gV, float* gc);
+                               float* gV, float* gc, float wscale = 1.f);
+// (wscale != 1, here and in the first-layer reductions below: g_W is multiplied by it on the way out, g_b is not -- the
+// GEMMs ran on wscale W, so the slabs hold dL / d(wscale W))
 
 // ---- first-layer weight gradient: g_W0[c][d] = sum_n G[n][c] x[n][d], g_b0[c] = sum_n G[n][c]
 int colreduce_blocks(int64_t n);
 // partial must have room for prereduce_room(colreduce_blocks(n)) * C * 5 floats
-hipError_t launch_colreduce_final(hipStream_t s, int C, int D, int64_t n, float* partial, float* gW0, float* gb0);
-hipError_t launch_colreduce_final_blocks(hipStream_t s, int C, int D, int nblk, float* partial, float* gW0, float* gb0);
+hipError_t launch_colreduce_final(hipStream_t s, int C, int D, int64_t n, float* partial, float* gW0, float* gb0,
+                                  float wscale = 1.f);
+hipError_t launch_colreduce_final_blocks(hipStream_t s, int C, int D, int nblk, float* partial, float* gW0, float* gb0,
+                                         float wscale = 1.f);
 hipError_t launch_colreduce(hipStream_t s, const float* G, int ldg, int C, const float* x, int D,
-                            int64_t n, float* partial, float* gW0, float* gb0);
+                            int64_t n, float* partial, float* gW0, float* gb0, float wscale = 1.f);
 
 // ---- 3M complex path: slab reduction
 hipError_t launch_wgrad3m_reduce(hipStream_t s, const float* slab, const float* bslab, int S, int K, int Kin,

@@ -94,10 +94,12 @@ hipError_t launch_final_reduce(hipStream_t s, int kind, float* part_w, float* pa
 // ===========================================================================
 // block = 64 input features x 4 groups of row splits (group q sums splits q, q + 4, ... with four loads in
 // flight); the four partial sums are combined through LDS in a fixed order (deterministic, no atomics).
+// WS (real kinds): g_W is multiplied by ws on the way out, g_b is not (launch_wgrad_reduce: wscale)
+template <bool WS>
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(int kind, const float* __restrict__ slab,
                                     const float* __restrict__ bslab, int S, int K, int Kin, int Pm,
                                     int Pn, float* __restrict__ gW, float* __restrict__ gb,
-                                    float* __restrict__ gV, float* __restrict__ gc) {
+                                    float* __restrict__ gV, float* __restrict__ gc, float ws) {
   __shared__ float red[4][4][64];       // [value][group][feature]
   const int tx = threadIdx.x & 63, q = threadIdx.x >> 6;
   const int i = blockIdx.x * 64 + tx;
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(int kind, const float
           gWm[((size_t)o * Kin + i) * 2] = wr;
           gWm[((size_t)o * Kin + i) * 2 + 1] = wi;
         } else {
-          gWm[(size_t)o * Kin + i] = wr;
+          gWm[(size_t)o * Kin + i] = WS ? ws * wr : wr;
         }
       }
       if (tx == 0 && blockIdx.x == 0) {
@@ -161,10 +163,14 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(int kind, const float
 
 hipError_t launch_wgrad_reduce(hipStream_t s, int kind, const float* slab, const float* bslab,
                                int S, int K, int Kin, int Pm, int Pn, float* gW, float* gb,
-                               float* gV, float* gc) {
+                               float* gV, float* gc, float wscale) {
   dim3 grid(cdiv(Kin, 64), (unsigned)K);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, grid, dim3(256), 0, s, kind, slab, bslab, S, K, Kin, Pm,
-                     Pn, gW, gb, gV, gc);
+  if (wscale != 1.f)
+    hipLaunchKernelGGL(wgrad_reduce_kernel<true>, grid, dim3(256), 0, s, kind, slab, bslab, S, K, Kin, Pm,
+                       Pn, gW, gb, gV, gc, wscale);
+  else
+    hipLaunchKernelGGL(wgrad_reduce_kernel<false>, grid, dim3(256), 0, s, kind, slab, bslab, S, K, Kin, Pm,
+                       Pn, gW, gb, gV, gc, 1.f);
   return hipGetLastError();
 }
 
@@ -222,9 +228,10 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict_
   }
 }
 
+template <bool WS>
 __global__ __launch_bounds__(256) void colreduce_final_kernel(const float* __restrict__ partial, int nblk,
                                                               int C, int D, float* __restrict__ gW0,
-                                                              float* __restrict__ gb0) {
+                                                              float* __restrict__ gb0, float ws) {
   __shared__ float red[4][64][5];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx;
@@ -242,33 +249,39 @@ __global__ __launch_bounds__(256) void colreduce_final_kernel(const float* __res
   if (ty == 0 && c < C) {
 #pragma unroll
     for (int d = 0; d < 5; ++d) acc[d] = (red[0][tx][d] + red[1][tx][d]) + (red[2][tx][d] + red[3][tx][d]);
-    for (int d = 0; d < D; ++d) gW0[c * D + d] = acc[d];
+    for (int d = 0; d < D; ++d) gW0[c * D + d] = WS ? ws * acc[d] : acc[d];
     gb0[c] = acc[4];
   }
 }
 
 // stage 2 alone: partial[colreduce_blocks(n)][C][5] already holds the per-256-row sums (written by the data-gradient
 // epilogue of wire_gemmx3h.hip, GemmEpiParams::cr_partial)
-hipError_t launch_colreduce_final(hipStream_t s, int C, int D, int64_t n, float* partial, float* gW0, float* gb0) {
-  return launch_colreduce_final_blocks(s, C, D, colreduce_blocks(n), partial, gW0, gb0);
+hipError_t launch_colreduce_final(hipStream_t s, int C, int D, int64_t n, float* partial, float* gW0, float* gb0,
+                                  float wscale) {
+  return launch_colreduce_final_blocks(s, C, D, colreduce_blocks(n), partial, gW0, gb0, wscale);
 }
 // the same over nblk blocks of any row count (the data-gradient chain of wire_fused.hip writes one per workgroup); partial
 // must have room for prereduce_room(nblk) * C * 5 floats
-hipError_t launch_colreduce_final_blocks(hipStream_t s, int C, int D, int nblk, float* partial, float* gW0, float* gb0) {
+hipError_t launch_colreduce_final_blocks(hipStream_t s, int C, int D, int nblk, float* partial, float* gW0, float* gb0,
+                                         float wscale) {
   if (D > 4 || nblk < 1) return hipErrorInvalidValue;
   float* p2 = partial + (size_t)nblk * C * 5;            // the slack prereduce_room reserves
   const int nb = prereduce(s, partial, nblk, C * 5, p2);
-  hipLaunchKernelGGL(colreduce_final_kernel, dim3(cdiv(C, 64)), dim3(256), 0, s, nb == nblk ? partial : p2, nb,
-                     C, D, gW0, gb0);
+  if (wscale != 1.f)
+    hipLaunchKernelGGL(colreduce_final_kernel<true>, dim3(cdiv(C, 64)), dim3(256), 0, s, nb == nblk ? partial : p2, nb,
+                       C, D, gW0, gb0, wscale);
+  else
+    hipLaunchKernelGGL(colreduce_final_kernel<false>, dim3(cdiv(C, 64)), dim3(256), 0, s, nb == nblk ? partial : p2, nb,
+                       C, D, gW0, gb0, 1.f);
   return hipGetLastError();
 }
 hipError_t launch_colreduce(hipStream_t s, const float* G, int ldg, int C, const float* x, int D,
-                            int64_t n, float* partial, float* gW0, float* gb0) {
+                            int64_t n, float* partial, float* gW0, float* gb0, float wscale) {
   if (D > 4 || (ldg & 3)) return hipErrorInvalidValue;
   const int nblk = colreduce_blocks(n);
   dim3 grid((unsigned)nblk, cdiv(C, 256));
   hipLaunchKernelGGL(colreduce_kernel, grid, dim3(256), 0, s, G, ldg, C, x, D, (long long)n, partial);
-  return launch_colreduce_final(s, C, D, n, partial, gW0, gb0);
+  return launch_colreduce_final(s, C, D, n, partial, gW0, gb0, wscale);
 }
 
 // ===========================================================================

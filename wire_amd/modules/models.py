@@ -13,13 +13,18 @@ arguments its own signature has, so both call styles work:
     get_INR('wire', 2, 300, 0, 2, 3, scale_tensor=[0.0], ...)   # bspline_* style
 
 The multiplicative filter network is reached as ``wire_amd.modules.mfn.INR(...)``; ``get_INR('mfn', ...)`` raises
-NotImplementedError naming that constructor until the factory moves over.
+NotImplementedError naming that constructor until the factory moves over.  The cubic B-spline net runs on the MI355X hot
+path too, through its own constructor ``wire_amd.modules.bspline_cubic.INR(...)``; ``get_INR('bspline_cubic', ...)`` still
+raises: tests pin that, and the reference's own factory cannot build the net either -- ``bspline_cubic.INR`` takes
+``hidden_layers`` before ``scaled_hidden_features`` and ``get_INR`` passes the two positionally in the other order.
 """
 from . import bspline_form, bspline_mscale_2, bspline_mscale_HL, bspline_mscale_hier, gauss, relu, siren, wire, wire2d
 
 # keys of modules/models.py:15-25 that this factory builds.  'mfn' is on the MI355X path but is not built here yet (three
 # tests pin the NotImplementedError): construct it with wire_amd.modules.mfn.INR, as the reference's own factory cannot
-# build it either.  'bspline_cubic' is out of scope (SURVEY.md section 2.1 row 8).
+# build it either.  'bspline_cubic' is on the MI355X path as well, through wire_amd.modules.bspline_cubic.INR; the factory
+# keeps raising for it for the same two reasons (pinned by tests; the reference's get_INR swaps its hidden_layers and
+# scaled_hidden_features), so the tuple below now names the keys this factory does not build, not kinds without kernels.
 model_dict = {'bspline_form': bspline_form,
               'bspline_mscale_2': bspline_mscale_2,
               'bspline_mscale_HL': bspline_mscale_HL,
