@@ -82,7 +82,8 @@ hipError_t layer_nt(hipStream_t s, const Plan& p, WireFamily f, const float* pac
   switch (f) {
     case FAM_X2:
       ep.amax_a = amax_a; ep.amax_b = amax_b; ep.amax_out = amax_out;
-      return launch_gemmx2h_nt(s, epi, A, Kd, packed + (dg ? p.off_dg_x2 : p.off_fwd_x2)[l], n, Nc, Kd, ep);
+      return launch_gemmx2h_nt(s, epi, A, Kd, packed + (dg ? p.off_dg_x2 : p.off_fwd_x2)[l], n, Nc, Kd, ep,
+                               x2_waits(p.k_nt_bfirst, p.k_epi_early));
     case FAM_3M:
       return launch_gemm3m_nt(s, epi, A, Kd, packed + (dg ? p.off_dg_3m : p.off_fwd_3m)[l], Kd, n, Nc / 2, Kd / 2, ep);
     case FAM_X3: return launch_gemmx3_nt(s, epi, A, Kd, packed + (dg ? p.off_dg_x3 : p.off_fwd_x3)[l], n, Nc, Kd, ep);

@@ -165,8 +165,14 @@ int64_t gemmx2_b_image_floats(int Nc, int Kd);
 #define X2_SPLIT_MAXB 32
 struct X2SplitBatch { const float* src[X2_SPLIT_MAXB]; void* dst[X2_SPLIT_MAXB]; const unsigned* slots[X2_SPLIT_MAXB]; };
 hipError_t launch_x2_split_b_batch(hipStream_t s, const X2SplitBatch& sb, int nb, int ldb, int Nc, int Kd);
+// waits: how the main loop of the editions that read A through LDS waits (wire_gemmx2h.hip: WT; 0 = as ever, same bits) --
+// X2_WT_BFIRST (knob "nt_bfirst"): weight pieces first, a stage barrier that does not wait for the wave's rows;
+// X2_WT_EARLY (knob "epi_early"): the epilogue's first loads under the last stage's MFMAs, for the forms that have some
+#define X2_WT_BFIRST 1
+#define X2_WT_EARLY 2
+inline int x2_waits(bool nt_bfirst, bool epi_early) { return (nt_bfirst ? X2_WT_BFIRST : 0) | (epi_early ? X2_WT_EARLY : 0); }
 hipError_t launch_gemmx2h_nt(hipStream_t s, int epi, const float* A, int lda, const void* Bx2, int64_t M, int Nc,
-                             int Kd, const GemmEpiParams& ep);
+                             int Kd, const GemmEpiParams& ep, int waits = 0);
 bool gemmx2_tn_applies(int Pm, int Pn);
 int gemmx2_tn_splits(int64_t n, int Pm, int Pn, int max_splits);
 hipError_t launch_gemmx2_tn(hipStream_t s, const float* G, int ldg, const float* Z, int ldz, int64_t n, int Pm,

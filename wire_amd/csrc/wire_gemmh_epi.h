@@ -4,6 +4,8 @@
 // Reference arithmetic: modules/wire.py:88-93, wire2d.py:56-67, siren.py:48-49, gauss.py:27-28, relu.py:28-29 and the
 // autograd backward of each.
 #pragma once
+#include <type_traits>
+
 #include "wire_dev.h"
 #include "wire_gemm.h"
 
@@ -62,6 +64,39 @@ WIRE_DEVINL void h_cg_store(const float (&cg)[4], const GemmEpiParams& ep, const
 }
 
 // ---------------------------------------------------------------------------
+// The epilogue's first loads, issued by the GEMM under the MFMAs of its last stage (wire_gemmx2h.hip, knob "epi_early")
+// and handed to h_epilogue, which then does not load them again: the same values, one memory round trip earlier.
+//   HPreLin   EPI_GABOR_BWD | EPI_LA: lin of row block 0 of the first group ([rows 0-7 | 8-15]; the look-ahead itself
+//             loads every later block, the second group's first one included, under the block before it)
+//   HPreFirst EPI_GABOR_BWD_FIRST | EPI_D2: the lane's coordinates, W0 / b0 of both groups (below)
+// A group outside the matrix (the last column tile of a width that is no multiple of 128) is loaded from group 0's
+// addresses and not used.  HPreNone: every other form, and "epi_early" = 0 -- among them the forms whose early
+// edition spills: lin of both groups' block 0 for EPI_LA (64 bytes per lane), the layer-1 forms with
+// EPI_CG or EPI_D3 (16 - 80), and wire2d's layer-1 forms, which spill as they are; and EPI_GABOR_FWD, whose only
+// load is 2 KB of bias per tile: loaded early it moved the forward launches by nothing (1.7588 -> 1.7586 ms per step).
+// ---------------------------------------------------------------------------
+struct HPreNone {};
+struct HPreLin { f32x4 u[2], v[2]; };
+template <int DN, int NRB> struct HPreFirst { float xs[2 * NRB][DN], w[2][4][DN], bb[2][4]; };
+template <int EPIX, int NRB>
+using h_pre_t = std::conditional_t<EPIX == (EPI_GABOR_BWD | EPI_LA), HPreLin,
+                                   std::conditional_t<EPIX == (EPI_GABOR_BWD_FIRST | EPI_D2), HPreFirst<2, NRB>, HPreNone>>;
+
+WIRE_DEVINL void h_pre_load(HPreNone&, const GemmEpiParams&, const int, const int, const int, const int, const int) {}
+WIRE_DEVINL void h_pre_load(HPreLin& pre, const GemmEpiParams& ep, const int M, const int m_w, const int n_w,
+                            const int Nc, const int lane) {
+  const int rr = lane & 7, cq = 16 * ((lane >> 3) & 1) + 4 * (lane >> 4);
+#pragma unroll
+  for (int hr = 0; hr < 2; ++hr) {                                // (= load_lin(0, ..) of h_gabor_bwd_la)
+    int row = m_w + 8 * hr + rr;
+    row = row < M ? row : M - 1;
+    const float* Lp = ep.i0 + (size_t)row * ep.ld0 + n_w + cq;
+    pre.u[hr] = *reinterpret_cast<const f32x4*>(Lp);
+    pre.v[hr] = *reinterpret_cast<const f32x4*>(Lp + 32);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // The layer-1 data-gradient forms of the complex nets with the input width a compile-time constant DN = 2, 3 (EPI_D2,
 // EPI_D3; knob "first_dn").  Same values as the plain forms in h_epilogue below, which run every chain over four terms with
 // x[d] = w[d] = +0 for d >= D: fmaf(+0, +0, u) = u for every u but -0 (which it turns into +0: the plain form departs
@@ -109,15 +144,12 @@ WIRE_DEVINL void h_crs_to_lds_dn(const float (&crs)[4][DN + 1], float* red, cons
   }
 }
 
-template <bool CG, int DN, int NRB>
-WIRE_DEVINL void h_gabor_bwd_first_dn(const f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const int M, const int m_w,
-                                      const int n_w, const int Nc, const int lane, unsigned char* lds, const int wave,
-                                      const int rt) {
+// the lane's coordinates and the first layer's parameters of both column groups (pad features: 0)
+template <int DN, int NRB>
+WIRE_DEVINL void h_pre_load(HPreFirst<DN, NRB>& pre, const GemmEpiParams& ep, const int M, const int m_w, const int n_w,
+                            const int Nc, const int lane) {
   const int rr = lane & 7, cq = 16 * ((lane >> 3) & 1) + 4 * (lane >> 4);
-  const float w0 = ep.omega, m2s2 = -2.f * ep.scale * ep.scale;
-  float xs[2 * NRB][DN];
-  h_load_rows_dn<DN, NRB>(xs, ep, M, m_w, rr);
-  float w[2][4][DN], bb[2][4];
+  h_load_rows_dn<DN, NRB>(pre.xs, ep, M, m_w, rr);
 #pragma unroll
   for (int G = 0; G < 2; ++G) {
     const int c0 = n_w + 64 * G + cq;
@@ -125,11 +157,26 @@ WIRE_DEVINL void h_gabor_bwd_first_dn(const f32x4 (&acc)[NRB][8], const GemmEpiP
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const bool valid = f0 + q < ep.kvalid;
-      bb[G][q] = valid ? ep.b0[f0 + q] : 0.f;
+      pre.bb[G][q] = valid ? ep.b0[f0 + q] : 0.f;
 #pragma unroll
-      for (int d = 0; d < DN; ++d) w[G][q][d] = valid ? ep.W0[(f0 + q) * DN + d] : 0.f;
+      for (int d = 0; d < DN; ++d) pre.w[G][q][d] = valid ? ep.W0[(f0 + q) * DN + d] : 0.f;
     }
   }
+}
+
+// PRE = HPreFirst<DN, NRB>: the GEMM loaded them (above); HPreNone: loaded here
+template <bool CG, int DN, int NRB, typename PRE>
+WIRE_DEVINL void h_gabor_bwd_first_dn(const f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const int M, const int m_w,
+                                      const int n_w, const int Nc, const int lane, unsigned char* lds, const int wave,
+                                      const int rt, const PRE& pre) {
+  const int rr = lane & 7, cq = 16 * ((lane >> 3) & 1) + 4 * (lane >> 4);
+  const float w0 = ep.omega, m2s2 = -2.f * ep.scale * ep.scale;
+  HPreFirst<DN, NRB> ld;
+  if constexpr (std::is_same_v<PRE, HPreFirst<DN, NRB>>) ld = pre;
+  else h_pre_load(ld, ep, M, m_w, n_w, Nc, lane);
+  const auto& xs = ld.xs;
+  const auto& w = ld.w;
+  const auto& bb = ld.bb;
   float cg[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int G = 0; G < 2; ++G) {
@@ -351,9 +398,11 @@ WIRE_DEVINL void h_gabor2d_bwd_first_dn(const f32x4 (&acc)[NRB][8], const GemmEp
 // (Tried and dropped: a second copy of the loop with unconditional stores for waves whose rows all lie inside the matrix,
 // so that the waits need not allow for a store that was branched over -- the freer schedule spills, 64 - 104 bytes.)
 // ---------------------------------------------------------------------------
-template <bool X2, int NRB>
+// PRE = HPreLin: row block 0 came in under the GEMM's last stage (h_pre_load above)
+template <bool X2, int NRB, typename PRE>
 WIRE_DEVINL void h_gabor_bwd_la(const f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const int M, const int m_w,
-                                const int n_w, const int Nc, const int lane, float& amx) {
+                                const int n_w, const int Nc, const int lane, float& amx, const PRE& pre) {
+  constexpr bool EARLY = std::is_same_v<PRE, HPreLin>;
   const int rr = lane & 7, cq = 16 * ((lane >> 3) & 1) + 4 * (lane >> 4);
   const float w0 = ep.omega, w0l2e = ep.omega * 1.44269502f, ns2l2e = -(ep.scale * ep.scale) * 1.44269502f;
   const float m2s2 = -2.f * ep.scale * ep.scale;
@@ -370,7 +419,8 @@ WIRE_DEVINL void h_gabor_bwd_la(const f32x4 (&acc)[NRB][8], const GemmEpiParams&
     }
   };
   f32x4 lu[2], lv[2];
-  load_lin(0, lu, lv);
+  if constexpr (EARLY) { lu[0] = pre.u[0]; lu[1] = pre.u[1]; lv[0] = pre.v[0]; lv[1] = pre.v[1]; }
+  else load_lin(0, lu, lv);
 #pragma unroll
   for (int i = 0; i < 2 * NRB; ++i) {
     const int G = i / NRB, rb = i % NRB;
@@ -423,11 +473,14 @@ WIRE_DEVINL void h_gabor_bwd_la(const f32x4 (&acc)[NRB][8], const GemmEpiParams&
 // EPIX = an EPI_* code, | EPI_CG for the layer-1 data-gradient forms that also write coordinate-gradient partials
 // (ep.cg_partial): a separate instantiation, so the forms without it keep their registers; | EPI_D2 or EPI_D3 for the
 // compile-time-width editions of the *_BWD_FIRST forms above; | EPI_LA for the look-ahead edition of GABOR_BWD
-template <int EPIX, bool X2 = false, int NRB = 4>
+// PRE = h_pre_t<EPIX, NRB>: the form's first loads, already issued by the caller (h_pre_load); HPreNone: none
+template <int EPIX, bool X2 = false, int NRB = 4, typename PRE = HPreNone>
 WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const int M, const int m_w, const int n_w,
                             const int Nc, const int lane, unsigned char* lds, const int wave, const int rt,
-                            const float acc_scale = 1.f) {
+                            const float acc_scale = 1.f, const PRE& pre = PRE{}) {
   constexpr int EPI = EPIX & ~EPI_FLAGS;
+  constexpr bool EARLY = !std::is_same_v<PRE, HPreNone>;
+  static_assert(!EARLY || std::is_same_v<PRE, h_pre_t<EPIX, NRB>>, "the early loads of this form");
   constexpr bool CG = (EPIX & EPI_CG) != 0;
   constexpr int DN = (EPIX & EPI_D2) ? 2 : (EPIX & EPI_D3) ? 3 : 0;   // compile-time input width of the *_BWD_FIRST forms
   constexpr bool LA = (EPIX & EPI_LA) != 0;
@@ -702,9 +755,9 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
       }
     }
   } else if constexpr (EPI == EPI_GABOR_BWD && LA) {
-    h_gabor_bwd_la<X2, NRB>(acc, ep, M, m_w, n_w, Nc, lane, amx);
+    h_gabor_bwd_la<X2, NRB>(acc, ep, M, m_w, n_w, Nc, lane, amx, pre);
   } else if constexpr (EPI == EPI_GABOR_BWD_FIRST && DN != 0) {
-    h_gabor_bwd_first_dn<CG, DN, NRB>(acc, ep, M, m_w, n_w, Nc, lane, lds, wave, rt);
+    h_gabor_bwd_first_dn<CG, DN, NRB>(acc, ep, M, m_w, n_w, Nc, lane, lds, wave, rt, pre);
   } else if constexpr (EPI == EPI_GABOR2D_BWD_FIRST && DN != 0) {
     h_gabor2d_bwd_first_dn<CG, DN, NRB>(acc, ep, M, m_w, n_w, Nc, lane, lds, wave, rt);
   } else if constexpr (EPI == EPI_GABOR2D_BWD || EPI == EPI_GABOR2D_BWD_FIRST) {
@@ -939,7 +992,8 @@ WIRE_DEVINL void h_epilogue(f32x4 (&acc)[NRB][8], const GemmEpiParams& ep, const
                 o_re[q] = valid ? a : 0.f;
                 o_im[q] = valid ? b : 0.f;
               }
-              if constexpr (X2) { h_amax4(amx, o_re); h_amax4(amx, o_im); }
+              // (null: out_l is stored pre-split with a scale fixed on the host -- nobody reads its maximum)
+              if (X2 && ep.amax_out) { h_amax4(amx, o_re); h_amax4(amx, o_im); }
               if (row < M) {
                 float* Op = ep.o1 + (size_t)row * ep.ld1 + c0;
                 wire_store_out4(Op, o_re, X2 ? ep.o1_split : 0.f);

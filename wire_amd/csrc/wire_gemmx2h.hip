@@ -151,7 +151,18 @@ hipError_t launch_x2_split_b_batch(hipStream_t s, const X2SplitBatch& sb, int nb
 // APRE: A is a pre-split activation (wire_dev.h: wire_store_out4; scale fixed on the host, ep.a_split_inv): the 32 bytes a
 // lane loads per 16-row block ARE its two fragments up to a register shuffle -- no vector arithmetic between the loads and
 // the MFMAs (measured with the loaded bytes taken as the fragments, profiles/r03_gemm_x2_presplit_probe.txt: - 7 % per launch).
-template <int EPI, int AMODE, int NRB, int PFD = 1, bool APRE = false>
+// WT = how the main loop waits (A through LDS, PFD 1 only; 0 = the loop as it was), the same bits either way.  Every WT != 0
+// edition runs its last stage, in which nothing is issued, as a copy of its own behind the loop.
+//  X2_WT_BFIRST (wire_gemm.h; "nt_bfirst"): the weight pieces of stage kt + 1 go out BEFORE the wave's own rows, and the stage
+//    ends with s_waitcnt vmcnt(2 NRB) ahead of the barrier -- loads return in order, so that guarantees the wave's four weight pieces
+//    and leaves its rows in flight.  The barrier is about the shared weight stage alone (its pieces published, the other
+//    buffer free); the rows land in a region no other wave reads, and their owner waits for them (vmcnt(0)) at the top of
+//    the next stage, just ahead of the ds_reads.  With vmcnt(0) at the barrier every wave of the workgroup waits for the
+//    slowest wave's HBM round trip, 16 times per tile at K = 256.
+//  X2_WT_EARLY ("epi_early", AMODE 2, the forms with an h_pre_t): after the last stage's split -- the 32 raw registers are
+//    dead from there on -- the epilogue's first loads go out (wire_gemmh_epi.h: h_pre_load) and land under the
+//    stage's 96 MFMAs instead of opening the epilogue with a round trip that nothing hides.
+template <int EPI, int AMODE, int NRB, int PFD = 1, bool APRE = false, int WT = 0>
 __global__ __launch_bounds__(256, (NRB == 2 ? 3 : 2)) void gemmx2h_nt_kernel(const float* __restrict__ A, int lda,
                                                             const unsigned short* __restrict__ Bx2, int M, int Nc,
                                                             int Kd, int tiles_m, int tiles_n, GemmEpiParams ep) {
@@ -162,6 +173,8 @@ __global__ __launch_bounds__(256, (NRB == 2 ? 3 : 2)) void gemmx2h_nt_kernel(con
                 "two stages of prefetch: 128-row tile, A in registers; weight ring: the default tile");
   constexpr bool BRING = PFD == 3;
   static_assert(!APRE || ((AMODE == 1 || AMODE == 2) && NRB == 4 && PFD == 1), "pre-split A: the 256-row editions only");
+  static_assert(WT == 0 || ((AMODE == 0 || AMODE == 2) && NRB == 4 && PFD == 1), "the loosened waits: A through LDS, one stage ahead");
+  static_assert(!(WT & X2_WT_EARLY) || AMODE == 2, "early epilogue loads: the default A mode only");
   constexpr int A_LDS = NRB == 4 ? X2_ABYTES : 0;      // (AMODE 1 at NRB 4: this part only serves the epilogues' reductions)
   constexpr int TBM = 64 * NRB;
   __shared__ __attribute__((aligned(1024))) unsigned char smem[A_LDS + (PFD == 1 ? 2 : 3) * X2_BSTAGE];
@@ -244,7 +257,7 @@ __global__ __launch_bounds__(256, (NRB == 2 ? 3 : 2)) void gemmx2h_nt_kernel(con
       araw[rb][1] = *reinterpret_cast<const f32x4*>(ab + g_off[rb] + 16);
     }
   };
-  auto issue = [&](int kt, int buf) {
+  auto issue_a = [&](int kt) {
     const char* ab = a_tile + (size_t)kt * (X2_BK * 4);
     if constexpr (AMODE == 0) {
 #pragma unroll
@@ -260,11 +273,14 @@ __global__ __launch_bounds__(256, (NRB == 2 ? 3 : 2)) void gemmx2h_nt_kernel(con
         x2_dma16(ab + a_off2[rb][1], a_lds + rb * 2048 + 1024);
       }
     }
+  };
+  auto issue_b = [&](int kt, int buf) {
     const char* bb = b_tile + (size_t)kt * X2_BSTAGE;
     unsigned char* S = smem + A_LDS + buf * X2_BSTAGE + wave * 1024;
 #pragma unroll
     for (int j = 0; j < 4; ++j) x2_dma16(bb + b_off + j * 4096, S + j * 4096);
   };
+  auto issue = [&](int kt, int buf) { issue_a(kt); issue_b(kt, buf); };
 
   f32x4 acc[NRB][8];
 #pragma unroll
@@ -348,6 +364,94 @@ __global__ __launch_bounds__(256, (NRB == 2 ? 3 : 2)) void gemmx2h_nt_kernel(con
       half_stage(ar1, kt + 1);
     }
     h_epilogue<EPI, true, NRB>(acc, ep, M, m_base + wave * (16 * NRB), n_base, Nc, lane, smem, wave, rt, inv_a * inv_b);
+    return;
+  }
+
+  if constexpr (WT != 0) {
+    constexpr bool BF = (WT & X2_WT_BFIRST) != 0, EARLY = (WT & X2_WT_EARLY) != 0;
+    // what the end-of-stage wait of BF leaves in flight: the wave's own rows of the next stage, issued after its weight pieces
+    constexpr int A_PIECES = 2 * NRB;
+    static_assert(A_PIECES == 8, "the in-flight count of the end-of-stage wait");
+    std::conditional_t<EARLY, h_pre_t<EPI, NRB>, HPreNone> pre;
+    static_assert(!EARLY || !std::is_same_v<h_pre_t<EPI, NRB>, HPreNone>, "early loads: the forms that have some");
+    auto stage = [&](const int kt, const int buf, auto last_c) {
+      constexpr bool LAST = decltype(last_c)::value;
+      // the wave's rows of this stage (BF: still in flight at the barrier behind us; nothing else is)
+      if constexpr (BF) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int rb = 0; rb < NRB; ++rb) {
+        if constexpr (AMODE == 2) {
+          araw[rb][0] = *reinterpret_cast<const f32x4*>(smem + a2_rd0 + rb * 2048);
+          araw[rb][1] = *reinterpret_cast<const f32x4*>(smem + a2_rd1 + rb * 2048);
+        } else {
+          araw[rb][0] = *reinterpret_cast<const f32x4*>(smem + a_rd + rb * 2048);
+          araw[rb][1] = *reinterpret_cast<const f32x4*>(smem + a_rd + rb * 2048 + 256);
+        }
+      }
+      // the region is refilled right away: every read of it must have returned
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (!LAST) {
+        if constexpr (BF) { issue_b(kt + 1, buf ^ 1); issue_a(kt + 1); }
+        else issue(kt + 1, buf ^ 1);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      f16x8 ah[NRB], al[NRB];
+#pragma unroll
+      for (int rb = 0; rb < NRB; ++rb) {
+        if constexpr (APRE) {
+          const x2u32x4 u0 = __builtin_bit_cast(x2u32x4, araw[rb][0]), u1 = __builtin_bit_cast(x2u32x4, araw[rb][1]);
+          ah[rb] = __builtin_bit_cast(f16x8, x2u32x4{u0[0], u0[1], u1[0], u1[1]});
+          al[rb] = __builtin_bit_cast(f16x8, x2u32x4{u0[2], u0[3], u1[2], u1[3]});
+        } else {
+          unsigned H[4], L[4];
+          x2_split2(araw[rb][0][0], araw[rb][0][1], s_a, H[0], L[0]);
+          x2_split2(araw[rb][0][2], araw[rb][0][3], s_a, H[1], L[1]);
+          x2_split2(araw[rb][1][0], araw[rb][1][1], s_a, H[2], L[2]);
+          x2_split2(araw[rb][1][2], araw[rb][1][3], s_a, H[3], L[3]);
+          ah[rb] = __builtin_bit_cast(f16x8, x2u32x4{H[0], H[1], H[2], H[3]});
+          al[rb] = __builtin_bit_cast(f16x8, x2u32x4{L[0], L[1], L[2], L[3]});
+        }
+      }
+      if constexpr (LAST && EARLY) {
+        // nothing was issued in this stage and the raw registers are free: the epilogue's first loads
+        __builtin_amdgcn_sched_barrier(0);
+        h_pre_load(pre, ep, M, m_base + wave * (16 * NRB), n_base, Nc, lane);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      const unsigned char* S = smem + b_rd + buf * X2_BSTAGE;
+#pragma unroll
+      for (int hb = 0; hb < 2; ++hb) {
+        if (hb == 1 && half_tile) break;
+        f16x8 bh[4], bl[4];
+#pragma unroll
+        for (int cq = 0; cq < 4; ++cq) {
+          bh[cq] = *reinterpret_cast<const f16x8*>(S + (4 * hb + cq) * 1024);
+          bl[cq] = *reinterpret_cast<const f16x8*>(S + X2_BPLANE + (4 * hb + cq) * 1024);
+        }
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb)
+#pragma unroll
+          for (int cq = 0; cq < 4; ++cq) {
+            X2_MFMA(bl[cq], ah[rb], acc[rb][4 * hb + cq]);
+            X2_MFMA(bh[cq], al[rb], acc[rb][4 * hb + cq]);
+            X2_MFMA(bh[cq], ah[rb], acc[rb][4 * hb + cq]);
+          }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      // the weight pieces of the next stage; BF: not the rows behind them.  The last stage has no piece in flight (the
+      // barrier stays: the epilogues' reductions reuse the stage buffers), and EARLY must not wait for its loads here
+      if constexpr (!LAST && BF) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // = A_PIECES
+      else if constexpr (!(LAST && EARLY)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    issue(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    for (int kt = 0; kt < nk - 1; ++kt) stage(kt, kt & 1, std::false_type{});
+    stage(nk - 1, (nk - 1) & 1, std::true_type{});
+    h_epilogue<EPI, true, NRB>(acc, ep, M, m_base + wave * (16 * NRB), n_base, Nc, lane, smem, wave, rt, inv_a * inv_b, pre);
     return;
   }
 
@@ -441,7 +545,7 @@ __global__ __launch_bounds__(256, (NRB == 2 ? 3 : 2)) void gemmx2h_nt_kernel(con
 
 template <int EPI>
 static hipError_t launchx2h_t(hipStream_t s, const float* A, int lda, const unsigned short* Bx2, int64_t M, int Nc,
-                              int Kd, const GemmEpiParams& ep) {
+                              int Kd, const GemmEpiParams& ep, const int waits) {
   // (128-row tiles at three workgroups per CU, two stages of prefetch, a ring of three weight stages: bit-identical and measured
   //  no faster -- profiles/r03_gemm_x2_rows128.txt, r03_gemm_x2_prefetch2.txt; they live on in tools/wire_gemmx2h_probe.hip)
   const int tbm = X2_TBM;
@@ -449,13 +553,19 @@ static hipError_t launchx2h_t(hipStream_t s, const float* A, int lda, const unsi
   const int tiles_n = (Nc + X2_TBN - 1) / X2_TBN;
   const int tiles_m_pad = (tiles_m + 7) & ~7;
   const dim3 grid((unsigned)(tiles_m_pad * tiles_n));
+  // the loosened waits (WT, above) of the editions that read A through LDS; early loads where the form has some
+  constexpr bool HAS_PRE = !std::is_same_v<h_pre_t<EPI, 4>, HPreNone>;
+  const int amode = knob(K_X2_AMODE);
+  const int wt = amode == 1 ? 0 : waits & (X2_WT_BFIRST | (HAS_PRE && amode == 2 ? X2_WT_EARLY : 0));
+#define X2_LAUNCH_WT(E, AM, AP, W) \
+  hipLaunchKernelGGL((gemmx2h_nt_kernel<E, AM, 4, 1, AP, W>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep)
   if (ep.a_split_inv != 0.f) {
     // (only the forward forms read an activation; the data gradients read g_lin, which has no a-priori bound)
     if constexpr (EPI == EPI_STORE || EPI == EPI_GABOR_FWD || EPI == EPI_GABOR2D_FWD || EPI == EPI_SIREN_FWD ||
                   EPI == EPI_GAUSS_FWD || EPI == EPI_BSPLINE_FWD || EPI == EPI_BSPLINE3_FWD) {
-      if (knob(K_X2_AMODE) == 2)
-        hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 2, 4, 1, true>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m,
-                           tiles_n, ep);
+      // (no forward form has early loads)
+      if (amode == 2 && wt == X2_WT_BFIRST) X2_LAUNCH_WT(EPI, 2, true, X2_WT_BFIRST);
+      else if (amode == 2) X2_LAUNCH_WT(EPI, 2, true, 0);
       else
         hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 1, 4, 1, true>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m,
                            tiles_n, ep);
@@ -467,35 +577,43 @@ static hipError_t launchx2h_t(hipStream_t s, const float* A, int lda, const unsi
   // (the compile-time-width editions of the layer-1 forms and the look-ahead edition of GABOR_BWD exist for the default A
   //  mode only: the same values either way)
   constexpr int EPI0 = EPI & ~(EPI_D2 | EPI_D3 | EPI_LA);
-  if (knob(K_X2_AMODE) == 2)
-    hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 2, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
-  else if (knob(K_X2_AMODE) == 1)
+  if (amode == 2) {
+    if constexpr (HAS_PRE) {
+      if (wt == 3) X2_LAUNCH_WT(EPI, 2, false, 3);
+      else if (wt == 2) X2_LAUNCH_WT(EPI, 2, false, 2);
+    }
+    if (wt == 1) X2_LAUNCH_WT(EPI, 2, false, 1);
+    else if (wt == 0) X2_LAUNCH_WT(EPI, 2, false, 0);
+  } else if (amode == 1)
     hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI0, 1, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
+  else if (wt == 1)
+    X2_LAUNCH_WT(EPI0, 0, false, 1);
   else
-    hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI0, 0, 4>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep);
+    X2_LAUNCH_WT(EPI0, 0, false, 0);
+#undef X2_LAUNCH_WT
   return hipGetLastError();
 }
 // the layer-1 forms of the complex nets: | EPI_CG when the call wants the coordinate-gradient partials, | EPI_D2 / EPI_D3
 // when the route asks for the compile-time input width (ep.first_dn) and D is 2 or 3
 template <int EPI>
 static hipError_t launchx2h_first(hipStream_t s, const float* A, int lda, const unsigned short* Bx2, int64_t M, int Nc,
-                                  int Kd, const GemmEpiParams& ep) {
+                                  int Kd, const GemmEpiParams& ep, const int waits) {
   // (wire2d at D = 3: both Linears' parameters of both column groups and 24 coordinates spill 150 - 260 bytes where the
   //  plain form spills 16 - 124 -- no such edition; its D = 2 edition spills less than the plain form)
   constexpr int E3 = EPI == EPI_GABOR2D_BWD_FIRST ? 0 : EPI_D3;
   const int dn = ep.first_dn && ep.coords && (ep.D == 2 || (ep.D == 3 && E3)) ? ep.D : 0;
   if (ep.cg_partial)
-    return dn == 2 ? launchx2h_t<EPI | EPI_CG | EPI_D2>(s, A, lda, Bx2, M, Nc, Kd, ep)
-         : dn == 3 ? launchx2h_t<EPI | EPI_CG | E3>(s, A, lda, Bx2, M, Nc, Kd, ep)
-                   : launchx2h_t<EPI | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep);
-  return dn == 2 ? launchx2h_t<EPI | EPI_D2>(s, A, lda, Bx2, M, Nc, Kd, ep)
-       : dn == 3 ? launchx2h_t<EPI | E3>(s, A, lda, Bx2, M, Nc, Kd, ep)
-                 : launchx2h_t<EPI>(s, A, lda, Bx2, M, Nc, Kd, ep);
+    return dn == 2 ? launchx2h_t<EPI | EPI_CG | EPI_D2>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+         : dn == 3 ? launchx2h_t<EPI | EPI_CG | E3>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+                   : launchx2h_t<EPI | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+  return dn == 2 ? launchx2h_t<EPI | EPI_D2>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+       : dn == 3 ? launchx2h_t<EPI | E3>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+                 : launchx2h_t<EPI>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
 }
 
 // Bx2: the image of launch_x2_split_b_batch; ep.amax_a / ep.amax_b: the operands' maximum slots
 hipError_t launch_gemmx2h_nt(hipStream_t s, int epi, const float* A, int lda, const void* Bx2v, int64_t M, int Nc,
-                             int Kd, const GemmEpiParams& ep) {
+                             int Kd, const GemmEpiParams& ep, int waits) {
   if (M <= 0) return hipSuccess;
   if ((Nc & 63) || (Kd & 31) || (lda & 3) || M > 0x7fffff00LL || (!ep.amax_a && ep.a_split_inv == 0.f) || !ep.amax_b)
     return hipErrorInvalidValue;
@@ -503,39 +621,39 @@ hipError_t launch_gemmx2h_nt(hipStream_t s, int epi, const float* A, int lda, co
   if ((int64_t)lda * 4 * X2_TBM > 0x7fffffffLL) return hipErrorInvalidValue;
   const unsigned short* Bx2 = (const unsigned short*)Bx2v;
   switch (epi) {
-    case EPI_STORE: return launchx2h_t<EPI_STORE>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR_FWD: return launchx2h_t<EPI_GABOR_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+    case EPI_STORE: return launchx2h_t<EPI_STORE>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_GABOR_FWD: return launchx2h_t<EPI_GABOR_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
     case EPI_GABOR_BWD:
-      return ep.lookahead && ep.recompute_out ? launchx2h_t<EPI_GABOR_BWD | EPI_LA>(s, A, lda, Bx2, M, Nc, Kd, ep)
-                          : launchx2h_t<EPI_GABOR_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD_FIRST: return launchx2h_first<EPI_GABOR_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_SIREN_FWD: return launchx2h_t<EPI_SIREN_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GAUSS_FWD: return launchx2h_t<EPI_GAUSS_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_RELU_FWD: return launchx2h_t<EPI_RELU_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+      return ep.lookahead && ep.recompute_out ? launchx2h_t<EPI_GABOR_BWD | EPI_LA>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+                          : launchx2h_t<EPI_GABOR_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_GABOR_BWD_FIRST: return launchx2h_first<EPI_GABOR_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_SIREN_FWD: return launchx2h_t<EPI_SIREN_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_GAUSS_FWD: return launchx2h_t<EPI_GAUSS_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_RELU_FWD: return launchx2h_t<EPI_RELU_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
     case EPI_SIREN_BWD:
-      return ep.cg_partial ? launchx2h_t<EPI_SIREN_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep)
-                           : launchx2h_t<EPI_SIREN_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+      return ep.cg_partial ? launchx2h_t<EPI_SIREN_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+                           : launchx2h_t<EPI_SIREN_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
     case EPI_GAUSS_BWD:
-      return ep.cg_partial ? launchx2h_t<EPI_GAUSS_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep)
-                           : launchx2h_t<EPI_GAUSS_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+      return ep.cg_partial ? launchx2h_t<EPI_GAUSS_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+                           : launchx2h_t<EPI_GAUSS_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
     case EPI_RELU_BWD:
-      return ep.cg_partial ? launchx2h_t<EPI_RELU_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep)
-                           : launchx2h_t<EPI_RELU_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_BSPLINE_FWD: return launchx2h_t<EPI_BSPLINE_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+      return ep.cg_partial ? launchx2h_t<EPI_RELU_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+                           : launchx2h_t<EPI_RELU_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_BSPLINE_FWD: return launchx2h_t<EPI_BSPLINE_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
     case EPI_BSPLINE_BWD:
-      return ep.cg_partial ? launchx2h_t<EPI_BSPLINE_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep)
-                           : launchx2h_t<EPI_BSPLINE_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_BSPLINE3_FWD: return launchx2h_t<EPI_BSPLINE3_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+      return ep.cg_partial ? launchx2h_t<EPI_BSPLINE_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+                           : launchx2h_t<EPI_BSPLINE_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_BSPLINE3_FWD: return launchx2h_t<EPI_BSPLINE3_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
     case EPI_BSPLINE3_BWD:
-      return ep.cg_partial ? launchx2h_t<EPI_BSPLINE3_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep)
-                           : launchx2h_t<EPI_BSPLINE3_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_MFN_FWD: return launchx2h_t<EPI_MFN_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_MFN_BWD: return launchx2h_t<EPI_MFN_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
+      return ep.cg_partial ? launchx2h_t<EPI_BSPLINE3_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+                           : launchx2h_t<EPI_BSPLINE3_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_MFN_FWD: return launchx2h_t<EPI_MFN_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_MFN_BWD: return launchx2h_t<EPI_MFN_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
     case EPI_GABOR2D_FWD:
       if (Nc & 127) return hipErrorInvalidValue;
-      return launchx2h_t<EPI_GABOR2D_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD: return launchx2h_t<EPI_GABOR2D_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD_FIRST: return launchx2h_first<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep);
+      return launchx2h_t<EPI_GABOR2D_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_GABOR2D_BWD: return launchx2h_t<EPI_GABOR2D_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    case EPI_GABOR2D_BWD_FIRST: return launchx2h_first<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
     default: return hipErrorInvalidValue;
   }
 }

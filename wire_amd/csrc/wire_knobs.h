@@ -8,7 +8,7 @@
 enum Knob {
   K_COMPLEX_3M, K_SPLIT_BF16, K_SPLIT_F16, K_SPLIT_OUT, K_RECOMPUTE_OUT, K_FIRST_SUMS, K_FIRST_DN, K_BWD_LOOKAHEAD, K_FUSED_RSTORE, K_WGRAD_BATCH,
   K_FUSED_FWD, K_FUSED_TRAIN, K_FUSED_TRAIN_P384, K_FUSED_FINAL, K_FUSED_BWD, K_FUSED_BWD_W,
-  K_NT_BK, K_X2_AMODE, K_X2_TN_ROWS, K_X2_TN_P384, K_X3_TALL, K_X3_TALL_REAL, K_X3_TN_TALL, K_X3_TN16, K_X3_H16,
+  K_NT_BK, K_X2_AMODE, K_NT_BFIRST, K_EPI_EARLY, K_X2_TN_ROWS, K_X2_TN_P384, K_X3_TALL, K_X3_TALL_REAL, K_X3_TN_TALL, K_X3_TN16, K_X3_H16,
   K_X3H_STAGGER,
   K_FX_ABLATE, K_FXB_ABLATE, K_TN_ABL,
   K_COUNT

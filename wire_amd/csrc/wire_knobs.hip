@@ -106,6 +106,17 @@ constexpr KnobDef kKnobs[] = {
     // register loads of AMODE 1 (16 rows x 64 bytes per instruction) put twice the line requests on the vector-memory path
     // for the same bytes (profiles/r03_gemm_x2_whole_line.txt).
     range_knob(K_X2_AMODE, "x2_amode", "WIRE_X2_AMODE", 2, 0, 2),
+    // 2 x fp16 NT GEMM, A through LDS (x2_amode 2 and 0): a stage's weight pieces are issued BEFORE the wave's own rows and
+    // the stage-end wait leaves the rows in flight (s_waitcnt vmcnt(2 NRB) ahead of s_barrier): the barrier publishes the
+    // shared weight stage only, and a wave waits for its own rows alone, at the top of the next stage, ahead of the
+    // ds_reads of its private region.  0 = rows first, vmcnt(0) ahead of the barrier: all four waves of a workgroup wait
+    // for the slowest wave's rows at every stage.  Same bits.  (make_plan snapshots this and epi_early)
+    flag_knob(K_NT_BFIRST, "nt_bfirst", "WIRE_NT_BFIRST", 1),
+    // 2 x fp16 NT GEMM, x2_amode 2, wire's data-gradient forms: the epilogue's first loads go out under the MFMAs of the
+    // last stage, into the registers the raw rows leave free -- EPI_GABOR_BWD with look-ahead: lin of row block 0; the
+    // layer-1 form at D = 2: the lane's coordinates and W0 / b0 of both column groups (wire_gemmh_epi.h: h_pre_load).
+    // 0 = the epilogue loads them itself.  Same bits.
+    flag_knob(K_EPI_EARLY, "epi_early", "WIRE_EPI_EARLY", 1),
     // upper bound on the rows ONE 2 x fp16 weight-gradient workgroup accumulates sequentially in its fp32 accumulators
     // (0 = the fill-the-chip policy of gemmx2_tn_splits alone).  A shorter chain means more row splits, i.e. more slabs
     // for wgrad_reduce_kernel: the knob of the summation-order measurement (tools/wgrad_order_probe.py).

@@ -134,7 +134,8 @@ struct LayerGemm {
       if (e != hipSuccess) return e;
       GemmEpiParams e2 = ep;
       e2.amax_a = sa; e2.amax_b = slots(1);
-      return launch_gemmx2h_nt(s, epi, A, Kd, dgrad ? img_d : img_f, n, Nc, Kd, e2);
+      return launch_gemmx2h_nt(s, epi, A, Kd, dgrad ? img_d : img_f, n, Nc, Kd, e2,
+                               x2_waits(knob(K_NT_BFIRST) != 0, knob(K_EPI_EARLY) != 0));
     }
     if (fam == FAM_X3) return launch_gemmx3_nt(s, epi, A, Kd, dgrad ? btd_x3 : btf_x3, n, Nc, Kd, ep);
     if (fam == FAM_3M) return launch_gemm3m_nt(s, epi, A, Kd, dgrad ? btd : btf, Kd, n, Nc / 2, Kd / 2, ep);

@@ -120,6 +120,7 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   // (the forward and the backward of the autograd path are separate calls: knobs must not change between them)
   p.k_split_out = knob(K_SPLIT_OUT) != 0; p.k_recompute_out = knob(K_RECOMPUTE_OUT) != 0;
   p.k_first_sums = knob(K_FIRST_SUMS) != 0; p.k_first_dn = knob(K_FIRST_DN) != 0;
+  p.k_nt_bfirst = knob(K_NT_BFIRST) != 0; p.k_epi_early = knob(K_EPI_EARLY) != 0;
   p.k_bwd_lookahead = knob(K_BWD_LOOKAHEAD) != 0; p.k_rstore = knob(K_FUSED_RSTORE) != 0; p.k_wgrad_batch = knob(K_WGRAD_BATCH) != 0;
   p.k_fused_fwd = knob(K_FUSED_FWD) != 0; p.k_fused_train = p.k_fused_fwd && knob(K_FUSED_TRAIN);
   p.k_fused_train_p384 = knob(K_FUSED_TRAIN_P384) != 0;
