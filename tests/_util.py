@@ -2,6 +2,7 @@
 import contextlib
 import ctypes as C
 import os
+import re
 import sys
 
 import numpy as np
@@ -331,3 +332,20 @@ def _prof(fn):
     finally:
         L.wire_prof_enable(0)
     return list(launches)
+
+
+def kernel_names(fn):
+    """Name of every kernel (and copy) that one call of fn launches, from torch.profiler; fn runs once before, unprofiled."""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return [e.name for e in prof.events()]
+
+
+def _nt_editions(fn):
+    """EPI template codes (wire_gemm.h, flags included) of the 16 x 16 x 32 NT GEMM kernels one call of fn launches."""
+    names = kernel_names(fn)
+    return {int(m.group(1)) for k in names for m in [re.search(r"gemmx[23]h_nt_kernel<(\d+)", k)] if m}, names

@@ -8,13 +8,11 @@ tests/_util.within_ref).
 Every case runs the 2 x fp16 route (>= 4096 rows) on 4096 + 37 rows: 17 row tiles of 256, the last one ragged (the
 epilogue's `row < M` paths and its clamped coordinate loads).  Widths: K = 256 (P = 512, what bench.py times) and
 K = 181 (P = 384: pad features in the last 64-column group, 3 column tiles)."""
-import re
-
 import numpy as np
 import pytest
 import torch
 
-from _util import final_bias_within_ref, oracle_grads_chunked, params_np, relmax, tune, within_ref
+from _util import _nt_editions, final_bias_within_ref, oracle_grads_chunked, params_np, relmax, tune, within_ref
 from oracle import wire_oracle as wo
 
 pytestmark = pytest.mark.gpu
@@ -74,18 +72,6 @@ def test_knobs_are_on_by_default():
     from wire_amd import _lib
     for k in KNOBS:
         assert _lib.lib().wire_tune_get(k.encode()) == 1, k
-
-
-def _nt_editions(fn):
-    """EPI template codes (wire_gemm.h, flags included) of the 16 x 16 x 32 NT GEMM kernels one call of fn launches."""
-    from torch.profiler import ProfilerActivity, profile
-    fn()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events()]
-    return {int(m.group(1)) for k in names for m in [re.search(r"gemmx[23]h_nt_kernel<(\d+)", k)] if m}, names
 
 
 EPI_BWD, EPI_BWD_FIRST, EPI_2D_BWD_FIRST = 2, 3, 12            # wire_gemm.h

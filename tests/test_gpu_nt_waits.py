@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import final_bias_within_ref, oracle_grads_chunked, params_np, relmax, tune, within_ref
+from _util import final_bias_within_ref, kernel_names, oracle_grads_chunked, params_np, relmax, tune, within_ref
 from oracle import wire_oracle as wo
 
 pytestmark = pytest.mark.gpu
@@ -97,13 +97,7 @@ def test_knobs_are_on_by_default():
 def _nt_editions(fn):
     """(EPI code, WT) -- first and last template argument (wire_gemmx2h.hip) -- of the 2 x fp16 NT GEMM kernels one
     call of fn launches."""
-    from torch.profiler import ProfilerActivity, profile
-    fn()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events()]
+    names = kernel_names(fn)
     args = [m.group(1).split(",") for k in names for m in [re.search(r"gemmx2h_nt_kernel<([^>]*)>", k)] if m]
     return {(int(a[0]), int(a[-1])) for a in args}, names
 

@@ -33,10 +33,9 @@ import torch
 
 import envelope_ref as er
 import test_gpu_coords_grad as cg
-from _util import abi_train_step, family_ctx, final_bias_within_ref, relmax, tune, within_ref
+from _util import _nt_editions, abi_train_step, family_ctx, final_bias_within_ref, relmax, tune, within_ref
 from oracle import torch_ref
 from oracle import wire_oracle as wo
-from test_gpu_bwd_epilogues import _nt_editions
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"

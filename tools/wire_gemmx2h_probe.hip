@@ -610,8 +610,7 @@ static hipError_t launchx2h_t(hipStream_t s, const float* A, int lda, const unsi
 #endif
   if (ep.a_split_inv != 0.f) {
     // (only the forward forms read an activation; the data gradients read g_lin, which has no a-priori bound)
-    if constexpr (EPI == EPI_STORE || EPI == EPI_GABOR_FWD || EPI == EPI_GABOR2D_FWD || EPI == EPI_SIREN_FWD ||
-                  EPI == EPI_GAUSS_FWD) {
+    if constexpr (epi_presplit_a(EPI)) {
       if (g_x2_amode == 2)
         hipLaunchKernelGGL((gemmx2h_nt_kernel<EPI, 2, 4, 1, true>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m,
                            tiles_n, ep);
@@ -641,24 +640,15 @@ hipError_t launch_gemmx2h_nt(hipStream_t s, int epi, const float* A, int lda, co
   // 32-bit row offsets inside a 256-row tile
   if ((int64_t)lda * 4 * X2_TBM > 0x7fffffffLL) return hipErrorInvalidValue;
   const unsigned short* Bx2 = (const unsigned short*)Bx2v;
-  switch (epi) {
-    case EPI_STORE: return launchx2h_t<EPI_STORE>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR_FWD: return launchx2h_t<EPI_GABOR_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD: return launchx2h_t<EPI_GABOR_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD_FIRST: return launchx2h_t<EPI_GABOR_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_SIREN_FWD: return launchx2h_t<EPI_SIREN_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GAUSS_FWD: return launchx2h_t<EPI_GAUSS_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_RELU_FWD: return launchx2h_t<EPI_RELU_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_SIREN_BWD: return launchx2h_t<EPI_SIREN_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GAUSS_BWD: return launchx2h_t<EPI_GAUSS_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_RELU_BWD: return launchx2h_t<EPI_RELU_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR2D_FWD:
-      if (Nc & 127) return hipErrorInvalidValue;
-      return launchx2h_t<EPI_GABOR2D_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD: return launchx2h_t<EPI_GABOR2D_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD_FIRST: return launchx2h_t<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep);
-    default: return hipErrorInvalidValue;
-  }
+  return with_epi(epi, [&](auto e) -> hipError_t {
+    constexpr int E = decltype(e)::value;
+    if constexpr (E <= EPI_GABOR2D_BWD_FIRST) {          // the forms this copy of the kernels was taken with
+      if (E == EPI_GABOR2D_FWD && (Nc & 127)) return hipErrorInvalidValue;
+      return launchx2h_t<E>(s, A, lda, Bx2, M, Nc, Kd, ep);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
 }
 
 // ---------------------------------------------------------------------------

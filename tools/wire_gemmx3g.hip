@@ -319,33 +319,18 @@ hipError_t launch_gemmx3g_nt(hipStream_t s, int epi, const float* A, int lda, co
   // wave per SIMD
   if (g_x3_glds == 3 && epi == EPI_STORE) return launchx3g_t<EPI_STORE, 2, 4, 4, 1, 4>(s, A, lda, Bx3, M, Nc, Kd, ep);
 #endif
-#define X3G_CASE(E)                                                                                  \
-  case E:                                                                                            \
-    return g_x3_glds == 2 ? launchx3g_t<E, 2, 4, 4, 2, 3>(s, A, lda, Bx3, M, Nc, Kd, ep)             \
-                          : launchx3g_t<E, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-  switch (epi) {
-    X3G_CASE(EPI_STORE)
-    X3G_CASE(EPI_GABOR_FWD)
-    X3G_CASE(EPI_GABOR_BWD)
-    X3G_CASE(EPI_GABOR_BWD_FIRST)
-    default: break;
-  }
-#undef X3G_CASE
-  // the other net kinds: 256 x 128 tile only
-  switch (epi) {
-    case EPI_SIREN_FWD: return launchx3g_t<EPI_SIREN_FWD, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GAUSS_FWD: return launchx3g_t<EPI_GAUSS_FWD, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_RELU_FWD: return launchx3g_t<EPI_RELU_FWD, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_SIREN_BWD: return launchx3g_t<EPI_SIREN_BWD, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GAUSS_BWD: return launchx3g_t<EPI_GAUSS_BWD, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_RELU_BWD: return launchx3g_t<EPI_RELU_BWD, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GABOR2D_FWD:
-      if (Nc & 127) return hipErrorInvalidValue;
-      return launchx3g_t<EPI_GABOR2D_FWD, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD: return launchx3g_t<EPI_GABOR2D_BWD, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD_FIRST: return launchx3g_t<EPI_GABOR2D_BWD_FIRST, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    default: return hipErrorInvalidValue;
-  }
+  return with_epi(epi, [&](auto e) -> hipError_t {
+    constexpr int E = decltype(e)::value;
+    if constexpr (epi_wire_form(E)) {
+      return g_x3_glds == 2 ? launchx3g_t<E, 2, 4, 4, 2, 3>(s, A, lda, Bx3, M, Nc, Kd, ep)
+                            : launchx3g_t<E, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+    } else if constexpr (E <= EPI_GABOR2D_BWD_FIRST) {   // the other net kinds this edition was built for: 256 x 128 tile only
+      if (E == EPI_GABOR2D_FWD && (Nc & 127)) return hipErrorInvalidValue;
+      return launchx3g_t<E, 2, 4, 4, 1, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
 }
 
 // This file is not part of libwire_hip.so (round 3: the staging experiment it served is recorded in DESIGN.md 4.1): the

@@ -506,12 +506,6 @@ int Bwd::chain() {
   return WIRE_OK;
 }
 
-// the weight-gradient loader's form of Z = act(r) under rstore (launch_gemmx2_tn, z_act): sine 2, Gaussian 3, B-spline 4,
-// cubic B-spline 5
-static int rstore_zmode(int kind) {
-  return kind == WIRE_KIND_SIREN ? 2 : kind == WIRE_KIND_GAUSS ? 3 : kind == WIRE_KIND_BSPLINE_CUBIC ? 5 : 4;
-}
-
 // 4. the weight-gradient batch of layers wb_l0 .. L (make_route), behind the chain
 int Bwd::wgrad_batch() {
   const int l0 = r.wb_l0, nb = r.wb_n;
@@ -520,7 +514,7 @@ int Bwd::wgrad_batch() {
   ProfScope ps(s, 2, 2.0 * n * p.Pl * p.P * nb);
   HIPCHK(launch_gemmx2_tn(s, Sx + sc.gch + l0 * sc.gch_stride, p.Pl, rs ? lin_l(l0 - 1) : out_l(l0 - 1), rs ? p.Pl : p.P,
                           n, p.Pl, p.P, r.wb_S, Sx + sc.slab, Sx + sc.bslab, gslots(l0), oslots(l0 - 1),
-                          rs ? 1.f / 16384.f : (s_z != 0.f ? 1.f / s_z : 0.f), rs ? rstore_zmode(p.kind) : 0,
+                          rs ? 1.f / 16384.f : (s_z != 0.f ? 1.f / s_z : 0.f), rs ? known_kind(p.kind).z_act : 0,
                           nb, sc.gch_stride, rs ? a.np * p.Pl : a.np * p.P, WIRE_AMAX_SLOTS));
   return WIRE_OK;
 }
@@ -535,7 +529,7 @@ hipError_t Bwd::hidden_tn(int l) {
     case FAM_X2:
       if (r.rstore)   // Z = act(r_{l-1}) evaluated by the loader from the stored pre-activation (no out_{l-1}), scale 2^14
         return launch_gemmx2_tn(s, gcur, p.Pl, lin_l(l - 1), p.Pl, n, p.Pl, p.P, S, slab, bslab, gslots(l), nullptr,
-                                1.f / 16384.f, rstore_zmode(p.kind));
+                                1.f / 16384.f, known_kind(p.kind).z_act);
       return launch_gemmx2_tn(s, gcur, p.Pl, out_l(l - 1), p.P, n, p.Pl, p.P, S, slab, bslab, gslots(l), oslots(l - 1),
                               r.out_scale[l - 1] != 0.f ? 1.f / r.out_scale[l - 1] : 0.f);
     case FAM_X3: return launch_gemmx3_tn(s, gcur, p.Pl, out_l(l - 1), p.P, n, p.Pl, p.P, S, slab, bslab);

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wire_kinds.h"
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -140,13 +142,6 @@ WIRE_DEVINL void gabor2d_fwd(float u, float v, float p, float q, float w0, float
   o_re = e * cs;
   o_im = e * sn;
 }
-
-// real sweep activations (config 5) and the quadratic B-spline (modules/bspline_form.py)
-// and the cubic B-spline (modules/bspline_cubic.py)
-enum { ACT_SIREN = 0, ACT_GAUSS = 1, ACT_RELU = 2, ACT_BSPLINE = 3, ACT_BSPLINE3 = 4 };
-// whether act'(lin) reads the stored activation out (gauss: -2 s^2 lin out; relu: [out > 0]); siren and the B-splines
-// need lin alone
-constexpr bool act_bwd_reads_out(int act) { return act == ACT_GAUSS || act == ACT_RELU; }
 
 // Centred quadratic B-spline of r = c lin, c = 1 / |sigma0| (modules/bspline_form.py:38-49 computes it as
 // 0.5 relu(r+1.5)^2 - 1.5 relu(r+0.5)^2 + 1.5 relu(r-0.5)^2 - 0.5 relu(r-1.5)^2 with r = lin / sigma0; B is even, so

@@ -178,7 +178,7 @@ hipError_t launch_final_bwd(hipStream_t s, int kind, int raw, const float* g_y, 
                             float* part_b, unsigned* amax_g) {
   if (n <= 0) return hipSuccess;
   if (O > WIRE_MAXO) return hipErrorInvalidValue;
-  const bool cplx = (kind == NK_WIRE || kind == NK_WIRE2D);
+  const bool cplx = kind_is_cplx(kind);
   const int nfeat = cplx ? P / 2 : P;
   dim3 grid((unsigned)final_bwd_blocks(n), cdiv(nfeat, 256));
 #define FB_LAUNCH(KK, RR)                                                                        \
@@ -186,20 +186,13 @@ hipError_t launch_final_bwd(hipStream_t s, int kind, int raw, const float* g_y, 
                      lin, out, K, P, omega, scale, g_lin, part_w, part_b, amax_g)
   if (raw) {
     if (cplx) FB_LAUNCH(NK_WIRE, true); else FB_LAUNCH(NK_RELU, true);
-  } else {
-    switch (kind) {
-      case NK_WIRE: FB_LAUNCH(NK_WIRE, false); break;
-      case NK_WIRE2D: FB_LAUNCH(NK_WIRE2D, false); break;
-      case NK_SIREN: FB_LAUNCH(NK_SIREN, false); break;
-      case NK_GAUSS: FB_LAUNCH(NK_GAUSS, false); break;
-      case NK_RELU: FB_LAUNCH(NK_RELU, false); break;
-      case NK_BSPLINE: FB_LAUNCH(NK_BSPLINE, false); break;
-      case NK_BSPLINE3: FB_LAUNCH(NK_BSPLINE3, false); break;
-      default: return hipErrorInvalidValue;
-    }
+    return hipGetLastError();
   }
+  return with_kind(kind, [&](auto k) -> hipError_t {
+    FB_LAUNCH(decltype(k)::value, false);
+    return hipGetLastError();
+  });
 #undef FB_LAUNCH
-  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -556,30 +549,16 @@ hipError_t launch_final_fused(hipStream_t s, int kind, const float* out, const f
     case 2: case 3: FF_LAUNCH(NP, RW, KD, RC, 3); break;                                                     \
     default: FF_LAUNCH(NP, RW, KD, RC, 4); break;                                                            \
   }
+  // (relu: out_L cannot be formed again from a lin_L that is not stored -- refused above)
 #define FF_LAUNCH_K(NP, RW)                                                                                  \
-  switch (kind) {                                                                                            \
-    case NK_WIRE:                                                                                            \
-      if (out) { FF_LAUNCH_O(NP, RW, NK_WIRE, false); } else { FF_LAUNCH_O(NP, RW, NK_WIRE, true); }         \
-      break;                                                                                                 \
-    case NK_WIRE2D:                                                                                          \
-      if (out) { FF_LAUNCH_O(NP, RW, NK_WIRE2D, false); } else { FF_LAUNCH_O(NP, RW, NK_WIRE2D, true); }     \
-      break;                                                                                                 \
-    case NK_SIREN:                                                                                           \
-      if (out) { FF_LAUNCH_O(NP, RW, NK_SIREN, false); } else { FF_LAUNCH_O(NP, RW, NK_SIREN, true); }       \
-      break;                                                                                                 \
-    case NK_GAUSS:                                                                                           \
-      if (out) { FF_LAUNCH_O(NP, RW, NK_GAUSS, false); } else { FF_LAUNCH_O(NP, RW, NK_GAUSS, true); }       \
-      break;                                                                                                 \
-    case NK_RELU: FF_LAUNCH_O(NP, RW, NK_RELU, false); break;                                                \
-    case NK_BSPLINE:                                                                                         \
-      if (out) { FF_LAUNCH_O(NP, RW, NK_BSPLINE, false); } else { FF_LAUNCH_O(NP, RW, NK_BSPLINE, true); }   \
-      break;                                                                                                 \
-    case NK_BSPLINE3:                                                                                        \
-      if (out) { FF_LAUNCH_O(NP, RW, NK_BSPLINE3, false); } else { FF_LAUNCH_O(NP, RW, NK_BSPLINE3, true); } \
-      break;                                                                                                 \
-    default: return hipErrorInvalidValue;                                                                    \
-  }
-  if (P <= 256) { FF_LAUNCH_K(1, 2); } else if (P <= 512) { FF_LAUNCH_K(1, 1); } else { FF_LAUNCH_K(2, 1); }
+  if constexpr (KD == NK_RELU) { FF_LAUNCH_O(NP, RW, KD, false); }                                           \
+  else if (out) { FF_LAUNCH_O(NP, RW, KD, false); } else { FF_LAUNCH_O(NP, RW, KD, true); }
+  const hipError_t err = with_kind(kind, [&](auto k) -> hipError_t {
+    constexpr int KD = decltype(k)::value;
+    if (P <= 256) { FF_LAUNCH_K(1, 2) } else if (P <= 512) { FF_LAUNCH_K(1, 1) } else { FF_LAUNCH_K(2, 1) }
+    return hipSuccess;
+  });
+  if (err != hipSuccess) return err;
 #undef FF_LAUNCH_K
 #undef FF_LAUNCH_O
 #undef FF_LAUNCH

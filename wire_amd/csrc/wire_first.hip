@@ -84,25 +84,15 @@ hipError_t launch_first_fwd(hipStream_t s, int kind, const float* coords, int64_
                             int K, int P, float omega, float scale, float* lin, float* out, unsigned* amax_out) {
   if (n <= 0) return hipSuccess;
   if (D > 4) return hipErrorInvalidValue;
-  const bool cplx = (kind == NK_WIRE || kind == NK_WIRE2D);
+  const bool cplx = kind_is_cplx(kind);
   const int nfeat = cplx ? P / 2 : P;
   const int bx = nfeat >= 256 ? 256 : ((nfeat + 63) / 64) * 64;
   dim3 grid(cdiv(n, FIRST_ROWS), cdiv(nfeat, bx));
-#define FIRST_LAUNCH(KK)                                                                       \
-  hipLaunchKernelGGL(first_fwd_kernel<KK>, grid, dim3(bx), 0, s, coords, (long long)n, D, W0, b0, \
-                     V0, c0, K, P, omega, scale, lin, out, amax_out)
-  switch (kind) {
-    case NK_WIRE: FIRST_LAUNCH(NK_WIRE); break;
-    case NK_WIRE2D: FIRST_LAUNCH(NK_WIRE2D); break;
-    case NK_SIREN: FIRST_LAUNCH(NK_SIREN); break;
-    case NK_GAUSS: FIRST_LAUNCH(NK_GAUSS); break;
-    case NK_RELU: FIRST_LAUNCH(NK_RELU); break;
-    case NK_BSPLINE: FIRST_LAUNCH(NK_BSPLINE); break;
-    case NK_BSPLINE3: FIRST_LAUNCH(NK_BSPLINE3); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef FIRST_LAUNCH
-  return hipGetLastError();
+  return with_kind(kind, [&](auto k) -> hipError_t {
+    hipLaunchKernelGGL(first_fwd_kernel<decltype(k)::value>, grid, dim3(bx), 0, s, coords, (long long)n, D, W0, b0,
+                       V0, c0, K, P, omega, scale, lin, out, amax_out);
+    return hipGetLastError();
+  });
 }
 
 // ===========================================================================

@@ -160,8 +160,7 @@ hipError_t launch_fx_split_b_batch(hipStream_t s, const FxSplitBatch& sb, int nb
 template <int KIND>
 struct FxKind {
   static constexpr bool CPLX = KIND == NK_WIRE;
-  static constexpr int ACT = KIND == NK_SIREN ? ACT_SIREN : KIND == NK_GAUSS ? ACT_GAUSS : KIND == NK_BSPLINE ? ACT_BSPLINE
-                             : KIND == NK_BSPLINE3 ? ACT_BSPLINE3 : ACT_RELU;
+  static constexpr int ACT = nk_real_act(KIND);
   static constexpr int U = CPLX ? 4 : 2;          // column blocks of one epilogue unit (complex: re | im of 32 features)
 };
 
@@ -1167,7 +1166,7 @@ __global__ __launch_bounds__(64 * W, 8 / W) void fused_bwd_kernel(const FusedBwd
 // shapes with a kernel: the 256-feature real nets (BASELINE.json configs[4]) and `wire` at padded widths 192 / 256 / 384
 // (config 1's K = 90, K <= 128, hidden_features = 256 -> K = 181)
 bool fused_fwd_shape(int kind, int P) {
-  if (kind == NK_SIREN || kind == NK_GAUSS || kind == NK_RELU || kind == NK_BSPLINE || kind == NK_BSPLINE3) return P == 256;
+  if (kind_is_real(kind)) return P == 256;
   if (kind == NK_WIRE) return P == 192 || P == 256 || P == 384;
   return false;
 }
@@ -1186,7 +1185,7 @@ static hipError_t fx_launch_t(hipStream_t s, const FusedFwdParams& fp) {
   const unsigned grid = (unsigned)((fp.n + FX_ROWS - 1) / FX_ROWS);
   if (fp.out != nullptr) {                               // training forward: stores what the backward reads
     if constexpr (ABL == 0) {
-      if constexpr (KIND == NK_SIREN || KIND == NK_GAUSS || KIND == NK_BSPLINE || KIND == NK_BSPLINE3) {
+      if constexpr (kind_row(KIND)->rstore) {
         if (fp.rstore) {
           const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_fwd_kernel<KIND, NB, RING, 0, 2>),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
@@ -1240,7 +1239,7 @@ hipError_t launch_fused_fwd(hipStream_t s, int kind, int P, const FusedFwdParams
   if (!(fp.c_first > 0.f) || !(fp.c_hidden > 0.f)) return hipErrorInvalidValue;
   if (fp.pe_F > 0 && (kind != NK_RELU || !fp.bias0 || !fp.wamax0 || fp.D + 2 * fp.D * fp.pe_F > 64)) return hipErrorInvalidValue;
   if (fp.pe_F == 0 && (!fp.W0 || !fp.b0)) return hipErrorInvalidValue;
-  if (fp.out != nullptr && ((kind != NK_RELU && !fp.lin) || ((kind == NK_SIREN || kind == NK_GAUSS || kind == NK_BSPLINE || kind == NK_BSPLINE3) && !fp.lin0) || !fp.amax_out))
+  if (fp.out != nullptr && ((kind != NK_RELU && !fp.lin) || (known_kind(kind).lin0 && !fp.lin0) || !fp.amax_out))
     return hipErrorInvalidValue;
   if (fp.target != nullptr && (kind == NK_WIRE || !fp.out || !fp.wf || !fp.bfr || !fp.y || !fp.g_lin || !fp.part_w || !fp.part_b ||
                                !fp.loss_partial || !fp.amax_g))
@@ -1259,18 +1258,18 @@ hipError_t launch_fused_fwd(hipStream_t s, int kind, int P, const FusedFwdParams
     }
   }
 #endif
-  switch (kind) {
-    case NK_SIREN: return fx_launch_t<NK_SIREN, 16, 3>(s, fp);
-    case NK_GAUSS: return fx_launch_t<NK_GAUSS, 16, 3>(s, fp);
-    case NK_BSPLINE: return fx_launch_t<NK_BSPLINE, 16, 3>(s, fp);
-    case NK_BSPLINE3: return fx_launch_t<NK_BSPLINE3, 16, 3>(s, fp);
-    case NK_RELU: return fx_launch_t<NK_RELU, 16, 3>(s, fp);
-    case NK_WIRE:
-      if (P == 192) return fx_launch_t<NK_WIRE, 12, 3>(s, fp);
-      if (P == 256) return fx_launch_t<NK_WIRE, 16, 3>(s, fp);
-      return fx_launch_t<NK_WIRE, 24, 2>(s, fp);
-    default: return hipErrorInvalidValue;
-  }
+  return with_kind(kind, [&](auto k) -> hipError_t {
+    constexpr int KIND = decltype(k)::value;
+    if constexpr (kind_is_real(KIND)) {
+      return fx_launch_t<KIND, 16, 3>(s, fp);
+    } else if constexpr (KIND == NK_WIRE) {
+      if (P == 192) return fx_launch_t<KIND, 12, 3>(s, fp);
+      if (P == 256) return fx_launch_t<KIND, 16, 3>(s, fp);
+      return fx_launch_t<KIND, 24, 2>(s, fp);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
 }
 
 #ifdef FX_PROBE_ABL
@@ -1279,7 +1278,7 @@ template __global__ void fused_fwd_kernel<NK_SIREN, 16, 3, FX_PROBE_ABL>(const F
 
 // ---- the data-gradient chain (real nets, P = 256)
 bool fused_bwd_shape(int kind, int P) {
-  return (kind == NK_SIREN || kind == NK_GAUSS || kind == NK_RELU || kind == NK_BSPLINE || kind == NK_BSPLINE3) && P == 256;
+  return kind_is_real(kind) && P == 256;
 }
 // W = waves per workgroup (the "fused_bwd_w" knob, wire_knobs.hip: 8 or 4)
 template <int KIND, int W, int ABL = 0>
@@ -1326,12 +1325,8 @@ hipError_t launch_fused_bwd(hipStream_t s, int kind, int P, const FusedBwdParams
       !fp.wimg)
     return hipErrorInvalidValue;
   if (fp.crp && (!fp.coords || fp.D < 1 || fp.D > 4 || fp.C < 1 || fp.C > P)) return hipErrorInvalidValue;
-  switch (kind) {
-    case NK_SIREN: return fxb_launch_t<NK_SIREN>(s, fp, W);
-    case NK_GAUSS: return fxb_launch_t<NK_GAUSS>(s, fp, W);
-    case NK_BSPLINE: return fxb_launch_t<NK_BSPLINE>(s, fp, W);
-    case NK_BSPLINE3: return fxb_launch_t<NK_BSPLINE3>(s, fp, W);
-    case NK_RELU: return fxb_launch_t<NK_RELU>(s, fp, W);
-    default: return hipErrorInvalidValue;
-  }
+  return with_kind(kind, [&](auto k) -> hipError_t {
+    if constexpr (kind_is_real(decltype(k)::value)) return fxb_launch_t<decltype(k)::value>(s, fp, W);
+    else return hipErrorInvalidValue;
+  });
 }

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "wire_kinds.h"
 #include "wire_knobs.h"
 
 // GEMM family of a net's hidden layers: 4-multiplication fp32 MFMA, 3-multiplication complex fp32 MFMA (wire only), fp32
@@ -11,50 +14,33 @@
 enum WireFamily { FAM_4M = 0, FAM_3M = 1, FAM_X3 = 2, FAM_X2 = 3 };
 WireFamily wire_family_(int kind);   // wire_api.hip
 
-// Epilogue selector of the NT GEMM  C[M][Nc] = A[M][Kd] * Bt[Nc][Kd]^T.
-enum WireEpi {
-  EPI_STORE = 0,            // o0 = C
-  EPI_GABOR_FWD = 1,        // C = lin(re|im): o0 = lin (optional), o1 = gabor(lin + bias)
-  EPI_GABOR_BWD = 2,        // C = g_out: i0 = lin, i1 = out -> o0 = g_lin
-  EPI_GABOR_BWD_FIRST = 3,  // C = g_out0: i1 = out0, coords/W0/b0 -> u; o0 = g_u [M][ldu]
-  EPI_SIREN_FWD = 4, EPI_GAUSS_FWD = 5, EPI_RELU_FWD = 6,   // o0 = lin, o1 = act
-  EPI_SIREN_BWD = 7, EPI_GAUSS_BWD = 8, EPI_RELU_BWD = 9,   // i0 = lin, i1 = out -> o0 = g_lin
-  EPI_GABOR2D_FWD = 10,     // C = (lin|sy)(re|im) 128-col groups: o0 = linsy [M][2P], o1 = out [M][P]
-  EPI_GABOR2D_BWD = 11,     // C = g_out: i0 = linsy, i1 = out -> o0 = g_linsy [M][2P]
-  EPI_GABOR2D_BWD_FIRST = 12, // real first layer of wire2d: o0 = g_(u|p) [M][2*ldu]
-  EPI_BSPLINE_FWD = 13,     // quadratic B-spline (scale = c = 1 / |sigma0|): o0 = lin, o1 = act
-  EPI_BSPLINE_BWD = 14,     // i0 = lin -> o0 = g_lin (no out read)
-  // multiplicative filter network (modules/mfn.py:46-54): g = the Gabor filter of the row's coordinates (ep.coords,
-  // ep.D) and the column's entry of the filter table (ep.ftab, wire_dev.h: MfnCol)
-  EPI_MFN_FWD = 15,         // lin = C + bias: o0 = lin (optional), o1 = lin g
-  EPI_MFN_BWD = 16,         // C = g_z: i0 = lin -> o0 = g_z g (the layer below's g_lin), o1 = g_z lin (the filter's
-                            //   upstream gradient h); i0 null (filter 0): o1 = g_z alone
-  EPI_BSPLINE3_FWD = 17,    // cubic B-spline of lin (scale_0 sits in the packed weights): o0 = lin, o1 = act
-  EPI_BSPLINE3_BWD = 18,    // i0 = lin -> o0 = g_lin (no out read)
-  // flag on the layer-1 data-gradient forms of the 16 x 16 x 32 kernels (the real BWD forms, GABOR_BWD_FIRST,
-  // GABOR2D_BWD_FIRST): the instantiation that also writes ep.cg_partial.  Host code passes the plain code; the
-  // launchers pick the flagged instantiation when ep.cg_partial is set
-  EPI_CG = 64,
-  // flags on GABOR_BWD_FIRST / GABOR2D_BWD_FIRST of the 16 x 16 x 32 kernels: the instantiations whose input width D is a
-  // compile-time 2 or 3 (wire_gemmh_epi.h: h_gabor_bwd_first_dn, h_gabor2d_bwd_first_dn).  The launchers pick them when
-  // ep.first_dn is set and ep.D is 2 or 3; every other D keeps the plain form
-  EPI_D2 = 128, EPI_D3 = 256,
-  // flag on GABOR_BWD of the 16 x 16 x 32 kernels: the edition whose epilogue loads the next row block's lin ahead of
-  // the current block's arithmetic and stores (wire_gemmh_epi.h: h_gabor_bwd_la); picked when ep.lookahead is set
-  EPI_LA = 512
-};
-constexpr int EPI_FLAGS = EPI_CG | EPI_D2 | EPI_D3 | EPI_LA;
+// the only switch over the plain epilogue codes (WireEpi, wire_kinds.h): f(std::integral_constant<int, E>{}) for the
+// code's E; a launcher keeps what is particular to its family inside f, as `if constexpr` on E
+template <class F>
+hipError_t with_epi(int epi, F&& f) {
+#define WIRE_EPI_CASE(E) case E: return f(std::integral_constant<int, E>{});
+  switch (epi) {
+    WIRE_EPI_CASE(EPI_STORE) WIRE_EPI_CASE(EPI_GABOR_FWD) WIRE_EPI_CASE(EPI_GABOR_BWD) WIRE_EPI_CASE(EPI_GABOR_BWD_FIRST)
+    WIRE_EPI_CASE(EPI_SIREN_FWD) WIRE_EPI_CASE(EPI_GAUSS_FWD) WIRE_EPI_CASE(EPI_RELU_FWD)
+    WIRE_EPI_CASE(EPI_SIREN_BWD) WIRE_EPI_CASE(EPI_GAUSS_BWD) WIRE_EPI_CASE(EPI_RELU_BWD)
+    WIRE_EPI_CASE(EPI_GABOR2D_FWD) WIRE_EPI_CASE(EPI_GABOR2D_BWD) WIRE_EPI_CASE(EPI_GABOR2D_BWD_FIRST)
+    WIRE_EPI_CASE(EPI_BSPLINE_FWD) WIRE_EPI_CASE(EPI_BSPLINE_BWD) WIRE_EPI_CASE(EPI_MFN_FWD) WIRE_EPI_CASE(EPI_MFN_BWD)
+    WIRE_EPI_CASE(EPI_BSPLINE3_FWD) WIRE_EPI_CASE(EPI_BSPLINE3_BWD)
+    default: return hipErrorInvalidValue;
+  }
+#undef WIRE_EPI_CASE
+}
 
-// the real-valued activation epilogues (siren / gauss / relu / the B-splines) and their ACT_* code (wire_dev.h)
-constexpr bool epi_real_fwd(int e) {
-  return e == EPI_SIREN_FWD || e == EPI_GAUSS_FWD || e == EPI_RELU_FWD || e == EPI_BSPLINE_FWD || e == EPI_BSPLINE3_FWD;
-}
-constexpr bool epi_real_bwd(int e) {
-  return e == EPI_SIREN_BWD || e == EPI_GAUSS_BWD || e == EPI_RELU_BWD || e == EPI_BSPLINE_BWD || e == EPI_BSPLINE3_BWD;
-}
-constexpr int epi_real_act(int e) {
-  return (e == EPI_BSPLINE3_FWD || e == EPI_BSPLINE3_BWD) ? 4
-       : (e == EPI_BSPLINE_FWD || e == EPI_BSPLINE_BWD) ? 3 : epi_real_fwd(e) ? e - EPI_SIREN_FWD : e - EPI_SIREN_BWD;
+// the only switch over the base kinds (wire_kinds.h): f(std::integral_constant<int, NK_*>{})
+template <class F>
+hipError_t with_kind(int kind, F&& f) {
+#define WIRE_KIND_CASE(K) case K: return f(std::integral_constant<int, K>{});
+  switch (kind) {
+    WIRE_KIND_CASE(NK_WIRE) WIRE_KIND_CASE(NK_WIRE2D) WIRE_KIND_CASE(NK_SIREN) WIRE_KIND_CASE(NK_GAUSS)
+    WIRE_KIND_CASE(NK_RELU) WIRE_KIND_CASE(NK_BSPLINE) WIRE_KIND_CASE(NK_BSPLINE3)
+    default: return hipErrorInvalidValue;
+  }
+#undef WIRE_KIND_CASE
 }
 
 struct GemmEpiParams {

@@ -207,30 +207,15 @@ hipError_t launch_gemm_nt(hipStream_t s, int epi, const float* A, int lda, const
                           int64_t M, int Nc, int Kd, const GemmEpiParams& ep) {
   if (M <= 0) return hipSuccess;
   if ((Nc & 63) || (Kd & 31) || (lda & 3) || (ldb & 3) || M > 0x7fffff00LL) return hipErrorInvalidValue;
-  switch (epi) {
-    case EPI_STORE: return launch_nt_t<EPI_STORE, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_GABOR_FWD: return launch_nt_t<EPI_GABOR_FWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD: return launch_nt_t<EPI_GABOR_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD_FIRST: return launch_nt_t<EPI_GABOR_BWD_FIRST, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_SIREN_FWD: return launch_nt_t<EPI_SIREN_FWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_GAUSS_FWD: return launch_nt_t<EPI_GAUSS_FWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_RELU_FWD: return launch_nt_t<EPI_RELU_FWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_SIREN_BWD: return launch_nt_t<EPI_SIREN_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_GAUSS_BWD: return launch_nt_t<EPI_GAUSS_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_RELU_BWD: return launch_nt_t<EPI_RELU_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_BSPLINE_FWD: return launch_nt_t<EPI_BSPLINE_FWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_BSPLINE_BWD: return launch_nt_t<EPI_BSPLINE_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_BSPLINE3_FWD: return launch_nt_t<EPI_BSPLINE3_FWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_BSPLINE3_BWD: return launch_nt_t<EPI_BSPLINE3_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_MFN_FWD: return launch_nt_t<EPI_MFN_FWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_MFN_BWD: return launch_nt_t<EPI_MFN_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_GABOR2D_FWD:
+  return with_epi(epi, [&](auto e) -> hipError_t {
+    constexpr int E = decltype(e)::value;
+    if constexpr (E == EPI_GABOR2D_FWD) {              // (lin | sy) of a feature in one wave's 128 columns
       if (Nc & 127) return hipErrorInvalidValue;
-      return launch_nt_t<EPI_GABOR2D_FWD, 1, 4>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD: return launch_nt_t<EPI_GABOR2D_BWD, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD_FIRST: return launch_nt_t<EPI_GABOR2D_BWD_FIRST, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
-    default: return hipErrorInvalidValue;
-  }
+      return launch_nt_t<E, 1, 4>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
+    } else {
+      return launch_nt_t<E, 2, 2>(s, A, lda, Bt, ldb, M, Nc, Kd, ep);
+    }
+  });
 }
 
 // ---------------------------------------------------------------------------

@@ -344,13 +344,11 @@ hipError_t launch_gemm3m_nt(hipStream_t s, int epi, const float* A, int lda, con
   GemmEpiParams e2 = ep;
   if ((epi == EPI_GABOR_FWD || epi == EPI_GABOR_BWD) && ep.ld0 != ep.ld1) e2.wide = 1;
   if ((double)M * (double)(ep.ld1 > ep.ld0 ? ep.ld1 : ep.ld0) * 4.0 >= 4294967296.0) e2.wide = 1;
-  switch (epi) {
-    case EPI_STORE: return launch3m_t<EPI_STORE>(s, A, lda, B, ldb, M, Kp_out, Kp_in, e2);
-    case EPI_GABOR_FWD: return launch3m_t<EPI_GABOR_FWD>(s, A, lda, B, ldb, M, Kp_out, Kp_in, e2);
-    case EPI_GABOR_BWD: return launch3m_t<EPI_GABOR_BWD>(s, A, lda, B, ldb, M, Kp_out, Kp_in, e2);
-    case EPI_GABOR_BWD_FIRST: return launch3m_t<EPI_GABOR_BWD_FIRST>(s, A, lda, B, ldb, M, Kp_out, Kp_in, e2);
-    default: return hipErrorInvalidValue;
-  }
+  return with_epi(epi, [&](auto e) -> hipError_t {
+    constexpr int E = decltype(e)::value;
+    if constexpr (epi_wire_form(E)) return launch3m_t<E>(s, A, lda, B, ldb, M, Kp_out, Kp_in, e2);
+    else return hipErrorInvalidValue;
+  });
 }
 
 // ---------------------------------------------------------------------------

@@ -561,8 +561,7 @@ static hipError_t launchx2h_t(hipStream_t s, const float* A, int lda, const unsi
   hipLaunchKernelGGL((gemmx2h_nt_kernel<E, AM, 4, 1, AP, W>), grid, dim3(256), 0, s, A, lda, Bx2, (int)M, Nc, Kd, tiles_m, tiles_n, ep)
   if (ep.a_split_inv != 0.f) {
     // (only the forward forms read an activation; the data gradients read g_lin, which has no a-priori bound)
-    if constexpr (EPI == EPI_STORE || EPI == EPI_GABOR_FWD || EPI == EPI_GABOR2D_FWD || EPI == EPI_SIREN_FWD ||
-                  EPI == EPI_GAUSS_FWD || EPI == EPI_BSPLINE_FWD || EPI == EPI_BSPLINE3_FWD) {
+    if constexpr (epi_presplit_a(EPI)) {
       // (no forward form has early loads)
       if (amode == 2 && wt == X2_WT_BFIRST) X2_LAUNCH_WT(EPI, 2, true, X2_WT_BFIRST);
       else if (amode == 2) X2_LAUNCH_WT(EPI, 2, true, 0);
@@ -620,42 +619,21 @@ hipError_t launch_gemmx2h_nt(hipStream_t s, int epi, const float* A, int lda, co
   // 32-bit row offsets inside a 256-row tile
   if ((int64_t)lda * 4 * X2_TBM > 0x7fffffffLL) return hipErrorInvalidValue;
   const unsigned short* Bx2 = (const unsigned short*)Bx2v;
-  switch (epi) {
-    case EPI_STORE: return launchx2h_t<EPI_STORE>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_GABOR_FWD: return launchx2h_t<EPI_GABOR_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_GABOR_BWD:
-      return ep.lookahead && ep.recompute_out ? launchx2h_t<EPI_GABOR_BWD | EPI_LA>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
-                          : launchx2h_t<EPI_GABOR_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_GABOR_BWD_FIRST: return launchx2h_first<EPI_GABOR_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_SIREN_FWD: return launchx2h_t<EPI_SIREN_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_GAUSS_FWD: return launchx2h_t<EPI_GAUSS_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_RELU_FWD: return launchx2h_t<EPI_RELU_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_SIREN_BWD:
-      return ep.cg_partial ? launchx2h_t<EPI_SIREN_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
-                           : launchx2h_t<EPI_SIREN_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_GAUSS_BWD:
-      return ep.cg_partial ? launchx2h_t<EPI_GAUSS_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
-                           : launchx2h_t<EPI_GAUSS_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_RELU_BWD:
-      return ep.cg_partial ? launchx2h_t<EPI_RELU_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
-                           : launchx2h_t<EPI_RELU_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_BSPLINE_FWD: return launchx2h_t<EPI_BSPLINE_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_BSPLINE_BWD:
-      return ep.cg_partial ? launchx2h_t<EPI_BSPLINE_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
-                           : launchx2h_t<EPI_BSPLINE_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_BSPLINE3_FWD: return launchx2h_t<EPI_BSPLINE3_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_BSPLINE3_BWD:
-      return ep.cg_partial ? launchx2h_t<EPI_BSPLINE3_BWD | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
-                           : launchx2h_t<EPI_BSPLINE3_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_MFN_FWD: return launchx2h_t<EPI_MFN_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_MFN_BWD: return launchx2h_t<EPI_MFN_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_GABOR2D_FWD:
-      if (Nc & 127) return hipErrorInvalidValue;
-      return launchx2h_t<EPI_GABOR2D_FWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_GABOR2D_BWD: return launchx2h_t<EPI_GABOR2D_BWD>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    case EPI_GABOR2D_BWD_FIRST: return launchx2h_first<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
-    default: return hipErrorInvalidValue;
-  }
+  return with_epi(epi, [&](auto e) -> hipError_t {
+    constexpr int E = decltype(e)::value;
+    if constexpr (E == EPI_GABOR_BWD_FIRST || E == EPI_GABOR2D_BWD_FIRST) {
+      return launchx2h_first<E>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    } else if constexpr (E == EPI_GABOR_BWD) {
+      return ep.lookahead && ep.recompute_out ? launchx2h_t<E | EPI_LA>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+                                              : launchx2h_t<E>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    } else if constexpr (epi_real_bwd(E)) {
+      return ep.cg_partial ? launchx2h_t<E | EPI_CG>(s, A, lda, Bx2, M, Nc, Kd, ep, waits)
+                           : launchx2h_t<E>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    } else {
+      if (E == EPI_GABOR2D_FWD && (Nc & 127)) return hipErrorInvalidValue;
+      return launchx2h_t<E>(s, A, lda, Bx2, M, Nc, Kd, ep, waits);
+    }
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1081,6 +1059,7 @@ static hipError_t launch_x2_tn_t(hipStream_t s, dim3 grid, const float* G, int l
 #define X2_TN_Z(M) launch_x2_tn_z<WM, WN, M, RB>(s, grid, G, ldg, Z, ldz, n, Pm, Pn, tiles_n, used, chunk, slab, bslab, tiles, amax_g, \
                                             amax_z, z_pre_inv, g_step, z_step, amax_step)
   if constexpr (WM == 4 && WN == 2) {                      // the re-evaluating loaders: the 256-feature real nets only
+    static_assert(Z_ACT_MAX == 5, "one line per z_act of wire_kinds.h");
     if (z_act == 2) return X2_TN_Z(2);
     if (z_act == 3) return X2_TN_Z(3);
     if (z_act == 4) return X2_TN_Z(4);
@@ -1093,8 +1072,8 @@ static hipError_t launch_x2_tn_t(hipStream_t s, dim3 grid, const float* G, int l
 
 // `splits` from gemmx2_tn_splits; slabs [splits][Pm][Pn] (+ bslab [splits][Pm]) as launch_gemmx3_tn writes them.
 // z_pre_inv != 0: Z is a pre-split activation (wire_dev.h: wire_store_out4), 1 / its scale; amax_z is not read.
-// z_act = 2 / 3 / 4 / 5: Z holds the pre-activation r of a sine / Gaussian / quadratic / cubic B-spline layer as wire_fused.hip stored it; the loader evaluates the
-// activation again and splits with scale 1 / z_pre_inv (which must be given).
+// z_act >= 2 (a row's z_act, wire_kinds.h): Z holds the pre-activation r of that kind's layer as wire_fused.hip stored it; the
+// loader evaluates the activation again and splits with scale 1 / z_pre_inv (which must be given).
 // batch > 1: `batch` weight gradients of the same shape in one launch -- member j reads G + j g_step, Z + j z_step and the
 // maximum slots amax_g + j amax_step (amax_z likewise) and writes the slabs [j][splits][Pm][Pn] (+ bslab [j][splits][Pm]).
 hipError_t launch_gemmx2_tn(hipStream_t s, const float* G, int ldg, const float* Z, int ldz, int64_t n, int Pm,
@@ -1103,7 +1082,7 @@ hipError_t launch_gemmx2_tn(hipStream_t s, const float* G, int ldg, const float*
                             long long z_step, int amax_step) {
   const int shp = x2_tn_shape(Pm, Pn);
   if (!shp || (ldg & 3) || (ldz & 3) || splits < 1 || n < 1 || !amax_g || (!amax_z && z_pre_inv == 0.f) ||
-      (z_act != 0 && (z_act < 2 || z_act > 5 || z_pre_inv == 0.f)) || batch < 1 || batch > 8)
+      (z_act != 0 && (!z_act_known(z_act) || z_pre_inv == 0.f)) || batch < 1 || batch > 8)
     return hipErrorInvalidValue;
   const int TMf = x2_tn_tm(shp), TNf = x2_tn_tn(shp);
   const int tiles_m = Pm / TMf, tiles_n = (Pn + TNf - 1) / TNf;

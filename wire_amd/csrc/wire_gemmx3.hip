@@ -397,54 +397,22 @@ hipError_t launch_gemmx3_nt(hipStream_t s, int epi, const float* A, int lda, con
     ep.wide = 1;
   if ((double)M * (double)(ep.ld1 > ep.ld0 ? ep.ld1 : ep.ld0) * 4.0 >= 4294967296.0) ep.wide = 1;
   // (256-row tiles for wire2d and the real nets were measured 5 % SLOWER on their steps: they stay on 128 rows)
-  if (knob(K_X3_TALL_REAL) && M >= 4096) {
-    switch (epi) {
-      case EPI_SIREN_FWD: return launchx3_nt_t<EPI_SIREN_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_GAUSS_FWD: return launchx3_nt_t<EPI_GAUSS_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_RELU_FWD: return launchx3_nt_t<EPI_RELU_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_SIREN_BWD: return launchx3_nt_t<EPI_SIREN_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_GAUSS_BWD: return launchx3_nt_t<EPI_GAUSS_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_RELU_BWD: return launchx3_nt_t<EPI_RELU_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_BSPLINE_FWD: return launchx3_nt_t<EPI_BSPLINE_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_BSPLINE_BWD: return launchx3_nt_t<EPI_BSPLINE_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_BSPLINE3_FWD: return launchx3_nt_t<EPI_BSPLINE3_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_BSPLINE3_BWD: return launchx3_nt_t<EPI_BSPLINE3_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      default: break;
+  const bool tall = M >= 4096;
+  return with_epi(epi, [&](auto e) -> hipError_t {
+    constexpr int E = decltype(e)::value;
+    if constexpr (epi_real_fwd(E) || epi_real_bwd(E)) {
+      if (tall && knob(K_X3_TALL_REAL)) return launchx3_nt_t<E, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     }
-  }
-  if (knob(K_X3_TALL) && M >= 4096) {
-    switch (epi) {
-      case EPI_STORE: return launchx3_nt_t<EPI_STORE, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_GABOR_FWD: return launchx3_nt_t<EPI_GABOR_FWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_GABOR_BWD: return launchx3_nt_t<EPI_GABOR_BWD, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      case EPI_GABOR_BWD_FIRST: return launchx3_nt_t<EPI_GABOR_BWD_FIRST, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-      default: break;
+    if constexpr (epi_wire_form(E)) {
+      if (tall && knob(K_X3_TALL)) return launchx3_nt_t<E, 4, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
     }
-  }
-  switch (epi) {
-    case EPI_STORE: return launchx3_nt_t<EPI_STORE, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GABOR_FWD: return launchx3_nt_t<EPI_GABOR_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD: return launchx3_nt_t<EPI_GABOR_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD_FIRST: return launchx3_nt_t<EPI_GABOR_BWD_FIRST, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_SIREN_FWD: return launchx3_nt_t<EPI_SIREN_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GAUSS_FWD: return launchx3_nt_t<EPI_GAUSS_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_RELU_FWD: return launchx3_nt_t<EPI_RELU_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_SIREN_BWD: return launchx3_nt_t<EPI_SIREN_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GAUSS_BWD: return launchx3_nt_t<EPI_GAUSS_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_RELU_BWD: return launchx3_nt_t<EPI_RELU_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_BSPLINE_FWD: return launchx3_nt_t<EPI_BSPLINE_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_BSPLINE_BWD: return launchx3_nt_t<EPI_BSPLINE_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_BSPLINE3_FWD: return launchx3_nt_t<EPI_BSPLINE3_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_BSPLINE3_BWD: return launchx3_nt_t<EPI_BSPLINE3_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_MFN_FWD: return launchx3_nt_t<EPI_MFN_FWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_MFN_BWD: return launchx3_nt_t<EPI_MFN_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GABOR2D_FWD:
+    if constexpr (E == EPI_GABOR2D_FWD) {
       if (Nc & 127) return hipErrorInvalidValue;
-      return launchx3_nt_t<EPI_GABOR2D_FWD, 1, 4>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD: return launchx3_nt_t<EPI_GABOR2D_BWD, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD_FIRST: return launchx3_nt_t<EPI_GABOR2D_BWD_FIRST, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
-    default: return hipErrorInvalidValue;
-  }
+      return launchx3_nt_t<E, 1, 4>(s, A, lda, Bx3, M, Nc, Kd, ep);
+    } else {
+      return launchx3_nt_t<E, 2, 2>(s, A, lda, Bx3, M, Nc, Kd, ep);
+    }
+  });
 }
 
 // ---------------------------------------------------------------------------

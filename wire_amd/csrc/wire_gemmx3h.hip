@@ -270,40 +270,19 @@ hipError_t launch_gemmx3h_nt(hipStream_t s, int epi, const float* A, int lda, co
   GemmEpiParams ep = ep_in;
   ep.stagger = knob(K_X3H_STAGGER); ep.stagger_lo = 256; ep.stagger_hi = 512;
   const unsigned short* Bu = (const unsigned short*)Bx3 + (size_t)gemmx3_b_image_floats(Nc, Kd);   // = half the image, in ushorts
-  switch (epi) {
-    case EPI_STORE: return launchx3h_t<EPI_STORE>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR_FWD: return launchx3h_t<EPI_GABOR_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD:
-      return ep.lookahead && ep.recompute_out ? launchx3h_t<EPI_GABOR_BWD | EPI_LA>(s, A, lda, Bu, M, Nc, Kd, ep)
-                          : launchx3h_t<EPI_GABOR_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR_BWD_FIRST: return launchx3h_first<EPI_GABOR_BWD_FIRST>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_SIREN_FWD: return launchx3h_t<EPI_SIREN_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GAUSS_FWD: return launchx3h_t<EPI_GAUSS_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_RELU_FWD: return launchx3h_t<EPI_RELU_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_SIREN_BWD:
-      return ep.cg_partial ? launchx3h_t<EPI_SIREN_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
-                           : launchx3h_t<EPI_SIREN_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GAUSS_BWD:
-      return ep.cg_partial ? launchx3h_t<EPI_GAUSS_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
-                           : launchx3h_t<EPI_GAUSS_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_RELU_BWD:
-      return ep.cg_partial ? launchx3h_t<EPI_RELU_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
-                           : launchx3h_t<EPI_RELU_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_BSPLINE_FWD: return launchx3h_t<EPI_BSPLINE_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_BSPLINE_BWD:
-      return ep.cg_partial ? launchx3h_t<EPI_BSPLINE_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
-                           : launchx3h_t<EPI_BSPLINE_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_BSPLINE3_FWD: return launchx3h_t<EPI_BSPLINE3_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_BSPLINE3_BWD:
-      return ep.cg_partial ? launchx3h_t<EPI_BSPLINE3_BWD | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
-                           : launchx3h_t<EPI_BSPLINE3_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_MFN_FWD: return launchx3h_t<EPI_MFN_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_MFN_BWD: return launchx3h_t<EPI_MFN_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR2D_FWD:
-      if (Nc & 127) return hipErrorInvalidValue;
-      return launchx3h_t<EPI_GABOR2D_FWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD: return launchx3h_t<EPI_GABOR2D_BWD>(s, A, lda, Bu, M, Nc, Kd, ep);
-    case EPI_GABOR2D_BWD_FIRST: return launchx3h_first<EPI_GABOR2D_BWD_FIRST>(s, A, lda, Bu, M, Nc, Kd, ep);
-    default: return hipErrorInvalidValue;
-  }
+  return with_epi(epi, [&](auto e) -> hipError_t {
+    constexpr int E = decltype(e)::value;
+    if constexpr (E == EPI_GABOR_BWD_FIRST || E == EPI_GABOR2D_BWD_FIRST) {
+      return launchx3h_first<E>(s, A, lda, Bu, M, Nc, Kd, ep);
+    } else if constexpr (E == EPI_GABOR_BWD) {
+      return ep.lookahead && ep.recompute_out ? launchx3h_t<E | EPI_LA>(s, A, lda, Bu, M, Nc, Kd, ep)
+                                              : launchx3h_t<E>(s, A, lda, Bu, M, Nc, Kd, ep);
+    } else if constexpr (epi_real_bwd(E)) {
+      return ep.cg_partial ? launchx3h_t<E | EPI_CG>(s, A, lda, Bu, M, Nc, Kd, ep)
+                           : launchx3h_t<E>(s, A, lda, Bu, M, Nc, Kd, ep);
+    } else {
+      if (E == EPI_GABOR2D_FWD && (Nc & 127)) return hipErrorInvalidValue;
+      return launchx3h_t<E>(s, A, lda, Bu, M, Nc, Kd, ep);
+    }
+  });
 }

@@ -355,22 +355,8 @@ extern "C" int wire_final_bwd(void* stream, const float* g_y, const void* z, con
 // (modules/siren.py:48-49, gauss.py:27-28, relu.py:28-29, bspline_form.py:38-49, bspline_cubic.py:44-52) on native
 // [n][in] f32 tensors.
 // ---------------------------------------------------------------------------
-static int real_epi_fwd(int kind) {
-  return kind == WIRE_KIND_SIREN ? EPI_SIREN_FWD : kind == WIRE_KIND_GAUSS ? EPI_GAUSS_FWD
-       : kind == WIRE_KIND_BSPLINE ? EPI_BSPLINE_FWD : kind == WIRE_KIND_BSPLINE_CUBIC ? EPI_BSPLINE3_FWD : EPI_RELU_FWD;
-}
-static bool real_kind(int kind) { return (kind >= WIRE_KIND_SIREN && kind <= WIRE_KIND_BSPLINE) || kind == WIRE_KIND_BSPLINE_CUBIC; }
-// the kernels' scale of a real layer: the B-spline's sigma0 is a divisor, passed on as c = 1 / |sigma0| (B is even); false:
-// sigma0 is zero or not finite.  The cubic B-spline's scale_0 multiplies the layer's input: it goes into the packed weights
-// (wscale: s W in both images, the bias as it is; g_W is multiplied by it on the way out) and the kernels' scale is 1
-static bool real_scale(int kind, float& scale0, float& wscale) {
-  wscale = 1.f;
-  if (kind != WIRE_KIND_BSPLINE && kind != WIRE_KIND_BSPLINE_CUBIC) return true;
-  if (!(std::isfinite(scale0) && scale0 != 0.f)) return false;
-  if (kind == WIRE_KIND_BSPLINE_CUBIC) { wscale = scale0; scale0 = 1.f; }
-  else scale0 = (float)(1.0 / fabs((double)scale0));
-  return true;
-}
+// (the kernels' scale and the factor in the packed weights: kind_scale, wire_kinds.h -- wscale: s W in both images, the bias
+// as it is; g_W is multiplied by it on the way out)
 // the 2 x fp16 region of a real layer's workspace, or null: a cubic B-spline layer of at most 64 inputs stays on the
 // 3 x bf16 kernels at every row count.  The 2 x fp16 split drops the l l product (2^-22 of each product); the 2 to 64
 // products of such a row do not average that out, and the layer's scale_0 sits in the operand (|s W| is 15 times the
@@ -389,7 +375,7 @@ static int real_forward_ws(hipStream_t s, const LayerWs& w, float* W_, int kind,
   GemmEpiParams ep;
   ep.bias = W_ + w.bias; ep.o0 = W_ + w.lin; ep.o1 = W_ + w.out; ep.ld0 = Pout; ep.ld1 = Pout;
   ep.omega = omega0; ep.scale = scale0; ep.kvalid = out;
-  LCHK(g.nt(s, real_epi_fwd(kind), W_ + w.xb, n, Pout, Pin, false, W_ + w.btf, W_ + w.btd, W_ + w.btf_x3,
+  LCHK(g.nt(s, epi_fwd(kind), W_ + w.xb, n, Pout, Pin, false, W_ + w.btf, W_ + w.btd, W_ + w.btf_x3,
             W_ + w.btd_x3, ep));
   return WIRE_OK;
 }
@@ -397,9 +383,9 @@ static int real_forward_ws(hipStream_t s, const LayerWs& w, float* W_, int kind,
 extern "C" int wire_real_layer_fwd(void* stream, int kind, const float* x, const float* W, const float* b,
                                    float omega0, float scale0, int64_t n, int in_features, int out_features,
                                    float* act_out, void* ws, int64_t ws_bytes) {
-  float wscale;
-  if (!real_kind(kind) || n < 0 || in_features < 1 || out_features < 1 || !x ||
-      !W || !b || !act_out || !ws || !real_scale(kind, scale0, wscale))
+  float kscale, wscale;
+  if (!kind_is_real(kind) || n < 0 || in_features < 1 || out_features < 1 || !x ||
+      !W || !b || !act_out || !ws || !kind_scale(kind, scale0, kscale, wscale))
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_real_layer_fwd");
   if (n == 0) return WIRE_OK;
   const LayerWs w = layer_ws(n, in_features, out_features);   // complex sizing is an upper bound
@@ -407,7 +393,7 @@ extern "C" int wire_real_layer_fwd(void* stream, int kind, const float* x, const
   const int Pin = rup(in_features, 64), Pout = rup(out_features, 64);
   hipStream_t s = (hipStream_t)stream;
   float* W_ = (float*)ws;
-  if (int rc = real_forward_ws(s, w, W_, kind, x, W, b, omega0, scale0, wscale, n, in_features, out_features, Pin, Pout))
+  if (int rc = real_forward_ws(s, w, W_, kind, x, W, b, omega0, kscale, wscale, n, in_features, out_features, Pin, Pout))
     return rc;
   LCHK(launch_unpad_rows(s, W_ + w.out, n, out_features, Pout, act_out));
   return WIRE_OK;
@@ -417,19 +403,19 @@ extern "C" int wire_real_layer_bwd(void* stream, int kind, const float* g_act, c
                                    const float* b, float omega0, float scale0, int64_t n, int in_features,
                                    int out_features, float* g_x, float* g_W, float* g_b, void* ws,
                                    int64_t ws_bytes) {
-  float wscale;
-  if (!real_kind(kind) || n <= 0 || in_features < 1 || out_features < 1 ||
-      !g_act || !x || !W || !b || !g_W || !g_b || !ws || !real_scale(kind, scale0, wscale))
+  float kscale, wscale;
+  if (!kind_is_real(kind) || n <= 0 || in_features < 1 || out_features < 1 ||
+      !g_act || !x || !W || !b || !g_W || !g_b || !ws || !kind_scale(kind, scale0, kscale, wscale))
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_real_layer_bwd");
   const LayerWs w = layer_ws(n, in_features, out_features);
   if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
   const int Pin = rup(in_features, 64), Pout = rup(out_features, 64);
   hipStream_t s = (hipStream_t)stream;
   float* W_ = (float*)ws;
-  if (int rc = real_forward_ws(s, w, W_, kind, x, W, b, omega0, scale0, wscale, n, in_features, out_features, Pin, Pout))
+  if (int rc = real_forward_ws(s, w, W_, kind, x, W, b, omega0, kscale, wscale, n, in_features, out_features, Pin, Pout))
     return rc;
   LCHK(launch_pad_rows(s, g_act, n, out_features, Pout, W_ + w.gact));
-  LCHK(launch_real_act_bwd_point(s, kind, W_ + w.gact, W_ + w.lin, W_ + w.out, n, Pout, omega0, scale0,
+  LCHK(launch_real_act_bwd_point(s, kind, W_ + w.gact, W_ + w.lin, W_ + w.out, n, Pout, omega0, kscale,
                                  W_ + w.glin));
   const LayerGemm g{wire_family_(kind), real_x2_region(kind, Pin, W_ + w.x2)};
   if (g_x) {

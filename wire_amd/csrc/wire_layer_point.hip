@@ -173,15 +173,15 @@ hipError_t launch_real_act_bwd_point(hipStream_t s, int kind, const float* g, co
                                      float* g_lin) {
   if (n <= 0) return hipSuccess;
   dim3 grid((unsigned)n), blk(256);
-  switch (kind) {
-    case NK_SIREN: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_SIREN>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
-    case NK_GAUSS: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_GAUSS>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
-    case NK_RELU: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_RELU>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
-    case NK_BSPLINE: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_BSPLINE>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
-    case NK_BSPLINE3: hipLaunchKernelGGL(real_act_bwd_point_kernel<ACT_BSPLINE3>, grid, blk, 0, s, g, lin, out, (long long)n, P, omega, scale, g_lin); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_kind(kind, [&](auto k) -> hipError_t {
+    if constexpr (kind_is_real(decltype(k)::value)) {
+      hipLaunchKernelGGL(real_act_bwd_point_kernel<nk_real_act(decltype(k)::value)>, grid, blk, 0, s, g, lin, out,
+                         (long long)n, P, omega, scale, g_lin);
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
 }
 hipError_t launch_gabor_bwd_point(hipStream_t s, const float* g, const float* lin, const float* out,
                                   int64_t n, int P, float omega, float scale, float* g_lin) {

@@ -193,8 +193,9 @@ struct CoordLayout { int64_t cgp, gpe, total; int ntiles; };
 // (the multi-pass net: cgp holds the per-pass coordinate gradients [S2][n1][D] before their sum)
 CoordLayout coord_layout(const Plan& p, int64_t n);
 
-int epi_fwd(int kind);
-int epi_bwd(int kind);
+// hidden-layer epilogues of a plan's kind (a base kind: make_plan refused every other)
+inline int epi_fwd(int kind) { return known_kind(kind).epi_fwd; }
+inline int epi_bwd(int kind) { return known_kind(kind).epi_bwd; }
 
 // ---------------------------------------------------------------------------
 // route: what one whole-net call runs, decided once from (plan, n, entry point)

@@ -40,9 +40,9 @@ int make_plan(const wire_net_desc* d, Plan& p) {
   p.O = d->out_features; p.F = d->posenc_freqs;
   p.w1 = d->first_omega0; p.w = d->hidden_omega0; p.s = d->scale0;
   p.ws = 1.f;
-  if (p.kind < WIRE_KIND_WIRE || (p.kind > WIRE_KIND_BSPLINE_MS && p.kind != WIRE_KIND_BSPLINE_M2 &&
-                                  p.kind != WIRE_KIND_BSPLINE_HIER && p.kind != WIRE_KIND_MFN &&
-                                  p.kind != WIRE_KIND_BSPLINE_CUBIC))
+  // a base kind (wire_kinds.h) or one of the composite kinds rewritten onto one below
+  if (!kind_row(p.kind) && p.kind != WIRE_KIND_BSPLINE_MS && p.kind != WIRE_KIND_BSPLINE_M2 &&
+      p.kind != WIRE_KIND_BSPLINE_HIER && p.kind != WIRE_KIND_MFN)
     return fail(WIRE_ERR_ARG, "unknown kind %d", p.kind);
   if (p.kind == WIRE_KIND_MFN) {
     // modules/mfn.py: the omegas, `scale` and the positional encoding are carried and ignored; the K -> K layers are
@@ -86,24 +86,18 @@ int make_plan(const wire_net_desc* d, Plan& p) {
     p.kind = WIRE_KIND_BSPLINE;
     p.t0 = 2;
   }
-  if (p.kind == WIRE_KIND_BSPLINE) {
-    // sigma0 divides lin (modules/bspline_form.py:44); B is even, so every kernel multiplies by c = 1 / |sigma0| instead
-    if (!(std::isfinite(p.s) && p.s != 0.f)) return fail(WIRE_ERR_ARG, "bspline scale0 %g is zero or not finite", (double)p.s);
-    p.s = (float)(1.0 / fabs((double)p.s));
-  }
-  if (p.kind == WIRE_KIND_BSPLINE_CUBIC) {
-    // scale_0 multiplies the layer's input (modules/bspline_cubic.py:45), sign included: into the weights (Plan::ws); the
-    // activation is B(lin) itself, so the kernels' scale is 1 (the whole-net kernels fold c = 1, the chain reads fp.s = 1)
-    if (!(std::isfinite(p.s) && p.s != 0.f)) return fail(WIRE_ERR_ARG, "bspline_cubic scale0 %g is zero or not finite", (double)p.s);
-    p.ws = p.s;
-    p.s = 1.f;
-  }
+  // the kernels' scale and the factor in the packed weights (kind_scale: sigma0 divides bspline_form's lin, modules/
+  // bspline_form.py:44; scale_0 multiplies bspline_cubic's input, modules/bspline_cubic.py:45 -- the whole-net kernels then
+  // fold c = 1 and the chain reads fp.s = 1)
+  const float scale0 = p.s;
+  if (!kind_scale(p.kind, scale0, p.s, p.ws))
+    return fail(WIRE_ERR_ARG, "%s scale0 %g is zero or not finite", known_kind(p.kind).name, (double)scale0);
   if (p.D < 1 || p.D > 4) return fail(WIRE_ERR_ARG, "in_features %d outside 1..4", p.D);
   if (p.K < 1 || p.K > 4096) return fail(WIRE_ERR_ARG, "width %d outside 1..4096", p.K);
   if (p.L < 0 || p.L > 64) return fail(WIRE_ERR_ARG, "hidden_layers %d outside 0..64", p.L);
   if (p.O < 1 || p.O > 8) return fail(WIRE_ERR_ARG, "out_features %d outside 1..8", p.O);
   if (p.F < 0 || (p.F > 0 && p.kind != WIRE_KIND_RELU)) return fail(WIRE_ERR_ARG, "posenc only with relu");
-  p.cplx = (p.kind == WIRE_KIND_WIRE || p.kind == WIRE_KIND_WIRE2D);
+  p.cplx = kind_is_cplx(p.kind);
   p.P = p.cplx ? rup(2 * p.K, 64) : rup(p.K, 64);
   // final_fwd_kernel (wire_final.hip) stages W_f as [O][P] floats in the 64 KB of dynamic LDS a launch gets
   if ((int64_t)p.O * p.P > WIRE_FINAL_MAX_OP)
@@ -329,29 +323,6 @@ CoordLayout coord_layout(const Plan& p, int64_t n) {
   return c;
 }
 
-int epi_fwd(int kind) {
-  switch (kind) {
-    case WIRE_KIND_WIRE: return EPI_GABOR_FWD;
-    case WIRE_KIND_WIRE2D: return EPI_GABOR2D_FWD;
-    case WIRE_KIND_SIREN: return EPI_SIREN_FWD;
-    case WIRE_KIND_GAUSS: return EPI_GAUSS_FWD;
-    case WIRE_KIND_BSPLINE: return EPI_BSPLINE_FWD;
-    case WIRE_KIND_BSPLINE_CUBIC: return EPI_BSPLINE3_FWD;
-    default: return EPI_RELU_FWD;
-  }
-}
-int epi_bwd(int kind) {
-  switch (kind) {
-    case WIRE_KIND_WIRE: return EPI_GABOR_BWD;
-    case WIRE_KIND_WIRE2D: return EPI_GABOR2D_BWD;
-    case WIRE_KIND_SIREN: return EPI_SIREN_BWD;
-    case WIRE_KIND_GAUSS: return EPI_GAUSS_BWD;
-    case WIRE_KIND_BSPLINE: return EPI_BSPLINE_BWD;
-    case WIRE_KIND_BSPLINE_CUBIC: return EPI_BSPLINE3_BWD;
-    default: return EPI_RELU_BWD;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // route: what one whole-net call runs, decided once from (plan, n, entry point)
 // ---------------------------------------------------------------------------
@@ -420,17 +391,14 @@ Route make_route(const Plan& p, int64_t n, RouteMode mode) {
   const bool m2_chain = p.m2 && mode == MODE_TRAIN && fx && x2tn;
   r.chain = (r.fused_train || m2_chain) && p.k_fused_bwd && p.off_fxd >= 0;
   r.fused_final = r.chain && r.fused_train && !p.cplx && p.k_fused_final;
-  r.rstore = r.chain && r.fused_train && p.k_rstore &&
-             (p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_GAUSS || p.kind == WIRE_KIND_BSPLINE ||
-              p.kind == WIRE_KIND_BSPLINE_CUBIC);                                                       // 1.3 GB per step less
+  r.rstore = r.chain && r.fused_train && p.k_rstore && known_kind(p.kind).rstore;                        // 1.3 GB per step less
   // out_l is stored pre-split (wire_dev.h: wire_store_out4) when the call runs the 2 x fp16 kernels and every reader of
   // out_l understands the format: the forward GEMM of layer l + 1 (pre-split A edition), the weight-gradient GEMM of layer
   // l + 1 (gemmx2_tn16, pre-split Z) and NOTHING else -- the data-gradient epilogue of layer l + 1 must evaluate
   // act(lin_l) again rather than read out_l (recompute_out; sine and B-spline need no out), out_0 comes from first_fwd_kernel, out_L
   // feeds the final linear layer in fp32, relu's out carries its backward's sign decisions
   const bool split = x2tn && p.k_split_out && p.kind != WIRE_KIND_RELU &&
-                     (p.k_recompute_out || p.kind == WIRE_KIND_SIREN || p.kind == WIRE_KIND_BSPLINE ||
-                      p.kind == WIRE_KIND_BSPLINE_CUBIC);
+                     (p.k_recompute_out || known_kind(p.kind).split_out_free);
   for (int l = 1; l < p.L; ++l) r.out_scale[l] = !split ? 0.f : ftrain ? 1.f : act_bound_scale(p);
   // the layer-1 data gradient of a native first layer on the 16 x 16 x 32 kernel: its epilogue can sum g_lin_0 (wire:
   // g_u) [x | 1] per tile itself instead of storing it for a separate pass, and form the coordinate-gradient partials

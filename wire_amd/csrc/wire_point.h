@@ -7,11 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// (the values of wire_kind, include/wire_hip.h: a plan's kind is handed to the launchers as it is)
-enum { NK_WIRE = 0, NK_WIRE2D = 1, NK_SIREN = 2, NK_GAUSS = 3, NK_RELU = 4, NK_BSPLINE = 5, NK_BSPLINE3 = 12 };
-// the ACT_* code (wire_dev.h) of a real kind: siren 0 .. bspline 3 in the order of the NK_* values, the cubic B-spline 4;
-// 0 for the complex kinds, whose kernels never evaluate it
-constexpr int nk_real_act(int kind) { return kind == NK_BSPLINE3 ? 4 : kind < NK_SIREN ? 0 : kind - NK_SIREN; }
+#include "wire_gemm.h"   // with_kind, and wire_kinds.h through it
 
 #define WIRE_MAXO 8        // outputs of the final linear (the point kernels keep one accumulator per output in registers)
 // final_fwd_kernel keeps W_f [O][P] in dynamic LDS and a launch gets 64 KB of it without an opt-in: O x P floats at most.
