@@ -388,6 +388,50 @@ int wire_coded_fwd(void* stream, const float* video, const float* masks, int T, 
 int wire_coded_bwd(void* stream, const float* g_coded, const float* masks, int T, int64_t NP, int nframes,
                    int dup_last, float* g_video);
 
+/* Anisotropic total variation, utils.total_variation_loss of modules/utils.py:360-369, over `planes` images of H x W:
+ *   tv(x) = sum_{p, i<H-1, j} |x[p][i+1][j] - x[p][i][j]| + sum_{p, i, j<W-1} |x[p][i][j+1] - x[p][i][j]|
+ * -- a SUM, not a mean; H == 1 or W == 1 is legal and that direction contributes nothing.  Element (p, i, j) lies at
+ * x[p * plane_stride + (i * W + j) * pix_stride]: planes = O, pix_stride = O, plane_stride = 1 is the network's own
+ * [H*W][O] output, planes = B*C, pix_stride = 1, plane_stride = H*W a contiguous (B, C, H, W) tensor.  tv_out[0] is
+ * overwritten with the sum over all planes.  One grid-stride pass, a thread per pixel adding its planes in order (a
+ * block of 256 pixels loops above 262 144 pixels), the neighbours re-read through the caches; no atomics, every sum in
+ * a fixed order that depends on (planes, H, W) alone: the same call gives the same bits, and so does the same image
+ * under other strides.  partial: >= 1024 floats of scratch.  x, tv_out, partial: device.
+ * planes, H or W < 1, a stride < 1, sizes or a largest offset beyond 63 bits, or a NULL pointer: WIRE_ERR_ARG before
+ * any HIP call.                                                                                                  */
+int wire_tv_fwd(void* stream, const float* x, int planes, int H, int W, int64_t pix_stride, int64_t plane_stride,
+                float* tv_out, float* partial);
+/* Its gradient under torch's convention d|u|/du = s(u), s in {-1, 0, +1}, s(0) = 0, times the upstream gradient g_tv[0]
+ * (a DEVICE scalar: no host synchronisation):
+ *   g_x[p][i][j] = g_tv[0] * (  s(x[i][j] - x[i-1][j]) - s(x[i+1][j] - x[i][j])
+ *                             + s(x[i][j] - x[i][j-1]) - s(x[i][j+1] - x[i][j]) ),
+ * a term whose neighbour lies outside the image being 0.  s is taken by comparison, (a > b) - (a < b), so the integer
+ * factor in -4 .. 4 is exact whatever the denormal mode and every entry is one rounding of integer * g_tv[0].  g_x has
+ * the layout of x (same strides); every addressed element is written exactly once, nothing between them is touched.
+ * One thread per element, 256-element blocks that loop above 262 144 elements.
+ * Arguments are checked as in wire_tv_fwd.                                                                        */
+int wire_tv_bwd(void* stream, const float* x, int planes, int H, int W, int64_t pix_stride, int64_t plane_stride,
+                const float* g_tv, float* g_x);
+/* The loss of the TV-regularised image loop (bspline_image_denoise.py:160-172, there evaluated under no_grad; here the
+ * term acts on the weights), fused with its backward.  y, target and g_y are full-grid [H*W][O], row i*W + j.  The MSE
+ * runs over n_mse rows: idx[r] when idx != NULL (`first` is then ignored), otherwise rows first .. first + n_mse:
+ *   mse  = sum_{r, o} (y[row_r][o] - target[row_r][o])^2 / (n_mse O)          (0 when n_mse == 0)
+ *   loss = mse + lambda_tv tv(y)                                              (tv over the O planes of y)
+ *   g_y[n][o] = [n selected] 2 (y - t)[n][o] / (n_mse O) + lambda_tv dtv/dy[n][o]
+ * loss_out[0..2] = loss, mse, tv, overwritten (loss = fl(mse + fl(lambda_tv tv))).  rec (optional): rec[row_r][:] =
+ * y[row_r][:], as in wire_mse_grad.  EVERY element of g_y is written, the unselected rows with the TV term alone,
+ * lambda_tv * integer rounded once.  A range is handled inside the one pass over the image (one thread per element,
+ * 256-element blocks that loop above 262 144 elements); with idx the pass stores
+ * the TV term and a second launch over the n_mse rows adds their MSE term, each thread to its own element.  The rows of
+ * idx must lie in [0, H*W) (they are trusted, as in wire_mse_grad) and be DISTINCT, as a slice of a permutation is:
+ * if a row repeats, its MSE term in g_y is unspecified, and nothing outside the buffers is touched.  No atomics, every
+ * sum in a fixed order: the same call gives the same bits.  partial: >= 2048 floats of scratch.
+ * H, W or O < 1, O > 8, n_mse < 0 or > H*W, a range outside the grid (idx == NULL), or a NULL pointer other than idx /
+ * rec: WIRE_ERR_ARG before any HIP call.                                                                          */
+int wire_tv_mse_grad(void* stream, const float* y, int H, int W, int O, const float* target, const int64_t* idx,
+                     int64_t first, int64_t n_mse, float lambda_tv, float* g_y, float* loss_out, float* rec,
+                     float* partial);
+
 /* torch.optim.Adam single step over a flat fp32 buffer (complex tensors as
  * real pairs; wire_image_denoise.py:123-125).  step is 1-based.            */
 int wire_adam_step_flat(void* stream, float* param, const float* grad,

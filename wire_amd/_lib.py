@@ -35,7 +35,7 @@ SYMBOLS = [
     "wire_gabor2d_bwd_first_coords", "wire_mscale_first_fwd", "wire_m2_combine_fwd", "wire_m2_combine_ws_bytes",
     "wire_m2_combine_bwd", "wire_mfn_filter_fwd", "wire_mfn_filter_ws_bytes", "wire_mfn_filter_bwd",
     "wire_avgpool_mse_grad_frames", "wire_affine_coords", "wire_ssim_ws_bytes", "wire_ssim",
-    "wire_coded_mse_grad", "wire_coded_fwd", "wire_coded_bwd",
+    "wire_coded_mse_grad", "wire_coded_fwd", "wire_coded_bwd", "wire_tv_fwd", "wire_tv_bwd", "wire_tv_mse_grad",
 ]
 
 
@@ -133,6 +133,9 @@ def _declare(l: C.CDLL) -> None:
     l.wire_coded_mse_grad.argtypes = [vp, vp, i64, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     l.wire_coded_fwd.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp]
     l.wire_coded_bwd.argtypes = [vp, vp, vp, i32, i64, i32, i32, vp]
+    l.wire_tv_fwd.argtypes = [vp, vp, i32, i32, i32, i64, i64, vp, vp]
+    l.wire_tv_bwd.argtypes = [vp, vp, i32, i32, i32, i64, i64, vp, vp]
+    l.wire_tv_mse_grad.argtypes = [vp, vp, i32, i32, i32, vp, vp, i64, i64, f32, vp, vp, vp, vp]
     l.wire_train_fwd_bwd.argtypes = [vp, dp, vp, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp, vp, i64, vp, i64,
                                      C.POINTER(vp)]
     l.wire_train_fwd_bwd_hooked.argtypes = [vp, dp, vp, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp, vp, i64, vp, i64,

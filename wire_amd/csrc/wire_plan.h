@@ -1,5 +1,5 @@
 // wire_plan.h -- internal to the host layer (not installed): what wire_plan.hip, wire_api.hip, wire_hier_api.hip,
-// wire_mfn_api.hip, wire_misc_api.hip and wire_layer_api.hip share -- the error channel, the profiler's scope, the plan of a net, its
+// wire_mfn_api.hip, wire_misc_api.hip, wire_layer_api.hip and wire_tv.hip share -- the error channel, the profiler's scope, the plan of a net, its
 // buffer layouts and the route of a whole-net call.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -177,7 +177,8 @@ hipError_t launch_gabor2d_hparam_grad(hipStream_t s, const float* g, const float
                                       int K, int P, int is_first, float scale, float* partial, float* out2);
 
 // ===========================================================================
-// wire_train.hip -- the glue of a training run (and wire_ssim.hip, the one metric with a kernel file of its own)
+// wire_train.hip -- the glue of a training run (wire_ssim.hip and wire_tv.hip: a metric and a regulariser with kernel
+// files of their own)
 // ===========================================================================
 // ---- training glue
 // idx_out[r] = pi_seed(first + r), r < count: a keyed bijection pi_seed of [0, n_total) (the epoch's shuffle)
@@ -229,6 +230,20 @@ struct SsimWin { float w[SSIM_MAX_TAPS]; };
 int64_t ssim_tiles(int H, int W, int taps);
 hipError_t launch_ssim(hipStream_t s, const float* x, const float* y, int H, int W, int O, int taps, const SsimWin& win,
                        float cov, float c1, float c2, float* out1, float* map, float* partial);
+
+// ---- total variation (wire_tv.hip): tv(x) = sum |x[i+1][j] - x[i][j]| + sum |x[i][j+1] - x[i][j]| over `planes` images
+// of H x W, element (p, i, j) at x[p plane_stride + (i W + j) pix_stride]; its gradient times the device scalar g_tv[0];
+// and loss = mse + lambda_tv tv of a full-grid [H W][O] reconstruction, fused with its backward (the MSE over rows
+// idx[0 .. n_mse), or first .. first + n_mse when idx is null; loss_out[0..2] = loss, mse, tv).
+// partial: >= 1024 floats (launch_tv_fwd), >= 2048 floats (launch_tv_mse_grad)
+bool tv_shape_ok(int planes, int H, int W, int64_t pix_stride, int64_t plane_stride);
+hipError_t launch_tv_fwd(hipStream_t s, const float* x, int planes, int H, int W, int64_t pix_stride,
+                         int64_t plane_stride, float* tv_out, float* partial);
+hipError_t launch_tv_bwd(hipStream_t s, const float* x, int planes, int H, int W, int64_t pix_stride,
+                         int64_t plane_stride, const float* g_tv, float* g_x);
+hipError_t launch_tv_mse_grad(hipStream_t s, const float* y, int H, int W, int O, const float* target,
+                              const int64_t* idx, int64_t first, int64_t n_mse, float lambda_tv, float* g_y,
+                              float* loss_out, float* rec, float* partial);
 
 // ---- best-so-far tracking on the device and the sigmoid of the mesh-export query
 hipError_t launch_track_best(hipStream_t s, const float* metric, float* best, int force, const float* src,

@@ -634,3 +634,78 @@ def ssim(rec: torch.Tensor, gt: torch.Tensor, H: int, W: int, window="gaussian",
     CPU tensors raise WireHipError.  An image smaller than the window raises ValueError; this is stricter than
     pytorch_msssim, which warns and skips the smoothing along that axis."""
     return _ssim(rec, gt, H, W, window, data_range, full)[0]
+
+
+# ---------------------------------------------------------------------------
+# total variation on the device (wire_tv_fwd / wire_tv_bwd)
+# ---------------------------------------------------------------------------
+def _tv_layout(x: torch.Tensor):
+    """(pix_stride, plane_stride) of a (B, C, H, W) tensor whose element (b, c, i, j) lies at
+    (b*C + c) * plane_stride + (i*W + j) * pix_stride with planes and pixels that do not overlap, or None.  A contiguous
+    tensor gives (1, H*W); ``y.reshape(1, H, W, O).permute(0, 3, 1, 2)`` of a contiguous [H*W, O] gives (O, 1)."""
+    B, Cn, H, W = x.shape
+    sb, sc, sh, sw = x.stride()
+    if W > 1:
+        ps, ok = sw, H == 1 or sh == W * sw
+    else:
+        ps, ok = (sh if H > 1 else 1), True
+    if Cn > 1:
+        qs = sc
+        ok = ok and (B == 1 or sb == Cn * sc)
+    else:
+        qs = sb if B > 1 else 1
+    planes, npix = B * Cn, H * W
+    ok = ok and ps >= 1 and qs >= 1 and (qs >= (npix - 1) * ps + 1 or ps >= (planes - 1) * qs + 1
+                                         or planes == 1 or npix == 1)
+    return (ps, qs) if ok else None
+
+
+class _TotalVariationFunction(torch.autograd.Function):
+    """tv(x) of a (B, C, H, W) tensor and its gradient: wire_tv_fwd / wire_tv_bwd on the tensor's own memory when its
+    strides have the (pix_stride, plane_stride) form, on a contiguous copy otherwise."""
+
+    @staticmethod
+    def forward(ctx, x):
+        L = _lib.lib()
+        xin = x.detach()
+        lay = _tv_layout(xin)
+        if lay is None:
+            xin = xin.contiguous()
+            lay = _tv_layout(xin)
+        B, Cn, H, W = xin.shape
+        out = torch.empty((), dtype=torch.float32, device=xin.device)
+        partial = torch.empty(1024, dtype=torch.float32, device=xin.device)
+        _lib.check(L.wire_tv_fwd(_stream_ptr(xin.device), xin.data_ptr(), B * Cn, H, W, lay[0], lay[1], out.data_ptr(),
+                                 partial.data_ptr()), "wire_tv_fwd")
+        ctx.save_for_backward(xin)
+        ctx.lay = lay
+        return out
+
+    @staticmethod
+    def backward(ctx, g_tv):
+        L = _lib.lib()
+        xin, = ctx.saved_tensors
+        B, Cn, H, W = xin.shape
+        _no_second_order("total_variation")
+        g = g_tv.detach().to(torch.float32).reshape(1).contiguous()
+        gx = torch.empty_strided(xin.shape, xin.stride(), dtype=torch.float32, device=xin.device)
+        _lib.check(L.wire_tv_bwd(_stream_ptr(xin.device), xin.data_ptr(), B * Cn, H, W, ctx.lay[0], ctx.lay[1],
+                                 g.data_ptr(), gx.data_ptr()), "wire_tv_bwd")
+        return gx
+
+
+def total_variation(x: torch.Tensor) -> torch.Tensor:
+    """Anisotropic total variation of a (B, C, H, W) CUDA float32 tensor on the device, the reference's
+    ``utils.total_variation_loss`` (modules/utils.py:360-369):
+    ``sum |x[:, :, 1:, :] - x[:, :, :-1, :]| + sum |x[:, :, :, 1:] - x[:, :, :, :-1]|`` -- a sum, not a mean -- as a 0-dim
+    device tensor, differentiable with respect to ``x`` with torch's ``d|u|/du = sign(u)`` (0 at a tie).  One HIP pass
+    forward and one backward (the upstream gradient is read on the device: no sync).  A tensor whose strides have the
+    form (b*C + c) * plane_stride + (i*W + j) * pix_stride is read where it lies -- a contiguous tensor, and the drivers'
+    ``model(coords).reshape(1, H, W, O).permute(0, 3, 1, 2)`` view of the network's [H*W, O] output -- anything else is
+    made contiguous first.  First order only.  CPU tensors raise WireHipError; other ranks or dtypes ValueError."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.numel() == 0:
+        raise ValueError("total_variation expects a non-empty (B, C, H, W) tensor")
+    _require_cuda(x, "image")
+    if x.dtype != torch.float32:
+        raise ValueError("image must be float32")
+    return _TotalVariationFunction.apply(x)

@@ -2,7 +2,7 @@
 
 Only the functions the training/eval loop of wire_image_denoise.py and
 wire_occupancy.py touch are provided: coordinate grids, PSNR, parameter count,
-normalisation, the noise model and logging.  Plotting / montage / table helpers
+normalisation, the noise model, the total-variation regulariser and logging.  Plotting / montage / table helpers
 are out of scope -- except ``get_layer_outputs`` + ``build_montage``, the per-layer
 visualisation query SURVEY section 8 (f)3 names.
 """
@@ -41,6 +41,18 @@ def measure(x, noise_snr=40, tau=100):
         meas[~pos] = -np.random.poisson(-meas[~pos])
         return (meas + noise) / tau
     return meas + noise
+
+
+def total_variation_loss(image):
+    """Anisotropic total variation of a (B, C, H, W) image (modules/utils.py:360-369): the sum -- not the mean -- of
+    the absolute differences of vertical and of horizontal neighbours, a 0-dim device tensor, differentiable with respect
+    to ``image`` (``functional.total_variation``: one HIP pass each way, instead of the slicing, ``abs`` and ``sum``
+    launches of the torch expression).  The drivers' ``model(coords).reshape(1, H, W, 3).permute(0, 3, 1, 2)`` is read
+    as the view it is, without a copy.  The reference's drivers evaluate this term under ``torch.no_grad()``
+    (bspline_image_denoise.py:160-172), where it changes the reported loss and no gradient; a loop in which it acts on
+    the weights is ``FusedTrainer.step_tv``."""
+    from .. import functional
+    return functional.total_variation(image)
 
 
 def count_parameters(model):                    # modules/utils.py:159-160

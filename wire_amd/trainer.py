@@ -41,7 +41,7 @@ class FusedTrainer:
     loops of the reference's bspline_*.py drivers: a number steps the stages' tensors only -- the heads are not in
     ``model.parameters()`` there and keep their initial values, though their gradients are computed and present in
     ``flat_grad`` -- and a sequence steps stage s and head s with ``lr[s]`` (times the schedule's factor).  A sequence
-    for any other kind, or of the wrong length, is a ValueError.  ``step_downsampled``, ``step_radon``,
+    for any other kind, or of the wrong length, is a ValueError.  ``step_downsampled``, ``step_tv``, ``step_radon``,
     ``step_frames`` and ``step_coded`` work for bspline_mscale_hier as for the other kinds.
 
     ``target`` is the [npoints, O] signal of ``step`` / ``step_hashed`` and the default ``gt`` of the metrics.  The
@@ -455,6 +455,72 @@ class FusedTrainer:
         self.t += 1
         self._adam(stream, g)
         self.loss = g[self.count:self.count + 1].clone()
+        return self.loss
+
+    # ------------------------------------------------------------------ total-variation regularised step
+    def step_tv(self, lambda_tv: float, indices: Optional[torch.Tensor] = None, first: int = 0,
+                count: Optional[int] = None) -> torch.Tensor:
+        """One optimizer step of the TV-regularised image loop (bspline_image_denoise.py:160-172,
+        bspline_img_representation.py:147-158): the model is evaluated on the WHOLE 2-D grid in raster order and
+
+            loss = mse + lambda_tv * utils.total_variation_loss(model(coords).reshape(1, H, W, O).permute(0, 3, 1, 2))
+
+        with the mean squared error against ``self.target`` on the rows ``indices`` (contiguous int64 device tensor of
+        DISTINCT flat grid indices, such as a slice of a permutation) or the range [first, first+count) -- given exactly
+        as ``step`` takes them, all rows by default -- and the total variation (a sum, not a mean) of the full
+        reconstruction.  Loss and its gradient come from one fused kernel (wire_tv_mse_grad); backward through the
+        network, Adam.  The reference's drivers evaluate the TV term under ``torch.no_grad()``, where it changes the
+        reported loss and no gradient; here it acts on the weights, which is what their ``tvl`` switch was written for.
+        ``step_tv(0.0)`` on all rows is the plain full-grid MSE step.
+
+        Returns the device loss (no host sync); ``self.loss_parts`` holds [loss, mse, tv], the full reconstruction of
+        the step stays in ``self.y`` ([H*W, O]), and with ``keep_rec`` the selected rows go to ``self.rec``.
+        2-D grids, single process (a neighbour pair must not straddle two shards)."""
+        if self.tz is not None or len(self.grid) != 2:
+            raise ValueError("step_tv needs a 2-D grid")
+        if self.world != 1:
+            raise NotImplementedError("step_tv is single-process")
+        self._need_target("step_tv")
+        lam = float(lambda_tv)
+        if not np.isfinite(lam):
+            raise ValueError(f"lambda_tv must be finite, not {lam}")
+        H, W = int(self.grid[0]), int(self.grid[1])
+        n = H * W
+        if indices is not None:
+            if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64 or not indices.is_cuda \
+                    or indices.dim() != 1 or not indices.is_contiguous():
+                raise ValueError("indices must be a 1-D contiguous CUDA int64 tensor")
+            B = indices.numel()
+            if B > n:
+                raise ValueError(f"{B} indices for a grid of {n} points: the rows of indices must be distinct")
+            first = 0
+        else:
+            first = int(first)
+            B = int(count if count is not None else n - first)
+            if first < 0 or B < 0 or first + B > n:
+                raise ValueError(f"rows [{first}, {first + B}) outside the grid of {n} points")
+        L, d = self.L, C.byref(self.desc)
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        self._reserve(n)
+        g = self.gbuf[0]
+        if getattr(self, "loss_parts", None) is None:
+            self.loss_parts = torch.zeros(3, dtype=torch.float32, device=self.dev)
+        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
+        _lib.check(L.wire_coords_from_index(stream, None, 0, n, self.tx.data_ptr(), W, self.ty.data_ptr(), H,
+                                            None, 1, self.coords.data_ptr()), "coords")
+        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
+                                  self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
+        _lib.check(L.wire_tv_mse_grad(stream, self.y.data_ptr(), H, W, self.O, self.target.data_ptr(),
+                                      indices.data_ptr() if indices is not None else None, first, B, lam,
+                                      self.gy.data_ptr(), self.loss_parts.data_ptr(),
+                                      self.rec.data_ptr() if self.rec is not None else None,
+                                      self.partial.data_ptr()), "tv_mse_grad")
+        _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
+                                  self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
+                                  self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
+        self.t += 1
+        self._adam(stream, g)
+        self.loss = self.loss_parts[0:1].clone()              # loss_parts is overwritten by the next step
         return self.loss
 
     # ------------------------------------------------------------------ multi-image super-resolution step
