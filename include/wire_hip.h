@@ -41,6 +41,19 @@
  *    complex row of K features is stored as P = roundup(2K,64) floats; group
  *    g of 32 features occupies columns [64g,64g+32) = real parts and
  *    [64g+32,64g+64) = imaginary parts.  Pad features read as 0.
+ *
+ * Workspaces
+ *  - `packed`, `act`, `scratch`, `partial` and every `ws` are the caller's; the library keeps nothing in them between
+ *    calls except what this header says a later call reads: `packed` from wire_pack_params to the calls that take it,
+ *    `act` from a forward (wire_mlp_fwd with save_for_bwd = 1, or the forward inside wire_train_fwd_bwd) to the
+ *    backward that belongs to it.
+ *  - no call reads a byte of `packed`, `act`, `scratch`, `partial` or `ws` that the same call -- for `act`, the forward
+ *    it belongs to; for `packed`, wire_pack_params -- has not written.  The buffers need no initialisation, may be larger
+ *    than the size queries ask for, and may hold anything before the call: the leftovers of a larger batch, of another
+ *    net, of another GEMM family, NaN.  Results do not depend on their prior contents: where this header says that the
+ *    same call gives the same bits, it gives them whatever the workspaces held (tests/test_gpu_workspace_fill.py).
+ *  - the regions a call leaves unwritten (rows between n and the next multiple of 128, slabs of unused splits, partials
+ *    beyond the blocks of this n) are unspecified afterwards; DESIGN.md section 3, "Padded regions", lists them.
  */
 #ifndef WIRE_HIP_H
 #define WIRE_HIP_H
