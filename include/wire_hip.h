@@ -486,6 +486,44 @@ int wire_eval_metric(void* stream, int mode, const float* rec, const float* gt,
 int64_t wire_ssim_ws_bytes(int H, int W, int O, int taps);
 int wire_ssim(void* stream, const float* x, const float* y, int H, int W, int O, int taps, const float* window_host,
               float cov_norm, float c1, float c2, float* out1, float* map, void* ws, int64_t ws_bytes);
+/* The gradient of that mean with respect to the SECOND image, times the upstream gradient g_ssim[0] (a DEVICE scalar: no
+ * host synchronisation): x = gt, y = rec, the window and constants as in wire_ssim,
+ *   g_y[q] = g_ssim[0] / ((H-taps+1)(W-taps+1) O) * ( T(A)[q] + 2 y[q] T(B)[q] + x[q] T(C)[q] ),
+ *   A = dS/dmy - 2 cov_norm my dS/dvy - cov_norm mx dS/dvxy,  B = cov_norm dS/dvy,  C = cov_norm dS/dvxy,
+ *   dS/dmy = 2 mx n2 / (d1 d2) - 2 my S / d1,  dS/dvy = -S / d2,  dS/dvxy = 2 n1 / (d1 d2)
+ * (n1 = 2 mx my + c1, n2 = 2 vxy + c2, d1 = mx^2 + my^2 + c1, d2 = vx + vy + c2), T the transpose of the separable valid
+ * convolution: every input pixel collects the coefficient of each window that covers it under that window's tap.
+ * g_y [H][W][O]: every element is written exactly once.  A workgroup owns 16 x 32 input pixels, recomputes the moments
+ * of the windows that cover them from a halo of 2 (taps - 1) about a constant it subtracts from both images (the
+ * forward's cancellation-safe shift, exact for a window that does not sum to one), one channel at a time: at most
+ * 58 320 B of LDS, no intermediate in global memory, no atomics, every sum in a fixed order -- the same call gives the
+ * same bits.  ws: wire_ssim_bwd_ws_bytes(H, W, O, taps) bytes (a small constant today: the argument is there for a
+ * tiling that needs more).  Arguments are checked as in wire_ssim (g_ssim and g_y must not be NULL): WIRE_ERR_ARG before
+ * any HIP call, WIRE_ERR_SIZE for a ws that is too small.  x, y, g_ssim, g_y, ws: device.                          */
+int64_t wire_ssim_bwd_ws_bytes(int H, int W, int O, int taps);
+int wire_ssim_bwd(void* stream, const float* x, const float* y, int H, int W, int O, int taps, const float* window_host,
+                  float cov_norm, float c1, float c2, const float* g_ssim, float* g_y, void* ws, int64_t ws_bytes);
+/* The loss of an SSIM-regularised image loop, fused with its backward.  y, target and g_y are full-grid [H*W][O], row
+ * i*W + j.  The MSE runs over n_mse rows, given exactly as wire_tv_mse_grad takes them (idx[r] when idx != NULL, otherwise
+ * rows first .. first + n_mse); the index is that of the FULL reconstruction against the full target, wire_ssim(target, y):
+ *   mse  = sum_{r, o} (y[row_r][o] - target[row_r][o])^2 / (n_mse O)          (0 when n_mse == 0)
+ *   loss = mse + lambda_ssim (1 - ssim)
+ *   g_y[n][o] = [n selected] 2 (y - t)[n][o] / (n_mse O) - lambda_ssim dssim/dy[n][o]
+ * loss_out[0..2] = loss, mse, ssim, overwritten.  rec (optional): rec[row_r][:] = y[row_r][:].  EVERY element of g_y is
+ * written, the unselected rows with the SSIM term alone.  A range is handled inside the one pass of wire_ssim_bwd's
+ * tiles; with idx that pass stores the SSIM term and a second launch over the n_mse rows adds their MSE term, each
+ * thread to its own element.  The rows of idx are trusted and must be DISTINCT, as for wire_tv_mse_grad.  With
+ * lambda_ssim == 0 the index is not evaluated: loss = mse, loss_out[2] = 0, and g_y holds the bits wire_tv_mse_grad
+ * stores at lambda_tv = 0 (up to the sign of a zero).  No atomics, every sum in a fixed order, no host synchronisation.
+ * ws: wire_ssim_mse_grad_ws_bytes(H, W, O, taps) bytes, device.
+ * taps, O, H, W, cov_norm, c1, c2 as for wire_ssim, n_mse < 0 or > H*W, a range outside the grid (idx == NULL), a
+ * lambda_ssim that is not finite, or a NULL pointer other than idx / rec: WIRE_ERR_ARG before any HIP call; a ws that
+ * is too small: WIRE_ERR_SIZE.                                                                                      */
+int64_t wire_ssim_mse_grad_ws_bytes(int H, int W, int O, int taps);
+int wire_ssim_mse_grad(void* stream, const float* y, int H, int W, int O, const float* target, int taps,
+                       const float* window_host, float cov_norm, float c1, float c2, const int64_t* idx, int64_t first,
+                       int64_t n_mse, float lambda_ssim, float* g_y, float* loss_out, float* rec, void* ws,
+                       int64_t ws_bytes);
 
 /* Best-reconstruction tracking of the drivers without a device->host copy per epoch
  * (wire_image_denoise.py:176-178: `if (mse_array[epoch] < best_mse) or (epoch == 0): best_mse = ...; best_img = imrec`;

@@ -36,6 +36,7 @@ SYMBOLS = [
     "wire_m2_combine_bwd", "wire_mfn_filter_fwd", "wire_mfn_filter_ws_bytes", "wire_mfn_filter_bwd",
     "wire_avgpool_mse_grad_frames", "wire_affine_coords", "wire_ssim_ws_bytes", "wire_ssim",
     "wire_coded_mse_grad", "wire_coded_fwd", "wire_coded_bwd", "wire_tv_fwd", "wire_tv_bwd", "wire_tv_mse_grad",
+    "wire_ssim_bwd_ws_bytes", "wire_ssim_bwd", "wire_ssim_mse_grad_ws_bytes", "wire_ssim_mse_grad",
 ]
 
 
@@ -146,6 +147,13 @@ def _declare(l: C.CDLL) -> None:
     l.wire_ssim_ws_bytes.argtypes = [i32, i32, i32, i32]
     l.wire_ssim_ws_bytes.restype = i64
     l.wire_ssim.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(C.c_float), f32, f32, f32, vp, vp, vp, i64]
+    l.wire_ssim_bwd_ws_bytes.argtypes = [i32, i32, i32, i32]
+    l.wire_ssim_bwd_ws_bytes.restype = i64
+    l.wire_ssim_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(C.c_float), f32, f32, f32, vp, vp, vp, i64]
+    l.wire_ssim_mse_grad_ws_bytes.argtypes = [i32, i32, i32, i32]
+    l.wire_ssim_mse_grad_ws_bytes.restype = i64
+    l.wire_ssim_mse_grad.argtypes = [vp, vp, i32, i32, i32, vp, i32, C.POINTER(C.c_float), f32, f32, f32, vp, i64, i64,
+                                     f32, vp, vp, vp, vp, i64]
     l.wire_prof_enable.argtypes = [i32]
     l.wire_prof_read.argtypes = [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double)]
 

@@ -136,6 +136,48 @@ extern "C" int wire_ssim(void* stream, const float* x, const float* y, int H, in
   return WIRE_OK;
 }
 
+static bool ssim_grad_shape_ok(int H, int W, int O, int taps) {
+  return ssim_shape_ok(H, W, O, taps) && ssim_bwd_tiles(H, W) <= 0x3fffffff;
+}
+extern "C" int64_t wire_ssim_bwd_ws_bytes(int H, int W, int O, int taps) {
+  if (!ssim_grad_shape_ok(H, W, O, taps)) return fail(WIRE_ERR_ARG, "bad argument to wire_ssim_bwd_ws_bytes");
+  return 256;        // the tiles keep every intermediate in LDS; the argument stays for a tiling that does not
+}
+extern "C" int wire_ssim_bwd(void* stream, const float* x, const float* y, int H, int W, int O, int taps,
+                             const float* window_host, float cov_norm, float c1, float c2, const float* g_ssim,
+                             float* g_y, void* ws, int64_t ws_bytes) {
+  if (!ssim_grad_shape_ok(H, W, O, taps) || !x || !y || !window_host || !g_ssim || !g_y || !ws ||
+      !std::isfinite(cov_norm) || !std::isfinite(c1) || !std::isfinite(c2))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_ssim_bwd");
+  if (ws_bytes < wire_ssim_bwd_ws_bytes(H, W, O, taps)) return fail(WIRE_ERR_SIZE, "ws too small");
+  SsimWin win{};
+  for (int t = 0; t < taps; ++t) win.w[t] = window_host[t];
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_ssim_bwd((hipStream_t)stream, x, y, H, W, O, taps, win, cov_norm, c1, c2, g_ssim, g_y));
+  return WIRE_OK;
+}
+extern "C" int64_t wire_ssim_mse_grad_ws_bytes(int H, int W, int O, int taps) {
+  if (!ssim_grad_shape_ok(H, W, O, taps)) return fail(WIRE_ERR_ARG, "bad argument to wire_ssim_mse_grad_ws_bytes");
+  return ssim_loss_partials(H, W) * 4 + 256;
+}
+extern "C" int wire_ssim_mse_grad(void* stream, const float* y, int H, int W, int O, const float* target, int taps,
+                                  const float* window_host, float cov_norm, float c1, float c2, const int64_t* idx,
+                                  int64_t first, int64_t n_mse, float lambda_ssim, float* g_y, float* loss_out,
+                                  float* rec, void* ws, int64_t ws_bytes) {
+  const int64_t npix = (int64_t)H * W;
+  if (!ssim_grad_shape_ok(H, W, O, taps) || n_mse < 0 || n_mse > npix ||
+      (!idx && (first < 0 || first > npix - n_mse)) || !y || !target || !window_host || !g_y || !loss_out || !ws ||
+      !std::isfinite(cov_norm) || !std::isfinite(c1) || !std::isfinite(c2) || !std::isfinite(lambda_ssim))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_ssim_mse_grad");
+  if (ws_bytes < wire_ssim_mse_grad_ws_bytes(H, W, O, taps)) return fail(WIRE_ERR_SIZE, "ws too small");
+  SsimWin win{};
+  for (int t = 0; t < taps; ++t) win.w[t] = window_host[t];
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_ssim_mse_grad((hipStream_t)stream, y, H, W, O, target, taps, win, cov_norm, c1, c2, idx, first, n_mse,
+                              lambda_ssim, g_y, loss_out, rec, (float*)ws));
+  return WIRE_OK;
+}
+
 extern "C" int wire_track_best(void* stream, const float* metric, float* best_metric, int force, const float* src,
                                float* dst, int64_t count, int* updated) {
   if (!metric || !best_metric || count < 0 || (count > 0 && (!src || !dst)))

@@ -230,6 +230,17 @@ struct SsimWin { float w[SSIM_MAX_TAPS]; };
 int64_t ssim_tiles(int H, int W, int taps);
 hipError_t launch_ssim(hipStream_t s, const float* x, const float* y, int H, int W, int O, int taps, const SsimWin& win,
                        float cov, float c1, float c2, float* out1, float* map, float* partial);
+// ---- its gradient and the SSIM-regularised loss (wire_ssim_bwd.hip): g_y [H][W][O] = g_ssim[0] (a device scalar) times
+// d mean(S) / dy; and loss = mse + lambda (1 - ssim(target, y)) of a full-grid [H W][O] reconstruction, fused with its
+// backward (the MSE over rows idx[0 .. n_mse), or first .. first + n_mse when idx is null; loss_out[0..2] = loss, mse,
+// ssim; lambda == 0 leaves the index out).  partial: ssim_loss_partials(H, W) floats
+int64_t ssim_bwd_tiles(int H, int W);
+int64_t ssim_loss_partials(int H, int W);
+hipError_t launch_ssim_bwd(hipStream_t s, const float* x, const float* y, int H, int W, int O, int taps,
+                           const SsimWin& win, float cov, float c1, float c2, const float* g_ssim, float* g_y);
+hipError_t launch_ssim_mse_grad(hipStream_t s, const float* y, int H, int W, int O, const float* target, int taps,
+                                const SsimWin& win, float cov, float c1, float c2, const int64_t* idx, int64_t first,
+                                int64_t n_mse, float lambda, float* g_y, float* loss_out, float* rec, float* partial);
 
 // ---- total variation (wire_tv.hip): tv(x) = sum |x[i+1][j] - x[i][j]| + sum |x[i][j+1] - x[i][j]| over `planes` images
 // of H x W, element (p, i, j) at x[p plane_stride + (i W + j) pix_stride]; its gradient times the device scalar g_tv[0];

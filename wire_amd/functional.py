@@ -576,8 +576,8 @@ def _ssim_window(window):
     return _SSIM_WINDOWS[key]
 
 
-def _ssim(rec, gt, H, W, window, data_range, full, ws=None):
-    """ssim() with a workspace the caller may keep between calls; returns (result, workspace)."""
+def _ssim_check(rec, gt, H, W, window, data_range):
+    """The argument checks ssim() and ssim_loss() share; returns (H, W, O, taps, window, cov_norm, c1, c2)."""
     taps, win, cov = _ssim_window(window)
     uniform = window == "uniform" or (isinstance(window, tuple) and window[1] is None)
     if data_range is None:
@@ -600,6 +600,12 @@ def _ssim(rec, gt, H, W, window, data_range, full, ws=None):
     _require_cuda(gt, "gt")
     if rec.dtype != torch.float32 or gt.dtype != torch.float32:
         raise ValueError("rec and gt must be float32")
+    return H, W, O, taps, win, cov, (0.01 * float(data_range)) ** 2, (0.03 * float(data_range)) ** 2
+
+
+def _ssim(rec, gt, H, W, window, data_range, full, ws=None):
+    """ssim() with a workspace the caller may keep between calls; returns (result, workspace)."""
+    H, W, O, taps, win, cov, c1, c2 = _ssim_check(rec, gt, H, W, window, data_range)
     L = _lib.lib()
     dev = rec.device
     x, y = gt.detach().contiguous(), rec.detach().contiguous()
@@ -608,7 +614,6 @@ def _ssim(rec, gt, H, W, window, data_range, full, ws=None):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     out = torch.empty((), dtype=torch.float32, device=dev)
     smap = torch.empty(H - taps + 1, W - taps + 1, O, dtype=torch.float32, device=dev) if full else None
-    c1, c2 = (0.01 * float(data_range)) ** 2, (0.03 * float(data_range)) ** 2
     _lib.check(L.wire_ssim(_stream_ptr(dev), x.data_ptr(), y.data_ptr(), H, W, O, taps, win, cov, c1, c2, out.data_ptr(),
                            None if smap is None else smap.data_ptr(), ws.data_ptr(), ws.numel()), "wire_ssim")
     return ((out, smap) if full else out), ws
@@ -634,6 +639,53 @@ def ssim(rec: torch.Tensor, gt: torch.Tensor, H: int, W: int, window="gaussian",
     CPU tensors raise WireHipError.  An image smaller than the window raises ValueError; this is stricter than
     pytorch_msssim, which warns and skips the smoothing along that axis."""
     return _ssim(rec, gt, H, W, window, data_range, full)[0]
+
+
+class _SsimLossFunction(torch.autograd.Function):
+    """1 - ssim(rec, gt) and its gradient with respect to rec: wire_ssim forward, wire_ssim_bwd backward."""
+
+    @staticmethod
+    def forward(ctx, rec, gt, cfg):
+        H, W, O, taps, win, cov, c1, c2 = cfg
+        L = _lib.lib()
+        dev = rec.device
+        x, y = gt.detach().contiguous(), rec.detach().contiguous()
+        ws_bytes = _lib.check(L.wire_ssim_ws_bytes(H, W, O, taps), "wire_ssim_ws_bytes")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.check(L.wire_ssim(_stream_ptr(dev), x.data_ptr(), y.data_ptr(), H, W, O, taps, win, cov, c1, c2,
+                               out.data_ptr(), None, ws.data_ptr(), ws.numel()), "wire_ssim")
+        ctx.save_for_backward(x, y)
+        ctx.cfg = cfg
+        ctx.rec_shape = tuple(rec.shape)
+        return 1.0 - out
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        x, y = ctx.saved_tensors
+        H, W, O, taps, win, cov, c1, c2 = ctx.cfg
+        _no_second_order("ssim_loss")
+        L = _lib.lib()
+        dev = y.device
+        g = (-g_loss.detach().to(torch.float32)).reshape(1).contiguous()      # d(1 - ssim) = -d ssim; read on the device
+        ws_bytes = _lib.check(L.wire_ssim_bwd_ws_bytes(H, W, O, taps), "wire_ssim_bwd_ws_bytes")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        gy = torch.empty(H * W * O, dtype=torch.float32, device=dev)
+        _lib.check(L.wire_ssim_bwd(_stream_ptr(dev), x.data_ptr(), y.data_ptr(), H, W, O, taps, win, cov, c1, c2,
+                                   g.data_ptr(), gy.data_ptr(), ws.data_ptr(), ws.numel()), "wire_ssim_bwd")
+        return gy.reshape(ctx.rec_shape), None, None
+
+
+def ssim_loss(rec: torch.Tensor, gt: torch.Tensor, H: int, W: int, window="gaussian", data_range=None) -> torch.Tensor:
+    """``1 - ssim(rec, gt, H, W, window, data_range)`` as a 0-dim device tensor that is differentiable with respect to
+    ``rec`` (only): the perceptual term of ``loss = mse + lambda * ssim_loss(...)``.  Forward is wire_ssim, backward
+    wire_ssim_bwd -- one HIP launch, the closed-form gradient of the mean index gathered per input pixel, the upstream
+    gradient read on the device (no sync), the same bits for the same call.  First order only.
+
+    Shapes, dtypes, window specs, ``data_range`` and errors are those of ``ssim``; the gradient has the shape of
+    ``rec``.  ``gt`` receives no gradient."""
+    cfg = _ssim_check(rec, gt, H, W, window, data_range)
+    return _SsimLossFunction.apply(rec, gt, cfg)
 
 
 # ---------------------------------------------------------------------------

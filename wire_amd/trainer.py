@@ -523,6 +523,85 @@ class FusedTrainer:
         self.loss = self.loss_parts[0:1].clone()              # loss_parts is overwritten by the next step
         return self.loss
 
+    # ------------------------------------------------------------------ SSIM-regularised step
+    def step_ssim(self, lambda_ssim: float, indices: Optional[torch.Tensor] = None, first: int = 0,
+                  count: Optional[int] = None, window="gaussian", data_range=None) -> torch.Tensor:
+        """One optimizer step of an image loop with the perceptual term: the model is evaluated on the WHOLE 2-D grid in
+        raster order and
+
+            loss = mse + lambda_ssim * (1 - ssim(model(coords), target))
+
+        with the mean squared error against ``self.target`` on the rows ``indices`` or the range [first, first+count)
+        -- given exactly as ``step_tv`` takes them, all rows by default -- and the structural similarity
+        (``functional.ssim``: ``window`` and ``data_range`` as there) of the full reconstruction against the full
+        target.  Loss and its gradient come from one fused kernel (wire_ssim_mse_grad); backward through the network,
+        Adam.  With ``lambda_ssim == 0.0`` the index is not evaluated: the step leaves the parameters that
+        ``step_tv(0.0)`` leaves, and ``loss_parts[2]`` is 0.
+
+        Returns the device loss (no host sync); ``self.loss_parts`` holds [loss, mse, ssim], the full reconstruction of
+        the step stays in ``self.y`` ([H*W, O]), and with ``keep_rec`` the selected rows go to ``self.rec``.
+        2-D grids, single process (a window must not straddle two shards)."""
+        if self.tz is not None or len(self.grid) != 2:
+            raise ValueError("step_ssim needs a 2-D grid")
+        if self.world != 1:
+            raise NotImplementedError("step_ssim is single-process")
+        self._need_target("step_ssim")
+        lam = float(lambda_ssim)
+        if not np.isfinite(lam):
+            raise ValueError(f"lambda_ssim must be finite, not {lam}")
+        H, W = int(self.grid[0]), int(self.grid[1])
+        n = H * W
+        taps, win, cov = functional._ssim_window(window)
+        if data_range is None:
+            if window == "uniform" or (isinstance(window, tuple) and window[1] is None):
+                raise ValueError("a uniform window needs data_range (see functional.ssim)")
+            data_range = 1.0
+        if H < taps or W < taps:
+            raise ValueError(f"a {H} x {W} grid is smaller than the {taps}-tap window")
+        if not 1 <= self.O <= 8:
+            raise ValueError(f"{self.O} channels: the library takes 1..8")
+        if indices is not None:
+            if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64 or not indices.is_cuda \
+                    or indices.dim() != 1 or not indices.is_contiguous():
+                raise ValueError("indices must be a 1-D contiguous CUDA int64 tensor")
+            B = indices.numel()
+            if B > n:
+                raise ValueError(f"{B} indices for a grid of {n} points: the rows of indices must be distinct")
+            first = 0
+        else:
+            first = int(first)
+            B = int(count if count is not None else n - first)
+            if first < 0 or B < 0 or first + B > n:
+                raise ValueError(f"rows [{first}, {first + B}) outside the grid of {n} points")
+        L, d = self.L, C.byref(self.desc)
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        self._reserve(n)
+        g = self.gbuf[0]
+        if getattr(self, "loss_parts", None) is None:
+            self.loss_parts = torch.zeros(3, dtype=torch.float32, device=self.dev)
+        ws_bytes = _lib.check(L.wire_ssim_mse_grad_ws_bytes(H, W, self.O, taps), "ssim_mse_grad_ws_bytes")
+        ws = getattr(self, "_ssim_loss_ws", None)
+        if ws is None or ws.numel() < ws_bytes:
+            ws = self._ssim_loss_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.dev)
+        c1, c2 = (0.01 * float(data_range)) ** 2, (0.03 * float(data_range)) ** 2
+        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
+        _lib.check(L.wire_coords_from_index(stream, None, 0, n, self.tx.data_ptr(), W, self.ty.data_ptr(), H,
+                                            None, 1, self.coords.data_ptr()), "coords")
+        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
+                                  self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
+        _lib.check(L.wire_ssim_mse_grad(stream, self.y.data_ptr(), H, W, self.O, self.target.data_ptr(), taps, win, cov,
+                                        c1, c2, indices.data_ptr() if indices is not None else None, first, B, lam,
+                                        self.gy.data_ptr(), self.loss_parts.data_ptr(),
+                                        self.rec.data_ptr() if self.rec is not None else None,
+                                        ws.data_ptr(), ws.numel()), "ssim_mse_grad")
+        _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
+                                  self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
+                                  self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
+        self.t += 1
+        self._adam(stream, g)
+        self.loss = self.loss_parts[0:1].clone()              # loss_parts is overwritten by the next step
+        return self.loss
+
     # ------------------------------------------------------------------ multi-image super-resolution step
     def affine_coords(self, mats) -> torch.Tensor:
         """The coordinates of B frames of the trainer's grid, each moved by its 2 x 3 matrix -- ``motion.get_imstack``'s
