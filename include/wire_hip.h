@@ -444,6 +444,27 @@ int wire_tv_bwd(void* stream, const float* x, int planes, int H, int W, int64_t 
 int wire_tv_mse_grad(void* stream, const float* y, int H, int W, int O, const float* target, const int64_t* idx,
                      int64_t first, int64_t n_mse, float lambda_tv, float* g_y, float* loss_out, float* rec,
                      float* partial);
+/* The TV prior of an inverse problem, ADDED to the gradient that the operator's own backward has left in g_y (the Radon
+ * adjoint, the pooled or the coded-exposure loss).  y and g_y are the network's own rows [H*W*T][O]: element
+ * (i, j, k, o) lies at ((i*W + j)*T + k)*O + o; T = 1 is an image, T > 1 the (H, W, T) grid of the video step.
+ *   tv_s = sum |y[i+1,j,k,o] - y[i,j,k,o]| + sum |y[i,j+1,k,o] - y[i,j,k,o]|     (utils.total_variation_loss of every
+ *                                                                               frame and channel; a sum, not a mean)
+ *   tv_t = sum |y[i,j,k+1,o] - y[i,j,k,o]|                                       (the same sum along the frame axis)
+ *   g_y[e] = g_y[e] + (lambda_s k_s + lambda_t k_t)
+ * with k_s in -4 .. 4 and k_t in -2 .. 2 the exact integer sums of s over the element's spatial and temporal pairs,
+ * s by comparison and s(0) = 0 exactly as in wire_tv_bwd, a term whose neighbour lies outside the grid being 0.  Three
+ * roundings, in this order: p = fl(lambda_s k_s); q = fma(lambda_t, k_t, p); g_y[e] = fl(g_y[e] + q).  Every element
+ * is read and written once, by its own thread; with both lambdas 0 g_y keeps its bits up to the sign of a zero.
+ * loss_out[0..3] = loss, data, tv_s, tv_t, overwritten: data = data_loss[0], a DEVICE scalar such as the slot the
+ * operator wrote its loss to (no host synchronisation; NULL: 0), and
+ *   loss = fl(fl(data + fl(lambda_s tv_s)) + fl(lambda_t tv_t)).
+ * Both sums are reported whatever the lambdas are.  One thread per element, 256-element blocks that loop above
+ * 262 144 elements, the six neighbours (O, T*O and W*T*O floats away) re-read through the caches; no atomics, every
+ * sum in a fixed order: the same call gives the same bits.  partial: >= 2048 floats of scratch.
+ * H, W, T or O < 1, O > 8, a lambda that is not finite, sizes beyond 63 bits, or a NULL y, g_y, loss_out or partial:
+ * WIRE_ERR_ARG before any HIP call.                                                                              */
+int wire_tv_add_grad(void* stream, const float* y, int H, int W, int T, int O, float lambda_s, float lambda_t,
+                     const float* data_loss, float* g_y, float* loss_out, float* partial);
 
 /* torch.optim.Adam single step over a flat fp32 buffer (complex tensors as
  * real pairs; wire_image_denoise.py:123-125).  step is 1-based.            */

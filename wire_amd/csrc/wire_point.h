@@ -255,6 +255,11 @@ hipError_t launch_tv_bwd(hipStream_t s, const float* x, int planes, int H, int W
 hipError_t launch_tv_mse_grad(hipStream_t s, const float* y, int H, int W, int O, const float* target,
                               const int64_t* idx, int64_t first, int64_t n_mse, float lambda_tv, float* g_y,
                               float* loss_out, float* rec, float* partial);
+// the TV term of an (H, W, T) grid of O channels ([H W T][O] rows, T = 1: an image), its spatial and temporal sums
+// weighted apart, ADDED to the g_y an operator's backward has left; loss_out[0..3] = loss, data, tv_s, tv_t.
+// partial: >= 2048 floats
+hipError_t launch_tv_add_grad(hipStream_t s, const float* y, int H, int W, int T, int O, float lambda_s,
+                              float lambda_t, const float* data_loss, float* g_y, float* loss_out, float* partial);
 
 // ---- best-so-far tracking on the device and the sigmoid of the mesh-export query
 hipError_t launch_track_best(hipStream_t s, const float* metric, float* best, int force, const float* src,

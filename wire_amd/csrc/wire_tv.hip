@@ -26,7 +26,14 @@
 // SUMS: a thread's terms in order, the wave by shuffles, the four waves and then the blocks' partials in a fixed
 // order (tv_final_kernel).  No atomics: the same call gives the same bits.
 //
-// The three entry points of the C ABI (include/wire_hip.h) are at the end of this file.
+//   wire_tv_add_grad: the same one thread per flat element on the network's own [H*W*T][O] rows, a third axis (the
+//     frames of a video, k of row (i*W + j)*T + k) with its own weight, and the term ADDED to a g_y that an operator's
+//     backward has left.  Six neighbours, O, T*O and W*T*O floats away; the first two pairs lie within a few cache
+//     lines of the lane's own, the third is one image row of T*O*W floats away and is the `own` load of a thread
+//     that far off.  On a large video (256 x 256 x 16 x 3 floats = 12.6 MB, three XCD L2s' worth) whether that load
+//     still comes out of the L2 and not the Infinity Cache is UNMEASURED; no halo was built for it either.
+//
+// The four entry points of the C ABI (include/wire_hip.h) are at the end of this file.
 #include "wire_dev.h"
 #include "wire_plan.h"
 
@@ -188,6 +195,70 @@ __global__ __launch_bounds__(256) void tv_final_kernel(const float* __restrict__
   }
 }
 
+// ---- the TV term of an (H, W, T) grid of O channels, added to a gradient that is already there (wire_tv_add_grad)
+struct TvGeom3 {
+  long long total, sh, sw;     // H * W * T * O; the floats between two rows (W * T * O) and two columns (T * O)
+  int H, W, T, O;
+};
+
+// element e = ((i*W + j)*T + k)*O + o.  partial[b] receives the block's spatial sum, partial[TV_BLOCKS + b] its
+// temporal one.  g_y[e] = fl(g_y[e] + fma(lambda_t, k_t, fl(lambda_s * k_s))): three roundings.
+__global__ __launch_bounds__(256) void tv_add_grad_kernel(const float* __restrict__ y, TvGeom3 g, float lambda_s,
+                                                          float lambda_t, float* __restrict__ g_y,
+                                                          float* __restrict__ partial) {
+  __shared__ float red[4];
+  float tvs = 0.f, tvt = 0.f;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < g.total; e += (long long)gridDim.x * 256) {
+    const long long row = e / g.O, pix = row / g.T, r = pix / g.W;
+    const int k = (int)(row - pix * g.T), j = (int)(pix - r * g.W), i = (int)r;
+    const float v = y[e];
+    int ks = 0, kt = 0;
+    if (i > 0) ks += tv_sign(v, y[e - g.sh]);
+    if (i + 1 < g.H) { const float d = y[e + g.sh]; ks -= tv_sign(d, v); tvs += fabsf(d - v); }
+    if (j > 0) ks += tv_sign(v, y[e - g.sw]);
+    if (j + 1 < g.W) { const float d = y[e + g.sw]; ks -= tv_sign(d, v); tvs += fabsf(d - v); }
+    if (k > 0) kt += tv_sign(v, y[e - g.O]);
+    if (k + 1 < g.T) { const float d = y[e + g.O]; kt -= tv_sign(d, v); tvt += fabsf(d - v); }
+    const float term = __builtin_fmaf(lambda_t, (float)kt, __fmul_rn(lambda_s, (float)ks));
+    g_y[e] = __fadd_rn(g_y[e], term);
+  }
+  tvs = tv_block_sum(tvs, red);
+  tvt = tv_block_sum(tvt, red);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = tvs;
+    partial[TV_BLOCKS + blockIdx.x] = tvt;
+  }
+}
+
+// out[2] = tv_s and out[3] = tv_t, the sums of nb partials each; out[1] = data = data_loss[0] (0 when NULL);
+// out[0] = fl(fl(data + fl(lambda_s tv_s)) + fl(lambda_t tv_t))
+__global__ __launch_bounds__(256) void tv_add_final_kernel(const float* __restrict__ partial, int nb, float lambda_s,
+                                                           float lambda_t, const float* __restrict__ data_loss,
+                                                           float* __restrict__ out) {
+  __shared__ float red[4];
+  float a = 0.f, b = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) a += partial[i];
+  for (int i = threadIdx.x; i < nb; i += 256) b += partial[TV_BLOCKS + i];
+  a = tv_block_sum(a, red);
+  b = tv_block_sum(b, red);
+  if (threadIdx.x != 0) return;
+  const float data = data_loss ? data_loss[0] : 0.f;
+  out[0] = __fadd_rn(__fadd_rn(data, __fmul_rn(lambda_s, a)), __fmul_rn(lambda_t, b));
+  out[1] = data;
+  out[2] = a;
+  out[3] = b;
+}
+
+// false: the sizes do not fit 63 bits (the largest offset is total - 1)
+static bool tv_geom3(int H, int W, int T, int O, TvGeom3& g) {
+  if (H < 1 || W < 1 || T < 1 || O < 1) return false;
+  long long sw = (long long)T * O, sh, total;                         // T * O < 2^62
+  if (__builtin_mul_overflow(sw, (long long)W, &sh) || __builtin_mul_overflow(sh, (long long)H, &total)) return false;
+  g.total = total; g.sh = sh; g.sw = sw;
+  g.H = H; g.W = W; g.T = T; g.O = O;
+  return true;
+}
+
 // false: the sizes or the largest address do not fit 63 bits
 static bool tv_geom(int planes, int H, int W, int64_t ps, int64_t qs, TvGeom& g) {
   if (planes < 1 || H < 1 || W < 1 || ps < 1 || qs < 1) return false;
@@ -247,6 +318,17 @@ hipError_t launch_tv_mse_grad(hipStream_t s, const float* y, int H, int W, int O
   return hipGetLastError();
 }
 
+hipError_t launch_tv_add_grad(hipStream_t s, const float* y, int H, int W, int T, int O, float lambda_s,
+                              float lambda_t, const float* data_loss, float* g_y, float* loss_out, float* partial) {
+  TvGeom3 g;
+  if (!tv_geom3(H, W, T, O, g)) return hipErrorInvalidValue;
+  const unsigned nb = tv_blocks(g.total);
+  hipLaunchKernelGGL(tv_add_grad_kernel, dim3(nb), dim3(256), 0, s, y, g, lambda_s, lambda_t, g_y, partial);
+  hipLaunchKernelGGL(tv_add_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, lambda_s, lambda_t, data_loss,
+                     loss_out);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // entry points of the C ABI
 // ---------------------------------------------------------------------------
@@ -275,6 +357,17 @@ extern "C" int wire_tv_mse_grad(void* stream, const float* y, int H, int W, int 
     return fail(WIRE_ERR_ARG, "bad argument to wire_tv_mse_grad");
   ProfScope ps((hipStream_t)stream, 3, 0);
   HIPCHK(launch_tv_mse_grad((hipStream_t)stream, y, H, W, O, target, idx, first, n_mse, lambda_tv, g_y, loss_out, rec,
+                            partial));
+  return WIRE_OK;
+}
+extern "C" int wire_tv_add_grad(void* stream, const float* y, int H, int W, int T, int O, float lambda_s,
+                                float lambda_t, const float* data_loss, float* g_y, float* loss_out, float* partial) {
+  TvGeom3 g;
+  if (O > WIRE_MAXO || !tv_geom3(H, W, T, O, g) || !__builtin_isfinite(lambda_s) || !__builtin_isfinite(lambda_t) ||
+      !y || !g_y || !loss_out || !partial)
+    return fail(WIRE_ERR_ARG, "bad argument to wire_tv_add_grad");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  HIPCHK(launch_tv_add_grad((hipStream_t)stream, y, H, W, T, O, lambda_s, lambda_t, data_loss, g_y, loss_out,
                             partial));
   return WIRE_OK;
 }

@@ -411,19 +411,42 @@ class FusedTrainer:
                 raise RuntimeError(f"data-parallel replicas diverged at optimizer step {self.t} (WIRE_DP_CHECK)")
         return self.loss
 
+    # ------------------------------------------------------------------ the TV prior of the operator steps
+    @staticmethod
+    def _tv_weight(name: str, value) -> float:
+        lam = float(value)
+        if not np.isfinite(lam):
+            raise ValueError(f"{name} must be finite, not {lam}")
+        return lam
+
+    def _tv_add_grad(self, stream, H: int, W: int, T: int, lam_s: float, lam_t: float, data_loss: int) -> None:
+        """The TV term of the (H, W, T) grid in ``self.y``, added to the ``self.gy`` the operator's backward has left
+        (wire_tv_add_grad); ``self.tv_parts`` receives [loss, data, tv_s, tv_t], data being the device scalar at
+        ``data_loss``."""
+        if getattr(self, "tv_parts", None) is None:
+            self.tv_parts = torch.zeros(4, dtype=torch.float32, device=self.dev)
+        _lib.check(self.L.wire_tv_add_grad(stream, self.y.data_ptr(), H, W, T, self.O, lam_s, lam_t, data_loss,
+                                           self.gy.data_ptr(), self.tv_parts.data_ptr(), self.partial.data_ptr()),
+                   "tv_add_grad")
+
     # ------------------------------------------------------------------ super-resolution step
     def step_downsampled(self, gt_lr: torch.Tensor, scale: int,
-                         rec_lr: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         rec_lr: Optional[torch.Tensor] = None, lambda_tv: float = 0.0) -> torch.Tensor:
         """One optimizer step of the super-resolution loop (wire_SISR.py:151-178): the model is
         evaluated on the WHOLE high-resolution grid in raster order, ``torch.nn.AvgPool2d(scale)``
         brings the reconstruction to the resolution of ``gt_lr`` ([H//scale * W//scale, O], device
         float32), loss = mean squared error there; backward through the pooling and the network,
         Adam.  The high-resolution reconstruction of this step stays in ``self.y`` ([H*W, O]).
+        ``lambda_tv`` != 0 adds ``lambda_tv * utils.total_variation_loss`` of the high-resolution reconstruction
+        (bspline_SISR.py's ``lambda_tv``) to the loss and its gradient to dL/dy (wire_tv_add_grad, between the pooled
+        loss and the backward); the returned loss is the total and ``self.tv_parts`` holds [loss, mse, tv, 0].  With
+        0.0 that kernel is not launched and the step is the plain one, bit for bit.
         2-D grids, single process (a pooled window must not straddle two shards)."""
         if self.tz is not None or len(self.grid) != 2:
             raise ValueError("step_downsampled needs a 2-D grid")
         if self.world != 1:
             raise NotImplementedError("step_downsampled is single-process")
+        lam = self._tv_weight("lambda_tv", lambda_tv)
         H, W = int(self.grid[0]), int(self.grid[1])
         scale = int(scale)
         if scale < 1 or scale > min(H, W):
@@ -449,12 +472,15 @@ class FusedTrainer:
         _lib.check(L.wire_avgpool_mse_grad(stream, self.y.data_ptr(), H, W, self.O, scale, gt.data_ptr(),
                                            self.gy.data_ptr(), rec_lr.data_ptr() if rec_lr is not None else None,
                                            g.data_ptr() + 4 * self.count, self.partial.data_ptr()), "avgpool_mse_grad")
+        if lam != 0.0:
+            self._tv_add_grad(stream, H, W, 1, lam, 0.0, g.data_ptr() + 4 * self.count)
         _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
                                   self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
                                   self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
         self.t += 1
         self._adam(stream, g)
-        self.loss = g[self.count:self.count + 1].clone()
+        # tv_parts is overwritten by the next regularised step, the gradient buffer by the next step
+        self.loss = (self.tv_parts[0:1] if lam != 0.0 else g[self.count:self.count + 1]).clone()
         return self.loss
 
     # ------------------------------------------------------------------ total-variation regularised step
@@ -629,7 +655,9 @@ class FusedTrainer:
         loss = ``MSELoss()(output*mask, gt_lr*mask)`` (``mask`` shaped like ``gt_lr``, any values; None = ones); backward
         through the pooling and the network, Adam.  ``rec_lr`` (optional, shaped like ``gt_lr``) receives the unmasked
         pooled frames, and the high-resolution frames of this step stay in ``self.y`` ([B*H*W, O]).  B is read from
-        ``coords`` and may change from call to call (a last, smaller batch).  2-D grids, single process."""
+        ``coords`` and may change from call to call (a last, smaller batch).  2-D grids, single process.
+        No TV prior here (``step_downsampled``, ``step_radon`` and ``step_coded`` take one): the frames are warped
+        copies, and a prior belongs on the canonical grid, which this step never evaluates."""
         if self.tz is not None or len(self.grid) != 2:
             raise ValueError("step_frames needs a 2-D grid")
         if self.world != 1:
@@ -680,16 +708,20 @@ class FusedTrainer:
         return self.loss
 
     # ------------------------------------------------------------------ CT step
-    def step_radon(self, sinogram: torch.Tensor, thetas: torch.Tensor) -> torch.Tensor:
+    def step_radon(self, sinogram: torch.Tensor, thetas: torch.Tensor, lambda_tv: float = 0.0) -> torch.Tensor:
         """One optimizer step of the CT loop (wire_ct.py:128-139): the model is evaluated on the WHOLE grid in raster
         order (``img_estim = model(coords).reshape(-1, H, W)``), ``lin_inverse.radon`` turns it into a sinogram
         ([nangles, W]), loss = mean squared error against ``sinogram``; backward through the adjoint Radon kernel
-        and the network, Adam.  The image estimate of this step stays in ``self.y`` ([H*W, 1]).  2-D grids, one output
-        feature, single process."""
+        and the network, Adam.  The image estimate of this step stays in ``self.y`` ([H*W, 1]).
+        ``lambda_tv`` != 0 adds ``lambda_tv * utils.total_variation_loss(img_estim)`` (bspline_ct.py's ``lambda_tv``)
+        to the loss and its gradient to the adjoint's dL/dy (wire_tv_add_grad, between the adjoint and the backward);
+        the returned loss is the total and ``self.tv_parts`` holds [loss, mse, tv, 0].  With 0.0 that kernel is not
+        launched and the step issues the launches of the plain one.  2-D grids, one output feature, single process."""
         if self.tz is not None or len(self.grid) != 2 or self.O != 1:
             raise ValueError("step_radon needs a 2-D grid and out_features == 1")
         if self.world != 1:
             raise NotImplementedError("step_radon is single-process")
+        lam = self._tv_weight("lambda_tv", lambda_tv)
         H, W = int(self.grid[0]), int(self.grid[1])
         th = thetas.detach().to(self.dev, torch.float32).contiguous()
         A = th.numel()
@@ -716,17 +748,20 @@ class FusedTrainer:
                                    self.partial.data_ptr()), "mse_grad")
         _lib.check(L.wire_radon_bwd(stream, self._gsino.data_ptr(), th.data_ptr(), H, W, A, self.gy.data_ptr()),
                    "radon_bwd")
+        if lam != 0.0:
+            self._tv_add_grad(stream, H, W, 1, lam, 0.0, g.data_ptr() + 4 * self.count)
         _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
                                   self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
                                   self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
         self.t += 1
         self._adam(stream, g)
-        self.loss = g[self.count:self.count + 1].clone()
+        self.loss = (self.tv_parts[0:1] if lam != 0.0 else g[self.count:self.count + 1]).clone()
         return self.loss
 
     # ------------------------------------------------------------------ video compressive-sensing step
     def step_coded(self, coded: torch.Tensor, masks, nframes: int, dup_last: bool = True,
-                   slab: Optional[int] = None, est: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   slab: Optional[int] = None, est: Optional[torch.Tensor] = None, lambda_tv: float = 0.0,
+                   lambda_tv_t: float = 0.0) -> torch.Tensor:
         """One optimizer step of video compressive sensing (the coded exposure of modules/lin_inverse.py:42-95): the
         model is evaluated on the WHOLE (H, W, T) grid in row order (row (i*W + j)*T + k), every pixel's T frames are
         multiplied by its mask and summed in groups of ``nframes`` -- ``lin_inverse.video2codedvideo`` -- and the loss
@@ -745,7 +780,15 @@ class FusedTrainer:
         number of pixels: the step walks the pixel ranges [p0, p0 + slab), each a contiguous row range of whole pixels,
         sums their gradients and losses and runs Adam once, so the activations hold ``slab * T`` rows instead of
         ``H*W*T``; ``self.y`` then holds the last slab only -- ``render()`` gives the whole video.  ``slab >= H*W`` is
-        the one-pass path.  3-D grids, single process."""
+        the one-pass path.
+
+        ``lambda_tv`` / ``lambda_tv_t`` != 0 add ``lambda_tv * tv_s + lambda_tv_t * tv_t`` to the loss: tv_s is
+        ``utils.total_variation_loss`` of every frame, tv_t the same sum of absolute differences between consecutive
+        frames (ours; the reference has no video prior).  Its gradient is added to the coding's dL/dy
+        (wire_tv_add_grad, between the coded loss and the backward); the returned loss is the total and
+        ``self.tv_parts`` holds [loss, mse, tv_s, tv_t].  With both 0.0 that kernel is not launched and the step is the
+        plain one, bit for bit.  A prior needs the one-pass path: neighbour pairs would straddle the slabs.
+        3-D grids, single process."""
         if self.tz is None or len(self.grid) != 3:
             raise ValueError("step_coded needs a 3-D grid (H, W, T)")
         if self.world != 1:
@@ -755,6 +798,11 @@ class FusedTrainer:
         nframes = int(nframes)
         if nframes < 1:
             raise ValueError(f"nframes {nframes} must be >= 1")
+        lam_s, lam_t = self._tv_weight("lambda_tv", lambda_tv), self._tv_weight("lambda_tv_t", lambda_tv_t)
+        prior = lam_s != 0.0 or lam_t != 0.0
+        if prior and slab is not None and 1 <= int(slab) < NP:
+            raise ValueError(f"slab {int(slab)} splits the grid of {NP} pixels: a TV prior (lambda_tv, lambda_tv_t) "
+                             f"needs the one-pass path, slab=None or slab >= H*W")
         dup = int(bool(dup_last))
         Cp = (T + nframes - 1) // nframes + dup
         if not isinstance(coded, torch.Tensor) or not coded.is_cuda or coded.dtype != torch.float32 \
@@ -805,6 +853,8 @@ class FusedTrainer:
                                              mk.data_ptr(), gt.data_ptr(), self.gy.data_ptr(),
                                              est.data_ptr() if est is not None else None,
                                              g.data_ptr() + 4 * self.count, self.partial.data_ptr()), "coded_mse_grad")
+            if prior:                                          # one pass: p0 == 0 and y holds the whole grid
+                self._tv_add_grad(stream, H, W, T, lam_s, lam_t, g.data_ptr() + 4 * self.count)
             _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
                                       self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
                                       self.scratch.data_ptr(), self.scr_bytes, gp), "bwd")
@@ -813,7 +863,7 @@ class FusedTrainer:
         g = self.gbuf[0]
         self.t += 1
         self._adam(stream, g)
-        self.loss = g[self.count:self.count + 1].clone()
+        self.loss = (self.tv_parts[0:1] if prior else g[self.count:self.count + 1]).clone()
         return self.loss
 
     @property
