@@ -369,6 +369,34 @@ int wire_avgpool_mse_grad_frames(void* stream, const float* y, int B, int H, int
  * coords: [B][H*W][2].  B, H or W < 1 or a NULL pointer: WIRE_ERR_ARG before any HIP call.               */
 int wire_affine_coords(void* stream, const double* mats, int B, int H, int W, float* coords);
 
+/* A learnable registration of those frames: one 2 x 3 matrix theta[f] per frame, fp32, acting on the frame's NORMALISED
+ * coordinates -- the convention of motion.get_transformed_coords / F.affine_grid (modules/motion.py), identity =
+ * [[1,0,0],[0,1,0]], all six entries in one unit.  It composes with any base coordinates: those of wire_affine_coords,
+ * a homography flow, a plain grid.  coords, out, g_out, g_in: [B][n_per][2]; theta, g_theta: [B][2][3]; all DEVICE,
+ * the [..][2] arrays 8-byte aligned.
+ * wire_warp_coords_fwd: for frame f and row p, (x, y) = coords[f][p], t = theta[f], in fp64, left to right, no
+ *   contraction, rounded to fp32 once:
+ *     out[f][p] = ( float(t00 x + t01 y + t02), float(t10 x + t11 y + t12) )
+ *   The identity returns coords bit for bit.  out == coords (in place) is allowed; any other overlap is not.
+ * wire_warp_coords_bwd: with v = (x, y, 1) of the INPUT coordinates,
+ *     g_theta[f][a][c] = float( sum_p double(g_out[f][p][a]) * double(v_c) )        (each product exact in fp64)
+ *   overwritten; pin_first = 1 writes +0.0 into the six entries of frame 0 instead (the gauge: the reference keeps its
+ *   first frame unmoved), pin_first = 0 does not.  If g_in != NULL (it must not overlap another argument), in fp64,
+ *   left to right:
+ *     g_in[f][p] = ( float(t00 gx + t10 gy), float(t01 gx + t11 gy) ),   (gx, gy) = g_out[f][p]
+ *   every element written once.  A workgroup of 256 threads adds 2048 consecutive rows of one frame in fp64 (a thread
+ *   its rows in order, the wave by a fixed shuffle tree, the four waves in a fixed order) and stores six fp64 partials
+ *   to ws; a second launch adds each frame's partials in a fixed order and rounds to fp32 once.  No atomics, every sum
+ *   in an order that depends on (B, n_per) alone: the same call gives the same bits, whatever ws held before.
+ *   ws: wire_warp_coords_bwd_ws_bytes(B, n_per) bytes of scratch, 8-byte aligned.
+ * B or n_per < 1, sizes beyond 63 bits or more workgroups than a grid holds (2^31 - 1), pin_first not 0 / 1, a
+ * misaligned pointer, or a NULL pointer other than g_in: WIRE_ERR_ARG before any HIP call (the size query too); a ws
+ * that is too small: WIRE_ERR_SIZE.                                                                              */
+int wire_warp_coords_fwd(void* stream, const float* coords, const float* theta, int B, int64_t n_per, float* out);
+int64_t wire_warp_coords_bwd_ws_bytes(int B, int64_t n_per);
+int wire_warp_coords_bwd(void* stream, const float* coords, const float* theta, const float* g_out, int B,
+                         int64_t n_per, int pin_first, float* g_theta, float* g_in, void* ws, int64_t ws_bytes);
+
 /* Video compressive sensing (per-pixel coded exposure, modules/lin_inverse.py:42-95): the loss of a video estimate
  * against a coded video, fused with its backward.  The T frames of pixel p are multiplied by that pixel's mask and
  * summed in groups of nframes (lin_inverse.py:79-84) into C = ceil(T / nframes) coded frames; nframes > T gives one.

@@ -761,3 +761,66 @@ def total_variation(x: torch.Tensor) -> torch.Tensor:
     if x.dtype != torch.float32:
         raise ValueError("image must be float32")
     return _TotalVariationFunction.apply(x)
+
+
+# ---------------------------------------------------------------------------
+# a learnable registration of frames (wire_warp_coords_fwd / wire_warp_coords_bwd)
+# ---------------------------------------------------------------------------
+class _WarpCoordsFunction(torch.autograd.Function):
+    """theta[f] (x, y, 1) of every row of frame f and its adjoint: wire_warp_coords_fwd / wire_warp_coords_bwd."""
+
+    @staticmethod
+    def forward(ctx, coords, theta):
+        L = _lib.lib()
+        x, t = coords.detach(), theta.detach()
+        if x.data_ptr() % 8:                      # the kernels move a row as one 8-byte word
+            x = x.clone()
+        B, n_per = int(x.shape[0]), int(x.shape[1])
+        out = torch.empty_like(x)
+        _lib.check(L.wire_warp_coords_fwd(_stream_ptr(x.device), x.data_ptr(), t.data_ptr(), B, n_per, out.data_ptr()),
+                   "wire_warp_coords_fwd")
+        ctx.save_for_backward(x, t)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        L = _lib.lib()
+        x, t = ctx.saved_tensors
+        _no_second_order("warp_coords")
+        B, n_per = int(x.shape[0]), int(x.shape[1])
+        g = g_out.detach().to(torch.float32).contiguous()
+        if g.data_ptr() % 8:
+            g = g.clone()
+        g_theta = torch.empty_like(t)
+        g_in = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        ws_bytes = _lib.check(L.wire_warp_coords_bwd_ws_bytes(B, n_per), "wire_warp_coords_bwd_ws_bytes")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        _lib.check(L.wire_warp_coords_bwd(_stream_ptr(x.device), x.data_ptr(), t.data_ptr(), g.data_ptr(), B, n_per, 0,
+                                          g_theta.data_ptr(), g_in.data_ptr() if g_in is not None else None,
+                                          ws.data_ptr(), ws.numel()), "wire_warp_coords_bwd")
+        return g_in, g_theta
+
+
+def warp_coords(coords: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
+    """The coordinates of B frames, each moved by its own learnable 2 x 3 matrix: ``out[f, p] = theta[f] @ (x, y, 1)``
+    for ``(x, y) = coords[f, p]``, the convention of ``motion.get_transformed_coords`` / ``F.affine_grid`` (``theta``
+    acts on NORMALISED coordinates; the identity ``[[1, 0, 0], [0, 1, 0]]`` returns ``coords`` bit for bit).
+    ``coords``: [B, n, 2], ``theta``: [B, 2, 3], both contiguous CUDA float32.  Returns a new [B, n, 2] tensor that is
+    differentiable with respect to ``theta``, and to ``coords`` when they require a gradient: feed it to a model and a
+    torch optimiser refines the registration with the net.  Forward is wire_warp_coords_fwd, backward
+    wire_warp_coords_bwd -- fp64 arithmetic rounded to fp32 once, a deterministic reduction to the six numbers of
+    every frame (no atomics: the same call gives the same bits), no frame pinned (zero ``theta.grad[0]`` or leave frame 0
+    out of the optimiser to fix the gauge).  First order only.  CPU tensors raise WireHipError; other shapes, dtypes
+    or strides ValueError."""
+    if not isinstance(coords, torch.Tensor) or not isinstance(theta, torch.Tensor):
+        raise ValueError("warp_coords expects two tensors")
+    _require_cuda(coords, "coords")
+    _require_cuda(theta, "theta")
+    if coords.dtype != torch.float32 or coords.dim() != 3 or coords.shape[0] < 1 or coords.shape[1] < 1 \
+            or coords.shape[2] != 2 or not coords.is_contiguous():
+        raise ValueError("coords must be a contiguous float32 tensor [B, n, 2] with B, n >= 1")
+    if theta.dtype != torch.float32 or tuple(theta.shape) != (coords.shape[0], 2, 3) or not theta.is_contiguous():
+        raise ValueError(f"theta must be a contiguous float32 tensor [{coords.shape[0]}, 2, 3]")
+    if theta.device != coords.device:
+        raise ValueError("coords and theta must be on the same device")
+    return _WarpCoordsFunction.apply(coords, theta)

@@ -7,6 +7,12 @@ Only what that driver's data path needs and what depends on nothing beyond numpy
 ``FusedTrainer.affine_coords``), and the loop's loss is ``FusedTrainer.step_frames``.  Registration and resampling
 (``register_stack``, ``register_stack_ecc``, ``ecc_flow``, ``fb_flow``, ``get_imstack``'s ``cv2.remap``, ``prune_stack``,
 ``interp_lr``: cv2, kornia, pystackreg) are out of scope, as are ``mat2coords``, ``param2theta`` and ``flow2rgb``.
+
+A LEARNABLE registration -- what the reference's ``param2theta`` / ``get_transformed_coords`` / ``interp_lr`` were the
+pieces of -- is not in this module: a per-frame ``theta`` [B, 2, 3] of ``get_transformed_coords``' convention (a matrix on
+the normalised coordinates, identity ``[[1, 0, 0], [0, 1, 0]]``) applied to any base coordinates is
+``functional.warp_coords(coords, theta)``, differentiable for a torch optimiser, and training it jointly with the net in
+one sync-free step is ``FusedTrainer.step_frames_registered`` (both HIP: wire_warp_coords_fwd / wire_warp_coords_bwd).
 """
 from __future__ import annotations
 

@@ -36,6 +36,40 @@ from .modules.utils import axis_tables
 from .parallel import FlatGradAllReducer, replicas_identical, shard_bounds
 
 
+class FrameRegistration:
+    """The device state of a learnable registration of B frames (``FusedTrainer.step_frames_registered``): ``theta``
+    [B, 2, 3] float32, one matrix per frame acting on the frame's NORMALISED coordinates -- the convention of
+    ``motion.get_transformed_coords`` / ``F.affine_grid``, the identity unless given -- its gradient ``grad`` (written by
+    every step), Adam's ``exp_avg`` / ``exp_avg_sq`` and step count ``t``, the rate ``lr`` (a plain attribute: set it
+    between steps for a schedule), ``betas`` and ``eps``.  ``pin_first`` fixes the gauge as the reference does ("Ensure
+    first shift and theta are zero"): frame 0 receives a zero gradient, its moments stay zero and its matrix keeps its
+    bits.  ``FusedTrainer.registration`` builds one on the trainer's device."""
+
+    def __init__(self, B: int, device, lr: float = 1e-4, pin_first: bool = True, theta=None,
+                 betas=(0.9, 0.999), eps: float = 1e-8):
+        B = int(B)
+        if B < 1:
+            raise ValueError(f"a registration needs B >= 1 frames, not {B}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.WireHipError("FrameRegistration needs an MI355X device ('cuda')")
+        self.B = B
+        if theta is None:
+            host = torch.tensor([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]], dtype=torch.float32).repeat(B, 1, 1)
+        else:
+            host = torch.as_tensor(theta).detach().to(torch.float32)
+            if tuple(host.shape) != (B, 2, 3):
+                raise ValueError(f"theta must be [{B}, 2, 3]")
+        self.theta = host.to(device).contiguous().clone()
+        self.grad = torch.zeros_like(self.theta)
+        self.exp_avg = torch.zeros_like(self.theta)
+        self.exp_avg_sq = torch.zeros_like(self.theta)
+        self.t = 0
+        self.lr = float(lr)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.pin_first = bool(pin_first)
+
+
 class FusedTrainer:
     """``lr`` is a number for every net kind.  bspline_mscale_hier also takes a sequence of one rate per stage, the two
     loops of the reference's bspline_*.py drivers: a number steps the stages' tensors only -- the heads are not in
@@ -646,22 +680,13 @@ class FusedTrainer:
         _lib.check(self.L.wire_affine_coords(stream, m.data_ptr(), m.shape[0], H, W, out.data_ptr()), "affine_coords")
         return out
 
-    def step_frames(self, coords: torch.Tensor, gt_lr: torch.Tensor, scale: int, mask: Optional[torch.Tensor] = None,
-                    rec_lr: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One optimizer step of the multi-image super-resolution loop (wire_multi_sr.py:190-208) on a batch of B frames:
-        ``coords`` [B, H*W, 2] (contiguous device float32; frame f's rows are the trainer's grid moved by that frame's
-        motion -- ``affine_coords`` makes them) go through the model in ONE forward of B*H*W rows,
-        ``torch.nn.AvgPool2d(scale)`` brings every frame to the resolution of ``gt_lr`` ([B, H//scale * W//scale, O]),
-        loss = ``MSELoss()(output*mask, gt_lr*mask)`` (``mask`` shaped like ``gt_lr``, any values; None = ones); backward
-        through the pooling and the network, Adam.  ``rec_lr`` (optional, shaped like ``gt_lr``) receives the unmasked
-        pooled frames, and the high-resolution frames of this step stay in ``self.y`` ([B*H*W, O]).  B is read from
-        ``coords`` and may change from call to call (a last, smaller batch).  2-D grids, single process.
-        No TV prior here (``step_downsampled``, ``step_radon`` and ``step_coded`` take one): the frames are warped
-        copies, and a prior belongs on the canonical grid, which this step never evaluates."""
+    def _frames_args(self, what: str, coords, gt_lr, scale, mask, rec_lr):
+        """The argument checks of the multi-image steps -> (H, W, scale, coords, B, gt_lr, mask), detached and
+        contiguous."""
         if self.tz is not None or len(self.grid) != 2:
-            raise ValueError("step_frames needs a 2-D grid")
+            raise ValueError(f"{what} needs a 2-D grid")
         if self.world != 1:
-            raise NotImplementedError("step_frames is single-process")
+            raise NotImplementedError(f"{what} is single-process")
         H, W = int(self.grid[0]), int(self.grid[1])
         scale = int(scale)
         if scale < 1 or scale > min(H, W):
@@ -686,6 +711,21 @@ class FusedTrainer:
         if rec_lr is not None and (not rec_lr.is_cuda or rec_lr.dtype != torch.float32
                                    or rec_lr.numel() != gt.numel() or not rec_lr.is_contiguous()):
             raise ValueError("rec_lr must be a contiguous CUDA float32 tensor shaped like gt_lr")
+        return H, W, scale, xy, B, gt, mk
+
+    def step_frames(self, coords: torch.Tensor, gt_lr: torch.Tensor, scale: int, mask: Optional[torch.Tensor] = None,
+                    rec_lr: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One optimizer step of the multi-image super-resolution loop (wire_multi_sr.py:190-208) on a batch of B frames:
+        ``coords`` [B, H*W, 2] (contiguous device float32; frame f's rows are the trainer's grid moved by that frame's
+        motion -- ``affine_coords`` makes them) go through the model in ONE forward of B*H*W rows,
+        ``torch.nn.AvgPool2d(scale)`` brings every frame to the resolution of ``gt_lr`` ([B, H//scale * W//scale, O]),
+        loss = ``MSELoss()(output*mask, gt_lr*mask)`` (``mask`` shaped like ``gt_lr``, any values; None = ones); backward
+        through the pooling and the network, Adam.  ``rec_lr`` (optional, shaped like ``gt_lr``) receives the unmasked
+        pooled frames, and the high-resolution frames of this step stay in ``self.y`` ([B*H*W, O]).  B is read from
+        ``coords`` and may change from call to call (a last, smaller batch).  2-D grids, single process.
+        No TV prior here (``step_downsampled``, ``step_radon`` and ``step_coded`` take one): the frames are warped
+        copies, and a prior belongs on the canonical grid, which this step never evaluates."""
+        H, W, scale, xy, B, gt, mk = self._frames_args("step_frames", coords, gt_lr, scale, mask, rec_lr)
         L, d = self.L, C.byref(self.desc)
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         n = B * H * W
@@ -704,6 +744,81 @@ class FusedTrainer:
                                   self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
         self.t += 1
         self._adam(stream, g)
+        self.loss = g[self.count:self.count + 1].clone()
+        return self.loss
+
+    # ------------------------------------------------------------------ multi-image step with a learnable registration
+    def registration(self, B: int, lr: float = 1e-4, pin_first: bool = True, theta=None) -> "FrameRegistration":
+        """The registration state of B frames on the trainer's device, for ``step_frames_registered``: one 2 x 3 matrix
+        per frame in normalised coordinates, the identity unless ``theta`` ([B, 2, 3]) is given, with its own Adam
+        state and rate ``lr``.  ``pin_first`` keeps frame 0 where it is (the gauge).  2-D grids."""
+        if self.tz is not None or len(self.grid) != 2:
+            raise ValueError("registration needs a 2-D grid")
+        return FrameRegistration(B, self.dev, lr=lr, pin_first=pin_first, theta=theta)
+
+    def _reserve_registered(self, n: int, B: int) -> None:
+        """The buffers only the registered step needs: dL/dcoords of n rows, the scratch of the backward that computes it
+        (wire_bwd_coords_scratch_bytes >= wire_bwd_scratch_bytes) and the workspace of the reduction to B frames."""
+        if n > getattr(self, "_reg_cap", 0):
+            self.coords_scr_bytes = _lib.check(self.L.wire_bwd_coords_scratch_bytes(C.byref(self.desc), n))
+            self.coords_scratch = torch.empty(self.coords_scr_bytes, dtype=torch.uint8, device=self.dev)
+            self.g_coords = torch.empty(n, 2, dtype=torch.float32, device=self.dev)
+            self._reg_cap = n
+        # (frames of one grid: the workspace grows with B alone)
+        ws_bytes = _lib.check(self.L.wire_warp_coords_bwd_ws_bytes(B, n // B), "warp_coords_bwd_ws_bytes")
+        if getattr(self, "warp_ws", None) is None or self.warp_ws.numel() < ws_bytes:
+            self.warp_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.dev)
+
+    def step_frames_registered(self, reg: "FrameRegistration", coords: torch.Tensor, gt_lr: torch.Tensor, scale: int,
+                               mask: Optional[torch.Tensor] = None,
+                               rec_lr: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``step_frames`` with the frames' registration learned jointly with the net: ``coords`` [B, H*W, 2] are the
+        BASE coordinates (``affine_coords`` of an external registration, a plain grid ...), frame f's rows are moved by
+        ``reg.theta[f]`` -- a 2 x 3 matrix on the normalised coordinates, ``motion.get_transformed_coords``'
+        convention -- and the step goes on as ``step_frames`` does; the backward also gives dL/dcoords
+        (wire_mlp_bwd_coords), which a deterministic reduction turns into the six numbers dL/dtheta of every frame
+        (wire_warp_coords_bwd), and two Adam updates follow: the net's with the trainer's rate and schedule, and
+        ``reg.theta``'s with ``reg.lr`` (``lr = 0`` freezes either).  With ``reg.pin_first`` frame 0 receives a zero
+        gradient and keeps its matrix exactly.  One fixed sequence of launches, no host synchronisation.
+
+        Arguments, shapes and errors are those of ``step_frames``, and ``coords.shape[0]`` must be ``reg.B`` (every
+        call steps all the frames of the registration).  After the step ``self.coords`` holds the warped coordinates,
+        ``self.g_coords[:B*H*W]`` dL/d(warped coords), ``reg.grad`` dL/dtheta and ``self.y`` the high-resolution
+        frames.  Returns the device loss.  2-D grids, single process."""
+        H, W, scale, xy, B, gt, mk = self._frames_args("step_frames_registered", coords, gt_lr, scale, mask, rec_lr)
+        if not isinstance(reg, FrameRegistration) or reg.theta.device != self.dev:
+            raise ValueError("reg must be a FrameRegistration on the trainer's device (FusedTrainer.registration)")
+        if B != reg.B:
+            raise ValueError(f"coords hold {B} frames, the registration {reg.B}")
+        L, d = self.L, C.byref(self.desc)
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        n = B * H * W
+        self._reserve(n)
+        self._reserve_registered(n, B)
+        g = self.gbuf[0]
+        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
+        _lib.check(L.wire_warp_coords_fwd(stream, xy.data_ptr(), reg.theta.data_ptr(), B, H * W,
+                                          self.coords.data_ptr()), "warp_coords_fwd")
+        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
+                                  self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
+        _lib.check(L.wire_avgpool_mse_grad_frames(stream, self.y.data_ptr(), B, H, W, self.O, scale, gt.data_ptr(),
+                                                  mk.data_ptr() if mk is not None else None, self.gy.data_ptr(),
+                                                  rec_lr.data_ptr() if rec_lr is not None else None,
+                                                  g.data_ptr() + 4 * self.count, self.partial.data_ptr()),
+                   "avgpool_mse_grad_frames")
+        _lib.check(L.wire_mlp_bwd_coords(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
+                                         self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
+                                         self.coords_scratch.data_ptr(), self.coords_scr_bytes, self.grad_ptrs[0],
+                                         self.g_coords.data_ptr()), "bwd_coords")
+        _lib.check(L.wire_warp_coords_bwd(stream, xy.data_ptr(), reg.theta.data_ptr(), self.g_coords.data_ptr(), B,
+                                          H * W, int(reg.pin_first), reg.grad.data_ptr(), None,
+                                          self.warp_ws.data_ptr(), self.warp_ws.numel()), "warp_coords_bwd")
+        self.t += 1
+        self._adam(stream, g)
+        reg.t += 1
+        _lib.check(L.wire_adam_step_flat(stream, reg.theta.data_ptr(), reg.grad.data_ptr(), reg.exp_avg.data_ptr(),
+                                         reg.exp_avg_sq.data_ptr(), 6 * B, float(reg.lr), reg.betas[0], reg.betas[1],
+                                         reg.eps, reg.t), "adam (registration)")
         self.loss = g[self.count:self.count + 1].clone()
         return self.loss
 
