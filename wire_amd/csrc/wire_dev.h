@@ -13,6 +13,35 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define WIRE_DEVINL __device__ __forceinline__
 
+// ---- sums over a wave and over a block of 256 threads ---------------------
+// The two block sums associate differently and give different bits: a kernel keeps the one it has.
+// the sum over a wave, the same value (and bits) in every lane
+template <typename T>
+WIRE_DEVINL T wire_wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+// wave-shuffle block sum: (w0 + w1) + (w2 + w3) of the four waves' sums, in every thread (red: 4 floats of LDS;
+// barriers separate two uses)
+WIRE_DEVINL float wire_block_sum(float v, float* red) {
+  v = wire_wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+// LDS tree block sum: red[t] += red[t + sft], sft = 128 .. 1, and red[0] in every thread (red: 256 floats of LDS)
+WIRE_DEVINL float wire_block_tree_sum(float v, float* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int sft = 128; sft >= 1; sft >>= 1) {
+    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
+    __syncthreads();
+  }
+  return red[0];
+}
+
 // ---- blocked-planar complex layout --------------------------------------
 // feature o, part c (0 = re, 1 = im) -> column in a row of P floats.
 WIRE_DEVINL int blk_col(int o, int part) { return ((o >> 5) << 6) + (part << 5) + (o & 31); }

@@ -188,11 +188,6 @@ hipError_t launch_mscale_first(hipStream_t s, const float* coords, int64_t n, in
 // coordinate gradients: one wave per row, features strided over the lanes, a fixed butterfly across them (no atomics:
 // the same bits every run)
 // ===========================================================================
-WIRE_DEVINL float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 __global__ __launch_bounds__(256) void coordgrad_rows_kernel(const float* __restrict__ G, int ldg,
                                                              const float* __restrict__ G2, const float* __restrict__ W,
                                                              const float* __restrict__ V, int K, int D, long long n,
@@ -216,7 +211,7 @@ __global__ __launch_bounds__(256) void coordgrad_rows_kernel(const float* __rest
     }
   }
 #pragma unroll
-  for (int d = 0; d < 4; ++d) a[d] = wave_sum(a[d]);
+  for (int d = 0; d < 4; ++d) a[d] = wire_wave_sum(a[d]);
   if (lane < D) {
     float v = a[0];
 #pragma unroll
@@ -277,7 +272,7 @@ __global__ __launch_bounds__(256) void posenc_bwd_kernel(const float* __restrict
     for (int d = 0; d < 4; ++d) a[d] += d == j ? v : 0.f;
   }
 #pragma unroll
-  for (int d = 0; d < 4; ++d) a[d] = wave_sum(a[d]);
+  for (int d = 0; d < 4; ++d) a[d] = wire_wave_sum(a[d]);
   if (lane < D) {
     float v = a[0];
 #pragma unroll

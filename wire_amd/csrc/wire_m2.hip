@@ -187,13 +187,8 @@ __global__ __launch_bounds__(256) void m2_comb_bwd_kernel(M2Comb w, int S, int O
   }
   if (ls.target && loss_part) {
     __syncthreads();
-    red[tid] = lacc;
-    __syncthreads();
-    for (int sft = 128; sft >= 1; sft >>= 1) {
-      if (tid < sft) red[tid] += red[tid + sft];
-      __syncthreads();
-    }
-    if (tid == 0) loss_part[blockIdx.x] = red[0];
+    lacc = wire_block_tree_sum(lacc, red);
+    if (tid == 0) loss_part[blockIdx.x] = lacc;
   }
 }
 

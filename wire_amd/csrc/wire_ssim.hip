@@ -30,13 +30,6 @@ static inline int ssim_tiles_y(int H, int taps) { return (int)cdiv(H - taps + 1,
 static inline int ssim_tiles_x(int W, int taps) { return (int)cdiv(W - taps + 1, SSIM_TC); }
 int64_t ssim_tiles(int H, int W, int taps) { return (int64_t)ssim_tiles_y(H, taps) * ssim_tiles_x(W, taps); }
 
-// the sum over a wave, the same value (and bits) in every lane
-__device__ __forceinline__ float ssim_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 template <int TAPS>
 __global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict__ x, const float* __restrict__ y, int H,
                                                         int W, int O, SsimWin win, float wsum, float wdef, float cov,
@@ -82,7 +75,7 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict_
         s += a[u] + b[u];
       }
   }
-  s = ssim_wave_sum(s);
+  s = wire_wave_sum(s);
   if (lane == 0) red[wv] = s;
   __syncthreads();
   const float c = ((red[0] + red[1]) + (red[2] + red[3])) / (2.f * (float)(hrv * hwv));
@@ -142,7 +135,7 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict_
         }
     __syncthreads();
   }
-  acc = ssim_wave_sum(acc);
+  acc = wire_wave_sum(acc);
   if (lane == 0) red[wv] = acc;        // (the last read of red lies before the barriers above)
   __syncthreads();
   if (tid == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -154,10 +147,8 @@ __global__ __launch_bounds__(256) void ssim_final_kernel(const float* __restrict
   __shared__ float red[4];
   float a = 0.f;
   for (int i = threadIdx.x; i < ntiles; i += 256) a += partial[i];
-  a = ssim_wave_sum(a);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = ((red[0] + red[1]) + (red[2] + red[3])) / count;
+  a = wire_block_sum(a, red);
+  if (threadIdx.x == 0) out[0] = a / count;
 }
 
 template <int TAPS>

@@ -56,21 +56,6 @@ int64_t ssim_loss_partials(int H, int W) {
   return nt + (nt > SSIMB_ROWS_BLOCKS ? nt : SSIMB_ROWS_BLOCKS);
 }
 
-// the sum over a wave, the same value (and bits) in every lane
-__device__ __forceinline__ float ssimb_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-// the block's sum in every thread (red: 4 floats of LDS; barriers separate two uses)
-__device__ __forceinline__ float ssimb_block_sum(float v, float* red) {
-  v = ssimb_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 struct SsimLossArgs {
   long long first, n_mse;     // the rows of the MSE term inside this pass: [first, first + n_mse)
   float gscale;               // 2 / (n_mse O)
@@ -142,7 +127,7 @@ __global__ __launch_bounds__(256) void ssim_grad_kernel(const float* __restrict_
           s += xv + yv;
         }
       }
-      const float c = ssimb_block_sum(s, red) / (2.f * (float)((a1 - s0) * (b1 - u0)));     // (the barriers publish sx, sy)
+      const float c = wire_block_sum(s, red) / (2.f * (float)((a1 - s0) * (b1 - u0)));     // (the barriers publish sx, sy)
       const float cw = c * wsum, ccw = c * cw, cd = c * wdef;
       // ---- horizontal pass: the five moments of the shifted images, rows [s0, a1) x columns [u0, u1)
       for (int k = tid; k < HR * CC; k += 256) {
@@ -245,8 +230,8 @@ __global__ __launch_bounds__(256) void ssim_grad_kernel(const float* __restrict_
     }
   }
   if (partial) {
-    ssum = ssimb_block_sum(ssum, red);
-    sq = ssimb_block_sum(sq, red);
+    ssum = wire_block_sum(ssum, red);
+    sq = wire_block_sum(sq, red);
     if (tid == 0) {
       partial[blockIdx.x] = ssum;
       partial[ntiles + blockIdx.x] = sq;
@@ -274,7 +259,7 @@ __global__ __launch_bounds__(256) void ssim_mse_rows_kernel(const float* __restr
     if (rec) rec[e] = v;
     sq = __builtin_fmaf(d, d, sq);
   }
-  sq = ssimb_block_sum(sq, red);
+  sq = wire_block_sum(sq, red);
   if (threadIdx.x == 0) sq_partial[blockIdx.x] = sq;
 }
 
@@ -288,8 +273,8 @@ __global__ __launch_bounds__(256) void ssim_loss_final_kernel(const float* __res
   float a = 0.f, b = 0.f;
   for (int i = threadIdx.x; i < n_s; i += 256) a += partial[i];
   for (int i = threadIdx.x; i < n_sq; i += 256) b += partial[sq_off + i];
-  a = ssimb_block_sum(a, red);
-  b = ssimb_block_sum(b, red);
+  a = wire_block_sum(a, red);
+  b = wire_block_sum(b, red);
   if (threadIdx.x != 0) return;
   {
 #pragma clang fp contract(off)

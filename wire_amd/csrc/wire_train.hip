@@ -110,27 +110,19 @@ __global__ __launch_bounds__(256) void mse_grad_kernel(const float* __restrict__
     if (rec) rec[src * O + o] = yy;
     acc = __builtin_fmaf(d, d, acc);
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int sft = 128; sft >= 1; sft >>= 1) {
-    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  acc = wire_block_tree_sum(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 __global__ void mse_final_kernel(const float* __restrict__ partial, int nb, float lscale,
                                  float* __restrict__ loss_out) {
   __shared__ float red[256];
   float acc = 0.f;
   for (int i = threadIdx.x; i < nb; i += 256) acc += partial[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int sft = 128; sft >= 1; sft >>= 1) {
-    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_out[0] = red[0] * lscale;
+  acc = wire_block_tree_sum(acc, red);
+  if (threadIdx.x == 0) loss_out[0] = acc * lscale;
 }
+// the grid of a loss kernel over n elements: it depends on the shape alone
+static unsigned mse_blocks(long long n) { return n < (long long)MSE_BLOCKS * 256 ? cdiv(n, 256) : MSE_BLOCKS; }
 // loss_out[0] = lscale * sum of nb partial sums (one block)
 hipError_t launch_mse_final(hipStream_t s, const float* partial, int nb, float lscale, float* loss_out) {
   hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, nb, lscale, loss_out);
@@ -140,14 +132,11 @@ hipError_t launch_mse_grad(hipStream_t s, const float* y, const float* target, c
                            int64_t first, int64_t n, int O, float weight, float* g_y,
                            float* loss_out, float* rec, float* partial) {
   if (n <= 0) return hipSuccess;
-  unsigned nb = cdiv(n * O, 256);
-  if (nb > MSE_BLOCKS) nb = MSE_BLOCKS;
+  const unsigned nb = mse_blocks(n * O);
   const float inv = (float)(1.0 / ((double)n * (double)O));
   hipLaunchKernelGGL(mse_grad_kernel, dim3(nb), dim3(256), 0, s, y, target, idx, (long long)first,
                      (long long)n, O, weight * 2.f * inv, g_y, rec, partial);
-  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, weight * inv,
-                     loss_out);
-  return hipGetLastError();
+  return launch_mse_final(s, partial, (int)nb, weight * inv, loss_out);
 }
 
 // ===========================================================================
@@ -184,13 +173,8 @@ __global__ __launch_bounds__(256) void avgpool_mse_grad_kernel(const float* __re
       for (int b = 0; b < sc; ++b) dst[((size_t)a * W + b) * O] = g;
     acc = __builtin_fmaf(d, d, acc);
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int sft = 128; sft >= 1; sft >>= 1) {
-    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  acc = wire_block_tree_sum(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 hipError_t launch_avgpool_mse_grad(hipStream_t s, const float* y, int H, int W, int O, int scale,
                                    const float* gt_lr, float* g_y, float* rec_lr, float* loss_out,
@@ -203,13 +187,11 @@ hipError_t launch_avgpool_mse_grad(hipStream_t s, const float* y, int H, int W, 
     if (e != hipSuccess) return e;
   }
   const long long total = (long long)H2 * W2 * O;
-  unsigned nb = cdiv(total, 256);
-  if (nb > MSE_BLOCKS) nb = MSE_BLOCKS;
+  const unsigned nb = mse_blocks(total);
   const double invn = 1.0 / (double)total;
   hipLaunchKernelGGL(avgpool_mse_grad_kernel, dim3(nb), dim3(256), 0, s, y, H, W, O, scale, H2, W2, gt_lr,
                      (float)(2.0 * invn / ((double)scale * scale)), g_y, rec_lr, partial);
-  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, (float)invn, loss_out);
-  return hipGetLastError();
+  return launch_mse_final(s, partial, (int)nb, (float)invn, loss_out);
 }
 
 // ===========================================================================
@@ -284,13 +266,8 @@ __global__ __launch_bounds__(256) void avgpool_frames_kernel(const float* __rest
         for (int x = tid; x < nxw; x += 256) dst[x] = 0.f;
       }
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int sft = 128; sft >= 1; sft >>= 1) {
-    if (tid < sft) red[tid] += red[tid + sft];
-    __syncthreads();
-  }
-  if (tid == 0) partial[blockIdx.x] = red[0];
+  acc = wire_block_tree_sum(acc, red);
+  if (tid == 0) partial[blockIdx.x] = acc;
 }
 // scale * O > APF_CAP: one thread per pooled element reads and writes its own window (g_y's ragged borders are zeroed
 // by the launcher)
@@ -327,13 +304,8 @@ __global__ __launch_bounds__(256) void avgpool_frames_direct_kernel(const float*
       for (int b = 0; b < sc; ++b) g_y[off + a * rowf + (long long)b * O] = g;
     acc = __builtin_fmaf(d, d, acc);
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int sft = 128; sft >= 1; sft >>= 1) {
-    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  acc = wire_block_tree_sum(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 hipError_t launch_avgpool_mse_grad_frames(hipStream_t s, const float* y, int B, int H, int W, int O, int scale,
                                           const float* gt_lr, const float* mask, float* g_y, float* rec_lr,
@@ -357,12 +329,11 @@ hipError_t launch_avgpool_mse_grad_frames(hipStream_t s, const float* y, int B, 
       if (e != hipSuccess) return e;
     }
     const long long n = (long long)total;
-    nb = n < (long long)MSE_BLOCKS * 256 ? cdiv(n, 256) : MSE_BLOCKS;
+    nb = mse_blocks(n);
     hipLaunchKernelGGL(avgpool_frames_direct_kernel, dim3(nb), dim3(256), 0, s, y, B, H, W, O, scale, H2, W2, gt_lr,
                        mask, gscale, g_y, rec_lr, partial);
   }
-  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, (float)(1.0 / total), loss_out);
-  return hipGetLastError();
+  return launch_mse_final(s, partial, (int)nb, (float)(1.0 / total), loss_out);
 }
 
 // ===========================================================================
@@ -438,13 +409,8 @@ __global__ __launch_bounds__(256) void coded_mse_grad_kernel(const float* __rest
     }
     __syncthreads();                                           // the next tile overwrites ms
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int sft = 128; sft >= 1; sft >>= 1) {
-    if (tid < sft) red[tid] += red[tid + sft];
-    __syncthreads();
-  }
-  if (tid == 0) partial[blockIdx.x] = red[0];
+  acc = wire_block_tree_sum(acc, red);
+  if (tid == 0) partial[blockIdx.x] = acc;
 }
 // T * O > CV_CAP: one thread per (pixel, channel) walks its own frames, chunk by chunk
 __global__ __launch_bounds__(256) void coded_mse_grad_direct_kernel(const float* __restrict__ y, long long p0,
@@ -483,13 +449,8 @@ __global__ __launch_bounds__(256) void coded_mse_grad_direct_kernel(const float*
       for (int k = k0; k < k1; ++k) gp[(long long)k * O] = mp[k] * g;
     }
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int sft = 128; sft >= 1; sft >>= 1) {
-    if (threadIdx.x < sft) red[threadIdx.x] += red[threadIdx.x + sft];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  acc = wire_block_tree_sum(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 hipError_t launch_coded_mse_grad(hipStream_t s, const float* y, int64_t p0, int64_t n_pix, int64_t NP, int T, int O,
                                  int nframes, int dup_last, const float* mask, const float* gt, float* g_y, float* est,
@@ -510,12 +471,11 @@ hipError_t launch_coded_mse_grad(hipStream_t s, const float* y, int64_t p0, int6
                        (long long)NP, T, O, nframes, C, dup_last, TP, (int)PS, mask, gt, gscale, g_y, est, partial);
   } else {
     const long long n = (long long)n_pix * O;
-    nb = n < (long long)MSE_BLOCKS * 256 ? cdiv(n, 256) : MSE_BLOCKS;
+    nb = mse_blocks(n);
     hipLaunchKernelGGL(coded_mse_grad_direct_kernel, dim3(nb), dim3(256), 0, s, y, (long long)p0, (long long)n_pix,
                        (long long)NP, T, O, nframes, C, dup_last, mask, gt, gscale, g_y, est, partial);
   }
-  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, (float)(1.0 / count), loss_out);
-  return hipGetLastError();
+  return launch_mse_final(s, partial, (int)nb, (float)(1.0 / count), loss_out);
 }
 
 // The same operator on the reference's frame-major tensors (video, masks [T][NP], coded [C'][NP]) and its adjoint:

@@ -58,21 +58,6 @@ __device__ __forceinline__ long long tv_locate(const TvGeom& g, long long e, int
   return p * g.qs + pix * g.ps;
 }
 
-// the sum over a wave, the same value (and bits) in every lane
-__device__ __forceinline__ float tv_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-// the block's sum in thread 0 (red: 4 floats of LDS; a barrier separates two uses)
-__device__ __forceinline__ float tv_block_sum(float v, float* red) {
-  v = tv_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // |down - own| + |right - own| of element (i, j) at address a
 __device__ __forceinline__ float tv_pair_sum(const float* __restrict__ x, const TvGeom& g, long long a, int i, int j) {
   const float v = x[a];
@@ -102,7 +87,7 @@ __global__ __launch_bounds__(256) void tv_fwd_kernel(const float* __restrict__ x
     const long long a = pix * g.ps;
     for (int p = 0; p < g.planes; ++p) acc += tv_pair_sum(x, g, a + p * g.qs, i, j);
   }
-  acc = tv_block_sum(acc, red);
+  acc = wire_block_sum(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
@@ -141,8 +126,8 @@ __global__ __launch_bounds__(256) void tv_mse_grad_kernel(const float* __restric
     }
     g_y[e] = out;
   }
-  tv = tv_block_sum(tv, red);
-  sq = tv_block_sum(sq, red);
+  tv = wire_block_sum(tv, red);
+  sq = wire_block_sum(sq, red);
   if (threadIdx.x == 0) {
     partial[blockIdx.x] = tv;
     partial[TV_BLOCKS + blockIdx.x] = sq;
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(256) void tv_mse_rows_kernel(const float* __restric
     if (rec) rec[e] = v;
     sq = __builtin_fmaf(d, d, sq);
   }
-  sq = tv_block_sum(sq, red);
+  sq = wire_block_sum(sq, red);
   if (threadIdx.x == 0) partial[TV_BLOCKS + blockIdx.x] = sq;
 }
 
@@ -182,8 +167,8 @@ __global__ __launch_bounds__(256) void tv_final_kernel(const float* __restrict__
   float a = 0.f, b = 0.f;
   for (int i = threadIdx.x; i < n_tv; i += 256) a += partial[i];
   for (int i = threadIdx.x; i < n_sq; i += 256) b += partial[TV_BLOCKS + i];
-  a = tv_block_sum(a, red);
-  b = tv_block_sum(b, red);
+  a = wire_block_sum(a, red);
+  b = wire_block_sum(b, red);
   if (threadIdx.x != 0) return;
   if (n_sq < 0) { out[0] = a; return; }
   {  // (no contraction: the stored mse, not the unrounded product b * lscale, is what the loss adds)
@@ -222,8 +207,8 @@ __global__ __launch_bounds__(256) void tv_add_grad_kernel(const float* __restric
     const float term = __builtin_fmaf(lambda_t, (float)kt, __fmul_rn(lambda_s, (float)ks));
     g_y[e] = __fadd_rn(g_y[e], term);
   }
-  tvs = tv_block_sum(tvs, red);
-  tvt = tv_block_sum(tvt, red);
+  tvs = wire_block_sum(tvs, red);
+  tvt = wire_block_sum(tvt, red);
   if (threadIdx.x == 0) {
     partial[blockIdx.x] = tvs;
     partial[TV_BLOCKS + blockIdx.x] = tvt;
@@ -239,8 +224,8 @@ __global__ __launch_bounds__(256) void tv_add_final_kernel(const float* __restri
   float a = 0.f, b = 0.f;
   for (int i = threadIdx.x; i < nb; i += 256) a += partial[i];
   for (int i = threadIdx.x; i < nb; i += 256) b += partial[TV_BLOCKS + i];
-  a = tv_block_sum(a, red);
-  b = tv_block_sum(b, red);
+  a = wire_block_sum(a, red);
+  b = wire_block_sum(b, red);
   if (threadIdx.x != 0) return;
   const float data = data_loss ? data_loss[0] : 0.f;
   out[0] = __fadd_rn(__fadd_rn(data, __fmul_rn(lambda_s, a)), __fmul_rn(lambda_t, b));

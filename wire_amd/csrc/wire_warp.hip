@@ -46,13 +46,6 @@ __global__ __launch_bounds__(256) void warp_fwd_kernel(const float2* coords, con
   out[r] = o;
 }
 
-// the sum over a wave, the same value (and bits) in every lane
-__device__ __forceinline__ double warp_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void warp_bwd_kernel(const float2* __restrict__ coords,
                                                        const float* __restrict__ theta,
                                                        const float2* __restrict__ g_out, long long n_per,
@@ -80,7 +73,7 @@ __global__ __launch_bounds__(256) void warp_bwd_kernel(const float2* __restrict_
     }
   }
 #pragma unroll
-  for (int k = 0; k < 6; ++k) acc[k] = warp_wave_sum(acc[k]);
+  for (int k = 0; k < 6; ++k) acc[k] = wire_wave_sum(acc[k]);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) red[threadIdx.x >> 6][k] = acc[k];
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(384) void warp_final_kernel(const double* __restric
   const double* src = partial + (long long)blockIdx.x * chunks * 6 + k;
   double s = 0.0;
   for (long long c = lane; c < chunks; c += 64) s += src[c * 6];
-  s = warp_wave_sum(s);
+  s = wire_wave_sum(s);
   if (lane == 0) g_theta[(long long)blockIdx.x * 6 + k] = (pin_first && blockIdx.x == 0) ? 0.f : (float)s;
 }
 

@@ -384,23 +384,19 @@ class FusedTrainer:
             raise ValueError(f"positions [{first}, {first + B}) outside the epoch of {self.npoints} points")
         lo, hi = shard_bounds(B, self.world, self.rank)
         nloc = hi - lo
-        if self._hidx is None or self._hidx.numel() < nloc:
-            self._hidx = torch.empty(max(nloc, 1), dtype=torch.int64, device=self.dev)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        _lib.check(self.L.wire_perm_indices(stream, int(seed) & 0xFFFFFFFFFFFFFFFF, self.npoints, first + lo, nloc,
-                                            self._hidx.data_ptr()), "perm_indices")
-        return self._step_local(self._hidx.data_ptr(), 0, nloc, B)
+        hidx = self._buf("_hidx", max(nloc, 1), torch.int64)
+        _lib.check(self.L.wire_perm_indices(self._stream(), int(seed) & 0xFFFFFFFFFFFFFFFF, self.npoints, first + lo,
+                                            nloc, hidx.data_ptr()), "perm_indices")
+        return self._step_local(hidx.data_ptr(), 0, nloc, B)
 
     def _step_local(self, idx_ptr: Optional[int], first: int, nloc: int, B: int) -> torch.Tensor:
         """This rank's shard of a global batch of B rows: ``nloc`` rows whose flat grid indices are the int64
         device array at ``idx_ptr`` (or the range starting at ``first`` when None)."""
         L, d = self.L, C.byref(self.desc)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
+        stream = self._stream()
+        self._pack(stream)
         per = (nloc + self.micro - 1) // self.micro
         self._reserve(max(per, 1))
-        tz_ptr = self.tz.data_ptr() if self.tz is not None else None
-        Tn = self.grid[2] if self.tz is not None else 1
         for m in range(self.micro):
             mlo = m * per
             n = max(0, min(nloc, mlo + per) - mlo)
@@ -415,12 +411,10 @@ class FusedTrainer:
                     continue
             else:
                 ip = (idx_ptr + 8 * mlo) if idx_ptr is not None else None
-                _lib.check(L.wire_coords_from_index(stream, ip, first + mlo, n, self.tx.data_ptr(),
-                                                    self.grid[1], self.ty.data_ptr(), self.grid[0],
-                                                    tz_ptr, Tn, self.coords.data_ptr()), "coords")
+                self._grid_coords(stream, first + mlo, n, self.coords, ip)
                 args = (stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n, self.target.data_ptr(),
                         ip, first + mlo, n / float(B), self.y.data_ptr(), self.gy.data_ptr(),
-                        g.data_ptr() + 4 * self.count,
+                        self._loss_slot(g)[0],
                         self.rec.data_ptr() if self.rec is not None else None, self.partial.data_ptr(),
                         self.act.data_ptr(), self.act_bytes, self.scratch.data_ptr(), self.scr_bytes,
                         self.grad_ptrs[m])
@@ -437,13 +431,142 @@ class FusedTrainer:
         gsum = self.gbuf[0]
         for m in range(1, self.micro):
             gsum.add_(self.gbuf[m])
-        self.t += 1
-        self._adam(stream, gsum)
-        self.loss = gsum[self.count:self.count + 1].clone()   # the buffer is reused next step
+        self._finish(stream, gsum, self._loss_slot(gsum)[1])
         if self.check_every and self.world > 1 and self.t % self.check_every == 0:
             if not replicas_identical(self.flat, self.group):
                 raise RuntimeError(f"data-parallel replicas diverged at optimizer step {self.t} (WIRE_DP_CHECK)")
         return self.loss
+
+    # ------------------------------------------------------------------ the step skeleton
+    # An operator step checks its arguments, then names its loss: a callable loss(stream, g) that reads self.y, writes
+    # dL/dy to self.gy and a device loss (into the slot behind g, or into a buffer of its own).
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.dev).cuda_stream
+
+    def _buf(self, name: str, numel: int, dtype=torch.float32, zero: bool = False, exact: bool = False) -> torch.Tensor:
+        """The lazily made device buffer ``self.<name>`` of at least ``numel`` elements (``exact``: of exactly that
+        many), zero-filled when it is made if ``zero``; it only grows."""
+        b = getattr(self, name, None)
+        if b is None or (b.numel() != numel if exact else b.numel() < numel):
+            b = (torch.zeros if zero else torch.empty)(numel, dtype=dtype, device=self.dev)
+            setattr(self, name, b)
+        return b
+
+    def _pack(self, stream) -> None:
+        _lib.check(self.L.wire_pack_params(stream, C.byref(self.desc), self.param_ptrs, self.packed.data_ptr()), "pack")
+
+    def _grid_coords(self, stream, first: int, n: int, out: torch.Tensor, idx_ptr: Optional[int] = None) -> None:
+        """The coordinates of grid rows [first, first + n), or of the n flat indices at ``idx_ptr``, into ``out``."""
+        _lib.check(self.L.wire_coords_from_index(stream, idx_ptr, first, n, self.tx.data_ptr(), self.grid[1],
+                                                 self.ty.data_ptr(), self.grid[0],
+                                                 self.tz.data_ptr() if self.tz is not None else None,
+                                                 self.grid[2] if self.tz is not None else 1, out.data_ptr()), "coords")
+
+    def _loss_slot(self, g: torch.Tensor):
+        """(pointer to, view of) the float behind the last gradient of the flat buffer ``g``; made once per buffer (the
+        view keeps the storage, so its address stays this buffer's)."""
+        slots = self.__dict__.setdefault("_slots", {})
+        key = g.data_ptr()
+        if key not in slots:
+            slots[key] = (key + 4 * self.count, g[self.count:self.count + 1])
+        return slots[key]
+
+    def _fwd_loss_bwd(self, stream, coords_ptr: int, n: int, loss, g: torch.Tensor, gp, prior=None,
+                      coords_grad: bool = False) -> torch.Tensor:
+        """Forward of the ``n`` rows at ``coords_ptr`` into ``self.y``, ``loss(stream, g)``, the TV prior
+        ``(H, W, T, lam_s, lam_t)`` on top of it when one of its weights is nonzero, and the backward into the
+        gradient buffer ``g`` (``gp``: its pointer array; ``coords_grad``: also dL/dcoords into ``self.g_coords``).
+        Returns the view that holds the step's loss: ``tv_parts[0:1]`` with a prior, else the slot behind ``g``."""
+        L, d = self.L, C.byref(self.desc)
+        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), coords_ptr, n, self.y.data_ptr(),
+                                  self.act.data_ptr(), self.act_bytes, 1), "fwd")
+        loss(stream, g)
+        slot, src = self._loss_slot(g)
+        if prior is not None and (prior[3] != 0.0 or prior[4] != 0.0):
+            self._tv_add_grad(stream, *prior, slot)
+            src = self.tv_parts[0:1]
+        if coords_grad:
+            _lib.check(L.wire_mlp_bwd_coords(stream, d, self.packed.data_ptr(), coords_ptr, n, self.gy.data_ptr(),
+                                             self.act.data_ptr(), self.act_bytes, self.coords_scratch.data_ptr(),
+                                             self.coords_scr_bytes, gp, self.g_coords.data_ptr()), "bwd_coords")
+        else:
+            _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), coords_ptr, n, self.gy.data_ptr(),
+                                      self.act.data_ptr(), self.act_bytes, self.scratch.data_ptr(), self.scr_bytes, gp),
+                       "bwd")
+        return src
+
+    def _finish(self, stream, g: torch.Tensor, loss_src: torch.Tensor) -> torch.Tensor:
+        """Adam on the gradient in ``g``; the step's loss is a copy of ``loss_src``, which the next step overwrites."""
+        self.t += 1
+        self._adam(stream, g)
+        self.loss = loss_src.clone()
+        return self.loss
+
+    def _raster_step(self, loss, prior=None, loss_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A whole step over the 2-D grid in raster order: pack, coordinates, ``_fwd_loss_bwd``, ``_finish``.  The
+        loss is read from ``loss_src`` when the step's loss kernel keeps it in a buffer of its own."""
+        n = int(self.grid[0]) * int(self.grid[1])
+        stream = self._stream()
+        self._reserve(n)
+        g = self.gbuf[0]
+        self._pack(stream)
+        self._grid_coords(stream, 0, n, self.coords)
+        src = self._fwd_loss_bwd(stream, self.coords.data_ptr(), n, loss, g, self.grad_ptrs[0], prior)
+        return self._finish(stream, g, src if loss_src is None else loss_src)
+
+    # ---- argument checks: they read grid, world, O, tz and target alone, and come before the first device access
+    def _need_grid(self, what: str, rank: int = 2, one_output: bool = False, single_process: bool = True) -> None:
+        needs = "a 3-D grid (H, W, T)" if rank == 3 else "a 2-D grid and out_features == 1" if one_output \
+            else "a 2-D grid"
+        if (self.tz is None) == (rank == 3) or len(self.grid) != rank or (one_output and self.O != 1):
+            raise ValueError(f"{what} needs {needs}")
+        if single_process and self.world != 1:
+            raise NotImplementedError(f"{what} is single-process")
+
+    @staticmethod
+    def _rows_arg(indices, first, count, n: int):
+        """The rows of ``step_tv`` / ``step_ssim`` -> (indices, first, B): ``indices`` or the range [first, first+B)."""
+        if indices is not None:
+            if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64 or not indices.is_cuda \
+                    or indices.dim() != 1 or not indices.is_contiguous():
+                raise ValueError("indices must be a 1-D contiguous CUDA int64 tensor")
+            B = indices.numel()
+            if B > n:
+                raise ValueError(f"{B} indices for a grid of {n} points: the rows of indices must be distinct")
+            return indices, 0, B
+        first = int(first)
+        B = int(count if count is not None else n - first)
+        if first < 0 or B < 0 or first + B > n:
+            raise ValueError(f"rows [{first}, {first + B}) outside the grid of {n} points")
+        return None, first, B
+
+    @staticmethod
+    def _scale_arg(scale, H: int, W: int) -> int:
+        scale = int(scale)
+        if scale < 1 or scale > min(H, W):
+            raise ValueError(f"scale {scale} outside 1..min(H, W)")
+        return scale
+
+    @staticmethod
+    def _f32_elems(name: str, t, *dims: int) -> torch.Tensor:
+        """``t`` as a detached contiguous tensor, if it is CUDA float32 of dims[0] x dims[1] ... elements."""
+        numel = 1
+        for v in dims:
+            numel *= v
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.numel() != numel:
+            raise ValueError(f"{name} must be a CUDA float32 tensor of {' x '.join(str(v) for v in dims)} elements")
+        return t.detach().contiguous()
+
+    @staticmethod
+    def _f32_like(name: str, t, like: torch.Tensor, like_name: str) -> None:
+        """An optional output ``t``: contiguous CUDA float32 with the elements of ``like``."""
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.numel() != like.numel()
+                              or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous CUDA float32 tensor shaped like {like_name}")
+
+    @staticmethod
+    def _opt_ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+        return t.data_ptr() if t is not None else None
 
     # ------------------------------------------------------------------ the TV prior of the operator steps
     @staticmethod
@@ -457,10 +580,9 @@ class FusedTrainer:
         """The TV term of the (H, W, T) grid in ``self.y``, added to the ``self.gy`` the operator's backward has left
         (wire_tv_add_grad); ``self.tv_parts`` receives [loss, data, tv_s, tv_t], data being the device scalar at
         ``data_loss``."""
-        if getattr(self, "tv_parts", None) is None:
-            self.tv_parts = torch.zeros(4, dtype=torch.float32, device=self.dev)
+        tv_parts = self._buf("tv_parts", 4, zero=True)
         _lib.check(self.L.wire_tv_add_grad(stream, self.y.data_ptr(), H, W, T, self.O, lam_s, lam_t, data_loss,
-                                           self.gy.data_ptr(), self.tv_parts.data_ptr(), self.partial.data_ptr()),
+                                           self.gy.data_ptr(), tv_parts.data_ptr(), self.partial.data_ptr()),
                    "tv_add_grad")
 
     # ------------------------------------------------------------------ super-resolution step
@@ -476,46 +598,18 @@ class FusedTrainer:
         loss and the backward); the returned loss is the total and ``self.tv_parts`` holds [loss, mse, tv, 0].  With
         0.0 that kernel is not launched and the step is the plain one, bit for bit.
         2-D grids, single process (a pooled window must not straddle two shards)."""
-        if self.tz is not None or len(self.grid) != 2:
-            raise ValueError("step_downsampled needs a 2-D grid")
-        if self.world != 1:
-            raise NotImplementedError("step_downsampled is single-process")
+        self._need_grid("step_downsampled")
         lam = self._tv_weight("lambda_tv", lambda_tv)
         H, W = int(self.grid[0]), int(self.grid[1])
-        scale = int(scale)
-        if scale < 1 or scale > min(H, W):
-            raise ValueError(f"scale {scale} outside 1..min(H, W)")
-        H2, W2 = H // scale, W // scale
-        gt = gt_lr.detach()
-        if not gt.is_cuda or gt.dtype != torch.float32 or gt.numel() != H2 * W2 * self.O:
-            raise ValueError(f"gt_lr must be a CUDA float32 tensor of {H2 * W2} x {self.O} elements")
-        gt = gt.contiguous()
-        if rec_lr is not None and (not rec_lr.is_cuda or rec_lr.dtype != torch.float32
-                                   or rec_lr.numel() != gt.numel() or not rec_lr.is_contiguous()):
-            raise ValueError("rec_lr must be a contiguous CUDA float32 tensor shaped like gt_lr")
-        L, d = self.L, C.byref(self.desc)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        n = H * W
-        self._reserve(n)
-        g = self.gbuf[0]
-        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
-        _lib.check(L.wire_coords_from_index(stream, None, 0, n, self.tx.data_ptr(), W, self.ty.data_ptr(), H,
-                                            None, 1, self.coords.data_ptr()), "coords")
-        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                  self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
-        _lib.check(L.wire_avgpool_mse_grad(stream, self.y.data_ptr(), H, W, self.O, scale, gt.data_ptr(),
-                                           self.gy.data_ptr(), rec_lr.data_ptr() if rec_lr is not None else None,
-                                           g.data_ptr() + 4 * self.count, self.partial.data_ptr()), "avgpool_mse_grad")
-        if lam != 0.0:
-            self._tv_add_grad(stream, H, W, 1, lam, 0.0, g.data_ptr() + 4 * self.count)
-        _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                  self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
-                                  self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
-        self.t += 1
-        self._adam(stream, g)
-        # tv_parts is overwritten by the next regularised step, the gradient buffer by the next step
-        self.loss = (self.tv_parts[0:1] if lam != 0.0 else g[self.count:self.count + 1]).clone()
-        return self.loss
+        scale = self._scale_arg(scale, H, W)
+        gt = self._f32_elems("gt_lr", gt_lr, (H // scale) * (W // scale), self.O)
+        self._f32_like("rec_lr", rec_lr, gt, "gt_lr")
+
+        def loss(stream, g):
+            _lib.check(self.L.wire_avgpool_mse_grad(stream, self.y.data_ptr(), H, W, self.O, scale, gt.data_ptr(),
+                                                    self.gy.data_ptr(), self._opt_ptr(rec_lr), self._loss_slot(g)[0],
+                                                    self.partial.data_ptr()), "avgpool_mse_grad")
+        return self._raster_step(loss, prior=(H, W, 1, lam, 0.0))
 
     # ------------------------------------------------------------------ total-variation regularised step
     def step_tv(self, lambda_tv: float, indices: Optional[torch.Tensor] = None, first: int = 0,
@@ -536,52 +630,19 @@ class FusedTrainer:
         Returns the device loss (no host sync); ``self.loss_parts`` holds [loss, mse, tv], the full reconstruction of
         the step stays in ``self.y`` ([H*W, O]), and with ``keep_rec`` the selected rows go to ``self.rec``.
         2-D grids, single process (a neighbour pair must not straddle two shards)."""
-        if self.tz is not None or len(self.grid) != 2:
-            raise ValueError("step_tv needs a 2-D grid")
-        if self.world != 1:
-            raise NotImplementedError("step_tv is single-process")
+        self._need_grid("step_tv")
         self._need_target("step_tv")
-        lam = float(lambda_tv)
-        if not np.isfinite(lam):
-            raise ValueError(f"lambda_tv must be finite, not {lam}")
+        lam = self._tv_weight("lambda_tv", lambda_tv)
         H, W = int(self.grid[0]), int(self.grid[1])
-        n = H * W
-        if indices is not None:
-            if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64 or not indices.is_cuda \
-                    or indices.dim() != 1 or not indices.is_contiguous():
-                raise ValueError("indices must be a 1-D contiguous CUDA int64 tensor")
-            B = indices.numel()
-            if B > n:
-                raise ValueError(f"{B} indices for a grid of {n} points: the rows of indices must be distinct")
-            first = 0
-        else:
-            first = int(first)
-            B = int(count if count is not None else n - first)
-            if first < 0 or B < 0 or first + B > n:
-                raise ValueError(f"rows [{first}, {first + B}) outside the grid of {n} points")
-        L, d = self.L, C.byref(self.desc)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        self._reserve(n)
-        g = self.gbuf[0]
-        if getattr(self, "loss_parts", None) is None:
-            self.loss_parts = torch.zeros(3, dtype=torch.float32, device=self.dev)
-        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
-        _lib.check(L.wire_coords_from_index(stream, None, 0, n, self.tx.data_ptr(), W, self.ty.data_ptr(), H,
-                                            None, 1, self.coords.data_ptr()), "coords")
-        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                  self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
-        _lib.check(L.wire_tv_mse_grad(stream, self.y.data_ptr(), H, W, self.O, self.target.data_ptr(),
-                                      indices.data_ptr() if indices is not None else None, first, B, lam,
-                                      self.gy.data_ptr(), self.loss_parts.data_ptr(),
-                                      self.rec.data_ptr() if self.rec is not None else None,
-                                      self.partial.data_ptr()), "tv_mse_grad")
-        _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                  self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
-                                  self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
-        self.t += 1
-        self._adam(stream, g)
-        self.loss = self.loss_parts[0:1].clone()              # loss_parts is overwritten by the next step
-        return self.loss
+        indices, first, B = self._rows_arg(indices, first, count, H * W)
+        parts = self._buf("loss_parts", 3, zero=True)
+
+        def loss(stream, g):
+            _lib.check(self.L.wire_tv_mse_grad(stream, self.y.data_ptr(), H, W, self.O, self.target.data_ptr(),
+                                               self._opt_ptr(indices), first, B, lam, self.gy.data_ptr(),
+                                               parts.data_ptr(), self._opt_ptr(self.rec), self.partial.data_ptr()),
+                       "tv_mse_grad")
+        return self._raster_step(loss, loss_src=parts[0:1])
 
     # ------------------------------------------------------------------ SSIM-regularised step
     def step_ssim(self, lambda_ssim: float, indices: Optional[torch.Tensor] = None, first: int = 0,
@@ -601,16 +662,10 @@ class FusedTrainer:
         Returns the device loss (no host sync); ``self.loss_parts`` holds [loss, mse, ssim], the full reconstruction of
         the step stays in ``self.y`` ([H*W, O]), and with ``keep_rec`` the selected rows go to ``self.rec``.
         2-D grids, single process (a window must not straddle two shards)."""
-        if self.tz is not None or len(self.grid) != 2:
-            raise ValueError("step_ssim needs a 2-D grid")
-        if self.world != 1:
-            raise NotImplementedError("step_ssim is single-process")
+        self._need_grid("step_ssim")
         self._need_target("step_ssim")
-        lam = float(lambda_ssim)
-        if not np.isfinite(lam):
-            raise ValueError(f"lambda_ssim must be finite, not {lam}")
+        lam = self._tv_weight("lambda_ssim", lambda_ssim)
         H, W = int(self.grid[0]), int(self.grid[1])
-        n = H * W
         taps, win, cov = functional._ssim_window(window)
         if data_range is None:
             if window == "uniform" or (isinstance(window, tuple) and window[1] is None):
@@ -620,47 +675,18 @@ class FusedTrainer:
             raise ValueError(f"a {H} x {W} grid is smaller than the {taps}-tap window")
         if not 1 <= self.O <= 8:
             raise ValueError(f"{self.O} channels: the library takes 1..8")
-        if indices is not None:
-            if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64 or not indices.is_cuda \
-                    or indices.dim() != 1 or not indices.is_contiguous():
-                raise ValueError("indices must be a 1-D contiguous CUDA int64 tensor")
-            B = indices.numel()
-            if B > n:
-                raise ValueError(f"{B} indices for a grid of {n} points: the rows of indices must be distinct")
-            first = 0
-        else:
-            first = int(first)
-            B = int(count if count is not None else n - first)
-            if first < 0 or B < 0 or first + B > n:
-                raise ValueError(f"rows [{first}, {first + B}) outside the grid of {n} points")
-        L, d = self.L, C.byref(self.desc)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        self._reserve(n)
-        g = self.gbuf[0]
-        if getattr(self, "loss_parts", None) is None:
-            self.loss_parts = torch.zeros(3, dtype=torch.float32, device=self.dev)
-        ws_bytes = _lib.check(L.wire_ssim_mse_grad_ws_bytes(H, W, self.O, taps), "ssim_mse_grad_ws_bytes")
-        ws = getattr(self, "_ssim_loss_ws", None)
-        if ws is None or ws.numel() < ws_bytes:
-            ws = self._ssim_loss_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.dev)
+        indices, first, B = self._rows_arg(indices, first, count, H * W)
+        parts = self._buf("loss_parts", 3, zero=True)
+        ws = self._buf("_ssim_loss_ws", _lib.check(self.L.wire_ssim_mse_grad_ws_bytes(H, W, self.O, taps),
+                                                   "ssim_mse_grad_ws_bytes"), torch.uint8)
         c1, c2 = (0.01 * float(data_range)) ** 2, (0.03 * float(data_range)) ** 2
-        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
-        _lib.check(L.wire_coords_from_index(stream, None, 0, n, self.tx.data_ptr(), W, self.ty.data_ptr(), H,
-                                            None, 1, self.coords.data_ptr()), "coords")
-        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                  self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
-        _lib.check(L.wire_ssim_mse_grad(stream, self.y.data_ptr(), H, W, self.O, self.target.data_ptr(), taps, win, cov,
-                                        c1, c2, indices.data_ptr() if indices is not None else None, first, B, lam,
-                                        self.gy.data_ptr(), self.loss_parts.data_ptr(),
-                                        self.rec.data_ptr() if self.rec is not None else None,
-                                        ws.data_ptr(), ws.numel()), "ssim_mse_grad")
-        _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                  self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
-                                  self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
-        self.t += 1
-        self._adam(stream, g)
-        self.loss = self.loss_parts[0:1].clone()              # loss_parts is overwritten by the next step
-        return self.loss
+
+        def loss(stream, g):
+            _lib.check(self.L.wire_ssim_mse_grad(stream, self.y.data_ptr(), H, W, self.O, self.target.data_ptr(), taps,
+                                                 win, cov, c1, c2, self._opt_ptr(indices), first, B, lam,
+                                                 self.gy.data_ptr(), parts.data_ptr(), self._opt_ptr(self.rec),
+                                                 ws.data_ptr(), ws.numel()), "ssim_mse_grad")
+        return self._raster_step(loss, loss_src=parts[0:1])
 
     # ------------------------------------------------------------------ multi-image super-resolution step
     def affine_coords(self, mats) -> torch.Tensor:
@@ -668,29 +694,22 @@ class FusedTrainer:
         ``Xstack`` / ``Ystack`` at scale 1 (modules/motion.py:284-318, wire_multi_sr.py:74-78) as ``ImageSRDataset``
         stacks them -- computed on the device in fp64 (wire_affine_coords): the 2 x 3 matrices are all that crosses the
         bus.  ``mats``: [B, 2, 3] array or tensor.  Returns the contiguous float32 device tensor [B, H*W, 2]."""
-        if self.tz is not None or len(self.grid) != 2:
-            raise ValueError("affine_coords needs a 2-D grid")
+        self._need_grid("affine_coords", single_process=False)
         m = torch.as_tensor(mats).detach().to(self.dev, torch.float64)
         if m.dim() != 3 or tuple(m.shape[1:]) != (2, 3) or m.shape[0] < 1:
             raise ValueError("mats must be [B, 2, 3] with B >= 1")
         m = m.contiguous()
         H, W = int(self.grid[0]), int(self.grid[1])
         out = torch.empty(m.shape[0], H * W, 2, dtype=torch.float32, device=self.dev)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        _lib.check(self.L.wire_affine_coords(stream, m.data_ptr(), m.shape[0], H, W, out.data_ptr()), "affine_coords")
+        _lib.check(self.L.wire_affine_coords(self._stream(), m.data_ptr(), m.shape[0], H, W, out.data_ptr()), "affine_coords")
         return out
 
     def _frames_args(self, what: str, coords, gt_lr, scale, mask, rec_lr):
         """The argument checks of the multi-image steps -> (H, W, scale, coords, B, gt_lr, mask), detached and
         contiguous."""
-        if self.tz is not None or len(self.grid) != 2:
-            raise ValueError(f"{what} needs a 2-D grid")
-        if self.world != 1:
-            raise NotImplementedError(f"{what} is single-process")
+        self._need_grid(what)
         H, W = int(self.grid[0]), int(self.grid[1])
-        scale = int(scale)
-        if scale < 1 or scale > min(H, W):
-            raise ValueError(f"scale {scale} outside 1..min(H, W)")
+        scale = self._scale_arg(scale, H, W)
         H2, W2 = H // scale, W // scale
         if not isinstance(coords, torch.Tensor) or not coords.is_cuda or coords.dtype != torch.float32 \
                 or coords.dim() != 3 or coords.shape[0] < 1 or tuple(coords.shape[1:]) != (H * W, 2) \
@@ -698,19 +717,9 @@ class FusedTrainer:
             raise ValueError(f"coords must be a contiguous CUDA float32 tensor [B, {H * W}, 2]")
         xy = coords.detach()
         B = int(xy.shape[0])
-        gt = gt_lr.detach()
-        if not gt.is_cuda or gt.dtype != torch.float32 or gt.numel() != B * H2 * W2 * self.O:
-            raise ValueError(f"gt_lr must be a CUDA float32 tensor of {B} x {H2 * W2} x {self.O} elements")
-        gt = gt.contiguous()
-        mk = None
-        if mask is not None:
-            mk = mask.detach()
-            if not mk.is_cuda or mk.dtype != torch.float32 or mk.numel() != gt.numel():
-                raise ValueError(f"mask must be a CUDA float32 tensor of {B} x {H2 * W2} x {self.O} elements")
-            mk = mk.contiguous()
-        if rec_lr is not None and (not rec_lr.is_cuda or rec_lr.dtype != torch.float32
-                                   or rec_lr.numel() != gt.numel() or not rec_lr.is_contiguous()):
-            raise ValueError("rec_lr must be a contiguous CUDA float32 tensor shaped like gt_lr")
+        gt = self._f32_elems("gt_lr", gt_lr, B, H2 * W2, self.O)
+        mk = None if mask is None else self._f32_elems("mask", mask, B, H2 * W2, self.O)
+        self._f32_like("rec_lr", rec_lr, gt, "gt_lr")
         return H, W, scale, xy, B, gt, mk
 
     def step_frames(self, coords: torch.Tensor, gt_lr: torch.Tensor, scale: int, mask: Optional[torch.Tensor] = None,
@@ -726,34 +735,30 @@ class FusedTrainer:
         No TV prior here (``step_downsampled``, ``step_radon`` and ``step_coded`` take one): the frames are warped
         copies, and a prior belongs on the canonical grid, which this step never evaluates."""
         H, W, scale, xy, B, gt, mk = self._frames_args("step_frames", coords, gt_lr, scale, mask, rec_lr)
-        L, d = self.L, C.byref(self.desc)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        stream = self._stream()
         n = B * H * W
         self._reserve(n)
         g = self.gbuf[0]
-        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
-        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), xy.data_ptr(), n,
-                                  self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
-        _lib.check(L.wire_avgpool_mse_grad_frames(stream, self.y.data_ptr(), B, H, W, self.O, scale, gt.data_ptr(),
-                                                  mk.data_ptr() if mk is not None else None, self.gy.data_ptr(),
-                                                  rec_lr.data_ptr() if rec_lr is not None else None,
-                                                  g.data_ptr() + 4 * self.count, self.partial.data_ptr()),
-                   "avgpool_mse_grad_frames")
-        _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), xy.data_ptr(), n,
-                                  self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
-                                  self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
-        self.t += 1
-        self._adam(stream, g)
-        self.loss = g[self.count:self.count + 1].clone()
-        return self.loss
+        self._pack(stream)
+        src = self._fwd_loss_bwd(stream, xy.data_ptr(), n, self._frames_loss(B, H, W, scale, gt, mk, rec_lr), g,
+                                 self.grad_ptrs[0])
+        return self._finish(stream, g, src)
+
+    def _frames_loss(self, B: int, H: int, W: int, scale: int, gt, mk, rec_lr):
+        """The masked, pooled loss of the multi-image steps."""
+        def loss(stream, g):
+            _lib.check(self.L.wire_avgpool_mse_grad_frames(stream, self.y.data_ptr(), B, H, W, self.O, scale,
+                                                           gt.data_ptr(), self._opt_ptr(mk), self.gy.data_ptr(),
+                                                           self._opt_ptr(rec_lr), self._loss_slot(g)[0],
+                                                           self.partial.data_ptr()), "avgpool_mse_grad_frames")
+        return loss
 
     # ------------------------------------------------------------------ multi-image step with a learnable registration
     def registration(self, B: int, lr: float = 1e-4, pin_first: bool = True, theta=None) -> "FrameRegistration":
         """The registration state of B frames on the trainer's device, for ``step_frames_registered``: one 2 x 3 matrix
         per frame in normalised coordinates, the identity unless ``theta`` ([B, 2, 3]) is given, with its own Adam
         state and rate ``lr``.  ``pin_first`` keeps frame 0 where it is (the gauge).  2-D grids."""
-        if self.tz is not None or len(self.grid) != 2:
-            raise ValueError("registration needs a 2-D grid")
+        self._need_grid("registration", single_process=False)
         return FrameRegistration(B, self.dev, lr=lr, pin_first=pin_first, theta=theta)
 
     def _reserve_registered(self, n: int, B: int) -> None:
@@ -765,9 +770,8 @@ class FusedTrainer:
             self.g_coords = torch.empty(n, 2, dtype=torch.float32, device=self.dev)
             self._reg_cap = n
         # (frames of one grid: the workspace grows with B alone)
-        ws_bytes = _lib.check(self.L.wire_warp_coords_bwd_ws_bytes(B, n // B), "warp_coords_bwd_ws_bytes")
-        if getattr(self, "warp_ws", None) is None or self.warp_ws.numel() < ws_bytes:
-            self.warp_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.dev)
+        self._buf("warp_ws", _lib.check(self.L.wire_warp_coords_bwd_ws_bytes(B, n // B), "warp_coords_bwd_ws_bytes"),
+                  torch.uint8)
 
     def step_frames_registered(self, reg: "FrameRegistration", coords: torch.Tensor, gt_lr: torch.Tensor, scale: int,
                                mask: Optional[torch.Tensor] = None,
@@ -790,36 +794,25 @@ class FusedTrainer:
             raise ValueError("reg must be a FrameRegistration on the trainer's device (FusedTrainer.registration)")
         if B != reg.B:
             raise ValueError(f"coords hold {B} frames, the registration {reg.B}")
-        L, d = self.L, C.byref(self.desc)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        L = self.L
+        stream = self._stream()
         n = B * H * W
         self._reserve(n)
         self._reserve_registered(n, B)
         g = self.gbuf[0]
-        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
+        self._pack(stream)
         _lib.check(L.wire_warp_coords_fwd(stream, xy.data_ptr(), reg.theta.data_ptr(), B, H * W,
                                           self.coords.data_ptr()), "warp_coords_fwd")
-        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                  self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
-        _lib.check(L.wire_avgpool_mse_grad_frames(stream, self.y.data_ptr(), B, H, W, self.O, scale, gt.data_ptr(),
-                                                  mk.data_ptr() if mk is not None else None, self.gy.data_ptr(),
-                                                  rec_lr.data_ptr() if rec_lr is not None else None,
-                                                  g.data_ptr() + 4 * self.count, self.partial.data_ptr()),
-                   "avgpool_mse_grad_frames")
-        _lib.check(L.wire_mlp_bwd_coords(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                         self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
-                                         self.coords_scratch.data_ptr(), self.coords_scr_bytes, self.grad_ptrs[0],
-                                         self.g_coords.data_ptr()), "bwd_coords")
+        src = self._fwd_loss_bwd(stream, self.coords.data_ptr(), n, self._frames_loss(B, H, W, scale, gt, mk, rec_lr),
+                                 g, self.grad_ptrs[0], coords_grad=True)
         _lib.check(L.wire_warp_coords_bwd(stream, xy.data_ptr(), reg.theta.data_ptr(), self.g_coords.data_ptr(), B,
                                           H * W, int(reg.pin_first), reg.grad.data_ptr(), None,
                                           self.warp_ws.data_ptr(), self.warp_ws.numel()), "warp_coords_bwd")
-        self.t += 1
-        self._adam(stream, g)
+        self._finish(stream, g, src)
         reg.t += 1
         _lib.check(L.wire_adam_step_flat(stream, reg.theta.data_ptr(), reg.grad.data_ptr(), reg.exp_avg.data_ptr(),
                                          reg.exp_avg_sq.data_ptr(), 6 * B, float(reg.lr), reg.betas[0], reg.betas[1],
                                          reg.eps, reg.t), "adam (registration)")
-        self.loss = g[self.count:self.count + 1].clone()
         return self.loss
 
     # ------------------------------------------------------------------ CT step
@@ -832,46 +825,24 @@ class FusedTrainer:
         to the loss and its gradient to the adjoint's dL/dy (wire_tv_add_grad, between the adjoint and the backward);
         the returned loss is the total and ``self.tv_parts`` holds [loss, mse, tv, 0].  With 0.0 that kernel is not
         launched and the step issues the launches of the plain one.  2-D grids, one output feature, single process."""
-        if self.tz is not None or len(self.grid) != 2 or self.O != 1:
-            raise ValueError("step_radon needs a 2-D grid and out_features == 1")
-        if self.world != 1:
-            raise NotImplementedError("step_radon is single-process")
+        self._need_grid("step_radon", one_output=True)
         lam = self._tv_weight("lambda_tv", lambda_tv)
         H, W = int(self.grid[0]), int(self.grid[1])
         th = thetas.detach().to(self.dev, torch.float32).contiguous()
         A = th.numel()
-        tgt = sinogram.detach()
-        if not tgt.is_cuda or tgt.dtype != torch.float32 or tgt.numel() != A * W:
-            raise ValueError(f"sinogram must be a CUDA float32 tensor of {A} x {W} elements")
-        tgt = tgt.contiguous()
-        L, d = self.L, C.byref(self.desc)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        n = H * W
-        self._reserve(n)
-        if getattr(self, "_sino", None) is None or self._sino.numel() != A * W:
-            self._sino = torch.empty(A * W, dtype=torch.float32, device=self.dev)
-            self._gsino = torch.empty(A * W, dtype=torch.float32, device=self.dev)
-        g = self.gbuf[0]
-        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
-        _lib.check(L.wire_coords_from_index(stream, None, 0, n, self.tx.data_ptr(), W, self.ty.data_ptr(), H,
-                                            None, 1, self.coords.data_ptr()), "coords")
-        _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                  self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
-        _lib.check(L.wire_radon_fwd(stream, self.y.data_ptr(), th.data_ptr(), H, W, A, self._sino.data_ptr()), "radon")
-        _lib.check(L.wire_mse_grad(stream, self._sino.data_ptr(), tgt.data_ptr(), None, 0, A * W, 1, 1.0,
-                                   self._gsino.data_ptr(), g.data_ptr() + 4 * self.count, None,
-                                   self.partial.data_ptr()), "mse_grad")
-        _lib.check(L.wire_radon_bwd(stream, self._gsino.data_ptr(), th.data_ptr(), H, W, A, self.gy.data_ptr()),
-                   "radon_bwd")
-        if lam != 0.0:
-            self._tv_add_grad(stream, H, W, 1, lam, 0.0, g.data_ptr() + 4 * self.count)
-        _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                  self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
-                                  self.scratch.data_ptr(), self.scr_bytes, self.grad_ptrs[0]), "bwd")
-        self.t += 1
-        self._adam(stream, g)
-        self.loss = (self.tv_parts[0:1] if lam != 0.0 else g[self.count:self.count + 1]).clone()
-        return self.loss
+        tgt = self._f32_elems("sinogram", sinogram, A, W)
+        # (of exactly A * W elements: tests/test_gpu_workspace_fill.py fills the two whole)
+        sino, gsino = self._buf("_sino", A * W, exact=True), self._buf("_gsino", A * W, exact=True)
+
+        def loss(stream, g):
+            L = self.L
+            _lib.check(L.wire_radon_fwd(stream, self.y.data_ptr(), th.data_ptr(), H, W, A, sino.data_ptr()), "radon")
+            _lib.check(L.wire_mse_grad(stream, sino.data_ptr(), tgt.data_ptr(), None, 0, A * W, 1, 1.0,
+                                       gsino.data_ptr(), self._loss_slot(g)[0], None, self.partial.data_ptr()),
+                       "mse_grad")
+            _lib.check(L.wire_radon_bwd(stream, gsino.data_ptr(), th.data_ptr(), H, W, A, self.gy.data_ptr()),
+                       "radon_bwd")
+        return self._raster_step(loss, prior=(H, W, 1, lam, 0.0))
 
     # ------------------------------------------------------------------ video compressive-sensing step
     def step_coded(self, coded: torch.Tensor, masks, nframes: int, dup_last: bool = True,
@@ -904,10 +875,7 @@ class FusedTrainer:
         ``self.tv_parts`` holds [loss, mse, tv_s, tv_t].  With both 0.0 that kernel is not launched and the step is the
         plain one, bit for bit.  A prior needs the one-pass path: neighbour pairs would straddle the slabs.
         3-D grids, single process."""
-        if self.tz is None or len(self.grid) != 3:
-            raise ValueError("step_coded needs a 3-D grid (H, W, T)")
-        if self.world != 1:
-            raise NotImplementedError("step_coded is single-process")
+        self._need_grid("step_coded", rank=3)
         H, W, T = (int(v) for v in self.grid)
         NP = H * W
         nframes = int(nframes)
@@ -920,10 +888,7 @@ class FusedTrainer:
                              f"needs the one-pass path, slab=None or slab >= H*W")
         dup = int(bool(dup_last))
         Cp = (T + nframes - 1) // nframes + dup
-        if not isinstance(coded, torch.Tensor) or not coded.is_cuda or coded.dtype != torch.float32 \
-                or coded.numel() != Cp * NP * self.O:
-            raise ValueError(f"coded must be a CUDA float32 tensor of {Cp} x {NP} x {self.O} elements")
-        gt = coded.detach().contiguous()
+        gt = self._f32_elems("coded", coded, Cp, NP, self.O)
         if isinstance(masks, torch.Tensor):
             mk = masks.detach()
             if not mk.is_cuda or mk.dtype != torch.float32 or mk.numel() != NP * T:
@@ -938,48 +903,35 @@ class FusedTrainer:
                     .to(self.dev)
                 self._coded_masks_src = masks
             mk = self._coded_masks_dev
-        if est is not None and (not est.is_cuda or est.dtype != torch.float32 or est.numel() != gt.numel()
-                                or not est.is_contiguous()):
-            raise ValueError("est must be a contiguous CUDA float32 tensor shaped like coded")
+        self._f32_like("est", est, gt, "coded")
         per = NP if slab is None else int(slab)
         if per < 1:
             raise ValueError(f"slab {per} must be >= 1 pixel")
         per = min(per, NP)
-        L, d = self.L, C.byref(self.desc)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        stream = self._stream()
         self._reserve(per * T)
-        g = self.gbuf[0]
-        gp = self.grad_ptrs[0]
-        if per < NP and getattr(self, "_gslab", None) is None:
+        g0 = self.gbuf[0]
+        if per < NP and getattr(self, "_gslab_ptrs", None) is None:
             # wire_mlp_bwd overwrites its gradients: the slabs after the first write here and are added to gbuf[0]
-            self._gslab = torch.zeros(self.count + 1, dtype=torch.float32, device=self.dev)
-            self._gslab_ptrs = _lib.ptr_array([self._gslab.data_ptr() + 4 * o for o in self.offsets])
-        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
+            gs = self._buf("_gslab", self.count + 1, zero=True)
+            self._gslab_ptrs = _lib.ptr_array([gs.data_ptr() + 4 * o for o in self.offsets])
+        self._pack(stream)
         for p0 in range(0, NP, per):
             npix = min(per, NP - p0)
-            n = npix * T
+            g, gp = (g0, self.grad_ptrs[0]) if p0 == 0 else (self._gslab, self._gslab_ptrs)
+
+            def loss(stream, g):
+                _lib.check(self.L.wire_coded_mse_grad(stream, self.y.data_ptr(), p0, npix, NP, T, self.O, nframes, dup,
+                                                      mk.data_ptr(), gt.data_ptr(), self.gy.data_ptr(),
+                                                      self._opt_ptr(est), self._loss_slot(g)[0],
+                                                      self.partial.data_ptr()), "coded_mse_grad")
+            self._grid_coords(stream, p0 * T, npix * T, self.coords)
+            # (a prior means one pass: p0 == 0 and y holds the whole grid)
+            src = self._fwd_loss_bwd(stream, self.coords.data_ptr(), npix * T, loss, g, gp, (H, W, T, lam_s, lam_t))
             if p0 > 0:
-                g, gp = self._gslab, self._gslab_ptrs
-            _lib.check(L.wire_coords_from_index(stream, None, p0 * T, n, self.tx.data_ptr(), W, self.ty.data_ptr(), H,
-                                                self.tz.data_ptr(), T, self.coords.data_ptr()), "coords")
-            _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                      self.y.data_ptr(), self.act.data_ptr(), self.act_bytes, 1), "fwd")
-            _lib.check(L.wire_coded_mse_grad(stream, self.y.data_ptr(), p0, npix, NP, T, self.O, nframes, dup,
-                                             mk.data_ptr(), gt.data_ptr(), self.gy.data_ptr(),
-                                             est.data_ptr() if est is not None else None,
-                                             g.data_ptr() + 4 * self.count, self.partial.data_ptr()), "coded_mse_grad")
-            if prior:                                          # one pass: p0 == 0 and y holds the whole grid
-                self._tv_add_grad(stream, H, W, T, lam_s, lam_t, g.data_ptr() + 4 * self.count)
-            _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), n,
-                                      self.gy.data_ptr(), self.act.data_ptr(), self.act_bytes,
-                                      self.scratch.data_ptr(), self.scr_bytes, gp), "bwd")
-            if p0 > 0:
-                self.gbuf[0].add_(g)
-        g = self.gbuf[0]
-        self.t += 1
-        self._adam(stream, g)
-        self.loss = (self.tv_parts[0:1] if prior else g[self.count:self.count + 1]).clone()
-        return self.loss
+                g0.add_(g)
+        # (one pass, or no prior: the total is in the slot behind gbuf[0])
+        return self._finish(stream, g0, src if prior else self._loss_slot(g0)[1])
 
     @property
     def flat_grad(self) -> torch.Tensor:
@@ -1026,7 +978,7 @@ class FusedTrainer:
         if rec.numel() != gt.numel():
             raise ValueError("metric operands differ in size")
         out = torch.empty(2, dtype=torch.float32, device=self.dev)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        stream = self._stream()
         _lib.check(self.L.wire_eval_metric(stream, mode, rec.data_ptr(), gt.data_ptr(), rec.numel(), thres,
                                            out.data_ptr(), self.partial.data_ptr()), "metric")
         return out
@@ -1048,7 +1000,7 @@ class FusedTrainer:
         if getattr(self, "best_img", None) is None or self.best_img.numel() != img.numel():
             self.best_img = torch.zeros_like(img)
             self.best_metric = torch.full((1,), float("inf"), dtype=torch.float32, device=self.dev)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        stream = self._stream()
         _lib.check(self.L.wire_track_best(stream, m.data_ptr(), self.best_metric.data_ptr(), int(bool(force)),
                                           img.data_ptr(), self.best_img.data_ptr(), img.numel(), None), "track_best")
 
@@ -1061,21 +1013,17 @@ class FusedTrainer:
         ``torch.sigmoid`` to the result, the occupancy cube ``export_mesh`` hands to marching cubes
         (modules/volutils.py:124-133; the meshing itself is out of scope)."""
         L, d = self.L, C.byref(self.desc)
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        stream = self._stream()
         count = int(count if count is not None else self.npoints - first)
         out = torch.empty(count, self.O, dtype=torch.float32, device=self.dev)
-        _lib.check(L.wire_pack_params(stream, d, self.param_ptrs, self.packed.data_ptr()), "pack")
+        self._pack(stream)
         tile = min(tile, max(count, 1))
         ab = _lib.check(L.wire_act_bytes(d, tile, 0))
         act = torch.empty(ab, dtype=torch.uint8, device=self.dev)
         coords = torch.empty(tile * self.desc.in_features, dtype=torch.float32, device=self.dev)
-        tz_ptr = self.tz.data_ptr() if self.tz is not None else None
-        Tn = self.grid[2] if self.tz is not None else 1
         for s in range(0, count, tile):
             n = min(tile, count - s)
-            _lib.check(L.wire_coords_from_index(stream, None, first + s, n, self.tx.data_ptr(), self.grid[1],
-                                                self.ty.data_ptr(), self.grid[0], tz_ptr, Tn,
-                                                coords.data_ptr()), "coords")
+            self._grid_coords(stream, first + s, n, coords)
             _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), coords.data_ptr(), n,
                                       out.data_ptr() + 4 * s * self.O, act.data_ptr(), ab, 0), "fwd")
         if sigmoid:
