@@ -494,6 +494,39 @@ int wire_tv_mse_grad(void* stream, const float* y, int H, int W, int O, const fl
 int wire_tv_add_grad(void* stream, const float* y, int H, int W, int T, int O, float lambda_s, float lambda_t,
                      const float* data_loss, float* g_y, float* loss_out, float* partial);
 
+/* ---- iso-surface extraction (what modules/volutils.py:94-142 hands to PyMCubes) -------------------------------
+ * The surface {vol >= thres} of a volume vol [H][W][T] (fp32, row-major; NaN counts as outside) as a welded, indexed
+ * triangle mesh: marching tetrahedra on the six-tetrahedron Kuhn split of every cell (wire_amd/csrc/wire_iso.hip
+ * states the rules).  Closed wherever the volume's boundary does not cut it, consistently wound with the normal
+ * pointing from inside to outside -- by combinatorics, so also when thres equals a data value.  NOT PyMCubes' triangles.
+ *   vertices: one per lattice edge (7 directions: the 3 axes, the 3 face diagonals, the body diagonal) whose ends lie
+ *     on different sides, at p + t d, t = (thres - vol[p]) / (vol[p + d] - vol[p]) in fp32, in index units
+ *     (i, j, k) -- the PyMCubes convention; ordered by (linear index of the lower end p, direction).
+ *   faces: three vertex ids each, ordered by (linear index of the cell, tetrahedron, triangle).
+ * Two passes.  wire_iso_count classifies, scans (reduce-then-scan in separate launches: no workgroup waits on another,
+ * no atomics) and leaves in ws what the second pass needs; counts (DEVICE, 8-byte aligned) receives {vertices, faces}.
+ * wire_iso_emit, with the same vol, sizes, thres and the ws the count left, writes verts [nverts][3] and faces
+ * [nfaces][3].  It reads the two counts back from ws (16 bytes, one synchronisation of the stream) and, when
+ * nverts > cap_v or nfaces > cap_f, returns WIRE_ERR_SIZE having written nothing; the kernels guard every store by the
+ * capacities besides.  cap_v == 0 / cap_f == 0 allow a NULL verts / faces.  Same call, same bits, whatever ws held.
+ * ws: wire_iso_ws_bytes bytes (about 9 per lattice point), device, 16-byte aligned.
+ * A side < 2, more than 2^28 lattice points (so every vertex id fits an int32 and every face offset 32 bits), a NaN
+ * thres, a NULL or misaligned pointer: WIRE_ERR_ARG before any HIP call (the size query too).
+ * wire_iso_tet_case: host only -- the compile-time table the emit pass winds by, for tetrahedron perm (0..5, the
+ * permutations of the axes in lexicographic order) and inside mask (bit n = corner v_n inside): bits 0-1 = the number
+ * of triangles, then three bits per corner, triangle 0 at bits 2 / 5 / 8 and triangle 1 at bits 11 / 14 / 17, each the
+ * edge 01 02 03 12 13 23 (0..5) of the tetrahedron that the corner lies on.                                          */
+int64_t wire_iso_ws_bytes(int H, int W, int T);
+int wire_iso_count(void* stream, const float* vol, int H, int W, int T, float thres, void* ws, int64_t* counts);
+int wire_iso_emit(void* stream, const float* vol, int H, int W, int T, float thres, const void* ws, float* verts,
+                  int64_t cap_v, int32_t* faces, int64_t cap_f);
+int wire_iso_tet_case(int perm, int inside_mask);
+/* Separable Gaussian blur of a volume [H][W][T]: 2 R + 1 taps per axis, R = floor(4 sigma + 0.5) <= 32, weights
+ * exp(-x^2 / 2 sigma^2) normalised in fp64 and rounded to fp32, edge values replicated; axis T, then W, then H, per
+ * axis the taps added from -R to +R, every product and sum rounded once.  in, tmp, out: three distinct device buffers
+ * of H W T floats; in is not written.  A side < 1, sigma not in (0, 8], a NULL pointer or two equal ones: WIRE_ERR_ARG. */
+int wire_gauss3_blur(void* stream, const float* in, int H, int W, int T, float sigma, float* tmp, float* out);
+
 /* torch.optim.Adam single step over a flat fp32 buffer (complex tensors as
  * real pairs; wire_image_denoise.py:123-125).  step is 1-based.            */
 int wire_adam_step_flat(void* stream, float* param, const float* grad,

@@ -38,6 +38,7 @@ SYMBOLS = [
     "wire_coded_mse_grad", "wire_coded_fwd", "wire_coded_bwd", "wire_tv_fwd", "wire_tv_bwd", "wire_tv_mse_grad",
     "wire_ssim_bwd_ws_bytes", "wire_ssim_bwd", "wire_ssim_mse_grad_ws_bytes", "wire_ssim_mse_grad",
     "wire_tv_add_grad", "wire_warp_coords_fwd", "wire_warp_coords_bwd_ws_bytes", "wire_warp_coords_bwd",
+    "wire_iso_ws_bytes", "wire_iso_count", "wire_iso_emit", "wire_iso_tet_case", "wire_gauss3_blur",
 ]
 
 
@@ -143,6 +144,12 @@ def _declare(l: C.CDLL) -> None:
     l.wire_warp_coords_bwd_ws_bytes.argtypes = [i32, i64]
     l.wire_warp_coords_bwd_ws_bytes.restype = i64
     l.wire_warp_coords_bwd.argtypes = [vp, vp, vp, vp, i32, i64, i32, vp, vp, vp, i64]
+    l.wire_iso_ws_bytes.argtypes = [i32, i32, i32]
+    l.wire_iso_ws_bytes.restype = i64
+    l.wire_iso_count.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]
+    l.wire_iso_emit.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp, i64, vp, i64]
+    l.wire_iso_tet_case.argtypes = [i32, i32]
+    l.wire_gauss3_blur.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]
     l.wire_train_fwd_bwd.argtypes = [vp, dp, vp, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp, vp, i64, vp, i64,
                                      C.POINTER(vp)]
     l.wire_train_fwd_bwd_hooked.argtypes = [vp, dp, vp, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp, vp, i64, vp, i64,

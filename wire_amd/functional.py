@@ -824,3 +824,68 @@ def warp_coords(coords: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
     if theta.device != coords.device:
         raise ValueError("coords and theta must be on the same device")
     return _WarpCoordsFunction.apply(coords, theta)
+
+
+# ---------------------------------------------------------------------------
+# iso-surface extraction on the device (wire_iso_count / wire_iso_emit) and the blur of march_and_save's `smoothen`
+# ---------------------------------------------------------------------------
+def _check_volume(volume, what: str, min_side: int = 1) -> None:
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 3:
+        raise ValueError(f"{what} expects a rank-3 (H, W, T) tensor")
+    if min(volume.shape) < min_side:
+        raise ValueError(f"{what}: a volume of shape {tuple(volume.shape)} (every side must be >= {min_side})")
+    _require_cuda(volume, "volume")
+    if volume.dtype != torch.float32:
+        raise ValueError("volume must be float32")
+
+
+def iso_surface(volume: torch.Tensor, thres: float):
+    """The surface ``{volume >= thres}`` of a float32 CUDA tensor of shape (H, W, T) as a welded triangle mesh:
+    ``(vertices [V, 3] float32, faces [F, 3] int32)``, both on the device.  Marching tetrahedra on the six-tetrahedron
+    Kuhn split of every cell (csrc/wire_iso.hip): closed wherever the volume's boundary does not cut it, every triangle
+    wound so that its normal points from inside (``>= thres``; NaN is outside) to outside, also when ``thres`` equals a
+    data value.  Vertices are in index units (i, j, k), the PyMCubes convention, one per crossed lattice edge, ordered by
+    (lower end, direction); faces by (cell, tetrahedron, triangle): the same input gives the same bits.  These are NOT
+    PyMCubes' triangles.
+
+    Two HIP passes with a device prefix sum between them.  The sizes of the outputs are only known after the first, so
+    the call performs one host synchronisation -- the read of the two counts (the second pass checks them against
+    the capacities it is given by reading the same 16 bytes once more, on a stream that has nothing left to wait for).
+    That is acceptable at the end of a run, not inside a training loop.  Every side must be >= 2 and H W T <= 2^28.
+    CPU tensors raise WireHipError; other ranks, dtypes or sizes ValueError."""
+    _check_volume(volume, "iso_surface", 2)
+    H, W, T = (int(s) for s in volume.shape)
+    if H * W * T > 1 << 28:
+        raise ValueError(f"iso_surface: a {H} x {W} x {T} volume has more than 2^28 points")
+    thres = float(thres)
+    if thres != thres:
+        raise ValueError("iso_surface: the threshold is NaN")
+    L = _lib.lib()
+    vol = volume.detach().contiguous()
+    dev, stream = vol.device, _stream_ptr(vol.device)
+    ws = torch.empty(_lib.check(L.wire_iso_ws_bytes(H, W, T), "wire_iso_ws_bytes"), dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    _lib.check(L.wire_iso_count(stream, vol.data_ptr(), H, W, T, thres, ws.data_ptr(), counts.data_ptr()),
+               "wire_iso_count")
+    nv, nf = (int(c) for c in counts.tolist())           # the one host sync
+    verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    if nv:
+        _lib.check(L.wire_iso_emit(stream, vol.data_ptr(), H, W, T, thres, ws.data_ptr(), verts.data_ptr(), nv,
+                                   faces.data_ptr(), nf), "wire_iso_emit")
+    return verts, faces
+
+
+def gauss3_blur(volume: torch.Tensor, sigma: float = 1.0) -> torch.Tensor:
+    """Separable Gaussian blur of a float32 CUDA (H, W, T) tensor on the device (wire_gauss3_blur): truncated at
+    4 sigma, edge values replicated, fp32.  Returns a new tensor."""
+    _check_volume(volume, "gauss3_blur")
+    if not 0.0 < float(sigma) <= 8.0:
+        raise ValueError("gauss3_blur: sigma outside (0, 8]")
+    L = _lib.lib()
+    vol = volume.detach().contiguous()
+    H, W, T = (int(s) for s in vol.shape)
+    tmp, out = torch.empty_like(vol), torch.empty_like(vol)
+    _lib.check(L.wire_gauss3_blur(_stream_ptr(vol.device), vol.data_ptr(), H, W, T, float(sigma), tmp.data_ptr(),
+                                  out.data_ptr()), "wire_gauss3_blur")
+    return out

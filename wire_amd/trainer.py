@@ -1004,6 +1004,28 @@ class FusedTrainer:
         _lib.check(self.L.wire_track_best(stream, m.data_ptr(), self.best_metric.data_ptr(), int(bool(force)),
                                           img.data_ptr(), self.best_img.data_ptr(), img.numel(), None), "track_best")
 
+    # ------------------------------------------------------------------ mesh of a trained occupancy
+    def extract_mesh(self, thres: float = 0.5, volume: Optional[torch.Tensor] = None, smoothen: bool = False):
+        """The iso-surface of the trainer's (H, W, T) volume at ``thres`` as ``(vertices [V, 3] float32, faces [F, 3]
+        int32)`` on the device -- what the occupancy driver's last lines hand to ``march_and_save``
+        (wire_occupancy.py:198-201), without the copy of the volume to the host; ``volutils.save_mesh`` writes it.
+        ``volume=None`` takes the best tracked image (``update_best``) if there is one, else ``rec`` (``keep_rec=True``);
+        with neither it is a ValueError.  A 3-D grid with one output only.  ``smoothen`` as in
+        ``volutils.march_and_save``.  One host sync (functional.iso_surface)."""
+        from .modules import volutils
+        if self.tz is None or len(self.grid) != 3 or self.O != 1:
+            raise ValueError("extract_mesh needs a 3-D grid (H, W, T) and out_features == 1")
+        if volume is None:
+            volume = getattr(self, "best_img", None)
+            if volume is None:
+                volume = self.rec
+            if volume is None:
+                raise ValueError("extract_mesh: no volume -- pass one, track one with update_best, or build the trainer "
+                                 "with keep_rec=True")
+        if not isinstance(volume, torch.Tensor) or volume.numel() != self.npoints:
+            raise ValueError(f"extract_mesh: the volume must be a tensor of {self.npoints} values")
+        return volutils.march(volume.reshape(*self.grid), thres, smoothen)
+
     # ------------------------------------------------------------------ inference
     @torch.no_grad()
     def render(self, first: int = 0, count: Optional[int] = None, tile: int = 1 << 20,
@@ -1011,7 +1033,7 @@ class FusedTrainer:
         """Forward-only dense query of grid rows [first, first+count) in tiles
         (no saved activations): the reference's full-image / volume evaluation.  ``sigmoid=True`` applies
         ``torch.sigmoid`` to the result, the occupancy cube ``export_mesh`` hands to marching cubes
-        (modules/volutils.py:124-133; the meshing itself is out of scope)."""
+        (modules/volutils.py:124-133; ``extract_mesh`` / ``volutils.march_and_save`` mesh it)."""
         L, d = self.L, C.byref(self.desc)
         stream = self._stream()
         count = int(count if count is not None else self.npoints - first)
