@@ -262,7 +262,8 @@ int wire_train_fwd_bwd_hooked(void* stream, const wire_net_desc* d, const float*
  *   g_coords NULL: exactly what wire_mlp_bwd produces; both NULL is an argument error.
  *   scratch: wire_bwd_coords_scratch_bytes(d, n) when g_coords is given (>= wire_bwd_scratch_bytes).
  *   The result is deterministic: every sum runs in a fixed order.
- * wire_posenc_bwd: backward of wire_posenc_fwd, g_pe [n][D + 2 D F] -> g_coords [n][D].                  */
+ * wire_posenc_bwd: backward of wire_posenc_fwd, g_pe [n][D + 2 D F] -> g_coords [n][D].  n < 0, D outside 1..4, F outside
+ *   0..30, or (n > 0) a NULL pointer: WIRE_ERR_ARG before any HIP call; n == 0 returns WIRE_OK and touches nothing.  */
 int64_t wire_bwd_coords_scratch_bytes(const wire_net_desc* d, int64_t n);
 int wire_mlp_bwd_coords(void* stream, const wire_net_desc* d, const float* packed, const float* coords, int64_t n,
                         const float* g_y, const void* act, int64_t act_bytes, void* scratch, int64_t scratch_bytes,
@@ -287,7 +288,9 @@ int wire_gabor_bwd(void* stream, const void* g_act, const void* x,
                    void* g_x, void* g_W, void* g_b, void* ws, int64_t ws_bytes);
 /* gradient of a TRAINABLE omega_0 / scale_0 (ComplexGaborLayer(..., trainable=True), modules/wire.py:80-81):
  * out2 (device, 2 floats) = { dL/d omega_0, dL/d scale_0 } for the upstream gradient g_act; same operands and
- * workspace as wire_gabor_bwd.                                                                       */
+ * workspace as wire_gabor_bwd.  Rows are summed in blocks of 32, the blocks' sums by one block, in a fixed order: the
+ * same call gives the same bits.  n, in_features or out_features < 1 or a NULL pointer: WIRE_ERR_ARG before any HIP
+ * call; ws_bytes < wire_layer_ws_bytes(n, in, out): WIRE_ERR_SIZE; is_first with in_features > 4: WIRE_ERR_ARG.     */
 int wire_gabor_hparam_grad(void* stream, const void* g_act, const void* x, const void* W, const void* b,
                            float omega0, float scale0, int64_t n, int in_features, int out_features,
                            int is_first, float* out2, void* ws, int64_t ws_bytes);
@@ -323,7 +326,9 @@ int wire_real_layer_bwd(void* stream, int kind, const float* g_act, const float*
 /* coords[r] = grid point of flat index idx[r] (idx NULL -> first + r).
  * 2-D (tz NULL): idx = i*W + j -> (tx[j], ty[i])   (wire_image_denoise.py:63-66)
  * 3-D: idx = (i*W + j)*T + k -> (tx[j], ty[i], tz[k]) (modules/utils.py:171-176)
- * tx/ty/tz are the caller's linspace tables (device).                      */
+ * tx/ty/tz are the caller's linspace tables (device).  The indices are trusted.
+ * n < 0, W or H < 1, T < 1 with tz given, or tx, ty or coords NULL: WIRE_ERR_ARG
+ * before any HIP call; n == 0 returns WIRE_OK and touches nothing.           */
 int wire_coords_from_index(void* stream, const int64_t* idx, int64_t first,
                            int64_t n, const float* tx, int W, const float* ty,
                            int H, const float* tz, int T, float* coords);
@@ -338,7 +343,11 @@ int wire_perm_indices(void* stream, uint64_t seed, int64_t n_total, int64_t firs
  * (= n/B for a shard of a global batch B; 1 for a whole batch);
  * g_y = weight * 2/(n*O) * (y - t).  loss_out[0] += is NOT used: it is
  * overwritten.  rec (optional): rec[idx[r]][:] = y[r][:]
- * (wire_image_denoise.py:150-153).  partial: scratch of >= 4096 floats.    */
+ * (wire_image_denoise.py:150-153).  partial: scratch of >= 4096 floats.
+ * Per-block sums in a grid that depends on n*O alone, added in a fixed order:
+ * the same call gives the same bits.  n < 0, O < 1, or a NULL pointer other
+ * than idx / rec: WIRE_ERR_ARG before any HIP call.  n == 0 returns WIRE_OK
+ * and touches nothing, loss_out included.  The rows of idx are trusted.      */
 int wire_mse_grad(void* stream, const float* y, const float* target,
                   const int64_t* idx, int64_t first, int64_t n, int O,
                   float weight, float* g_y, float* loss_out, float* rec,
@@ -346,7 +355,9 @@ int wire_mse_grad(void* stream, const float* y, const float* target,
 /* Super-resolution loss of wire_SISR.py:151-161: rec = torch.nn.AvgPool2d(scale) of the full-grid
  * reconstruction y [H*W][O] (row n = i*W + j), loss = mean((gt_lr - rec)^2) over [H/scale][W/scale][O]
  * (floor: ragged borders are dropped and receive zero gradient).  Writes loss_out[0], g_y = dL/dy [H*W][O]
- * and, if rec_lr != NULL, the pooled image.  partial: >= 1024 floats of scratch.                       */
+ * and, if rec_lr != NULL, the pooled image.  partial: >= 1024 floats of scratch.  EVERY element of g_y is written (the
+ * ragged borders with +0.0).  H, W, O or scale < 1, scale > min(H, W), or a NULL pointer other than rec_lr: WIRE_ERR_ARG
+ * before any HIP call.  No atomics: the same call gives the same bits.                                  */
 int wire_avgpool_mse_grad(void* stream, const float* y, int H, int W, int O, int scale,
                           const float* gt_lr, float* g_y, float* rec_lr, float* loss_out,
                           float* partial);
@@ -528,7 +539,11 @@ int wire_iso_tet_case(int perm, int inside_mask);
 int wire_gauss3_blur(void* stream, const float* in, int H, int W, int T, float sigma, float* tmp, float* out);
 
 /* torch.optim.Adam single step over a flat fp32 buffer (complex tensors as
- * real pairs; wire_image_denoise.py:123-125).  step is 1-based.            */
+ * real pairs; wire_image_denoise.py:123-125).  step is 1-based.  param,
+ * exp_avg and exp_avg_sq are updated in place; the bias corrections are taken
+ * in fp64 on the host.  With lr == 0 param keeps its bits.  count < 0,
+ * step < 1 or a NULL pointer: WIRE_ERR_ARG before any HIP call; count == 0
+ * returns WIRE_OK and touches nothing.                                       */
 int wire_adam_step_flat(void* stream, float* param, const float* grad,
                         float* exp_avg, float* exp_avg_sq, int64_t count,
                         float lr, float beta1, float beta2, float eps,
@@ -541,7 +556,12 @@ int wire_adam_step_flat(void* stream, float* param, const float* grad,
  *   mode 0: out2 = { sum (gt-rec)^2, max(gt) }  -> utils.psnr = 10 log10(max / (sum/count))
  *                                                   (modules/utils.py:67-82: max(x), not max^2)
  *   mode 1: out2 = { |rec>=thres & gt!=0|, |rec>=thres or gt!=0| }  -> IoU = out2[0] / out2[1]
- *           (rec is NOT binarised in place, unlike get_I_and_U)               */
+ *           (rec is NOT binarised in place, unlike get_I_and_U).  The comparisons are the IEEE ones: a NaN in rec
+ *           is below every threshold, a NaN in gt is != 0, -0.0 is == 0.
+ * max(gt) is a value of gt, exact.  The two counts are sums of fp32 ones: EXACT up to 2^24 elements per call (every
+ * partial sum is an integer <= 2^24), rounded to fp32 beyond -- a caller with more elements splits them into calls of
+ * at most 2^24 and adds the counts itself (modules/volutils.py does).  Fixed summation order: the same call gives the
+ * same bits.  mode outside {0, 1}, count < 1 or a NULL pointer: WIRE_ERR_ARG before any HIP call.  */
 int wire_eval_metric(void* stream, int mode, const float* rec, const float* gt,
                      int64_t count, float thres, float* out2, float* partial);
 
@@ -610,18 +630,31 @@ int wire_ssim_mse_grad(void* stream, const float* y, int H, int W, int O, const 
 /* Best-reconstruction tracking of the drivers without a device->host copy per epoch
  * (wire_image_denoise.py:176-178: `if (mse_array[epoch] < best_mse) or (epoch == 0): best_mse = ...; best_img = imrec`;
  * wire_occupancy.py:170-172 with lossval): if force != 0 or metric[0] < best_metric[0], copy src[0..count) to dst
- * and metric[0] to best_metric[0]; updated (optional, device int) receives 1 / 0.  All pointers device.      */
+ * and metric[0] to best_metric[0]; updated (optional, device int) receives 1 / 0.  All pointers device.  A NaN metric
+ * is never taken (unless forced); any metric below +inf replaces a best of +inf.  Not taken: dst and best_metric keep
+ * their bits.  The copy moves 16 bytes per thread: with count > 0, src and dst must be 16-BYTE ALIGNED (count itself may
+ * be any number; the last count % 4 floats are copied one by one, and nothing behind dst[count - 1] is written).
+ * count == 0 updates the scalar alone (src / dst may be NULL).  metric or best_metric NULL, count < 0, count > 0 with
+ * src or dst NULL or misaligned: WIRE_ERR_ARG before any HIP call.                                              */
 int wire_track_best(void* stream, const float* metric, float* best_metric, int force, const float* src,
                     float* dst, int64_t count, int* updated);
 /* CT forward operator of wire_ct.py:128-133 -- lin_inverse.radon (modules/lin_inverse.py:19-40): every angle
  * rotates the image (kornia.geometry.rotate of kornia 0.6.5: about ((W-1)/2, (H-1)/2), counter-clockwise degrees,
  * bilinear, zero padding, align_corners) and sums over the rows: img [H][W] -> sino [nangles][W].  wire_radon_bwd
  * is its adjoint, g_sino [nangles][W] -> g_img [H][W] (overwritten; float atomics: summation order, hence the last
- * bits, vary from run to run).                                                                              */
+ * bits, vary from run to run; the forward has a fixed order and gives the same bits).  With c / s = cos / sin of angle a,
+ * (cx, cy) = ((W-1)/2, (H-1)/2), xj = j - cx, yi = i - cy:
+ *   sino[a][j] = sum_i bilinear(img, x = c xj - s yi + cx, y = s xj + c yi + cy),
+ * taps outside the image reading zero (a sample up to one pixel outside still interpolates against the border).
+ * A side of 1 has no reference behaviour (kornia divides by W - 1 and H - 1); here the formula as written holds there.
+ * H, W or nangles < 1 or a NULL pointer: WIRE_ERR_ARG before any HIP call.                                   */
 int wire_radon_fwd(void* stream, const float* img, const float* angles_deg, int H, int W, int nangles, float* sino);
 int wire_radon_bwd(void* stream, const float* g_sino, const float* angles_deg, int H, int W, int nangles,
                    float* g_img);
-/* torch.sigmoid of the dense occupancy query before the cube is written (modules/volutils.py:128-131)       */
+/* torch.sigmoid of the dense occupancy query before the cube is written (modules/volutils.py:128-131), in place.
+ * NaN stays NaN; +inf and every x >= 17 give exactly 1, -inf exactly 0; below x = -87.33 the true value is denormal
+ * and the result lies in [0, 2^-126]; elsewhere the relative error is <= 2^-21.  count < 0, or count > 0 with x NULL:
+ * WIRE_ERR_ARG before any HIP call; count == 0 returns WIRE_OK.                                                  */
 int wire_sigmoid_inplace(void* stream, float* x, int64_t count);
 
 /* ---- ComplexGaborLayer2D (modules/wire2d.py:21-67) on native tensors ---------------------
@@ -648,7 +681,8 @@ int wire_gabor2d_bwd_first_coords(void* stream, const void* g_act, const float* 
                                   float* g_V, float* g_c, void* ws, int64_t ws_bytes);
 
 /* trainable omega_0 / scale_0 of ComplexGaborLayer2D (modules/wire2d.py:42-43 with trainable=True):
- * out2 (device, 2 floats) = { dL/d omega_0, dL/d scale_0 }; operands and workspace as wire_gabor2d_bwd. */
+ * out2 (device, 2 floats) = { dL/d omega_0, dL/d scale_0 }; operands and workspace as wire_gabor2d_bwd.  Summation
+ * and refusals as wire_gabor_hparam_grad (V and c must not be NULL; ws: wire_layer2d_ws_bytes).              */
 int wire_gabor2d_hparam_grad(void* stream, const void* g_act, const void* x, const void* W, const void* b,
                              const void* V, const void* c, float omega0, float scale0, int64_t n, int in_features,
                              int out_features, int is_first, float* out2, void* ws, int64_t ws_bytes);
@@ -698,6 +732,10 @@ int wire_blocked_width(int K);   /* P = roundup(2K, 64) */
  * hidden layer either (r = c lin in their place); with split_out the inner hidden layers 1 .. hidden_layers - 1 hold fp16
  * pairs, see the knob -- set these knobs to 0 to read the activations.) */
 int64_t wire_act_out_offset(const wire_net_desc* d, int64_t n, int layer);
+/* complex64 [n][K] (interleaved) <-> the blocked-planar rows [n][wire_blocked_width(K)] described at the top of this
+ * file.  wire_c64_to_blocked writes EVERY float of dst, the pad columns with +0.0; wire_blocked_to_c64 does not read the
+ * pads.  Pure copies: bit-exact both ways.  n < 0, K < 1 or a NULL pointer: WIRE_ERR_ARG before any HIP call; n == 0
+ * returns WIRE_OK and touches nothing.                                                                            */
 int wire_c64_to_blocked(void* stream, const void* src, int64_t n, int K, float* dst);
 int wire_blocked_to_c64(void* stream, const float* src, int64_t n, int K, void* dst);
 

@@ -54,6 +54,7 @@ WIRE_DEVINL void blk_decode(int col, int& o, int& part) {
 // ---- transcendental kernels ---------------------------------------------
 // exp(a) as exp2 on the hardware unit (v_exp_f32) with the rounding error of
 // a*log2(e) folded back in: ~1-2 ulp for every a the Gabor envelope produces.
+// Domain: finite a up to the overflow point (a <= 88.72); above it and for +-inf the result is NaN (inf * tl + inf), not inf.
 WIRE_DEVINL float wire_exp(float a) {
   const float L2E_HI = 1.44269502e+00f;   // float(log2 e)
   const float L2E_LO = 1.92596299e-08f;   // log2 e - L2E_HI

@@ -664,9 +664,19 @@ hipError_t launch_track_best(hipStream_t s, const float* metric, float* best, in
 }
 
 // torch.sigmoid of the dense occupancy query before the cube is written out (modules/volutils.py:128-131)
+// wire_exp takes finite arguments below its overflow point (wire_dev.h), so it is evaluated on a = -min(|x|, 128) and
+// the result is 1 / (1 + e) or e / (1 + e) by the sign of x; at a = -128 e is 0, which is also the answer for +-inf.
+// Below -64 the argument is shifted by 32 (exact: both are multiples of 2^-17) and e^-32 is multiplied back, so that
+// the hardware exp2, which flushes a denormal result, stays in its normal range and the product rounds into the
+// denormals.  NaN keeps its bits.
 __global__ void sigmoid_kernel(float* __restrict__ x, long long count) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) x[i] = 1.f / (1.f + wire_exp(-x[i]));
+  if (i >= count) return;
+  const float v = x[i];
+  if (v != v) return;
+  const float a = -fminf(fabsf(v), 128.f);
+  const float e = a < -64.f ? wire_exp(a + 32.f) * 1.2664165549e-14f : wire_exp(a);
+  x[i] = v >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
 }
 hipError_t launch_sigmoid(hipStream_t s, float* x, int64_t count) {
   if (count <= 0) return hipSuccess;
