@@ -651,6 +651,23 @@ int wire_track_best(void* stream, const float* metric, float* best_metric, int f
 int wire_radon_fwd(void* stream, const float* img, const float* angles_deg, int H, int W, int nangles, float* sino);
 int wire_radon_bwd(void* stream, const float* g_sino, const float* angles_deg, int H, int W, int nangles,
                    float* g_img);
+/* The volume form of the CT operator (lin_inverse.radon(imten, angles, is_3d=True), modules/lin_inverse.py:19-40), on
+ * CHANNEL-LAST data: vol [H][W][C] -> sino [nangles][W][C], the channel -- the slice of the volume -- innermost, which
+ * is how the rows of a 3-D grid, (i W + j) T + k, already hold a network's output.  Channel c is wire_radon_fwd on
+ * slice c, in the same arithmetic with the rows added in ascending i: wire_radon_vol_fwd gives, channel by channel,
+ * the BITS of wire_radon_fwd on that slice (C = 1: of wire_radon_fwd).  wire_radon_vol_bwd is the adjoint,
+ * g_sino [nangles][W][C] -> g_vol [H][W][C], as a gather: every element of g_vol is written exactly once (no memset
+ * is needed, and none is made), no atomics, every sum in a fixed order -- the same call gives the same bits.  Its
+ * taps and weights are the forward's, tap for tap: each candidate sample's position is evaluated as the forward
+ * evaluates it, and the forward's floor decides whether the pixel is one of its taps.
+ * H, W, C or nangles < 1, H W or nangles W above 2^31 - 1, more workgroups than one launch takes (forward:
+ * nangles ceil(W C / 256), with C / 4 for C when C % 4 == 0 and both pointers are 16-byte aligned, above 2^31 - 1;
+ * adjoint: C > 64 * 65535) or a NULL pointer: WIRE_ERR_ARG before any HIP call.  Sides of 1 are ordinary cases;
+ * H W C and nangles W C may pass 2^31.                                                                          */
+int wire_radon_vol_fwd(void* stream, const float* vol, const float* angles_deg, int H, int W, int C, int nangles,
+                       float* sino);
+int wire_radon_vol_bwd(void* stream, const float* g_sino, const float* angles_deg, int H, int W, int C, int nangles,
+                       float* g_vol);
 /* torch.sigmoid of the dense occupancy query before the cube is written (modules/volutils.py:128-131), in place.
  * NaN stays NaN; +inf and every x >= 17 give exactly 1, -inf exactly 0; below x = -87.33 the true value is denormal
  * and the result lies in [0, 2^-126]; elsewhere the relative error is <= 2^-21.  count < 0, or count > 0 with x NULL:

@@ -39,6 +39,7 @@ SYMBOLS = [
     "wire_ssim_bwd_ws_bytes", "wire_ssim_bwd", "wire_ssim_mse_grad_ws_bytes", "wire_ssim_mse_grad",
     "wire_tv_add_grad", "wire_warp_coords_fwd", "wire_warp_coords_bwd_ws_bytes", "wire_warp_coords_bwd",
     "wire_iso_ws_bytes", "wire_iso_count", "wire_iso_emit", "wire_iso_tet_case", "wire_gauss3_blur",
+    "wire_radon_vol_fwd", "wire_radon_vol_bwd",
 ]
 
 
@@ -113,6 +114,8 @@ def _declare(l: C.CDLL) -> None:
     l.wire_act_out_offset.restype = i64
     l.wire_radon_fwd.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     l.wire_radon_bwd.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    l.wire_radon_vol_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    l.wire_radon_vol_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     l.wire_final_fwd.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, i64]
     l.wire_final_bwd.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i64]
     l.wire_coords_from_index.argtypes = [vp, vp, i64, i64, vp, i32, vp, i32, vp, i32, vp]

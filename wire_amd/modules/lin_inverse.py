@@ -3,7 +3,8 @@
 ``radon``: the CT forward operator the WIRE driver uses (wire_ct.py:128-133).  The reference rotates the image once
 per angle with ``kornia.geometry.rotate`` and sums over the rows; here the rotate-and-sum and its adjoint are one HIP
 kernel each (wire_radon_fwd / wire_radon_bwd), wrapped in an autograd.Function so that ``loss.backward()`` reaches
-the model.
+the model.  ``radon_volume`` is the volume form (the reference's ``is_3d=True``) on slice-last data: one launch each way
+(wire_radon_vol_fwd / wire_radon_vol_bwd), the adjoint a gather without atomics.
 
 ``get_video_coding_frames`` / ``video2codedvideo``: video compressive sensing, the per-pixel coded exposure of Hitomi
 et al. (modules/lin_inverse.py:42-95).  The masks are host numpy with the reference's random draw (the same
@@ -65,6 +66,55 @@ def radon(imten, angles, is_3d=False):
     if is_3d:
         return sino
     return sino.permute(1, 0, 2).squeeze()
+
+
+class _RadonVolumeFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vol, angles):
+        L = _lib.lib()
+        H, W, T = vol.shape
+        x = vol.detach().to(torch.float32).contiguous()
+        ang = angles.detach().to(vol.device, torch.float32).contiguous().reshape(-1)
+        A = ang.numel()
+        out = torch.empty(A, W, T, dtype=torch.float32, device=vol.device)
+        stream = torch.cuda.current_stream(vol.device).cuda_stream
+        _lib.check(L.wire_radon_vol_fwd(stream, x.data_ptr(), ang.data_ptr(), H, W, T, A, out.data_ptr()),
+                   "wire_radon_vol_fwd")
+        ctx.save_for_backward(ang)
+        ctx.args = (H, W, T, A, vol.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        L = _lib.lib()
+        (ang,) = ctx.saved_tensors
+        H, W, T, A, dtype = ctx.args
+        gg = g.detach().to(torch.float32).contiguous()
+        gv = torch.empty(H, W, T, dtype=torch.float32, device=g.device)
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        _lib.check(L.wire_radon_vol_bwd(stream, gg.data_ptr(), ang.data_ptr(), H, W, T, A, gv.data_ptr()),
+                   "wire_radon_vol_bwd")
+        return gv.to(dtype), None
+
+
+def radon_volume(vol, angles):
+    """The Radon transform of every slice of a volume stored slice-last (ours; the layout of a 3-D grid's rows).
+
+    vol: (H, W, T) tensor on the MI355X, slice k being ``vol[:, :, k]``; angles: (nangles) degrees.  Returns the
+    (nangles, W, T) float32 stack of sinograms.  In the reference's layout this is
+
+        radon(v.permute(2, 0, 1)[None], angles, is_3d=True).permute(1, 2, 0)
+
+    bit for bit, as one launch over contiguous memory (wire_radon_vol_fwd) instead of one per slice and two transposes.
+    The backward is the gather adjoint (wire_radon_vol_bwd): no atomics, the same bits on every call, which ``radon``'s
+    scatter does not give.  The gradient flows to ``vol`` only."""
+    if not isinstance(vol, torch.Tensor) or vol.dim() != 3 or min(vol.shape) < 1:
+        raise ValueError("radon_volume expects vol of shape (H, W, T)")
+    if not isinstance(angles, torch.Tensor) or angles.numel() < 1:
+        raise ValueError("radon_volume expects at least one angle")
+    if not vol.is_cuda:
+        raise _lib.WireHipError("radon_volume: tensors must be on the MI355X ('cuda'); wire_amd has no CPU path")
+    return _RadonVolumeFunction.apply(vol, angles)
 
 
 def get_video_coding_frames(video_size, nframes):

@@ -76,7 +76,7 @@ class FusedTrainer:
     ``model.parameters()`` there and keep their initial values, though their gradients are computed and present in
     ``flat_grad`` -- and a sequence steps stage s and head s with ``lr[s]`` (times the schedule's factor).  A sequence
     for any other kind, or of the wrong length, is a ValueError.  ``step_downsampled``, ``step_tv``, ``step_radon``,
-    ``step_frames`` and ``step_coded`` work for bspline_mscale_hier as for the other kinds.
+    ``step_frames``, ``step_coded`` and ``step_radon_volume`` work for bspline_mscale_hier as for the other kinds.
 
     ``target`` is the [npoints, O] signal of ``step`` / ``step_hashed`` and the default ``gt`` of the metrics.  The
     operator steps bring their own data, so a trainer that only runs those may pass ``target=None``; ``step``,
@@ -472,25 +472,30 @@ class FusedTrainer:
         return slots[key]
 
     def _fwd_loss_bwd(self, stream, coords_ptr: int, n: int, loss, g: torch.Tensor, gp, prior=None,
-                      coords_grad: bool = False) -> torch.Tensor:
+                      coords_grad: bool = False, gy_ptr: Optional[int] = None) -> torch.Tensor:
         """Forward of the ``n`` rows at ``coords_ptr`` into ``self.y``, ``loss(stream, g)``, the TV prior
         ``(H, W, T, lam_s, lam_t)`` on top of it when one of its weights is nonzero, and the backward into the
         gradient buffer ``g`` (``gp``: its pointer array; ``coords_grad``: also dL/dcoords into ``self.g_coords``).
+        ``loss=None`` with ``gy_ptr``: the rows' dL/dy exists already, at that address (a range of a full-grid buffer),
+        and the backward reads it there instead of ``self.gy``.
         Returns the view that holds the step's loss: ``tv_parts[0:1]`` with a prior, else the slot behind ``g``."""
         L, d = self.L, C.byref(self.desc)
         _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), coords_ptr, n, self.y.data_ptr(),
                                   self.act.data_ptr(), self.act_bytes, 1), "fwd")
-        loss(stream, g)
+        if loss is not None:
+            loss(stream, g)
+        if gy_ptr is None:
+            gy_ptr = self.gy.data_ptr()
         slot, src = self._loss_slot(g)
         if prior is not None and (prior[3] != 0.0 or prior[4] != 0.0):
             self._tv_add_grad(stream, *prior, slot)
             src = self.tv_parts[0:1]
         if coords_grad:
-            _lib.check(L.wire_mlp_bwd_coords(stream, d, self.packed.data_ptr(), coords_ptr, n, self.gy.data_ptr(),
+            _lib.check(L.wire_mlp_bwd_coords(stream, d, self.packed.data_ptr(), coords_ptr, n, gy_ptr,
                                              self.act.data_ptr(), self.act_bytes, self.coords_scratch.data_ptr(),
                                              self.coords_scr_bytes, gp, self.g_coords.data_ptr()), "bwd_coords")
         else:
-            _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), coords_ptr, n, self.gy.data_ptr(),
+            _lib.check(L.wire_mlp_bwd(stream, d, self.packed.data_ptr(), coords_ptr, n, gy_ptr,
                                       self.act.data_ptr(), self.act_bytes, self.scratch.data_ptr(), self.scr_bytes, gp),
                        "bwd")
         return src
@@ -516,8 +521,8 @@ class FusedTrainer:
 
     # ---- argument checks: they read grid, world, O, tz and target alone, and come before the first device access
     def _need_grid(self, what: str, rank: int = 2, one_output: bool = False, single_process: bool = True) -> None:
-        needs = "a 3-D grid (H, W, T)" if rank == 3 else "a 2-D grid and out_features == 1" if one_output \
-            else "a 2-D grid"
+        needs = ("a 3-D grid (H, W, T)" if rank == 3 else "a 2-D grid") + \
+            (" and out_features == 1" if one_output else "")
         if (self.tz is None) == (rank == 3) or len(self.grid) != rank or (one_output and self.O != 1):
             raise ValueError(f"{what} needs {needs}")
         if single_process and self.world != 1:
@@ -576,13 +581,15 @@ class FusedTrainer:
             raise ValueError(f"{name} must be finite, not {lam}")
         return lam
 
-    def _tv_add_grad(self, stream, H: int, W: int, T: int, lam_s: float, lam_t: float, data_loss: int) -> None:
+    def _tv_add_grad(self, stream, H: int, W: int, T: int, lam_s: float, lam_t: float, data_loss: int,
+                     y: Optional[torch.Tensor] = None, gy: Optional[torch.Tensor] = None) -> None:
         """The TV term of the (H, W, T) grid in ``self.y``, added to the ``self.gy`` the operator's backward has left
         (wire_tv_add_grad); ``self.tv_parts`` receives [loss, data, tv_s, tv_t], data being the device scalar at
-        ``data_loss``."""
+        ``data_loss``.  ``y`` / ``gy``: full-grid buffers that stand in for ``self.y`` / ``self.gy``."""
         tv_parts = self._buf("tv_parts", 4, zero=True)
-        _lib.check(self.L.wire_tv_add_grad(stream, self.y.data_ptr(), H, W, T, self.O, lam_s, lam_t, data_loss,
-                                           self.gy.data_ptr(), tv_parts.data_ptr(), self.partial.data_ptr()),
+        y, gy = self.y if y is None else y, self.gy if gy is None else gy
+        _lib.check(self.L.wire_tv_add_grad(stream, y.data_ptr(), H, W, T, self.O, lam_s, lam_t, data_loss,
+                                           gy.data_ptr(), tv_parts.data_ptr(), self.partial.data_ptr()),
                    "tv_add_grad")
 
     # ------------------------------------------------------------------ super-resolution step
@@ -843,6 +850,100 @@ class FusedTrainer:
             _lib.check(L.wire_radon_bwd(stream, gsino.data_ptr(), th.data_ptr(), H, W, A, self.gy.data_ptr()),
                        "radon_bwd")
         return self._raster_step(loss, prior=(H, W, 1, lam, 0.0))
+
+    # ------------------------------------------------------------------ volume CT step
+    def step_radon_volume(self, sinogram: torch.Tensor, thetas: torch.Tensor, slab: Optional[int] = None,
+                          lambda_tv: float = 0.0, lambda_tv_t: float = 0.0) -> torch.Tensor:
+        """One optimizer step of CT on a volume: the model is evaluated on the WHOLE (H, W, T) grid in row order (row
+        (i*W + j)*T + k), so its output is the volume as [H][W][T] with the slice index innermost;
+        ``lin_inverse.radon_volume`` turns it into the stack of sinograms ([nangles, W, T]: the reference's
+        ``radon(..., is_3d=True)`` with the slice last, wire_radon_vol_fwd), loss = mean squared error against
+        ``sinogram`` (CUDA float32 of nangles * W * T elements in that order); backward through the gather adjoint
+        (wire_radon_vol_bwd) and the network, Adam.  No transpose of the volume is made either way, and unlike
+        ``step_radon`` the step is reproducible: the same call gives the same bits.
+
+        ``slab=None``: one pass, and the volume estimate of the step stays in ``self.y`` ([H*W*T, 1]).  ``slab`` = a
+        number of pixels, 1 <= slab < H*W: the operator mixes all pixels, but it is linear, so dL/dy of the whole volume
+        needs no stored activations.  Pass 1 renders the volume forward-only, slab by slab, into ``self.y_vol``
+        ([H*W*T]); the operator, the loss, the adjoint and the prior run on the full buffers and leave dL/dy of every
+        row; pass 2 walks the pixel ranges [p0, p0 + slab), each a contiguous row range of whole pixels, runs the
+        storing forward and the backward against that range of dL/dy, sums the gradients and runs Adam once.  The
+        activations then hold ``slab * T`` rows instead of ``H*W*T``, at the price of ONE EXTRA FORWARD and of 8 bytes
+        per row for the two full buffers; the full volume of the step is in ``self.y_vol``, and ``self.y`` holds the
+        last slab only.  ``slab >= H*W`` is the one-pass path.
+
+        ``lambda_tv`` / ``lambda_tv_t`` != 0 add ``step_coded``'s prior, ``lambda_tv * tv_s + lambda_tv_t * tv_t`` of
+        the (H, W, T) volume (wire_tv_add_grad, between the adjoint and the backward); the full volume and the full
+        dL/dy exist on both paths, so the prior works with slabs too.  The returned loss is the total and
+        ``self.tv_parts`` holds [loss, mse, tv_s, tv_t].  With both 0.0 that kernel is not launched.
+        3-D grids, one output feature, single process."""
+        self._need_grid("step_radon_volume", rank=3, one_output=True)
+        H, W, T = (int(v) for v in self.grid)
+        NP, n = H * W, H * W * T
+        lam_s, lam_t = self._tv_weight("lambda_tv", lambda_tv), self._tv_weight("lambda_tv_t", lambda_tv_t)
+        prior = lam_s != 0.0 or lam_t != 0.0
+        per = NP if slab is None else int(slab)
+        if per < 1:
+            raise ValueError(f"slab {per} must be >= 1 pixel")
+        per = min(per, NP)
+        if not isinstance(thetas, torch.Tensor) or thetas.numel() < 1:
+            raise ValueError("thetas must be a tensor of at least one angle (degrees)")
+        A = thetas.numel()
+        tgt = self._f32_elems("sinogram", sinogram, A, W, T)
+        th = thetas.detach().to(self.dev, torch.float32).contiguous()
+        L, d = self.L, C.byref(self.desc)
+        sino, gsino = self._buf("_vsino", A * W * T), self._buf("_gvsino", A * W * T)
+        stream = self._stream()
+        self._reserve(per * T)
+        g0 = self.gbuf[0]
+
+        def operator(y: torch.Tensor, gy: torch.Tensor):
+            """y -> sinograms -> loss (behind g0) and its gradient -> dL/dy into gy, all on the full grid."""
+            def loss(stream, g):
+                _lib.check(L.wire_radon_vol_fwd(stream, y.data_ptr(), th.data_ptr(), H, W, T, A, sino.data_ptr()),
+                           "radon_vol_fwd")
+                _lib.check(L.wire_mse_grad(stream, sino.data_ptr(), tgt.data_ptr(), None, 0, A * W * T, 1, 1.0,
+                                           gsino.data_ptr(), self._loss_slot(g)[0], None, self.partial.data_ptr()),
+                           "mse_grad")
+                _lib.check(L.wire_radon_vol_bwd(stream, gsino.data_ptr(), th.data_ptr(), H, W, T, A, gy.data_ptr()),
+                           "radon_vol_bwd")
+            return loss
+
+        self._pack(stream)
+        if per == NP:
+            self._grid_coords(stream, 0, n, self.coords)
+            src = self._fwd_loss_bwd(stream, self.coords.data_ptr(), n, operator(self.y, self.gy), g0,
+                                     self.grad_ptrs[0], (H, W, T, lam_s, lam_t))
+            return self._finish(stream, g0, src)
+        rows = per * T
+        yv, gv = self._buf("y_vol", n, exact=True), self._buf("_gy_vol", n, exact=True)
+        # pass 1: the volume, forward-only (no stored activations: the step's act buffer is more than that takes)
+        ab = _lib.check(L.wire_act_bytes(d, rows, 0))
+        act = self.act if ab <= self.act_bytes else self._buf("_act_fwd", ab, torch.uint8)
+        for r0 in range(0, n, rows):
+            nr = min(rows, n - r0)
+            self._grid_coords(stream, r0, nr, self.coords)
+            _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), self.coords.data_ptr(), nr,
+                                      yv.data_ptr() + 4 * r0, act.data_ptr(), act.numel(), 0), "fwd")
+        operator(yv, gv)(stream, g0)
+        slot, src = self._loss_slot(g0)
+        if prior:
+            self._tv_add_grad(stream, H, W, T, lam_s, lam_t, slot, yv, gv)
+            src = self.tv_parts[0:1]
+        # pass 2: storing forward and backward, slab by slab, against dL/dy of the slab's rows
+        if getattr(self, "_gslab_ptrs", None) is None:
+            # wire_mlp_bwd overwrites its gradients: the slabs after the first write here and are added to gbuf[0]
+            gs = self._buf("_gslab", self.count + 1, zero=True)
+            self._gslab_ptrs = _lib.ptr_array([gs.data_ptr() + 4 * o for o in self.offsets])
+        for r0 in range(0, n, rows):
+            nr = min(rows, n - r0)
+            g, gp = (g0, self.grad_ptrs[0]) if r0 == 0 else (self._gslab, self._gslab_ptrs)
+            self._grid_coords(stream, r0, nr, self.coords)
+            self._fwd_loss_bwd(stream, self.coords.data_ptr(), nr, None, g, gp, gy_ptr=gv.data_ptr() + 4 * r0)
+            if r0 > 0:
+                # (the gradients alone: the float behind them is the loss slot, which step_coded's slabs use)
+                g0[:self.count].add_(g[:self.count])
+        return self._finish(stream, g0, src)
 
     # ------------------------------------------------------------------ video compressive-sensing step
     def step_coded(self, coded: torch.Tensor, masks, nframes: int, dup_last: bool = True,
