@@ -1,14 +1,19 @@
-// wire_layer_api.hip -- per-layer entry points of the C ABI:
-// ComplexGaborLayer.forward / its backward and the final complex Linear + .real
-// on native (interleaved complex64) tensors.  These serve `model.net[i](x)`
-// (reference modules/utils.py:246-252) and standalone layers; the training hot
-// path is wire_mlp_fwd / wire_mlp_bwd, which never leaves the blocked layout.
-// The backward recomputes the layer's forward from x (one extra GEMM) instead
-// of asking the caller to keep lin/act in a private layout.
+// wire_layer_api.hip -- per-layer entry points of the C ABI: one layer's forward / backward on native tensors
+// (interleaved complex64, or fp32 for the real kinds and a first layer's coordinates), and the final complex
+// Linear + .real.  These serve `model.net[i](x)` (reference modules/utils.py:246-252) and standalone layers; the
+// training hot path is wire_mlp_fwd / wire_mlp_bwd, which never leaves the blocked layout.  The backward recomputes
+// the layer's forward from x (one extra GEMM) instead of asking the caller to keep lin/act in a private layout.
+//
+// The file has no kernel and says each thing once:
+//   layer_ws       the one workspace table, plain or 2-D
+//   LayerGemm      one layer's GEMMs on the selected family, over that table
+//   FORMS          what ComplexGaborLayer, ComplexGaborLayer2D and the real layers differ in -- the place to extend
+//   Layer          a call: form, shape, arguments and workspace; Layer::open is the preamble every entry point shares
+//   layer_forward / layer_bwd / layer_bwd_first / layer_hparam   the four routines, driven by the form
+// An extern "C" function is its own argument test (host tests pin every refusal) and a call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 
 #include "wire_plan.h"
 
@@ -17,13 +22,15 @@
 // The per-layer entry points run the SAME kernels as wire_mlp_fwd / wire_mlp_bwd, so the per-layer parity
 // tests (protocol step (i)) check the code the bench times.
 
+#define LCHK(expr)                                                   \
+  do {                                                               \
+    hipError_t e_ = (expr);                                          \
+    if (e_ != hipSuccess) return wire_fail_(WIRE_ERR_HIP, hipGetErrorString(e_)); \
+  } while (0)
+
 namespace {
 inline int64_t rup64(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-struct LayerWs {
-  int Pin, Pout, S;
-  int64_t xb, lin, out, gact, glin, gxb, gu, btf, btd, bias, slab, bslab, fpw, fpb, crp, wf, bfr, btf_x3, btd_x3, x2, total;
-};
 // 2 x fp16 family in the per-layer entry points (split_f16, batches the 16 x 16 x 32 kernels take): a region of the
 // workspace holds 4 maximum-slot sets (A operand, weights, G, Z) and the two split weight images.  The operand maxima of
 // the fused path come from the producers' epilogues; here the tensors arrive from the caller, so one reduction pass
@@ -38,72 +45,109 @@ inline int layer_splits(int fam, int64_t n, int Pout, int Pin) {
   if (fam == FAM_3M) return gemm3m_tn_splits(n, Pout / 2, Pin / 2, 64);
   return gemm_tn_splits(n, Pout, Pin, 64);
 }
-LayerWs layer_ws(int64_t n, int in, int out) {
+
+// The workspace of a layer call, in floats from its base.  Pin / Pout are the complex sizing (a real layer's narrower
+// rows fit it); Ng is the GEMM's width: Pout, or 2 Pout where the 2-D Gabor layer runs both its Linears as one GEMM
+// (lin | sy).  lin / glin rows are Ng wide, gu rows Ng / 2, out / gact rows Pout; fpw / fpb / wf / bfr belong to the final
+// layer and are empty in the 2-D table.
+struct LayerWs {
+  int Pin, Pout, Ng;
+  int64_t xb, lin, out, gact, glin, gxb, gu, btf, btd, bias, slab, bslab, fpw, fpb, crp, wf, bfr, btf_x3, btd_x3, x2, total;
+};
+LayerWs layer_ws(int64_t n, int in, int out, bool two) {
   LayerWs w{};
   w.Pin = rup(2 * in, 64);
   w.Pout = rup(2 * out, 64);
+  w.Ng = two ? 2 * w.Pout : w.Pout;
   const int Pmax = w.Pin > w.Pout ? w.Pin : w.Pout;
-  w.S = layer_splits(FAM_4M, n, w.Pout, w.Pin);
-  // weight-gradient slabs: room for every family, for the complex sizing and for the real layers' own
-  // (narrower rows split finer, so neither sizing dominates the other)
+  // weight-gradient slabs.  The two tables size them by different rules, and wire_layer_ws_bytes / wire_layer2d_ws_bytes
+  // are pinned to both (tests/golden/size_queries.json):
+  //   plain: room for every family (4M, 3M with its 3 quarter-size products, 3 x bf16, 2 x fp16), for the complex sizing
+  //          and for the real layers' own (narrower rows split finer, so neither sizing dominates the other)
+  //   2-D:   the larger of the 4M splits and the 3 x bf16 maximum, full-size slabs (the 3M family never runs this layer)
   int64_t slab_f = 0, bslab_f = 0;
-  auto fit = [&](int Pm, int Pn) {
-    for (int fam = FAM_4M; fam <= FAM_X3; ++fam) {
-      int64_t S = fam == FAM_X3 ? gemmx3_tn_splits_max(n, Pm, Pn, 256) : layer_splits(fam, n, Pm, Pn);
-      if (fam == FAM_X3 && gemmx2_tn_splits(n, Pm, Pn, 256) > S) S = gemmx2_tn_splits(n, Pm, Pn, 256);
-      const int64_t sl = fam == FAM_3M ? S * 3 * (Pm / 2) * (Pn / 2) : S * Pm * Pn;
-      if (sl > slab_f) slab_f = sl;
-      if (S * Pm > bslab_f) bslab_f = S * Pm;
-    }
-  };
-  fit(w.Pout, w.Pin);
-  fit(rup(out, 64), rup(in, 64));
+  if (two) {
+    const int64_t s_max = std::max<int64_t>(gemm_tn_splits(n, w.Ng, w.Pin, 64), gemmx3_tn_splits_max(n, w.Ng, w.Pin, 256));
+    slab_f = s_max * w.Ng * w.Pin;
+    bslab_f = s_max * w.Ng;
+  } else {
+    auto fit = [&](int Pm, int Pn) {
+      for (int fam = FAM_4M; fam <= FAM_X3; ++fam) {
+        int64_t S = fam == FAM_X3 ? gemmx3_tn_splits_max(n, Pm, Pn, 256) : layer_splits(fam, n, Pm, Pn);
+        if (fam == FAM_X3 && gemmx2_tn_splits(n, Pm, Pn, 256) > S) S = gemmx2_tn_splits(n, Pm, Pn, 256);
+        const int64_t sl = fam == FAM_3M ? S * 3 * (Pm / 2) * (Pn / 2) : S * Pm * Pn;
+        if (sl > slab_f) slab_f = sl;
+        if (S * Pm > bslab_f) bslab_f = S * Pm;
+      }
+    };
+    fit(w.Pout, w.Pin);
+    fit(rup(out, 64), rup(in, 64));
+  }
+  const int64_t fin = two ? 0 : 1;     // the final layer's regions
   int64_t off = 0;
   auto take = [&](int64_t cnt) { int64_t o = off; off += rup64(cnt, 64); return o; };
   w.xb = take(n * w.Pin);
-  w.lin = take(n * w.Pout);
+  w.lin = take(n * w.Ng);
   w.out = take(n * w.Pout);
   w.gact = take(n * w.Pout);
-  w.glin = take(n * w.Pout);
+  w.glin = take(n * w.Ng);
   w.gxb = take(n * w.Pin);
-  w.gu = take(n * (w.Pout / 2));
-  w.btf = take((int64_t)w.Pout * w.Pin);
-  w.btd = take((int64_t)w.Pout * w.Pin);
-  w.bias = take(w.Pout);
+  w.gu = take(n * (w.Ng / 2));
+  w.btf = take((int64_t)w.Ng * w.Pin);
+  w.btd = take((int64_t)w.Ng * w.Pin);
+  w.bias = take(w.Ng);
   w.slab = take(slab_f);
   w.bslab = take(bslab_f);
-  w.fpw = take((int64_t)prereduce_room(final_bwd_blocks(n)) * 8 * Pmax);
-  w.fpb = take((int64_t)prereduce_room(final_bwd_blocks(n)) * 8);
+  w.fpw = take(fin * prereduce_room(final_bwd_blocks(n)) * 8 * Pmax);
+  w.fpb = take(fin * prereduce_room(final_bwd_blocks(n)) * 8);
   w.crp = take((int64_t)prereduce_room(colreduce_blocks(n)) * (w.Pout / 2) * 5);
-  w.wf = take((int64_t)8 * Pmax);
-  w.bfr = take(64);
-  w.btf_x3 = take(gemmx3_b_image_floats(w.Pout, w.Pin));
-  w.btd_x3 = take(gemmx3_b_image_floats(w.Pin, w.Pout));
-  w.x2 = take(x2_region_floats(w.Pout, w.Pin));
+  w.wf = take(fin * 8 * Pmax);
+  w.bfr = take(fin * 64);
+  w.btf_x3 = take(gemmx3_b_image_floats(w.Ng, w.Pin));
+  w.btd_x3 = take(gemmx3_b_image_floats(w.Pin, w.Ng));
+  w.x2 = take(x2_region_floats(w.Ng, w.Pin));
   w.total = off;
   return w;
 }
 
+// What every launching entry point does after its own argument test: the table, the size test, the stream, the base.
+struct LayerCall {
+  LayerWs w;
+  hipStream_t s;
+  float* W_;
+  float* at(int64_t off) const { return W_ + off; }
+  int open(int64_t n, int in, int out, bool two, void* stream, void* ws, int64_t ws_bytes) {
+    w = layer_ws(n, in, out, two);
+    if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
+    s = (hipStream_t)stream;
+    W_ = (float*)ws;
+    return WIRE_OK;
+  }
+};
+
 // One layer's GEMMs on the selected family.  All three take blocked rows (wire_dev.h) and leave the same
-// outputs; they differ in the weight image (pack_*) and in the slab format of the weight gradient.
+// outputs; they differ in the weight image (pack_*) and in the slab format of the weight gradient.  The images, the
+// bias and the slabs lie where the call's table says: btf / btd hold the fp32 images of the family, btf_x3 / btd_x3 the
+// split images.
 struct LayerGemm {
   WireFamily fam;
+  const LayerCall* c;
   float* x2ws;       // x2_region_floats(...) of the workspace, or null: never the 2 x fp16 kernels
   bool use_x2(int epi, int64_t n) const {
     return fam == FAM_X3 && x2ws && knob(K_SPLIT_F16) && gemmx3_nt_is_h16(epi, n);
   }
   unsigned* slots(int which) const { return reinterpret_cast<unsigned*>(x2ws) + which * WIRE_AMAX_SLOTS; }
-  // weights: W_ + btf / btd hold the fp32 images of the family, btf_x3 / btd_x3 the split images
-  hipError_t pack(hipStream_t s, int kind, const float* W, const float* b, const float* V, const float* c, int out,
-                  int in, int Pout_g, int Pin, float* btf, float* btd, float* bias, float* btf_x3,
-                  float* btd_x3, float wscale = 1.f) const {
+  hipError_t pack(int kind, const float* W, const float* b, const float* V, const float* cc, int out, int in, int Pout_g,
+                  int Pin, float wscale) const {
+    hipStream_t s = c->s;
+    float *btf = c->at(c->w.btf), *btd = c->at(c->w.btd), *bias = c->at(c->w.bias);
     if (fam == FAM_3M) return launch_pack3m(s, W, b, out, in, Pout_g / 2, Pin / 2, btf, btd, bias);
-    hipError_t e = launch_pack_hidden(s, kind, W, b, V, c, out, in, kind == NK_WIRE2D ? Pout_g / 2 : Pout_g, Pin,
+    hipError_t e = launch_pack_hidden(s, kind, W, b, V, cc, out, in, kind == NK_WIRE2D ? Pout_g / 2 : Pout_g, Pin,
                                       btf, btd, bias, wscale);
     if (e != hipSuccess || fam != FAM_X3) return e;
-    e = launch_x3_split_b(s, btf, Pin, Pout_g, Pin, btf_x3);
+    e = launch_x3_split_b(s, btf, Pin, Pout_g, Pin, c->at(c->w.btf_x3));
     if (e != hipSuccess) return e;
-    e = launch_x3_split_b(s, btd, Pout_g, Pin, Pout_g, btd_x3);
+    e = launch_x3_split_b(s, btd, Pout_g, Pin, Pout_g, c->at(c->w.btd_x3));
     if (e != hipSuccess || !x2ws || !knob(K_SPLIT_F16)) return e;
     // 2 x fp16 images: max |weight| (the transposed image holds the same values), then both scaled splits
     e = hipMemsetAsync(x2ws, 0, 4 * WIRE_AMAX_SLOTS * sizeof(float), s);
@@ -120,8 +164,8 @@ struct LayerGemm {
     return launch_x2_split_b_batch(s, xd, 1, Pout_g, Pin, Pout_g);
   }
   // C[n][Nc] = A[n][Kd] * image^T + epilogue; dgrad = true uses the transposed-conjugate image
-  hipError_t nt(hipStream_t s, int epi, const float* A, int64_t n, int Nc, int Kd, bool dgrad, const float* btf,
-                const float* btd, const float* btf_x3, const float* btd_x3, const GemmEpiParams& ep) const {
+  hipError_t nt(int epi, const float* A, int64_t n, int Nc, int Kd, bool dgrad, const GemmEpiParams& ep) const {
+    hipStream_t s = c->s;
     if (use_x2(epi, n)) {
       // forward: image [Nc = Pout_g][Kd = Pin]; data gradient: the transposed image [Nc = Pin][Kd = Pout_g]
       const int Pout_g = dgrad ? Kd : Nc, Pin = dgrad ? Nc : Kd;
@@ -137,13 +181,16 @@ struct LayerGemm {
       return launch_gemmx2h_nt(s, epi, A, Kd, dgrad ? img_d : img_f, n, Nc, Kd, e2,
                                x2_waits(knob(K_NT_BFIRST) != 0, knob(K_EPI_EARLY) != 0));
     }
-    if (fam == FAM_X3) return launch_gemmx3_nt(s, epi, A, Kd, dgrad ? btd_x3 : btf_x3, n, Nc, Kd, ep);
-    if (fam == FAM_3M) return launch_gemm3m_nt(s, epi, A, Kd, dgrad ? btd : btf, Kd, n, Nc / 2, Kd / 2, ep);
-    return launch_gemm_nt(s, epi, A, Kd, dgrad ? btd : btf, Kd, n, Nc, Kd, ep);
+    if (fam == FAM_X3)
+      return launch_gemmx3_nt(s, epi, A, Kd, c->at(dgrad ? c->w.btd_x3 : c->w.btf_x3), n, Nc, Kd, ep);
+    const float* img = c->at(dgrad ? c->w.btd : c->w.btf);
+    if (fam == FAM_3M) return launch_gemm3m_nt(s, epi, A, Kd, img, Kd, n, Nc / 2, Kd / 2, ep);
+    return launch_gemm_nt(s, epi, A, Kd, img, Kd, n, Nc, Kd, ep);
   }
-  hipError_t tn_reduce(hipStream_t s, int kind, const float* G, const float* Z, int64_t n, int Pm, int Pn, int out,
-                       int in, float* slab, float* bslab, float* gW, float* gb, float* gV, float* gc,
-                       float wscale = 1.f) const {
+  hipError_t tn_reduce(int kind, const float* G, const float* Z, int64_t n, int Pm, int Pn, int out, int in, float* gW,
+                       float* gb, float* gV, float* gc, float wscale) const {
+    hipStream_t s = c->s;
+    float *slab = c->at(c->w.slab), *bslab = c->at(c->w.bslab);
     hipError_t e;
     if (use_x2(EPI_STORE, n) && gemmx2_tn_applies(Pm, Pn)) {
       const int S2 = gemmx2_tn_splits(n, Pm, Pn, 256);
@@ -169,43 +216,169 @@ struct LayerGemm {
     return launch_wgrad_reduce(s, kind, slab, bslab, S, out, in, Pm, Pn, gW, gb, gV, gc, wscale);
   }
 };
-}  // namespace
 
-#define LCHK(expr)                                                   \
-  do {                                                               \
-    hipError_t e_ = (expr);                                          \
-    if (e_ != hipSuccess) return wire_fail_(WIRE_ERR_HIP, hipGetErrorString(e_)); \
-  } while (0)
+// ---------------------------------------------------------------------------
+// The layer forms.  A form is everything in which the routines below differ between
+//   ComplexGaborLayer    (modules/wire.py:88-93)     on complex64 rows, or fp32 coordinates when is_first
+//   ComplexGaborLayer2D  (modules/wire2d.py:21-67)   the same with a second Linear (V, c): both Linears are ONE GEMM
+//                                                    ([n, Pin] x [Pin -> 2 Pout], 128-column groups (lin_re | lin_im | sy_re | sy_im))
+//   the real layers      SineLayer / GaussLayer / ReLULayer / Bsplines_form / Bsplines_cubic .forward (modules/siren.py:48-49,
+//                        gauss.py:27-28, relu.py:28-29, bspline_form.py:38-49, bspline_cubic.py:44-52) on fp32 [n][in] rows
+// The net kind of a call selects its form; the kind itself goes to the pack, the family and the activation table
+// (forward epilogue = epi_fwd(kind)).  A new layer form is a new row here and its entry points' argument tests.
+// ---------------------------------------------------------------------------
+using RowConv = hipError_t (*)(hipStream_t, const float* src, int64_t n, int K, int P, float* dst);
+using PointFn = hipError_t (*)(hipStream_t, int kind, const float* g, const float* lin, const float* out, int64_t n, int P,
+                               float omega, float scale, float* g_lin);
+using FirstPointFn = hipError_t (*)(hipStream_t, const float* g, const float* out, const float* coords, int D,
+                                    const float* W0, const float* b0, const float* V0, const float* c0, int64_t n, int K,
+                                    int P, float omega, float scale, float* g_u, int ldu);
+using HparamFn = hipError_t (*)(hipStream_t, const float* g, const float* lin, const float* out, int64_t n, int K, int P,
+                                int is_first, float scale, float* partial, float* out2);
+struct LayerForm {
+  bool two;                  // (V, c) exist: the 2-D table, a GEMM 2 Pout wide, lin | sy and g_u | g_p side by side
+  int cw;                    // floats of a native element: rows are rup(cw * features, 64) wide in the workspace
+  RowConv rows_in, rows_out; // native rows <-> workspace rows: complex64 <-> blocked, fp32 <-> padded
+  PointFn point;             // g_act -> g_lin of a hidden layer
+  FirstPointFn first_point;  // g_act -> g_u (| g_p) of a first layer on coordinates; null: the form has no is_first
+  HparamFn hparam;           // {dL/d omega_0, dL/d scale_0}; null: the form has none
+};
+enum { FORM_GABOR, FORM_GABOR2D, FORM_REAL };
+const LayerForm FORMS[] = {
+  {false, 2, launch_c64_to_blocked, launch_blocked_to_c64,
+   [](hipStream_t s, int, const float* g, const float* lin, const float* out, int64_t n, int P, float om, float sc,
+      float* gl) { return launch_gabor_bwd_point(s, g, lin, out, n, P, om, sc, gl); },
+   [](hipStream_t s, const float* g, const float* out, const float* x, int D, const float* W0, const float* b0, const float*,
+      const float*, int64_t n, int K, int P, float om, float sc, float* gu, int ldu) {
+     return launch_gabor_bwd_first_point(s, g, out, x, D, W0, b0, n, K, P, om, sc, gu, ldu);
+   },
+   launch_gabor_hparam_grad},
+  {true, 2, launch_c64_to_blocked, launch_blocked_to_c64,
+   [](hipStream_t s, int, const float* g, const float* lin, const float* out, int64_t n, int P, float om, float sc,
+      float* gl) { return launch_gabor2d_bwd_point(s, g, lin, out, n, P, om, sc, gl); },
+   launch_gabor2d_bwd_first_point, launch_gabor2d_hparam_grad},
+  {false, 1, launch_pad_rows, launch_unpad_rows, launch_real_act_bwd_point, nullptr, nullptr},
+};
+inline int form_of(int kind) { return kind == NK_WIRE ? FORM_GABOR : kind == NK_WIRE2D ? FORM_GABOR2D : FORM_REAL; }
 
-extern "C" int64_t wire_layer_ws_bytes(int64_t n, int in_features, int out_features) {
-  if (n < 0 || in_features < 1 || out_features < 1) return wire_fail_(WIRE_ERR_ARG, "bad layer shape");
-  return layer_ws(n, in_features, out_features).total * 4 + 256;
-}
+// One call of a layer: the form, the shape the kernels see, the arguments and the workspace.
+struct Layer : LayerCall {
+  const LayerForm* f;
+  int kind, in, out, is_first;
+  int64_t n;
+  int Pin, Pout, Ng;                  // row widths of this form (a real layer's are narrower than the table's); GEMM width
+  const float *x, *W, *b, *V, *c;     // V, c: null unless f->two
+  float omega, scale, wscale;         // scale, wscale: kind_scale's pair (wire_kinds.h) -- s W in both images, the bias as
+                                      // it is, g_W multiplied by wscale on the way out; (scale_0, 1) for the Gabor layers
+  LayerGemm g;
+  float *xb, *lin, *act, *gact, *glin, *gxb, *gu;
 
-// forward into the workspace (lin, out blocked).  Shared by fwd and bwd.
-static int layer_forward_ws(hipStream_t s, const LayerWs& w, float* W_, const void* x, const void* Wt,
-                            const void* b, float omega0, float scale0, int64_t n, int in, int out,
-                            int is_first, bool want_lin = false) {
-  if (is_first) {
-    if (in > 4) return wire_fail_(WIRE_ERR_ARG, "is_first layers support in_features <= 4");
-    // u = x W0^T + b0 is real: [n][Pout / 2] rows in W_ + w.lin when asked for
-    LCHK(launch_first_fwd(s, NK_WIRE, (const float*)x, n, in, (const float*)Wt, (const float*)b,
-                          nullptr, nullptr, out, w.Pout, omega0, scale0, want_lin ? W_ + w.lin : nullptr,
-                          W_ + w.out));
+  int open(int kind_, void* stream, const void* x_, const void* W_t, const void* b_, const void* V_, const void* c_,
+           float omega0, float scale0, float wscale_, int64_t n_, int in_, int out_, int first, void* ws, int64_t ws_bytes) {
+    f = &FORMS[form_of(kind_)];
+    if (int rc = LayerCall::open(n_, in_, out_, f->two, stream, ws, ws_bytes)) return rc;
+    kind = kind_; in = in_; out = out_; is_first = first; n = n_;
+    Pin = rup(f->cw * in, 64); Pout = rup(f->cw * out, 64); Ng = f->two ? 2 * Pout : Pout;
+    x = (const float*)x_; W = (const float*)W_t; b = (const float*)b_; V = (const float*)V_; c = (const float*)c_;
+    omega = omega0; scale = scale0; wscale = wscale_;
+    // the 2 x fp16 region, or null: a cubic B-spline layer of at most 64 inputs stays on the 3 x bf16 kernels at every row
+    // count.  The 2 x fp16 split drops the l l product (2^-22 of each product); the 2 to 64 products of such a row do not
+    // average that out, and the layer's scale_0 sits in the operand (|s W| is 15 times the other kinds' at the class
+    // default): measured 3.5 times the fp32 error on lin at 2 -> 256, s = 15, 8229 rows, where the whole-net path's first
+    // layer is an fp32 FMA chain.  3 x bf16 carries 24 bits per operand.
+    g = LayerGemm{wire_family_(kind), this, kind == WIRE_KIND_BSPLINE_CUBIC && Pin <= 64 ? nullptr : at(w.x2)};
+    xb = at(w.xb); lin = at(w.lin); act = at(w.out); gact = at(w.gact); glin = at(w.glin); gxb = at(w.gxb); gu = at(w.gu);
     return WIRE_OK;
   }
-  const LayerGemm g{wire_family_(WIRE_KIND_WIRE), W_ + w.x2};
-  LCHK(launch_c64_to_blocked(s, (const float*)x, n, in, w.Pin, W_ + w.xb));
-  LCHK(g.pack(s, NK_WIRE, (const float*)Wt, (const float*)b, nullptr, nullptr, out, in, w.Pout, w.Pin, W_ + w.btf,
-              W_ + w.btd, W_ + w.bias, W_ + w.btf_x3, W_ + w.btd_x3));
+};
+
+// forward into the workspace (lin, act in workspace rows).  Shared by all four routines.
+int layer_forward(const Layer& l, bool want_lin = false) {
+  if (l.is_first) {
+    if (l.in > 4) return wire_fail_(WIRE_ERR_ARG, "is_first layers support in_features <= 4");
+    // u = x W0^T + b0 (| p = x V0^T + c0) is real: [n][Ng / 2] rows in lin when asked for
+    LCHK(launch_first_fwd(l.s, l.kind, l.x, l.n, l.in, l.W, l.b, l.V, l.c, l.out, l.Pout, l.omega, l.scale,
+                          want_lin ? l.lin : nullptr, l.act));
+    return WIRE_OK;
+  }
+  LCHK(l.f->rows_in(l.s, l.x, l.n, l.in, l.Pin, l.xb));
+  LCHK(l.g.pack(l.kind, l.W, l.b, l.V, l.c, l.out, l.in, l.Ng, l.Pin, l.wscale));
   GemmEpiParams ep;
-  ep.bias = W_ + w.bias; ep.o0 = W_ + w.lin; ep.o1 = W_ + w.out; ep.ld0 = w.Pout; ep.ld1 = w.Pout;
-  ep.omega = omega0; ep.scale = scale0; ep.kvalid = out;
-  LCHK(g.nt(s, EPI_GABOR_FWD, W_ + w.xb, n, w.Pout, w.Pin, false, W_ + w.btf, W_ + w.btd, W_ + w.btf_x3,
-            W_ + w.btd_x3, ep));
+  ep.bias = l.at(l.w.bias); ep.o0 = l.lin; ep.o1 = l.act; ep.ld0 = l.Ng; ep.ld1 = l.Pout;
+  ep.omega = l.omega; ep.scale = l.scale; ep.kvalid = l.out;
+  LCHK(l.g.nt(epi_fwd(l.kind), l.xb, l.n, l.Ng, l.Pin, false, ep));
   return WIRE_OK;
 }
 
+// act_out, and the pre-activation `lin` of modules/wire.py:89 when asked for (wire_gabor_fwd alone): native rows like
+// act_out, or float32 [n][out] for is_first
+int layer_fwd(const Layer& l, void* act_out, void* lin_out = nullptr) {
+  if (int rc = layer_forward(l, lin_out != nullptr)) return rc;
+  LCHK(l.f->rows_out(l.s, l.act, l.n, l.out, l.Pout, (float*)act_out));
+  if (lin_out) {
+    if (l.is_first) LCHK(launch_unpad_rows(l.s, l.lin, l.n, l.out, l.Pout / 2, (float*)lin_out));
+    else LCHK(l.f->rows_out(l.s, l.lin, l.n, l.out, l.Pout, (float*)lin_out));
+  }
+  return WIRE_OK;
+}
+
+// first layer on coordinates: g_u (| g_p) = the gradient at the real pre-activations, [n][Ng / 2] rows; the parameter
+// gradients are column reductions of it (g_W null: none), the coordinate gradient g_x [n][in] f32 = g_u W (+ g_p V)
+// (g_x null: none)
+int layer_bwd_first(const Layer& l, const void* g_act, float* g_x, float* g_W, float* g_b, float* g_V, float* g_c) {
+  if (int rc = layer_forward(l)) return rc;
+  LCHK(l.f->rows_in(l.s, (const float*)g_act, l.n, l.out, l.Pout, l.gact));
+  const int ldu = l.Pout / 2, ldg = l.Ng / 2;
+  LCHK(l.f->first_point(l.s, l.gact, l.act, l.x, l.in, l.W, l.b, l.V, l.c, l.n, l.out, l.Pout, l.omega, l.scale, l.gu, ldu));
+  if (g_W) {
+    LCHK(launch_colreduce(l.s, l.gu, ldg, l.out, l.x, l.in, l.n, l.at(l.w.crp), g_W, g_b));
+    if (l.f->two) LCHK(launch_colreduce(l.s, l.gu + ldu, ldg, l.out, l.x, l.in, l.n, l.at(l.w.crp), g_V, g_c));
+  }
+  if (g_x) LCHK(launch_coordgrad_rows(l.s, l.gu, ldg, l.f->two ? l.gu + ldu : nullptr, l.W, l.V, l.out, l.in, l.n, g_x));
+  return WIRE_OK;
+}
+
+// forward, g_act -> g_lin, the data-gradient GEMM when g_x is given, the weight-gradient GEMM and its reduction
+int layer_bwd(const Layer& l, const void* g_act, void* g_x, void* g_W, void* g_b, void* g_V, void* g_c) {
+  if (l.is_first) return layer_bwd_first(l, g_act, nullptr, (float*)g_W, (float*)g_b, (float*)g_V, (float*)g_c);
+  if (int rc = layer_forward(l)) return rc;
+  LCHK(l.f->rows_in(l.s, (const float*)g_act, l.n, l.out, l.Pout, l.gact));
+  LCHK(l.f->point(l.s, l.kind, l.gact, l.lin, l.act, l.n, l.Pout, l.omega, l.scale, l.glin));
+  if (g_x) {
+    GemmEpiParams ep; ep.o0 = l.gxb; ep.ld0 = l.Pin; ep.ld1 = l.Pin;
+    LCHK(l.g.nt(EPI_STORE, l.glin, l.n, l.Pin, l.Ng, true, ep));
+    LCHK(l.f->rows_out(l.s, l.gxb, l.n, l.in, l.Pin, (float*)g_x));
+  }
+  LCHK(l.g.tn_reduce(l.kind, l.glin, l.xb, l.n, l.Ng, l.Pin, l.out, l.in, (float*)g_W, (float*)g_b, (float*)g_V,
+                     (float*)g_c, l.wscale));
+  return WIRE_OK;
+}
+
+// trainable omega_0 / scale_0 (ComplexGaborLayer(trainable=True), modules/wire.py:80-81; ComplexGaborLayer2D,
+// modules/wire2d.py:42-43): out2 = {dL/d omega_0, dL/d scale_0} (device).  Recomputes the layer's forward from x, like
+// layer_bwd.  Partial sums live in the (unused here) g_lin region: 2 * ceil(n / 32) floats <= n * Pout
+int layer_hparam(const Layer& l, const void* g_act, float* out2) {
+  if (int rc = layer_forward(l, true)) return rc;
+  LCHK(l.f->rows_in(l.s, (const float*)g_act, l.n, l.out, l.Pout, l.gact));
+  LCHK(l.f->hparam(l.s, l.gact, l.lin, l.act, l.n, l.out, l.Pout, l.is_first, l.scale, l.glin, out2));
+  return WIRE_OK;
+}
+}  // namespace
+
+static int64_t ws_bytes_of(int64_t n, int in, int out, bool two) {
+  if (n < 0 || in < 1 || out < 1) return wire_fail_(WIRE_ERR_ARG, "bad layer shape");
+  return layer_ws(n, in, out, two).total * 4 + 256;
+}
+extern "C" int64_t wire_layer_ws_bytes(int64_t n, int in_features, int out_features) {
+  return ws_bytes_of(n, in_features, out_features, false);
+}
+extern "C" int64_t wire_layer2d_ws_bytes(int64_t n, int in_features, int out_features) {
+  return ws_bytes_of(n, in_features, out_features, true);
+}
+
+// ---------------------------------------------------------------------------
+// ComplexGaborLayer
+// ---------------------------------------------------------------------------
 extern "C" int wire_gabor_fwd(void* stream, const void* x, const void* W, const void* b,
                               float omega0, float scale0, int64_t n, int in_features,
                               int out_features, int is_first, void* lin_out, void* act_out,
@@ -213,20 +386,11 @@ extern "C" int wire_gabor_fwd(void* stream, const void* x, const void* W, const 
   if (n < 0 || in_features < 1 || out_features < 1 || !x || !W || !b || !act_out || !ws)
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_gabor_fwd");
   if (n == 0) return WIRE_OK;
-  const LayerWs w = layer_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  if (int rc = layer_forward_ws(s, w, W_, x, W, b, omega0, scale0, n, in_features, out_features, is_first,
-                                lin_out != nullptr))
+  Layer l;
+  if (int rc = l.open(WIRE_KIND_WIRE, stream, x, W, b, nullptr, nullptr, omega0, scale0, 1.f, n, in_features,
+                      out_features, is_first, ws, ws_bytes))
     return rc;
-  LCHK(launch_blocked_to_c64(s, W_ + w.out, n, out_features, w.Pout, (float*)act_out));
-  if (lin_out) {
-    // the pre-activation `lin` of modules/wire.py:89: complex64 [n][out], or float32 [n][out] for is_first
-    if (is_first) LCHK(launch_unpad_rows(s, W_ + w.lin, n, out_features, w.Pout / 2, (float*)lin_out));
-    else LCHK(launch_blocked_to_c64(s, W_ + w.lin, n, out_features, w.Pout, (float*)lin_out));
-  }
-  return WIRE_OK;
+  return layer_fwd(l, act_out, lin_out);
 }
 
 extern "C" int wire_gabor_bwd(void* stream, const void* g_act, const void* x, const void* W,
@@ -235,34 +399,11 @@ extern "C" int wire_gabor_bwd(void* stream, const void* g_act, const void* x, co
                               void* g_W, void* g_b, void* ws, int64_t ws_bytes) {
   if (n <= 0 || in_features < 1 || out_features < 1 || !g_act || !x || !W || !b || !g_W || !g_b || !ws)
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_gabor_bwd");
-  const LayerWs w = layer_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  if (int rc = layer_forward_ws(s, w, W_, x, W, b, omega0, scale0, n, in_features, out_features, is_first))
+  Layer l;
+  if (int rc = l.open(WIRE_KIND_WIRE, stream, x, W, b, nullptr, nullptr, omega0, scale0, 1.f, n, in_features,
+                      out_features, is_first, ws, ws_bytes))
     return rc;
-  LCHK(launch_c64_to_blocked(s, (const float*)g_act, n, out_features, w.Pout, W_ + w.gact));
-  if (is_first) {
-    const int ldu = w.Pout / 2;
-    LCHK(launch_gabor_bwd_first_point(s, W_ + w.gact, W_ + w.out, (const float*)x, in_features,
-                                      (const float*)W, (const float*)b, n, out_features, w.Pout,
-                                      omega0, scale0, W_ + w.gu, ldu));
-    LCHK(launch_colreduce(s, W_ + w.gu, ldu, out_features, (const float*)x, in_features, n,
-                          W_ + w.crp, (float*)g_W, (float*)g_b));
-    return WIRE_OK;
-  }
-  LCHK(launch_gabor_bwd_point(s, W_ + w.gact, W_ + w.lin, W_ + w.out, n, w.Pout, omega0, scale0,
-                              W_ + w.glin));
-  const LayerGemm g{wire_family_(WIRE_KIND_WIRE), W_ + w.x2};
-  if (g_x) {
-    GemmEpiParams ep; ep.o0 = W_ + w.gxb; ep.ld0 = w.Pin; ep.ld1 = w.Pin;
-    LCHK(g.nt(s, EPI_STORE, W_ + w.glin, n, w.Pin, w.Pout, true, W_ + w.btf, W_ + w.btd, W_ + w.btf_x3,
-              W_ + w.btd_x3, ep));
-    LCHK(launch_blocked_to_c64(s, W_ + w.gxb, n, in_features, w.Pin, (float*)g_x));
-  }
-  LCHK(g.tn_reduce(s, NK_WIRE, W_ + w.glin, W_ + w.xb, n, w.Pout, w.Pin, out_features, in_features, W_ + w.slab,
-                   W_ + w.bslab, (float*)g_W, (float*)g_b, nullptr, nullptr));
-  return WIRE_OK;
+  return layer_bwd(l, g_act, g_x, g_W, g_b, nullptr, nullptr);
 }
 
 // first layer with the coordinate gradient: g_x [n][in] f32 = g_u W (coordgrad_rows over the g_u the backward forms
@@ -273,40 +414,28 @@ extern "C" int wire_gabor_bwd_first_coords(void* stream, const void* g_act, cons
   if (n <= 0 || in_features < 1 || in_features > 4 || out_features < 1 || !g_act || !x || !W || !b || !g_x || !ws ||
       (!g_W) != (!g_b))
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_gabor_bwd_first_coords");
-  const LayerWs w = layer_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  if (int rc = layer_forward_ws(s, w, W_, x, W, b, omega0, scale0, n, in_features, out_features, 1)) return rc;
-  LCHK(launch_c64_to_blocked(s, (const float*)g_act, n, out_features, w.Pout, W_ + w.gact));
-  const int ldu = w.Pout / 2;
-  LCHK(launch_gabor_bwd_first_point(s, W_ + w.gact, W_ + w.out, x, in_features, W, b, n, out_features, w.Pout,
-                                    omega0, scale0, W_ + w.gu, ldu));
-  if (g_W) LCHK(launch_colreduce(s, W_ + w.gu, ldu, out_features, x, in_features, n, W_ + w.crp, g_W, g_b));
-  LCHK(launch_coordgrad_rows(s, W_ + w.gu, ldu, nullptr, W, nullptr, out_features, in_features, n, g_x));
-  return WIRE_OK;
+  Layer l;
+  if (int rc = l.open(WIRE_KIND_WIRE, stream, x, W, b, nullptr, nullptr, omega0, scale0, 1.f, n, in_features,
+                      out_features, 1, ws, ws_bytes))
+    return rc;
+  return layer_bwd_first(l, g_act, g_x, g_W, g_b, nullptr, nullptr);
 }
 
-// trainable omega_0 / scale_0 (ComplexGaborLayer(trainable=True), modules/wire.py:80-81): out2 = {dL/d omega_0,
-// dL/d scale_0} (device).  Recomputes the layer's forward from x, like wire_gabor_bwd.
 extern "C" int wire_gabor_hparam_grad(void* stream, const void* g_act, const void* x, const void* W, const void* b,
                                       float omega0, float scale0, int64_t n, int in_features, int out_features,
                                       int is_first, float* out2, void* ws, int64_t ws_bytes) {
   if (n <= 0 || in_features < 1 || out_features < 1 || !g_act || !x || !W || !b || !out2 || !ws)
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_gabor_hparam_grad");
-  const LayerWs w = layer_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  if (int rc = layer_forward_ws(s, w, W_, x, W, b, omega0, scale0, n, in_features, out_features, is_first, true))
+  Layer l;
+  if (int rc = l.open(WIRE_KIND_WIRE, stream, x, W, b, nullptr, nullptr, omega0, scale0, 1.f, n, in_features,
+                      out_features, is_first, ws, ws_bytes))
     return rc;
-  LCHK(launch_c64_to_blocked(s, (const float*)g_act, n, out_features, w.Pout, W_ + w.gact));
-  // partial sums live in the (unused here) g_lin region: 2 * ceil(n / 32) floats <= n * Pout
-  LCHK(launch_gabor_hparam_grad(s, W_ + w.gact, W_ + w.lin, W_ + w.out, n, out_features, w.Pout, is_first, scale0,
-                                W_ + w.glin, out2));
-  return WIRE_OK;
+  return layer_hparam(l, g_act, out2);
 }
 
+// ---------------------------------------------------------------------------
+// the final complex Linear + .real (the plain table's fpw / fpb / wf / bfr regions)
+// ---------------------------------------------------------------------------
 extern "C" int wire_final_fwd(void* stream, const void* z, const void* Wf, const void* bf, int64_t n,
                               int in_features, int out_features, float* y, void* ws,
                               int64_t ws_bytes) {
@@ -317,14 +446,13 @@ extern "C" int wire_final_fwd(void* stream, const void* z, const void* Wf, const
     return fail(WIRE_ERR_ARG, "out_features %d x padded row width %lld > %d (the final layer's weights in 64 KB)",
                 out_features, (long long)rup64(2 * (int64_t)in_features, 64), WIRE_FINAL_MAX_OP);
   if (n == 0) return WIRE_OK;
-  const LayerWs w = layer_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  LCHK(launch_c64_to_blocked(s, (const float*)z, n, in_features, w.Pin, W_ + w.xb));
-  LCHK(launch_pack_final(s, NK_WIRE, (const float*)Wf, (const float*)bf, in_features, w.Pin,
-                         out_features, W_ + w.wf, W_ + w.bfr));
-  LCHK(launch_final_fwd(s, W_ + w.xb, n, w.Pin, out_features, W_ + w.wf, W_ + w.bfr, y));
+  LayerCall c;
+  if (int rc = c.open(n, in_features, out_features, false, stream, ws, ws_bytes)) return rc;
+  const LayerWs& w = c.w;
+  LCHK(launch_c64_to_blocked(c.s, (const float*)z, n, in_features, w.Pin, c.at(w.xb)));
+  LCHK(launch_pack_final(c.s, NK_WIRE, (const float*)Wf, (const float*)bf, in_features, w.Pin,
+                         out_features, c.at(w.wf), c.at(w.bfr)));
+  LCHK(launch_final_fwd(c.s, c.at(w.xb), n, w.Pin, out_features, c.at(w.wf), c.at(w.bfr), y));
   return WIRE_OK;
 }
 
@@ -334,52 +462,24 @@ extern "C" int wire_final_bwd(void* stream, const float* g_y, const void* z, con
   if (n <= 0 || in_features < 1 || out_features < 1 || out_features > 8 || !g_y || !z || !Wf ||
       !g_Wf || !g_bf || !ws)
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_final_bwd");
-  const LayerWs w = layer_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  LCHK(launch_c64_to_blocked(s, (const float*)z, n, in_features, w.Pin, W_ + w.xb));
+  LayerCall c;
+  if (int rc = c.open(n, in_features, out_features, false, stream, ws, ws_bytes)) return rc;
+  const LayerWs& w = c.w;
+  LCHK(launch_c64_to_blocked(c.s, (const float*)z, n, in_features, w.Pin, c.at(w.xb)));
   // bias pointer is irrelevant for the gradient; reuse Wf so the kernel reads valid memory
-  LCHK(launch_pack_final(s, NK_WIRE, (const float*)Wf, (const float*)Wf, in_features, w.Pin,
-                         out_features, W_ + w.wf, W_ + w.bfr));
-  LCHK(launch_final_bwd(s, NK_WIRE, 1, g_y, n, out_features, W_ + w.wf, nullptr, W_ + w.xb,
-                        in_features, w.Pin, 0.f, 0.f, W_ + w.gxb, W_ + w.fpw, W_ + w.fpb));
-  LCHK(launch_final_reduce(s, NK_WIRE, W_ + w.fpw, W_ + w.fpb, final_bwd_blocks(n), out_features,
+  LCHK(launch_pack_final(c.s, NK_WIRE, (const float*)Wf, (const float*)Wf, in_features, w.Pin,
+                         out_features, c.at(w.wf), c.at(w.bfr)));
+  LCHK(launch_final_bwd(c.s, NK_WIRE, 1, g_y, n, out_features, c.at(w.wf), nullptr, c.at(w.xb),
+                        in_features, w.Pin, 0.f, 0.f, c.at(w.gxb), c.at(w.fpw), c.at(w.fpb)));
+  LCHK(launch_final_reduce(c.s, NK_WIRE, c.at(w.fpw), c.at(w.fpb), final_bwd_blocks(n), out_features,
                            in_features, w.Pin, (float*)g_Wf, (float*)g_bf));
-  if (g_z) LCHK(launch_blocked_to_c64(s, W_ + w.gxb, n, in_features, w.Pin, (float*)g_z));
+  if (g_z) LCHK(launch_blocked_to_c64(c.s, c.at(w.gxb), n, in_features, w.Pin, (float*)g_z));
   return WIRE_OK;
 }
 
 // ---------------------------------------------------------------------------
-// real-valued layers: SineLayer / GaussLayer / ReLULayer / Bsplines_form / Bsplines_cubic .forward
-// (modules/siren.py:48-49, gauss.py:27-28, relu.py:28-29, bspline_form.py:38-49, bspline_cubic.py:44-52) on native
-// [n][in] f32 tensors.
+// the real layers (the plain table: its complex sizing is an upper bound of theirs)
 // ---------------------------------------------------------------------------
-// (the kernels' scale and the factor in the packed weights: kind_scale, wire_kinds.h -- wscale: s W in both images, the bias
-// as it is; g_W is multiplied by it on the way out)
-// the 2 x fp16 region of a real layer's workspace, or null: a cubic B-spline layer of at most 64 inputs stays on the
-// 3 x bf16 kernels at every row count.  The 2 x fp16 split drops the l l product (2^-22 of each product); the 2 to 64
-// products of such a row do not average that out, and the layer's scale_0 sits in the operand (|s W| is 15 times the
-// other kinds' at the class default): measured 3.5 times the fp32 error on lin at 2 -> 256, s = 15, 8229 rows, where the
-// whole-net path's first layer is an fp32 FMA chain.  3 x bf16 carries 24 bits per operand.
-static float* real_x2_region(int kind, int Pin, float* x2) {
-  return kind == WIRE_KIND_BSPLINE_CUBIC && Pin <= 64 ? nullptr : x2;
-}
-static int real_forward_ws(hipStream_t s, const LayerWs& w, float* W_, int kind, const void* x, const void* Wt,
-                           const void* b, float omega0, float scale0, float wscale, int64_t n, int in, int out, int Pin,
-                           int Pout) {
-  const LayerGemm g{wire_family_(kind), real_x2_region(kind, Pin, W_ + w.x2)};
-  LCHK(launch_pad_rows(s, (const float*)x, n, in, Pin, W_ + w.xb));
-  LCHK(g.pack(s, kind, (const float*)Wt, (const float*)b, nullptr, nullptr, out, in, Pout, Pin, W_ + w.btf,
-              W_ + w.btd, W_ + w.bias, W_ + w.btf_x3, W_ + w.btd_x3, wscale));
-  GemmEpiParams ep;
-  ep.bias = W_ + w.bias; ep.o0 = W_ + w.lin; ep.o1 = W_ + w.out; ep.ld0 = Pout; ep.ld1 = Pout;
-  ep.omega = omega0; ep.scale = scale0; ep.kvalid = out;
-  LCHK(g.nt(s, epi_fwd(kind), W_ + w.xb, n, Pout, Pin, false, W_ + w.btf, W_ + w.btd, W_ + w.btf_x3,
-            W_ + w.btd_x3, ep));
-  return WIRE_OK;
-}
-
 extern "C" int wire_real_layer_fwd(void* stream, int kind, const float* x, const float* W, const float* b,
                                    float omega0, float scale0, int64_t n, int in_features, int out_features,
                                    float* act_out, void* ws, int64_t ws_bytes) {
@@ -388,15 +488,11 @@ extern "C" int wire_real_layer_fwd(void* stream, int kind, const float* x, const
       !W || !b || !act_out || !ws || !kind_scale(kind, scale0, kscale, wscale))
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_real_layer_fwd");
   if (n == 0) return WIRE_OK;
-  const LayerWs w = layer_ws(n, in_features, out_features);   // complex sizing is an upper bound
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  const int Pin = rup(in_features, 64), Pout = rup(out_features, 64);
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  if (int rc = real_forward_ws(s, w, W_, kind, x, W, b, omega0, kscale, wscale, n, in_features, out_features, Pin, Pout))
+  Layer l;
+  if (int rc = l.open(kind, stream, x, W, b, nullptr, nullptr, omega0, kscale, wscale, n, in_features, out_features, 0,
+                      ws, ws_bytes))
     return rc;
-  LCHK(launch_unpad_rows(s, W_ + w.out, n, out_features, Pout, act_out));
-  return WIRE_OK;
+  return layer_fwd(l, act_out);
 }
 
 extern "C" int wire_real_layer_bwd(void* stream, int kind, const float* g_act, const float* x, const float* W,
@@ -407,128 +503,40 @@ extern "C" int wire_real_layer_bwd(void* stream, int kind, const float* g_act, c
   if (!kind_is_real(kind) || n <= 0 || in_features < 1 || out_features < 1 ||
       !g_act || !x || !W || !b || !g_W || !g_b || !ws || !kind_scale(kind, scale0, kscale, wscale))
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_real_layer_bwd");
-  const LayerWs w = layer_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  const int Pin = rup(in_features, 64), Pout = rup(out_features, 64);
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  if (int rc = real_forward_ws(s, w, W_, kind, x, W, b, omega0, kscale, wscale, n, in_features, out_features, Pin, Pout))
+  Layer l;
+  if (int rc = l.open(kind, stream, x, W, b, nullptr, nullptr, omega0, kscale, wscale, n, in_features, out_features, 0,
+                      ws, ws_bytes))
     return rc;
-  LCHK(launch_pad_rows(s, g_act, n, out_features, Pout, W_ + w.gact));
-  LCHK(launch_real_act_bwd_point(s, kind, W_ + w.gact, W_ + w.lin, W_ + w.out, n, Pout, omega0, kscale,
-                                 W_ + w.glin));
-  const LayerGemm g{wire_family_(kind), real_x2_region(kind, Pin, W_ + w.x2)};
-  if (g_x) {
-    GemmEpiParams ep; ep.o0 = W_ + w.gxb; ep.ld0 = Pin; ep.ld1 = Pin;
-    LCHK(g.nt(s, EPI_STORE, W_ + w.glin, n, Pin, Pout, true, W_ + w.btf, W_ + w.btd, W_ + w.btf_x3, W_ + w.btd_x3,
-              ep));
-    LCHK(launch_unpad_rows(s, W_ + w.gxb, n, in_features, Pin, g_x));
-  }
-  LCHK(g.tn_reduce(s, kind, W_ + w.glin, W_ + w.xb, n, Pout, Pin, out_features, in_features, W_ + w.slab,
-                   W_ + w.bslab, g_W, g_b, nullptr, nullptr, wscale));
-  return WIRE_OK;
+  return layer_bwd(l, g_act, g_x, g_W, g_b, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------
-// ComplexGaborLayer2D (modules/wire2d.py:21-67) on native tensors: both Linears of the layer are ONE GEMM
-// ([n, Pin] x [Pin -> 2 Pout], 128-column groups (lin_re | lin_im | sy_re | sy_im)).
+// ComplexGaborLayer2D
 // ---------------------------------------------------------------------------
-namespace {
-struct Layer2dWs {
-  int Pin, Pout, S, ldu;
-  int64_t xb, linsy, out, gact, glinsy, gxb, gup, btf, btd, bias, slab, bslab, crp, btf_x3, btd_x3, x2, total;
-};
-Layer2dWs layer2d_ws(int64_t n, int in, int out) {
-  Layer2dWs w{};
-  w.Pin = rup(2 * in, 64);
-  w.Pout = rup(2 * out, 64);
-  w.ldu = w.Pout / 2;
-  w.S = gemm_tn_splits(n, 2 * w.Pout, w.Pin, 64);
-  const int64_t s_max = std::max<int64_t>(w.S, gemmx3_tn_splits_max(n, 2 * w.Pout, w.Pin, 256));
-  int64_t off = 0;
-  auto take = [&](int64_t cnt) { int64_t o = off; off += rup64(cnt, 64); return o; };
-  w.xb = take(n * w.Pin);
-  w.linsy = take(n * 2 * w.Pout);
-  w.out = take(n * w.Pout);
-  w.gact = take(n * w.Pout);
-  w.glinsy = take(n * 2 * w.Pout);
-  w.gxb = take(n * w.Pin);
-  w.gup = take(n * 2 * w.ldu);
-  w.btf = take((int64_t)2 * w.Pout * w.Pin);
-  w.btd = take((int64_t)2 * w.Pout * w.Pin);
-  w.bias = take(2 * w.Pout);
-  w.slab = take(s_max * 2 * w.Pout * w.Pin);
-  w.bslab = take(s_max * 2 * w.Pout);
-  w.crp = take((int64_t)prereduce_room(colreduce_blocks(n)) * w.ldu * 5);
-  w.btf_x3 = take(gemmx3_b_image_floats(2 * w.Pout, w.Pin));
-  w.btd_x3 = take(gemmx3_b_image_floats(w.Pin, 2 * w.Pout));
-  w.x2 = take(x2_region_floats(2 * w.Pout, w.Pin));
-  w.total = off;
-  return w;
-}
-
-// forward into the workspace (linsy, out blocked); shared by fwd and bwd
-int layer2d_forward_ws(hipStream_t s, const Layer2dWs& w, float* W_, const void* x, const void* Wt, const void* b,
-                       const void* Vt, const void* c, float omega0, float scale0, int64_t n, int in, int out,
-                       int is_first, bool want_lin = false) {
-  if (is_first) {
-    if (in > 4) return wire_fail_(WIRE_ERR_ARG, "is_first layers support in_features <= 4");
-    LCHK(launch_first_fwd(s, NK_WIRE2D, (const float*)x, n, in, (const float*)Wt, (const float*)b,
-                          (const float*)Vt, (const float*)c, out, w.Pout, omega0, scale0,
-                          want_lin ? W_ + w.linsy : nullptr, W_ + w.out));
-    return WIRE_OK;
-  }
-  const LayerGemm g{wire_family_(WIRE_KIND_WIRE2D), W_ + w.x2};
-  LCHK(launch_c64_to_blocked(s, (const float*)x, n, in, w.Pin, W_ + w.xb));
-  LCHK(g.pack(s, NK_WIRE2D, (const float*)Wt, (const float*)b, (const float*)Vt, (const float*)c, out, in,
-              2 * w.Pout, w.Pin, W_ + w.btf, W_ + w.btd, W_ + w.bias, W_ + w.btf_x3, W_ + w.btd_x3));
-  GemmEpiParams ep;
-  ep.bias = W_ + w.bias; ep.o0 = W_ + w.linsy; ep.o1 = W_ + w.out; ep.ld0 = 2 * w.Pout; ep.ld1 = w.Pout;
-  ep.omega = omega0; ep.scale = scale0; ep.kvalid = out;
-  LCHK(g.nt(s, EPI_GABOR2D_FWD, W_ + w.xb, n, 2 * w.Pout, w.Pin, false, W_ + w.btf, W_ + w.btd, W_ + w.btf_x3,
-            W_ + w.btd_x3, ep));
-  return WIRE_OK;
-}
-}  // namespace
-
-extern "C" int64_t wire_layer2d_ws_bytes(int64_t n, int in_features, int out_features) {
-  if (n < 0 || in_features < 1 || out_features < 1) return wire_fail_(WIRE_ERR_ARG, "bad layer shape");
-  return layer2d_ws(n, in_features, out_features).total * 4 + 256;
-}
-
 extern "C" int wire_gabor2d_fwd(void* stream, const void* x, const void* W, const void* b, const void* V,
                                 const void* c, float omega0, float scale0, int64_t n, int in_features,
                                 int out_features, int is_first, void* act_out, void* ws, int64_t ws_bytes) {
   if (n < 0 || in_features < 1 || out_features < 1 || !x || !W || !b || !V || !c || !act_out || !ws)
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_gabor2d_fwd");
   if (n == 0) return WIRE_OK;
-  const Layer2dWs w = layer2d_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  if (int rc = layer2d_forward_ws(s, w, W_, x, W, b, V, c, omega0, scale0, n, in_features, out_features, is_first))
+  Layer l;
+  if (int rc = l.open(WIRE_KIND_WIRE2D, stream, x, W, b, V, c, omega0, scale0, 1.f, n, in_features, out_features,
+                      is_first, ws, ws_bytes))
     return rc;
-  LCHK(launch_blocked_to_c64(s, W_ + w.out, n, out_features, w.Pout, (float*)act_out));
-  return WIRE_OK;
+  return layer_fwd(l, act_out);
 }
 
-// trainable omega_0 / scale_0 of ComplexGaborLayer2D (modules/wire2d.py:42-43): out2 = {dL/d omega_0, dL/d scale_0}
 extern "C" int wire_gabor2d_hparam_grad(void* stream, const void* g_act, const void* x, const void* W, const void* b,
                                         const void* V, const void* c, float omega0, float scale0, int64_t n,
                                         int in_features, int out_features, int is_first, float* out2, void* ws,
                                         int64_t ws_bytes) {
   if (n <= 0 || in_features < 1 || out_features < 1 || !g_act || !x || !W || !b || !V || !c || !out2 || !ws)
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_gabor2d_hparam_grad");
-  const Layer2dWs w = layer2d_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  if (int rc = layer2d_forward_ws(s, w, W_, x, W, b, V, c, omega0, scale0, n, in_features, out_features, is_first, true))
+  Layer l;
+  if (int rc = l.open(WIRE_KIND_WIRE2D, stream, x, W, b, V, c, omega0, scale0, 1.f, n, in_features, out_features,
+                      is_first, ws, ws_bytes))
     return rc;
-  LCHK(launch_c64_to_blocked(s, (const float*)g_act, n, out_features, w.Pout, W_ + w.gact));
-  LCHK(launch_gabor2d_hparam_grad(s, W_ + w.gact, W_ + w.linsy, W_ + w.out, n, out_features, w.Pout, is_first, scale0,
-                                  W_ + w.glinsy, out2));
-  return WIRE_OK;
+  return layer_hparam(l, g_act, out2);
 }
 
 extern "C" int wire_gabor2d_bwd(void* stream, const void* g_act, const void* x, const void* W, const void* b,
@@ -538,35 +546,11 @@ extern "C" int wire_gabor2d_bwd(void* stream, const void* g_act, const void* x, 
   if (n <= 0 || in_features < 1 || out_features < 1 || !g_act || !x || !W || !b || !V || !c || !g_W || !g_b ||
       !g_V || !g_c || !ws)
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_gabor2d_bwd");
-  const Layer2dWs w = layer2d_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  if (int rc = layer2d_forward_ws(s, w, W_, x, W, b, V, c, omega0, scale0, n, in_features, out_features, is_first))
+  Layer l;
+  if (int rc = l.open(WIRE_KIND_WIRE2D, stream, x, W, b, V, c, omega0, scale0, 1.f, n, in_features, out_features,
+                      is_first, ws, ws_bytes))
     return rc;
-  LCHK(launch_c64_to_blocked(s, (const float*)g_act, n, out_features, w.Pout, W_ + w.gact));
-  if (is_first) {
-    LCHK(launch_gabor2d_bwd_first_point(s, W_ + w.gact, W_ + w.out, (const float*)x, in_features,
-                                        (const float*)W, (const float*)b, (const float*)V, (const float*)c, n,
-                                        out_features, w.Pout, omega0, scale0, W_ + w.gup, w.ldu));
-    LCHK(launch_colreduce(s, W_ + w.gup, 2 * w.ldu, out_features, (const float*)x, in_features, n, W_ + w.crp,
-                          (float*)g_W, (float*)g_b));
-    LCHK(launch_colreduce(s, W_ + w.gup + w.ldu, 2 * w.ldu, out_features, (const float*)x, in_features, n,
-                          W_ + w.crp, (float*)g_V, (float*)g_c));
-    return WIRE_OK;
-  }
-  LCHK(launch_gabor2d_bwd_point(s, W_ + w.gact, W_ + w.linsy, W_ + w.out, n, w.Pout, omega0, scale0,
-                                W_ + w.glinsy));
-  const LayerGemm g{wire_family_(WIRE_KIND_WIRE2D), W_ + w.x2};
-  if (g_x) {
-    GemmEpiParams ep; ep.o0 = W_ + w.gxb; ep.ld0 = w.Pin; ep.ld1 = w.Pin;
-    LCHK(g.nt(s, EPI_STORE, W_ + w.glinsy, n, w.Pin, 2 * w.Pout, true, W_ + w.btf, W_ + w.btd, W_ + w.btf_x3,
-              W_ + w.btd_x3, ep));
-    LCHK(launch_blocked_to_c64(s, W_ + w.gxb, n, in_features, w.Pin, (float*)g_x));
-  }
-  LCHK(g.tn_reduce(s, NK_WIRE2D, W_ + w.glinsy, W_ + w.xb, n, 2 * w.Pout, w.Pin, out_features, in_features,
-                   W_ + w.slab, W_ + w.bslab, (float*)g_W, (float*)g_b, (float*)g_V, (float*)g_c));
-  return WIRE_OK;
+  return layer_bwd(l, g_act, g_x, g_W, g_b, g_V, g_c);
 }
 
 // wire2d first layer with the coordinate gradient: g_x [n][in] f32 = g_u W + g_p V; g_W .. g_c NULL together = the
@@ -579,18 +563,9 @@ extern "C" int wire_gabor2d_bwd_first_coords(void* stream, const void* g_act, co
   if (n <= 0 || in_features < 1 || in_features > 4 || out_features < 1 || !g_act || !x || !W || !b || !V || !c ||
       !g_x || !ws || (!pg && (g_W || g_b || g_V || g_c)))
     return wire_fail_(WIRE_ERR_ARG, "bad argument to wire_gabor2d_bwd_first_coords");
-  const Layer2dWs w = layer2d_ws(n, in_features, out_features);
-  if (ws_bytes < w.total * 4) return wire_fail_(WIRE_ERR_SIZE, "layer workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  float* W_ = (float*)ws;
-  if (int rc = layer2d_forward_ws(s, w, W_, x, W, b, V, c, omega0, scale0, n, in_features, out_features, 1)) return rc;
-  LCHK(launch_c64_to_blocked(s, (const float*)g_act, n, out_features, w.Pout, W_ + w.gact));
-  LCHK(launch_gabor2d_bwd_first_point(s, W_ + w.gact, W_ + w.out, x, in_features, W, b, V, c, n, out_features, w.Pout,
-                                      omega0, scale0, W_ + w.gup, w.ldu));
-  if (pg) {
-    LCHK(launch_colreduce(s, W_ + w.gup, 2 * w.ldu, out_features, x, in_features, n, W_ + w.crp, g_W, g_b));
-    LCHK(launch_colreduce(s, W_ + w.gup + w.ldu, 2 * w.ldu, out_features, x, in_features, n, W_ + w.crp, g_V, g_c));
-  }
-  LCHK(launch_coordgrad_rows(s, W_ + w.gup, 2 * w.ldu, W_ + w.gup + w.ldu, W, V, out_features, in_features, n, g_x));
-  return WIRE_OK;
+  Layer l;
+  if (int rc = l.open(WIRE_KIND_WIRE2D, stream, x, W, b, V, c, omega0, scale0, 1.f, n, in_features, out_features, 1,
+                      ws, ws_bytes))
+    return rc;
+  return layer_bwd_first(l, g_act, g_x, g_W, g_b, g_V, g_c);
 }

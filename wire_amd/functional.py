@@ -44,6 +44,12 @@ def _native(t: torch.Tensor) -> torch.Tensor:
     return t.detach().contiguous()
 
 
+def _workspace(query: str, dev: torch.device, *shape) -> torch.Tensor:
+    """A workspace for one call: ``query`` is the library's size query (a wire_*_ws_bytes name) and ``shape`` its
+    arguments.  The size to hand to the entry point is the tensor's numel()."""
+    return torch.empty(_lib.check(getattr(_lib.lib(), query)(*shape), query), dtype=torch.uint8, device=dev)
+
+
 class _INRFunction(torch.autograd.Function):
     """Whole-network forward/backward: wire_mlp_fwd / wire_mlp_bwd."""
 
@@ -173,11 +179,10 @@ class _M2CombineFunction(torch.autograd.Function):
         gy = g_y.detach().to(torch.float32).contiguous()
         g_t = torch.empty_like(tin)
         gw = [torch.empty_like(w) for w in (W1, b1, W2, b2)]
-        ws_bytes = _lib.check(L.wire_m2_combine_ws_bytes(S, O, n), "wire_m2_combine_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _workspace("wire_m2_combine_ws_bytes", dev, S, O, n)
         _lib.check(L.wire_m2_combine_bwd(_stream_ptr(dev), S, O, W1.data_ptr(), b1.data_ptr(), W2.data_ptr(),
                                          b2.data_ptr(), tin.data_ptr(), n, gy.data_ptr(), g_t.data_ptr(),
-                                         *[g.data_ptr() for g in gw], ws.data_ptr(), ws_bytes), "wire_m2_combine_bwd")
+                                         *[g.data_ptr() for g in gw], ws.data_ptr(), ws.numel()), "wire_m2_combine_bwd")
         return (g_t, *gw)
 
 
@@ -186,227 +191,99 @@ def m2_combine(outputs: Sequence[torch.Tensor], W1, b1, W2, b2) -> torch.Tensor:
     return _M2CombineFunction.apply(torch.stack(list(outputs)), W1, b1, W2, b2)
 
 
-class _GaborLayerFunction(torch.autograd.Function):
-    """One ComplexGaborLayer on native tensors: wire_gabor_fwd / wire_gabor_bwd."""
+# The two Gabor layer forms, ComplexGaborLayer (modules/wire.py) over the parameters (W, b) and ComplexGaborLayer2D
+# (modules/wire2d.py:56-67) over (W, b, V, c): the module's name in messages, the entry points, and what wire_*_fwd takes
+# between is_first and act_out (wire_gabor_fwd's lin_out).  Everything else about a form is the length of its parameter
+# tuple; a new form is a row here and its public wrappers.
+_GABOR_FORMS = {
+    "gabor": dict(name="ComplexGaborLayer", ws="wire_layer_ws_bytes", fwd="wire_gabor_fwd", fwd_extra=(None,),
+                  bwd="wire_gabor_bwd", first_coords="wire_gabor_bwd_first_coords", hparam="wire_gabor_hparam_grad"),
+    "gabor2d": dict(name="ComplexGaborLayer2D", ws="wire_layer2d_ws_bytes", fwd="wire_gabor2d_fwd", fwd_extra=(),
+                    bwd="wire_gabor2d_bwd", first_coords="wire_gabor2d_bwd_first_coords",
+                    hparam="wire_gabor2d_hparam_grad"),
+}
+
+
+class _GaborFunction(torch.autograd.Function):
+    """One Gabor layer of either form on native tensors: wire_gabor*_fwd / wire_gabor*_bwd, or
+    wire_gabor*_bwd_first_coords for a first layer whose coordinates require a gradient.  ``trainable``: omega and scale
+    are the layer's omega_0 / scale_0 tensors (trainable=True, modules/wire.py:80-81, wire2d.py:42-43) instead of floats,
+    and the backward adds wire_gabor*_hparam_grad for their two gradients."""
 
     @staticmethod
-    def forward(ctx, x, W, b, omega0: float, scale0: float, is_first: bool):
-        L = _lib.lib()
+    def forward(ctx, form: str, trainable: bool, x, omega, scale, is_first: bool, *params):
+        f = _GABOR_FORMS[form]
+        hshapes = None
+        if trainable:
+            hshapes = (omega.shape, scale.shape)
+            omega, scale = float(omega.detach().reshape(-1)[0]), float(scale.detach().reshape(-1)[0])
         _require_cuda(x, "layer input")
-        _require_cuda(W, "layer weight")
+        _require_cuda(params[0], "layer weight")
         dev = x.device
-        out_f, in_f = W.shape
+        out_f, in_f = params[0].shape
         xin = x.detach().to(torch.float32 if is_first else torch.complex64).contiguous()
         n = xin.numel() // in_f
-        Wn, bn = _native(W), _native(b)
-        ws_bytes = _lib.check(L.wire_layer_ws_bytes(n, in_f, out_f), "wire_layer_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        nat = [_native(p) for p in params]
+        ws = _workspace(f["ws"], dev, n, in_f, out_f)
         act = torch.empty(tuple(x.shape[:-1]) + (out_f,), dtype=torch.complex64, device=dev)
-        _lib.check(L.wire_gabor_fwd(_stream_ptr(dev), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(),
-                                    omega0, scale0, n, in_f, out_f, int(is_first), None,
-                                    act.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor_fwd")
-        ctx.save_for_backward(xin, Wn, bn)
-        ctx.cfg = (omega0, scale0, is_first, n, in_f, out_f, tuple(x.shape))
+        _lib.check(getattr(_lib.lib(), f["fwd"])(_stream_ptr(dev), xin.data_ptr(), *[p.data_ptr() for p in nat], omega,
+                                                 scale, n, in_f, out_f, int(is_first), *f["fwd_extra"], act.data_ptr(),
+                                                 ws.data_ptr(), ws.numel()), f["fwd"])
+        ctx.save_for_backward(xin, *nat)
+        ctx.cfg = (f, omega, scale, is_first, n, in_f, out_f, tuple(x.shape), hshapes)
         ctx.xdtype = x.dtype
         return act
 
     @staticmethod
     def backward(ctx, g_act):
         L = _lib.lib()
-        xin, Wn, bn = ctx.saved_tensors
-        omega0, scale0, is_first, n, in_f, out_f, xshape = ctx.cfg
+        xin, *nat = ctx.saved_tensors
+        f, omega0, scale0, is_first, n, in_f, out_f, xshape, hshapes = ctx.cfg
         dev = g_act.device
         g = g_act.detach().to(torch.complex64).contiguous()
-        ws_bytes = _lib.check(L.wire_layer_ws_bytes(n, in_f, out_f), "wire_layer_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        gW = torch.empty_like(Wn)
-        gb = torch.empty_like(bn)
-        if is_first and ctx.needs_input_grad[0]:
-            gx = _gabor_first_coords(L, g, xin, Wn, bn, omega0, scale0, n, in_f, out_f, gW, gb, ws, ws_bytes, xshape,
-                                     ctx.xdtype)
-            return gx, gW, gb, None, None, None
-        gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
-        _lib.check(L.wire_gabor_bwd(_stream_ptr(dev), g.data_ptr(), xin.data_ptr(), Wn.data_ptr(),
-                                    bn.data_ptr(), omega0, scale0, n, in_f, out_f, int(is_first),
-                                    None if gx is None else gx.data_ptr(), gW.data_ptr(),
-                                    gb.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor_bwd")
-        return gx, gW, gb, None, None, None
+        ws = _workspace(f["ws"], dev, n, in_f, out_f)
+        grads = [torch.empty_like(p) for p in nat]
+        # every backward entry point opens with `layer` and closes with `wsp`
+        layer = (_stream_ptr(dev), g.data_ptr(), xin.data_ptr(), *[p.data_ptr() for p in nat], omega0, scale0, n, in_f,
+                 out_f)
+        gptr, wsp = [t.data_ptr() for t in grads], (ws.data_ptr(), ws.numel())
+        if is_first and ctx.needs_input_grad[2]:
+            gx = _first_coords(L, f, layer, gptr, wsp, n, in_f, dev).reshape(xshape).to(ctx.xdtype)
+        else:
+            gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
+            _lib.check(getattr(L, f["bwd"])(*layer, int(is_first), None if gx is None else gx.data_ptr(), *gptr, *wsp),
+                       f["bwd"])
+        g_hp = (None, None)
+        if hshapes is not None:
+            hp = torch.empty(2, dtype=torch.float32, device=dev)
+            _lib.check(getattr(L, f["hparam"])(*layer, int(is_first), hp.data_ptr(), *wsp), f["hparam"])
+            g_hp = (hp[0].reshape(hshapes[0]), hp[1].reshape(hshapes[1]))
+        return (None, None, gx, *g_hp, None, *grads)
 
 
-def _gabor_first_coords(L, g, xin, Wn, bn, omega0, scale0, n, in_f, out_f, gW, gb, ws, ws_bytes, xshape, xdtype):
-    """First Gabor layer with the coordinate gradient: wire_gabor_bwd_first_coords (g_x = g_u W)."""
-    _no_second_order("ComplexGaborLayer (is_first)")
-    gx = torch.empty(n, in_f, dtype=torch.float32, device=g.device)
-    _lib.check(L.wire_gabor_bwd_first_coords(_stream_ptr(g.device), g.data_ptr(), xin.data_ptr(), Wn.data_ptr(),
-                                             bn.data_ptr(), omega0, scale0, n, in_f, out_f, gx.data_ptr(),
-                                             gW.data_ptr(), gb.data_ptr(), ws.data_ptr(), ws_bytes),
-               "wire_gabor_bwd_first_coords")
-    return gx.reshape(xshape).to(xdtype)
-
-
-def _gabor2d_first_coords(L, g, xin, Wn, bn, Vn, cn, omega0, scale0, n, in_f, out_f, gW, gb, gV, gc, ws, ws_bytes,
-                          xshape, xdtype):
-    """First Gabor-2D layer with the coordinate gradient: wire_gabor2d_bwd_first_coords (g_x = g_u W + g_p V)."""
-    _no_second_order("ComplexGaborLayer2D (is_first)")
-    gx = torch.empty(n, in_f, dtype=torch.float32, device=g.device)
-    _lib.check(L.wire_gabor2d_bwd_first_coords(_stream_ptr(g.device), g.data_ptr(), xin.data_ptr(), Wn.data_ptr(),
-                                               bn.data_ptr(), Vn.data_ptr(), cn.data_ptr(), omega0, scale0, n, in_f,
-                                               out_f, gx.data_ptr(), gW.data_ptr(), gb.data_ptr(), gV.data_ptr(),
-                                               gc.data_ptr(), ws.data_ptr(), ws_bytes),
-               "wire_gabor2d_bwd_first_coords")
-    return gx.reshape(xshape).to(xdtype)
+def _first_coords(L, f, layer, gptr, wsp, n, in_f, dev):
+    """First Gabor layer with the coordinate gradient: wire_gabor*_bwd_first_coords (g_x = g_u W, + g_p V for the 2-D
+    form); returns g_x [n, in_f] float32."""
+    _no_second_order(f"{f['name']} (is_first)")
+    gx = torch.empty(n, in_f, dtype=torch.float32, device=dev)
+    _lib.check(getattr(L, f["first_coords"])(*layer, gx.data_ptr(), *gptr, *wsp), f["first_coords"])
+    return gx
 
 
 def gabor_layer(x, W, b, omega0: float, scale0: float, is_first: bool):
-    return _GaborLayerFunction.apply(x, W, b, float(omega0), float(scale0), bool(is_first))
-
-
-class _GaborLayerTrainableFunction(torch.autograd.Function):
-    """ComplexGaborLayer with trainable omega_0 / scale_0 (modules/wire.py:80-81, trainable=True):
-    wire_gabor_fwd / wire_gabor_bwd + wire_gabor_hparam_grad."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, omega, scale, is_first: bool):
-        omega0, scale0 = float(omega.detach().reshape(-1)[0]), float(scale.detach().reshape(-1)[0])
-        with torch.no_grad():
-            act = _GaborLayerFunction.apply(x.detach(), W.detach(), b.detach(), omega0, scale0, is_first)
-        in_f = W.shape[1]
-        xin = x.detach().to(torch.float32 if is_first else torch.complex64).contiguous()
-        ctx.save_for_backward(xin, _native(W), _native(b))
-        ctx.cfg = (omega0, scale0, is_first, xin.numel() // in_f, in_f, W.shape[0], tuple(x.shape), omega.shape,
-                   scale.shape)
-        ctx.xdtype = x.dtype
-        return act
-
-    @staticmethod
-    def backward(ctx, g_act):
-        L = _lib.lib()
-        xin, Wn, bn = ctx.saved_tensors
-        omega0, scale0, is_first, n, in_f, out_f, xshape, oshape, sshape = ctx.cfg
-        dev = g_act.device
-        g = g_act.detach().to(torch.complex64).contiguous()
-        ws_bytes = _lib.check(L.wire_layer_ws_bytes(n, in_f, out_f), "wire_layer_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        gW, gb = torch.empty_like(Wn), torch.empty_like(bn)
-        stream = _stream_ptr(dev)
-        if is_first and ctx.needs_input_grad[0]:
-            gx = _gabor_first_coords(L, g, xin, Wn, bn, omega0, scale0, n, in_f, out_f, gW, gb, ws, ws_bytes, xshape,
-                                     ctx.xdtype)
-        else:
-            gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
-            _lib.check(L.wire_gabor_bwd(stream, g.data_ptr(), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(), omega0,
-                                        scale0, n, in_f, out_f, int(is_first), None if gx is None else gx.data_ptr(),
-                                        gW.data_ptr(), gb.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor_bwd")
-        hp = torch.empty(2, dtype=torch.float32, device=dev)
-        _lib.check(L.wire_gabor_hparam_grad(stream, g.data_ptr(), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(),
-                                            omega0, scale0, n, in_f, out_f, int(is_first), hp.data_ptr(),
-                                            ws.data_ptr(), ws_bytes), "wire_gabor_hparam_grad")
-        return gx, gW, gb, hp[0].reshape(oshape), hp[1].reshape(sshape), None
+    return _GaborFunction.apply("gabor", False, x, float(omega0), float(scale0), bool(is_first), W, b)
 
 
 def gabor_layer_trainable(x, W, b, omega: torch.Tensor, scale: torch.Tensor, is_first: bool):
-    return _GaborLayerTrainableFunction.apply(x, W, b, omega, scale, bool(is_first))
-
-
-class _Gabor2DLayerFunction(torch.autograd.Function):
-    """ComplexGaborLayer2D.forward (modules/wire2d.py:56-67): wire_gabor2d_fwd / wire_gabor2d_bwd."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, V, c, omega0: float, scale0: float, is_first: bool):
-        L = _lib.lib()
-        _require_cuda(x, "layer input")
-        _require_cuda(W, "layer weight")
-        dev = x.device
-        out_f, in_f = W.shape
-        xin = x.detach().to(torch.float32 if is_first else torch.complex64).contiguous()
-        n = xin.numel() // in_f
-        Wn, bn, Vn, cn = _native(W), _native(b), _native(V), _native(c)
-        ws_bytes = _lib.check(L.wire_layer2d_ws_bytes(n, in_f, out_f), "wire_layer2d_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        act = torch.empty(tuple(x.shape[:-1]) + (out_f,), dtype=torch.complex64, device=dev)
-        _lib.check(L.wire_gabor2d_fwd(_stream_ptr(dev), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(),
-                                      Vn.data_ptr(), cn.data_ptr(), omega0, scale0, n, in_f, out_f,
-                                      int(is_first), act.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor2d_fwd")
-        ctx.save_for_backward(xin, Wn, bn, Vn, cn)
-        ctx.cfg = (omega0, scale0, is_first, n, in_f, out_f, tuple(x.shape))
-        ctx.xdtype = x.dtype
-        return act
-
-    @staticmethod
-    def backward(ctx, g_act):
-        L = _lib.lib()
-        xin, Wn, bn, Vn, cn = ctx.saved_tensors
-        omega0, scale0, is_first, n, in_f, out_f, xshape = ctx.cfg
-        dev = g_act.device
-        g = g_act.detach().to(torch.complex64).contiguous()
-        ws_bytes = _lib.check(L.wire_layer2d_ws_bytes(n, in_f, out_f), "wire_layer2d_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        gW, gb, gV, gc = (torch.empty_like(t) for t in (Wn, bn, Vn, cn))
-        if is_first and ctx.needs_input_grad[0]:
-            gx = _gabor2d_first_coords(L, g, xin, Wn, bn, Vn, cn, omega0, scale0, n, in_f, out_f, gW, gb, gV, gc, ws,
-                                       ws_bytes, xshape, ctx.xdtype)
-            return gx, gW, gb, gV, gc, None, None, None
-        gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
-        _lib.check(L.wire_gabor2d_bwd(_stream_ptr(dev), g.data_ptr(), xin.data_ptr(), Wn.data_ptr(),
-                                      bn.data_ptr(), Vn.data_ptr(), cn.data_ptr(), omega0, scale0, n, in_f,
-                                      out_f, int(is_first), None if gx is None else gx.data_ptr(),
-                                      gW.data_ptr(), gb.data_ptr(), gV.data_ptr(), gc.data_ptr(),
-                                      ws.data_ptr(), ws_bytes), "wire_gabor2d_bwd")
-        return gx, gW, gb, gV, gc, None, None, None
+    return _GaborFunction.apply("gabor", True, x, omega, scale, bool(is_first), W, b)
 
 
 def gabor2d_layer(x, W, b, V, c, omega0: float, scale0: float, is_first: bool):
-    return _Gabor2DLayerFunction.apply(x, W, b, V, c, float(omega0), float(scale0), bool(is_first))
-
-
-class _Gabor2DLayerTrainableFunction(torch.autograd.Function):
-    """ComplexGaborLayer2D with trainable omega_0 / scale_0 (modules/wire2d.py:42-43, trainable=True):
-    wire_gabor2d_fwd / wire_gabor2d_bwd + wire_gabor2d_hparam_grad."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, V, c, omega, scale, is_first: bool):
-        omega0, scale0 = float(omega.detach().reshape(-1)[0]), float(scale.detach().reshape(-1)[0])
-        with torch.no_grad():
-            act = _Gabor2DLayerFunction.apply(x.detach(), W.detach(), b.detach(), V.detach(), c.detach(), omega0,
-                                              scale0, is_first)
-        in_f = W.shape[1]
-        xin = x.detach().to(torch.float32 if is_first else torch.complex64).contiguous()
-        ctx.save_for_backward(xin, _native(W), _native(b), _native(V), _native(c))
-        ctx.cfg = (omega0, scale0, is_first, xin.numel() // in_f, in_f, W.shape[0], tuple(x.shape), omega.shape,
-                   scale.shape)
-        ctx.xdtype = x.dtype
-        return act
-
-    @staticmethod
-    def backward(ctx, g_act):
-        L = _lib.lib()
-        xin, Wn, bn, Vn, cn = ctx.saved_tensors
-        omega0, scale0, is_first, n, in_f, out_f, xshape, oshape, sshape = ctx.cfg
-        dev = g_act.device
-        g = g_act.detach().to(torch.complex64).contiguous()
-        ws_bytes = _lib.check(L.wire_layer2d_ws_bytes(n, in_f, out_f), "wire_layer2d_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        gW, gb, gV, gc = (torch.empty_like(t) for t in (Wn, bn, Vn, cn))
-        stream = _stream_ptr(dev)
-        if is_first and ctx.needs_input_grad[0]:
-            gx = _gabor2d_first_coords(L, g, xin, Wn, bn, Vn, cn, omega0, scale0, n, in_f, out_f, gW, gb, gV, gc, ws,
-                                       ws_bytes, xshape, ctx.xdtype)
-        else:
-            gx = None if is_first else torch.empty(xshape, dtype=torch.complex64, device=dev)
-            _lib.check(L.wire_gabor2d_bwd(stream, g.data_ptr(), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(),
-                                          Vn.data_ptr(), cn.data_ptr(), omega0, scale0, n, in_f, out_f, int(is_first),
-                                          None if gx is None else gx.data_ptr(), gW.data_ptr(), gb.data_ptr(),
-                                          gV.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws_bytes), "wire_gabor2d_bwd")
-        hp = torch.empty(2, dtype=torch.float32, device=dev)
-        _lib.check(L.wire_gabor2d_hparam_grad(stream, g.data_ptr(), xin.data_ptr(), Wn.data_ptr(), bn.data_ptr(),
-                                              Vn.data_ptr(), cn.data_ptr(), omega0, scale0, n, in_f, out_f,
-                                              int(is_first), hp.data_ptr(), ws.data_ptr(), ws_bytes),
-                   "wire_gabor2d_hparam_grad")
-        return gx, gW, gb, gV, gc, hp[0].reshape(oshape), hp[1].reshape(sshape), None
+    return _GaborFunction.apply("gabor2d", False, x, float(omega0), float(scale0), bool(is_first), W, b, V, c)
 
 
 def gabor2d_layer_trainable(x, W, b, V, c, omega: torch.Tensor, scale: torch.Tensor, is_first: bool):
-    return _Gabor2DLayerTrainableFunction.apply(x, W, b, V, c, omega, scale, bool(is_first))
+    return _GaborFunction.apply("gabor2d", True, x, omega, scale, bool(is_first), W, b, V, c)
 
 
 class _FinalLinearFunction(torch.autograd.Function):
@@ -421,11 +298,10 @@ class _FinalLinearFunction(torch.autograd.Function):
         zin = z.detach().to(torch.complex64).contiguous()
         n = zin.numel() // in_f
         Wn, bn = _native(Wf), _native(bf)
-        ws_bytes = _lib.check(L.wire_layer_ws_bytes(n, in_f, out_f), "wire_layer_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _workspace("wire_layer_ws_bytes", dev, n, in_f, out_f)
         y = torch.empty(tuple(z.shape[:-1]) + (out_f,), dtype=torch.float32, device=dev)
         _lib.check(L.wire_final_fwd(_stream_ptr(dev), zin.data_ptr(), Wn.data_ptr(), bn.data_ptr(), n,
-                                    in_f, out_f, y.data_ptr(), ws.data_ptr(), ws_bytes),
+                                    in_f, out_f, y.data_ptr(), ws.data_ptr(), ws.numel()),
                    "wire_final_fwd")
         ctx.save_for_backward(zin, Wn)
         ctx.cfg = (n, in_f, out_f, tuple(z.shape), bn.shape)
@@ -438,14 +314,13 @@ class _FinalLinearFunction(torch.autograd.Function):
         n, in_f, out_f, zshape, bshape = ctx.cfg
         dev = g_y.device
         gy = g_y.detach().to(torch.float32).contiguous()
-        ws_bytes = _lib.check(L.wire_layer_ws_bytes(n, in_f, out_f), "wire_layer_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _workspace("wire_layer_ws_bytes", dev, n, in_f, out_f)
         gz = torch.empty(zshape, dtype=torch.complex64, device=dev)
         gW = torch.empty_like(Wn)
         gb = torch.empty(bshape, dtype=torch.complex64, device=dev)
         _lib.check(L.wire_final_bwd(_stream_ptr(dev), gy.data_ptr(), zin.data_ptr(), Wn.data_ptr(), n,
                                     in_f, out_f, gz.data_ptr(), gW.data_ptr(), gb.data_ptr(),
-                                    ws.data_ptr(), ws_bytes), "wire_final_bwd")
+                                    ws.data_ptr(), ws.numel()), "wire_final_bwd")
         return gz, gW, gb
 
 
@@ -466,12 +341,11 @@ class _RealLayerFunction(torch.autograd.Function):
         xin = x.detach().to(torch.float32).contiguous()
         n = xin.numel() // in_f
         Wn, bn = _native(W), _native(b)
-        ws_bytes = _lib.check(L.wire_layer_ws_bytes(n, in_f, out_f), "wire_layer_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _workspace("wire_layer_ws_bytes", dev, n, in_f, out_f)
         act = torch.empty(tuple(x.shape[:-1]) + (out_f,), dtype=torch.float32, device=dev)
         _lib.check(L.wire_real_layer_fwd(_stream_ptr(dev), _lib.KIND[kind], xin.data_ptr(), Wn.data_ptr(),
                                          bn.data_ptr(), omega0, scale0, n, in_f, out_f, act.data_ptr(),
-                                         ws.data_ptr(), ws_bytes), "wire_real_layer_fwd")
+                                         ws.data_ptr(), ws.numel()), "wire_real_layer_fwd")
         ctx.save_for_backward(xin, Wn, bn)
         ctx.cfg = (kind, omega0, scale0, n, in_f, out_f, tuple(x.shape), x.requires_grad)
         return act
@@ -483,15 +357,14 @@ class _RealLayerFunction(torch.autograd.Function):
         kind, omega0, scale0, n, in_f, out_f, xshape, need_gx = ctx.cfg
         dev = g_act.device
         g = g_act.detach().to(torch.float32).contiguous()
-        ws_bytes = _lib.check(L.wire_layer_ws_bytes(n, in_f, out_f), "wire_layer_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _workspace("wire_layer_ws_bytes", dev, n, in_f, out_f)
         gW = torch.empty_like(Wn)
         gb = torch.empty_like(bn)
         gx = torch.empty(xshape, dtype=torch.float32, device=dev) if need_gx else None
         _lib.check(L.wire_real_layer_bwd(_stream_ptr(dev), _lib.KIND[kind], g.data_ptr(), xin.data_ptr(),
                                          Wn.data_ptr(), bn.data_ptr(), omega0, scale0, n, in_f, out_f,
                                          None if gx is None else gx.data_ptr(), gW.data_ptr(), gb.data_ptr(),
-                                         ws.data_ptr(), ws_bytes), "wire_real_layer_bwd")
+                                         ws.data_ptr(), ws.numel()), "wire_real_layer_bwd")
         return gx, gW, gb, None, None, None
 
 
@@ -534,12 +407,11 @@ class _MfnFilterFunction(torch.autograd.Function):
             _no_second_order("mfn GaborLayer")
             gx = torch.zeros(n, D, dtype=torch.float32, device=dev)
         if n > 0:
-            ws_bytes = _lib.check(L.wire_mfn_filter_ws_bytes(n, K), "wire_mfn_filter_ws_bytes")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws = _workspace("wire_mfn_filter_ws_bytes", dev, n, K)
             _lib.check(L.wire_mfn_filter_bwd(_stream_ptr(dev), g.data_ptr(), xin.data_ptr(), mu.data_ptr(),
                                              gamma.data_ptr(), w.data_ptr(), c.data_ptr(), n, D, K,
                                              *[t.data_ptr() for t in grads], None if gx is None else gx.data_ptr(),
-                                             ws.data_ptr(), ws_bytes), "wire_mfn_filter_bwd")
+                                             ws.data_ptr(), ws.numel()), "wire_mfn_filter_bwd")
         return (None if gx is None else gx.to(ctx.xdtype), *grads)
 
 
@@ -650,8 +522,7 @@ class _SsimLossFunction(torch.autograd.Function):
         L = _lib.lib()
         dev = rec.device
         x, y = gt.detach().contiguous(), rec.detach().contiguous()
-        ws_bytes = _lib.check(L.wire_ssim_ws_bytes(H, W, O, taps), "wire_ssim_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _workspace("wire_ssim_ws_bytes", dev, H, W, O, taps)
         out = torch.empty((), dtype=torch.float32, device=dev)
         _lib.check(L.wire_ssim(_stream_ptr(dev), x.data_ptr(), y.data_ptr(), H, W, O, taps, win, cov, c1, c2,
                                out.data_ptr(), None, ws.data_ptr(), ws.numel()), "wire_ssim")
@@ -668,8 +539,7 @@ class _SsimLossFunction(torch.autograd.Function):
         L = _lib.lib()
         dev = y.device
         g = (-g_loss.detach().to(torch.float32)).reshape(1).contiguous()      # d(1 - ssim) = -d ssim; read on the device
-        ws_bytes = _lib.check(L.wire_ssim_bwd_ws_bytes(H, W, O, taps), "wire_ssim_bwd_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _workspace("wire_ssim_bwd_ws_bytes", dev, H, W, O, taps)
         gy = torch.empty(H * W * O, dtype=torch.float32, device=dev)
         _lib.check(L.wire_ssim_bwd(_stream_ptr(dev), x.data_ptr(), y.data_ptr(), H, W, O, taps, win, cov, c1, c2,
                                    g.data_ptr(), gy.data_ptr(), ws.data_ptr(), ws.numel()), "wire_ssim_bwd")
@@ -793,8 +663,7 @@ class _WarpCoordsFunction(torch.autograd.Function):
             g = g.clone()
         g_theta = torch.empty_like(t)
         g_in = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        ws_bytes = _lib.check(L.wire_warp_coords_bwd_ws_bytes(B, n_per), "wire_warp_coords_bwd_ws_bytes")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        ws = _workspace("wire_warp_coords_bwd_ws_bytes", x.device, B, n_per)
         _lib.check(L.wire_warp_coords_bwd(_stream_ptr(x.device), x.data_ptr(), t.data_ptr(), g.data_ptr(), B, n_per, 0,
                                           g_theta.data_ptr(), g_in.data_ptr() if g_in is not None else None,
                                           ws.data_ptr(), ws.numel()), "wire_warp_coords_bwd")
@@ -863,7 +732,7 @@ def iso_surface(volume: torch.Tensor, thres: float):
     L = _lib.lib()
     vol = volume.detach().contiguous()
     dev, stream = vol.device, _stream_ptr(vol.device)
-    ws = torch.empty(_lib.check(L.wire_iso_ws_bytes(H, W, T), "wire_iso_ws_bytes"), dtype=torch.uint8, device=dev)
+    ws = _workspace("wire_iso_ws_bytes", dev, H, W, T)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     _lib.check(L.wire_iso_count(stream, vol.data_ptr(), H, W, T, thres, ws.data_ptr(), counts.data_ptr()),
                "wire_iso_count")
