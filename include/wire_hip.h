@@ -352,6 +352,41 @@ int wire_mse_grad(void* stream, const float* y, const float* target,
                   const int64_t* idx, int64_t first, int64_t n, int O,
                   float weight, float* g_y, float* loss_out, float* rec,
                   float* partial);
+/* Pointwise data terms with a per-sample weight: what wire_mse_grad does for the square, for four functions rho of the
+ * residual.  Row r < n of y [n][O] pairs with table row src = idx ? idx[r] : first + r, exactly as in wire_mse_grad:
+ * target is [*][O] and weight is NULL (all ones), [*] (weight_per_elem == 0, one per row) or [*][O]
+ * (weight_per_elem == 1: a Bayer mosaic masks channels, not pixels), all read at src.  Weights may hold any finite
+ * value, not only 0 and 1.  With d = y - t:
+ *   loss_out[0] = shard * sum_e w_e rho(d_e) / (n O)            (overwritten)
+ *   g_y[e]      = shard * w_e rho'(d_e) / (n O)                 (EVERY element is written)
+ * The mean runs over every element, those of weight 0 included: MSELoss()(out * mask, gt * mask) with w = mask^2, the
+ * convention of wire_avgpool_mse_grad_frames; a caller who wants the mean over the kept elements scales the weights.
+ * shard is wire_mse_grad's `weight`: n/B for a shard of a global batch of B rows, 1 for a whole batch.
+ *   WIRE_LOSS_MSE       rho = d^2                                           rho' = 2 d
+ *   WIRE_LOSS_L1        rho = |d|                                           rho' = (y > t) - (y < t): +0 at a tie,
+ *                                                                           as torch.nn.L1Loss
+ *   WIRE_LOSS_HUBER     rho = d^2 / 2 if |d| <= delta,                      rho' = clamp(d, -delta, delta)
+ *                             delta (|d| - delta / 2) otherwise             (torch.nn.HuberLoss)
+ *   WIRE_LOSS_LOGISTIC  rho = max(z, 0) - t z + log1p(exp(-|z|))            rho' = sigmoid(z) - t
+ *                       z = y a logit, t in [0, 1]                          (torch.nn.BCEWithLogitsLoss)
+ * delta is read by WIRE_LOSS_HUBER alone.  The logistic form takes no exponential of a positive argument and divides by
+ * 1 + e with e in [0, 1]: finite for every finite z.
+ * rec (optional): rec[src][:] = y[r][:]; rows the call does not name stay untouched.  partial: >= 4096 floats of
+ * scratch.  One grid-stride pass of 256-thread blocks in a grid that depends on n*O alone, per-block sums added in a
+ * fixed order, no atomics: the same call gives the same bits.  WIRE_LOSS_MSE with weight == NULL writes the bits of
+ * wire_mse_grad(..., weight = shard, ...) into g_y, loss_out and rec.
+ * An unknown kind, n < 0, O < 1, delta not finite or <= 0 with WIRE_LOSS_HUBER, shard not finite, weight_per_elem
+ * outside {0, 1}, or a NULL pointer other than weight / idx / rec: WIRE_ERR_ARG before any HIP call.  n == 0 returns
+ * WIRE_OK and touches nothing, loss_out included.  The rows of idx are trusted.                                   */
+typedef enum wire_loss_kind {
+  WIRE_LOSS_MSE = 0,
+  WIRE_LOSS_L1 = 1,
+  WIRE_LOSS_HUBER = 2,
+  WIRE_LOSS_LOGISTIC = 3
+} wire_loss_kind;
+int wire_point_loss_grad(void* stream, int kind, float delta, const float* y, const float* target, const float* weight,
+                         int weight_per_elem, const int64_t* idx, int64_t first, int64_t n, int O, float shard,
+                         float* g_y, float* loss_out, float* rec, float* partial);
 /* Super-resolution loss of wire_SISR.py:151-161: rec = torch.nn.AvgPool2d(scale) of the full-grid
  * reconstruction y [H*W][O] (row n = i*W + j), loss = mean((gt_lr - rec)^2) over [H/scale][W/scale][O]
  * (floor: ragged borders are dropped and receive zero gradient).  Writes loss_out[0], g_y = dL/dy [H*W][O]

@@ -21,6 +21,8 @@ KIND = {"wire": 0, "wire2d": 1, "siren": 2, "gauss": 3, "relu": 4, "bspline_form
         "bspline_mscale_2": 8, "bspline_mscale_hier": 9, "mfn": 11, "bspline_cubic": 12}
 MS_MAX_SCALES = 8   # WIRE_MS_MAX_SCALES
 ABI_VERSION = 1
+# enum wire_loss_kind: the data terms of wire_point_loss_grad
+LOSS_KIND = {"mse": 0, "l1": 1, "huber": 2, "logistic": 3}
 
 # every symbol include/wire_hip.h declares (tests check the .so exports them)
 SYMBOLS = [
@@ -39,7 +41,7 @@ SYMBOLS = [
     "wire_ssim_bwd_ws_bytes", "wire_ssim_bwd", "wire_ssim_mse_grad_ws_bytes", "wire_ssim_mse_grad",
     "wire_tv_add_grad", "wire_warp_coords_fwd", "wire_warp_coords_bwd_ws_bytes", "wire_warp_coords_bwd",
     "wire_iso_ws_bytes", "wire_iso_count", "wire_iso_emit", "wire_iso_tet_case", "wire_gauss3_blur",
-    "wire_radon_vol_fwd", "wire_radon_vol_bwd",
+    "wire_radon_vol_fwd", "wire_radon_vol_bwd", "wire_point_loss_grad",
 ]
 
 
@@ -121,6 +123,7 @@ def _declare(l: C.CDLL) -> None:
     l.wire_coords_from_index.argtypes = [vp, vp, i64, i64, vp, i32, vp, i32, vp, i32, vp]
     l.wire_perm_indices.argtypes = [vp, C.c_uint64, i64, i64, i64, vp]
     l.wire_mse_grad.argtypes = [vp, vp, vp, vp, i64, i64, i32, f32, vp, vp, vp, vp]
+    l.wire_point_loss_grad.argtypes = [vp, i32, f32, vp, vp, vp, i32, vp, i64, i64, i32, f32, vp, vp, vp, vp]
     l.wire_adam_step_flat.argtypes = [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, i64]
     l.wire_blocked_width.argtypes = [i32]
     l.wire_c64_to_blocked.argtypes = [vp, vp, i64, i32, vp]

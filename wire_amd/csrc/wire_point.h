@@ -187,10 +187,18 @@ hipError_t launch_perm_indices(hipStream_t s, uint64_t seed, int64_t n_total, in
 hipError_t launch_coords(hipStream_t s, const int64_t* idx, int64_t first, int64_t n,
                          const float* tx, int W, const float* ty, int H, const float* tz, int T,
                          float* coords);
+// the grid of a loss kernel over n elements (at most 1024 blocks of 256); loss_out[0] = lscale * sum of nb partial sums
+unsigned mse_blocks(long long n);
 hipError_t launch_mse_final(hipStream_t s, const float* partial, int nb, float lscale, float* loss_out);
 hipError_t launch_mse_grad(hipStream_t s, const float* y, const float* target, const int64_t* idx,
                            int64_t first, int64_t n, int O, float weight, float* g_y,
                            float* loss_out, float* rec, float* partial);
+// pointwise data terms with a per-sample weight (wire_loss.hip): kind = WIRE_LOSS_*, weight null (ones), [*] or [*][O];
+// rows, rec and partial as launch_mse_grad, whose bits plain MSE without weights gives
+hipError_t launch_point_loss_grad(hipStream_t s, int kind, float delta, const float* y, const float* target,
+                                  const float* weight, int weight_per_elem, const int64_t* idx, int64_t first,
+                                  int64_t n, int O, float shard, float* g_y, float* loss_out, float* rec,
+                                  float* partial);
 // super-resolution loss: AvgPool2d(scale) of the [H W][O] reconstruction against gt_lr [H2 W2][O]
 // (wire_SISR.py:151-161): loss, dL/dy (g_y [H W][O]), optionally the pooled image; partial >= 1024 floats
 hipError_t launch_avgpool_mse_grad(hipStream_t s, const float* y, int H, int W, int O, int scale,

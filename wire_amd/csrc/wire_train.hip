@@ -122,7 +122,7 @@ __global__ void mse_final_kernel(const float* __restrict__ partial, int nb, floa
   if (threadIdx.x == 0) loss_out[0] = acc * lscale;
 }
 // the grid of a loss kernel over n elements: it depends on the shape alone
-static unsigned mse_blocks(long long n) { return n < (long long)MSE_BLOCKS * 256 ? cdiv(n, 256) : MSE_BLOCKS; }
+unsigned mse_blocks(long long n) { return n < (long long)MSE_BLOCKS * 256 ? cdiv(n, 256) : MSE_BLOCKS; }
 // loss_out[0] = lscale * sum of nb partial sums (one block)
 hipError_t launch_mse_final(hipStream_t s, const float* partial, int nb, float lscale, float* loss_out) {
   hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, partial, nb, lscale, loss_out);

@@ -634,6 +634,87 @@ def total_variation(x: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------
+# pointwise data terms with a per-sample weight (wire_point_loss_grad)
+# ---------------------------------------------------------------------------
+def _loss_kind(kind, delta):
+    """(enum wire_loss_kind, delta as a float) of a data term named "mse" | "l1" | "huber" | "logistic"; ``delta`` is
+    Huber's width and is checked for that kind alone."""
+    if not isinstance(kind, str) or kind not in _lib.LOSS_KIND:
+        raise ValueError(f"kind {kind!r}: one of {', '.join(repr(k) for k in _lib.LOSS_KIND)}")
+    delta = float(delta)
+    if kind == "huber" and not (delta > 0.0 and delta != float("inf")):
+        raise ValueError(f"delta must be finite and > 0 for the Huber loss, not {delta}")
+    return _lib.LOSS_KIND[kind], delta
+
+
+def _loss_weight(weight, n: int, O: int, like: torch.Tensor, rows: str = "n"):
+    """An optional weight table -> (detached tensor or None, weight_per_elem): [n] is one weight per row, [n, O] one per
+    element; contiguous float32 on the device of ``like``."""
+    if weight is None:
+        return None, 0
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or not weight.is_contiguous() \
+            or tuple(weight.shape) not in ((n,), (n, O)) or weight.device != like.device:
+        raise ValueError(f"weight must be a contiguous float32 tensor [{rows}] or [{rows}, {O}] on the device of the "
+                         "outputs")
+    return weight.detach(), int(weight.dim() == 2)
+
+
+class _PointLossFunction(torch.autograd.Function):
+    """loss and dL/dy in one launch of wire_point_loss_grad; backward scales the stored gradient."""
+
+    @staticmethod
+    def forward(ctx, y, target, weight, cfg):
+        code, delta, wpe = cfg
+        L = _lib.lib()
+        dev = y.device
+        yd = y.detach()
+        n, O = int(yd.shape[0]), int(yd.shape[1])
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        gy = torch.empty_like(yd)
+        partial = torch.empty(4096, dtype=torch.float32, device=dev)
+        _lib.check(L.wire_point_loss_grad(_stream_ptr(dev), code, delta, yd.data_ptr(), target.data_ptr(),
+                                          weight.data_ptr() if weight is not None else None, wpe, None, 0, n, O, 1.0,
+                                          gy.data_ptr(), out.data_ptr(), None, partial.data_ptr()),
+                   "wire_point_loss_grad")
+        ctx.save_for_backward(gy)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        gy, = ctx.saved_tensors
+        _no_second_order("point_loss")
+        return g_loss.detach().to(torch.float32) * gy, None, None, None
+
+
+def point_loss(y: torch.Tensor, target: torch.Tensor, kind: str = "mse", weight=None, delta: float = 1.0) -> torch.Tensor:
+    """A pointwise data term of the outputs ``y`` [n, O] against ``target`` [n, O] as a 0-dim device tensor,
+    ``sum_e w_e rho(y_e - t_e) / (n O)`` with rho by ``kind``:
+
+        "mse"       d^2                                       torch.nn.MSELoss
+        "l1"        |d|, gradient sign(d) with +0 at a tie     torch.nn.L1Loss
+        "huber"     d^2 / 2 up to |d| = delta, linear beyond   torch.nn.HuberLoss(delta=delta)
+        "logistic"  max(z,0) - t z + log1p(exp(-|z|)), z = y   torch.nn.BCEWithLogitsLoss (y a logit, target in [0, 1])
+
+    ``weight`` is None, [n] (one per row) or [n, O] (one per element, a Bayer mosaic), any finite values; the mean runs
+    over every element, those of weight 0 included (``MSELoss()(out * mask, gt * mask)``), so scale the weights for a
+    mean over the kept ones.  All tensors contiguous CUDA float32.  One HIP launch (wire_point_loss_grad) gives the loss
+    and dL/dy together; backward multiplies the stored gradient by the upstream scalar on the device (no sync).  The
+    gradient flows to ``y`` only; first order only.  No atomics: the same call gives the same bits.  CPU tensors raise
+    WireHipError; other dtypes, shapes, kinds or a bad ``delta`` ValueError, before any device access."""
+    cfg = _loss_kind(kind, delta)
+    if not isinstance(y, torch.Tensor) or not isinstance(target, torch.Tensor):
+        raise ValueError("point_loss expects two tensors")
+    if y.dtype != torch.float32 or y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1 or not y.is_contiguous():
+        raise ValueError("y must be a contiguous float32 tensor [n, O] with n, O >= 1")
+    if target.dtype != torch.float32 or target.shape != y.shape or not target.is_contiguous() \
+            or target.device != y.device:
+        raise ValueError(f"target must be a contiguous float32 tensor {list(y.shape)} on the device of y")
+    w, wpe = _loss_weight(weight, int(y.shape[0]), int(y.shape[1]), y)
+    _require_cuda(y, "y")
+    return _PointLossFunction.apply(y, target.detach(), w, cfg + (wpe,))
+
+
+# ---------------------------------------------------------------------------
 # a learnable registration of frames (wire_warp_coords_fwd / wire_warp_coords_bwd)
 # ---------------------------------------------------------------------------
 class _WarpCoordsFunction(torch.autograd.Function):

@@ -30,6 +30,43 @@ def psnr(x, xhat):
     return 10 * np.log10(np.max(x) / np.mean(err ** 2))
 
 
+def rsnr(x, xhat):
+    """Reconstruction SNR in dB, 20 log10(||x|| / ||x - xhat||) (modules/utils.py:49-64)."""
+    x, xhat = np.asarray(x), np.asarray(xhat)
+    return 20 * np.log10(np.linalg.norm(x.reshape(-1)) / np.linalg.norm((x - xhat).reshape(-1)))
+
+
+def add_salt_and_pepper_noise(image, salt_prob, pepper_prob):
+    """Impulse noise on a copy of an (H, W, C) image, same np.random call order as modules/utils.py:114-129: one
+    np.random.random((H, W)) draw sets whole pixels to 255, a second one sets whole pixels to 0 (pepper wins where both
+    fall).  An image on a 0..1 scale gets its salt as 255 too, as there; a driver on that scale sets the pixels itself
+    from the two masks.  The data term for such noise is ``FusedTrainer.step_loss("l1")`` or ``"huber"``."""
+    image = np.asarray(image)
+    noisy = np.copy(image)
+    noisy[np.random.random(image.shape[:2]) < salt_prob] = 255
+    noisy[np.random.random(image.shape[:2]) < pepper_prob] = 0
+    return noisy
+
+
+def get_inpainting_mask(imsize, mask_type='random2d', mask_frac=0.5):
+    """A float32 (H, W) mask of kept pixels for image inpainting (modules/utils.py:203-226), with the same np.random
+    consumption: 'random2d' keeps a pixel when np.random.rand(H, W) < mask_frac, 'random1d' draws one row of W and
+    repeats it, 'bayer' keeps the even rows and columns and draws nothing.  An unknown ``mask_type`` is a ValueError
+    (the reference runs into an UnboundLocalError).  The mask, flattened (and repeated per channel, or one channel's
+    sites per channel for a true mosaic), is the ``weight`` of ``FusedTrainer.step_loss``."""
+    H, W = imsize
+    if mask_type == 'random2d':
+        mask = np.random.rand(H, W) < mask_frac
+    elif mask_type == 'random1d':
+        mask = np.ones((H, 1)).dot(np.random.rand(1, W) < mask_frac)
+    elif mask_type == 'bayer':
+        mask = np.zeros((H, W))
+        mask[::2, ::2] = 1
+    else:
+        raise ValueError(f"mask_type {mask_type!r}: one of 'random2d', 'random1d', 'bayer'")
+    return mask.astype(np.float32)
+
+
 def measure(x, noise_snr=40, tau=100):
     """Photon + readout noise, same np.random call order as modules/utils.py:85-112."""
     meas = np.copy(x)

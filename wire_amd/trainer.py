@@ -79,8 +79,8 @@ class FusedTrainer:
     ``step_frames``, ``step_coded`` and ``step_radon_volume`` work for bspline_mscale_hier as for the other kinds.
 
     ``target`` is the [npoints, O] signal of ``step`` / ``step_hashed`` and the default ``gt`` of the metrics.  The
-    operator steps bring their own data, so a trainer that only runs those may pass ``target=None``; ``step``,
-    ``step_hashed`` and a metric called without ``gt`` then raise ValueError."""
+    operator steps and ``step_samples`` bring their own data, so a trainer that only runs those may pass
+    ``target=None``; ``step``, ``step_hashed``, ``step_loss`` and a metric called without ``gt`` then raise ValueError."""
 
     def __init__(self, model: HipINR, grid: Sequence[int], target: Optional[torch.Tensor], lr: float = 5e-3,
                  betas=(0.9, 0.999), eps: float = 1e-8, gamma: float = 0.1, niters: int = 2000,
@@ -694,6 +694,85 @@ class FusedTrainer:
                                                  self.gy.data_ptr(), parts.data_ptr(), self._opt_ptr(self.rec),
                                                  ws.data_ptr(), ws.numel()), "ssim_mse_grad")
         return self._raster_step(loss, loss_src=parts[0:1])
+
+    # ------------------------------------------------------------------ steps that choose their data term
+    def _point_loss(self, code: int, delta: float, table: torch.Tensor, w: Optional[torch.Tensor], wpe: int,
+                    idx_ptr: Optional[int], first: int, n: int, rec: Optional[torch.Tensor]):
+        """The pointwise loss of ``n`` rows of ``self.y`` against the rows of ``table`` (and of the weight table ``w``)
+        that ``idx_ptr`` / ``first`` name (wire_point_loss_grad)."""
+        def loss(stream, g):
+            _lib.check(self.L.wire_point_loss_grad(stream, code, delta, self.y.data_ptr(), table.data_ptr(),
+                                                   self._opt_ptr(w), wpe, idx_ptr, first, n, self.O, 1.0,
+                                                   self.gy.data_ptr(), self._loss_slot(g)[0], self._opt_ptr(rec),
+                                                   self.partial.data_ptr()), "point_loss_grad")
+        return loss
+
+    def _point_step(self, coords_ptr: int, n: int, loss) -> torch.Tensor:
+        """Pack, ``_fwd_loss_bwd`` on the ``n`` rows at ``coords_ptr``, ``_finish``."""
+        stream = self._stream()
+        g = self.gbuf[0]
+        self._pack(stream)
+        src = self._fwd_loss_bwd(stream, coords_ptr, n, loss, g, self.grad_ptrs[0])
+        return self._finish(stream, g, src)
+
+    def step_loss(self, kind: str, indices: Optional[torch.Tensor] = None, first: int = 0,
+                  count: Optional[int] = None, weight: Optional[torch.Tensor] = None,
+                  delta: float = 1.0) -> torch.Tensor:
+        """``step`` with a chosen data term and an optional per-sample weight: the rows ``indices`` (contiguous int64
+        device tensor of DISTINCT flat grid indices, such as a slice of a permutation) or the range
+        [first, first+count) -- given exactly as ``step`` takes them, all rows by default -- are evaluated, and only
+        those, and
+
+            loss = sum_e w_e rho(y_e - target_e) / (rows * O)
+
+        with rho by ``kind``: "mse", "l1" (impulse noise: ``utils.add_salt_and_pepper_noise``), "huber" (quadratic up to
+        ``delta``, linear beyond) or "logistic" (the output is a logit and the target a probability in [0, 1]: the
+        occupancy loop; ``functional.point_loss`` lists the formulas).  ``weight`` is a full-grid table [npoints] or
+        [npoints, O] of any finite values, gathered by the same rows -- ``utils.get_inpainting_mask`` flattened, or a
+        per-channel mosaic; the mean runs over every evaluated element, those of weight 0 included.  Loss and gradient
+        come from one kernel (wire_point_loss_grad); backward through the network, Adam.  ``step_loss("mse")`` without
+        a weight leaves the parameters that ``step_tv(0.0)`` leaves on the same rows.
+
+        Returns the device loss (no host sync); the rows' outputs stay in ``self.y[:rows*O]`` and with ``keep_rec`` go
+        to ``self.rec``.  Any grid, single process."""
+        if self.world != 1:
+            raise NotImplementedError("step_loss is single-process")
+        code, delta = functional._loss_kind(kind, delta)
+        self._need_target("step_loss")
+        indices, first, B = self._rows_arg(indices, first, count, self.npoints)
+        if B < 1:
+            raise ValueError("step_loss needs at least one row")
+        w, wpe = functional._loss_weight(weight, self.npoints, self.O, self.target, rows="npoints")
+        self._reserve(B)
+        ip = self._opt_ptr(indices)
+        self._grid_coords(self._stream(), first, B, self.coords, ip)
+        return self._point_step(self.coords.data_ptr(), B,
+                                self._point_loss(code, delta, self.target, w, wpe, ip, first, B, self.rec))
+
+    def step_samples(self, coords: torch.Tensor, values: torch.Tensor, kind: str = "mse",
+                     weight: Optional[torch.Tensor] = None, delta: float = 1.0) -> torch.Tensor:
+        """One optimizer step on scattered samples: ``coords`` [n, in_features] may lie anywhere -- jittered grid
+        points, surface samples of a point cloud, the registered low-resolution pixels of a multi-image loop -- and are
+        read where they are (no copy, no grid lookup); ``values`` [n, O] are their targets, ``weight`` None, [n] or
+        [n, O]; all contiguous CUDA float32, n >= 1, and n may change from call to call.  The data term is ``kind``
+        with ``delta``, as in ``step_loss``.  The trainer's grid and target are not used, so a trainer built with
+        ``target=None`` serves.  Returns the device loss (no host sync); the outputs of the step stay in
+        ``self.y[:n*O]``.  Single process."""
+        if self.world != 1:
+            raise NotImplementedError("step_samples is single-process")
+        code, delta = functional._loss_kind(kind, delta)
+        D = int(self.desc.in_features)
+        if not isinstance(coords, torch.Tensor) or coords.dtype != torch.float32 or coords.dim() != 2 \
+                or coords.shape[0] < 1 or coords.shape[1] != D or not coords.is_contiguous() or not coords.is_cuda:
+            raise ValueError(f"coords must be a contiguous CUDA float32 tensor [n, {D}] with n >= 1")
+        n = int(coords.shape[0])
+        if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or tuple(values.shape) != (n, self.O) \
+                or not values.is_contiguous() or values.device != coords.device:
+            raise ValueError(f"values must be a contiguous float32 tensor [{n}, {self.O}] on the device of coords")
+        w, wpe = functional._loss_weight(weight, n, self.O, coords)
+        xy, tab = coords.detach(), values.detach()
+        self._reserve(n)
+        return self._point_step(xy.data_ptr(), n, self._point_loss(code, delta, tab, w, wpe, None, 0, n, None))
 
     # ------------------------------------------------------------------ multi-image super-resolution step
     def affine_coords(self, mats) -> torch.Tensor:
