@@ -443,6 +443,51 @@ int64_t wire_warp_coords_bwd_ws_bytes(int B, int64_t n_per);
 int wire_warp_coords_bwd(void* stream, const float* coords, const float* theta, const float* g_out, int B,
                          int64_t n_per, int pin_first, float* g_theta, float* g_in, void* ws, int64_t ws_bytes);
 
+/* Registering those frames from their intensities (wire_register.hip): a bilinear resampler with its
+ * coordinate gradient, and one Gauss-Newton iteration of a least-squares registration.  All pointers DEVICE.
+ * wire_remap_bilinear_fwd: img [H][W][C] channel last, C = 1..8; xy [n][2] = (x, y), 8-byte aligned; out [n][C].
+ *   normalized = 0: pixel coordinates, pixel centres at integers (cv2.remap); normalized = 1: F.grid_sample's
+ *   align_corners = False, x_pix = ((x + 1) W - 1) / 2.  Taps outside the image contribute 0 (BORDER_CONSTANT 0,
+ *   padding_mode = 'zeros'); a NaN or infinite coordinate gives 0.  In fp64 from the fp32 inputs, left to right, no
+ *   contraction, rounded to fp32 once: x0 = floor(x), fx = x - x0, taps a b / c d,
+ *     out = float( (1 - fy) ((1 - fx) a + fx b) + fy ((1 - fx) c + fx d) )
+ * wire_remap_bilinear_bwd_xy: g_xy[p] = float( sum_c g_out[p][c] d out_c / d (x, y) ), c in order, the derivative of the
+ *   interpolant on the cell chosen by floor (the right-hand derivative at integers):
+ *     d/dx = (1 - fy) (b - a) + fy (d - c),   d/dy = ((1 - fx) c + fx d) - ((1 - fx) a + fx b)
+ *   multiplied by W / 2, H / 2 for normalized = 1; 0 where the forward's coordinate is not finite or no tap is inside.
+ *   g_xy [n][2], 8-byte aligned.  There is no adjoint with respect to img.  One thread per row, no atomics.
+ * H, W or n < 1, C outside 1..8, normalized not 0 / 1, a NULL or misaligned pointer: WIRE_ERR_ARG before any HIP call.
+ *
+ * wire_register_gn_step: one iteration, for each frame b < B and each of its K start candidates, of
+ *     minimise over M   E(M) = sum_(i,j) w(i,j) (R(M (j, i, 1)) - F_b(i, j))^2
+ *   ref R [H][W]; frames F [B][H][W]; weight [B][H][W] or NULL (all ones); mats DEVICE fp64 [B][K][2][3] in pixel units,
+ *   updated in place.  A pixel counts when u = M (j, i, 1) lies in [0, W - 1] x [0, H - 1], its weight is not 0 and
+ *   F_b(i, j) is not 0 (an exact zero is the resampler's border fill).  R and its derivatives are sampled as above (a
+ *   coordinate exactly on the last row / column takes the last cell inside the image).  With r = R(u) - F and
+ *   J = (Rx j, Rx i, Rx, Ry j, Ry i, Ry), the first launch adds, in fp64, the 29 sums
+ *     S[0..21) = sum (w J_a) J_b (a <= b, row-major),  S[21..27) = sum (w J_a) r,  S[27] = sum (w r) r,  S[28] = sum w
+ *   (256 threads own 2048 consecutive pixels of one (b, k): a thread its 8 pixels in order, the wave by a fixed shuffle
+ *   tree, the four waves as (w0 + w1) + (w2 + w3)); the second adds each (b, k)'s partials in a fixed order, projects
+ *   onto the model -- 0 translation (tx, ty), 1 Euclidean (angle = atan2(m10, m00), tx, ty; the updated matrix is rebuilt
+ *   from cos / sin of the new angle), 2 affine (six entries) -- solves (A + damping diag A) delta = -g by Cholesky and
+ *   adds delta.  stats fp64 [B][K][4] = (S[27] / S[28]: the mean weighted squared residual AT THE INPUT MATRIX;
+ *   S[28] / (H W): the covered weight per pixel; |delta|; valid).  On a non-positive or non-finite pivot, a non-finite
+ *   result, S[28] = 0 or a covered fraction < min_cover the matrix is left as it was, |delta| = 0 and valid = 0.
+ *   No atomics, no host synchronisation: the same call gives the same bits, whatever ws held before.
+ *   ws: wire_register_gn_ws_bytes(B, K, H, W) bytes, 8-byte aligned; after the call its first B K 29 doubles hold the
+ *   sums S of every (b, k).
+ * B, K, H or W < 1, more workgroups than a grid holds, model outside 0..2, damping or min_cover negative or not finite,
+ * a misaligned pointer, or a NULL pointer other than weight: WIRE_ERR_ARG before any HIP call (the size query too); a ws
+ * that is too small: WIRE_ERR_SIZE.                                                                               */
+int wire_remap_bilinear_fwd(void* stream, const float* img, int H, int W, int C, const float* xy, int64_t n,
+                            int normalized, float* out);
+int wire_remap_bilinear_bwd_xy(void* stream, const float* img, int H, int W, int C, const float* xy, const float* g_out,
+                               int64_t n, int normalized, float* g_xy);
+int64_t wire_register_gn_ws_bytes(int B, int K, int H, int W);
+int wire_register_gn_step(void* stream, const float* ref, const float* frames, const float* weight, int B, int K, int H,
+                          int W, int model, double damping, double min_cover, double* mats, double* stats, void* ws,
+                          int64_t ws_bytes);
+
 /* Video compressive sensing (per-pixel coded exposure, modules/lin_inverse.py:42-95): the loss of a video estimate
  * against a coded video, fused with its backward.  The T frames of pixel p are multiplied by that pixel's mask and
  * summed in groups of nframes (lin_inverse.py:79-84) into C = ceil(T / nframes) coded frames; nframes > T gives one.

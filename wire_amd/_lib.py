@@ -23,6 +23,9 @@ MS_MAX_SCALES = 8   # WIRE_MS_MAX_SCALES
 ABI_VERSION = 1
 # enum wire_loss_kind: the data terms of wire_point_loss_grad
 LOSS_KIND = {"mse": 0, "l1": 1, "huber": 2, "logistic": 3}
+# the motion models of wire_register_gn_step (cv2's MOTION_TRANSLATION / MOTION_EUCLIDEAN / MOTION_AFFINE integers)
+MOTION_MODEL = {"translation": 0, "euclidean": 1, "affine": 2}
+REG_NSUM = 29       # the sums wire_register_gn_step leaves at the start of its workspace, per (frame, candidate)
 
 # every symbol include/wire_hip.h declares (tests check the .so exports them)
 SYMBOLS = [
@@ -42,6 +45,7 @@ SYMBOLS = [
     "wire_tv_add_grad", "wire_warp_coords_fwd", "wire_warp_coords_bwd_ws_bytes", "wire_warp_coords_bwd",
     "wire_iso_ws_bytes", "wire_iso_count", "wire_iso_emit", "wire_iso_tet_case", "wire_gauss3_blur",
     "wire_radon_vol_fwd", "wire_radon_vol_bwd", "wire_point_loss_grad",
+    "wire_remap_bilinear_fwd", "wire_remap_bilinear_bwd_xy", "wire_register_gn_ws_bytes", "wire_register_gn_step",
 ]
 
 
@@ -150,6 +154,11 @@ def _declare(l: C.CDLL) -> None:
     l.wire_warp_coords_bwd_ws_bytes.argtypes = [i32, i64]
     l.wire_warp_coords_bwd_ws_bytes.restype = i64
     l.wire_warp_coords_bwd.argtypes = [vp, vp, vp, vp, i32, i64, i32, vp, vp, vp, i64]
+    l.wire_remap_bilinear_fwd.argtypes = [vp, vp, i32, i32, i32, vp, i64, i32, vp]
+    l.wire_remap_bilinear_bwd_xy.argtypes = [vp, vp, i32, i32, i32, vp, vp, i64, i32, vp]
+    l.wire_register_gn_ws_bytes.argtypes = [i32, i32, i32, i32]
+    l.wire_register_gn_ws_bytes.restype = i64
+    l.wire_register_gn_step.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, i64]
     l.wire_iso_ws_bytes.argtypes = [i32, i32, i32]
     l.wire_iso_ws_bytes.restype = i64
     l.wire_iso_count.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]

@@ -777,6 +777,130 @@ def warp_coords(coords: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------
+# registering frames from their intensities: the bilinear resampler and one Gauss-Newton iteration (wire_register.hip)
+# ---------------------------------------------------------------------------
+class _RemapFunction(torch.autograd.Function):
+    """Bilinear samples of an image at given coordinates and their coordinate gradient: wire_remap_bilinear_fwd /
+    wire_remap_bilinear_bwd_xy."""
+
+    @staticmethod
+    def forward(ctx, img, xy, normalized):
+        L = _lib.lib()
+        im, x = img.detach(), xy.detach()
+        if x.data_ptr() % 8:                      # the kernels move a coordinate pair as one 8-byte word
+            x = x.clone()
+        H, W, Cc = (int(v) for v in im.shape)
+        n = x.numel() // 2
+        out = torch.empty(tuple(x.shape[:-1]) + (Cc,), dtype=torch.float32, device=x.device)
+        _lib.check(L.wire_remap_bilinear_fwd(_stream_ptr(x.device), im.data_ptr(), H, W, Cc, x.data_ptr(), n,
+                                             int(normalized), out.data_ptr()), "wire_remap_bilinear_fwd")
+        ctx.save_for_backward(im, x)
+        ctx.normalized = int(normalized)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        L = _lib.lib()
+        im, x = ctx.saved_tensors
+        _no_second_order("remap")
+        H, W, Cc = (int(v) for v in im.shape)
+        g = g_out.detach().to(torch.float32).contiguous()
+        g_xy = torch.empty_like(x)
+        _lib.check(L.wire_remap_bilinear_bwd_xy(_stream_ptr(x.device), im.data_ptr(), H, W, Cc, x.data_ptr(),
+                                                g.data_ptr(), x.numel() // 2, ctx.normalized, g_xy.data_ptr()),
+                   "wire_remap_bilinear_bwd_xy")
+        return None, g_xy, None
+
+
+def remap(img: torch.Tensor, xy: torch.Tensor, normalized: bool = False) -> torch.Tensor:
+    """Bilinear samples of ``img`` [H, W, C] (channel last, C = 1..8) at ``xy`` [..., 2] = (x, y): a new [..., C] tensor.
+
+    ``normalized=False``: pixel coordinates with pixel centres at integers, ``cv2.remap(img, x, y, INTER_LINEAR)`` with
+    ``BORDER_CONSTANT`` 0 -- but with exact weights, where cv2 quantises them to 1/32 pixel.  ``normalized=True``:
+    ``F.grid_sample(mode='bilinear', padding_mode='zeros', align_corners=False)``.  Taps outside the image contribute 0;
+    a NaN or infinite coordinate gives 0 and a zero gradient.  fp64 arithmetic rounded to fp32 once
+    (wire_remap_bilinear_fwd); the gradient reaches ``xy`` only (wire_remap_bilinear_bwd_xy: the derivative of the
+    interpolant on the cell chosen by ``floor``, first order only).  There is no adjoint with respect to the image -- a
+    general warp's would need atomics, and this library's adjoints are deterministic gathers -- so an ``img`` that
+    requires grad raises NotImplementedError.  Contiguous CUDA float32 tensors; CPU tensors raise WireHipError."""
+    if not isinstance(img, torch.Tensor) or not isinstance(xy, torch.Tensor):
+        raise ValueError("remap expects two tensors")
+    if normalized not in (False, True, 0, 1):
+        raise ValueError("normalized must be a bool")
+    if img.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(
+            "remap: the gradient reaches xy only; there is no adjoint with respect to the image (a general warp's would "
+            "need atomics, and this library's adjoints are deterministic gathers). Detach img.")
+    _require_cuda(img, "img")
+    _require_cuda(xy, "xy")
+    if img.dtype != torch.float32 or img.dim() != 3 or min(img.shape) < 1 or not 1 <= img.shape[2] <= 8 \
+            or not img.is_contiguous():
+        raise ValueError("img must be a contiguous float32 tensor [H, W, C] with C in 1..8")
+    if xy.dtype != torch.float32 or xy.dim() < 1 or xy.shape[-1] != 2 or xy.numel() < 2 or not xy.is_contiguous():
+        raise ValueError("xy must be a contiguous float32 tensor [..., 2] with at least one row")
+    if xy.device != img.device:
+        raise ValueError("img and xy must be on the same device")
+    return _RemapFunction.apply(img, xy, bool(normalized))
+
+
+def _motion_model(model) -> int:
+    if isinstance(model, str) and model in _lib.MOTION_MODEL:
+        return _lib.MOTION_MODEL[model]
+    if not isinstance(model, (bool, str)) and model in (0, 1, 2):
+        return int(model)
+    if not isinstance(model, (bool, str)) and model == 3:
+        raise NotImplementedError("homography registration is out of scope: translation, euclidean or affine")
+    raise ValueError(f"model must be one of {sorted(_lib.MOTION_MODEL)} (or cv2's 0 / 1 / 2), not {model!r}")
+
+
+def register_gn_step(ref: torch.Tensor, frames: torch.Tensor, mats: torch.Tensor, weight=None, model="euclidean",
+                     damping: float = 0.0, min_cover: float = 0.0, ws=None) -> torch.Tensor:
+    """One Gauss-Newton iteration of the intensity registration of ``frames`` [B, H, W] onto ``ref`` [H, W]
+    (wire_register_gn_step): ``mats`` -- CUDA float64 [B, K, 2, 3], pixel units, K start candidates per frame -- is
+    UPDATED IN PLACE towards the minimum of ``sum w (ref(M (j, i, 1)) - frame(i, j))^2`` and the float64 stats
+    [B, K, 4] = (mean weighted squared residual at the INPUT matrix, covered weight per pixel, step norm, valid) are
+    returned.  ``weight``: [B, H, W] float32 or None.  ``model``: "translation" | "euclidean" | "affine" (or cv2's 0 / 1 /
+    2).  An invalid candidate (singular system, covered fraction < ``min_cover``, non-finite values) keeps its matrix.
+    No host synchronisation.  ``ws``: a uint8 workspace of wire_register_gn_ws_bytes(B, K, H, W) bytes to reuse across
+    calls; after the call its first B * K * 29 doubles hold the normal equations' sums."""
+    m = _motion_model(model)
+    for t, what in ((ref, "ref"), (frames, "frames"), (mats, "mats")):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what} must be a tensor")
+        _require_cuda(t, what)
+    if ref.dtype != torch.float32 or ref.dim() != 2 or ref.numel() < 1 or not ref.is_contiguous():
+        raise ValueError("ref must be a contiguous float32 tensor [H, W]")
+    H, W = int(ref.shape[0]), int(ref.shape[1])
+    if frames.dtype != torch.float32 or frames.dim() != 3 or frames.shape[0] < 1 or tuple(frames.shape[1:]) != (H, W) \
+            or not frames.is_contiguous():
+        raise ValueError(f"frames must be a contiguous float32 tensor [B, {H}, {W}]")
+    B = int(frames.shape[0])
+    if mats.dtype != torch.float64 or mats.dim() != 4 or mats.shape[0] != B or mats.shape[1] < 1 \
+            or tuple(mats.shape[2:]) != (2, 3) or not mats.is_contiguous():
+        raise ValueError(f"mats must be a contiguous float64 tensor [{B}, K, 2, 3]")
+    K = int(mats.shape[1])
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor):
+            raise ValueError("weight must be a tensor or None")
+        _require_cuda(weight, "weight")
+        if weight.dtype != torch.float32 or tuple(weight.shape) != (B, H, W) or not weight.is_contiguous():
+            raise ValueError(f"weight must be a contiguous float32 tensor [{B}, {H}, {W}]")
+    if not (float(damping) >= 0.0 and float(min_cover) >= 0.0):
+        raise ValueError("damping and min_cover must be >= 0")
+    dev = ref.device
+    if any(t.device != dev for t in (frames, mats)) or (weight is not None and weight.device != dev):
+        raise ValueError("all tensors must be on the same device")
+    if ws is None:
+        ws = _workspace("wire_register_gn_ws_bytes", dev, B, K, H, W)
+    stats = torch.empty(B, K, 4, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().wire_register_gn_step(
+        _stream_ptr(dev), ref.data_ptr(), frames.data_ptr(), weight.data_ptr() if weight is not None else None, B, K, H,
+        W, m, float(damping), float(min_cover), mats.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel()),
+        "wire_register_gn_step")
+    return stats
+
+
+# ---------------------------------------------------------------------------
 # iso-surface extraction on the device (wire_iso_count / wire_iso_emit) and the blur of march_and_save's `smoothen`
 # ---------------------------------------------------------------------------
 def _check_volume(volume, what: str, min_side: int = 1) -> None:
