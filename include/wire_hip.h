@@ -488,6 +488,70 @@ int wire_register_gn_step(void* stream, const float* ref, const float* frames, c
                           int W, int model, double damping, double min_cover, double* mats, double* stats, void* ws,
                           int64_t ws_bytes);
 
+/* Image-to-image resampling in cv2.resize's modes, its adjoint and the super-resolution loss under it (wire_resize.hip,
+ * DESIGN section 31).  R = R_v (x) R_h acts on a channel-last image x [H][W][C] (row n = i*W + j is the network's own
+ * layout) and gives [Hl][Wl][C]; it is separable and linear, and each axis (n_in sources, n_out outputs, scale s: sy for
+ * the rows, sx for the columns; cv2 uses s = n_in / n_out with an explicit size and s = 1 / f with fx / fy) is a table.
+ * Output d of an axis, in fp64:
+ *   NEAREST  one tap at min(floor(d s), n_in - 1)
+ *   LINEAR   x = (d + 0.5) s - 0.5, i = floor(x), f = x - i; taps (i, 1 - f), (i + 1, f)
+ *   CUBIC    the same x, i, f; taps i - 1 .. i + 2 with the Keys kernel at A = -0.75:
+ *              w0 = ((A (f+1) - 5A)(f+1) + 8A)(f+1) - 4A,  w1 = ((A+2) f - (A+3)) f^2 + 1,  w2 = w1 at 1 - f,
+ *              w3 = 1 - w0 - w1 - w2
+ *   AREA     the cell [a, b) = [d s, min((d + 1) s, n_in)); every source pixel i, floor(a) <= i < ceil(b), whose overlap
+ *            min(i + 1, b) - max(i, a) is positive is a tap of weight overlap / (b - a)
+ * Tap indices are clamped to [0, n_in - 1] and taps that meet after clamping are added into one (in tap order), so every
+ * output has a contiguous run of distinct sources start[d] .. start[d] + count[d] - 1.  s == 1 gives f = 0 and all weight
+ * on tap d in every mode; that one tap (weight exactly 1) is kept and its zero-weight neighbours are not.  A linear /
+ * cubic x more than four pixels outside the image puts weight 1 on the border pixel.  Weights are rounded to fp32 once,
+ * at the end.  start and start + count are non-decreasing in d, so the outputs whose run contains source i form a
+ * contiguous range lo[i] .. hi[i] (lo = hi + 1: none), and R^T is a GATHER over that range: no atomics.
+ * These are cv2's documented formulas, by construction and NOT measured against cv2 (which also quantises its weights
+ * for 8-bit images).  Two differences on purpose: cv2's non-integer INTER_AREA drops partial overlaps below 1e-3 without
+ * renormalising, this operator keeps them; cv2's INTER_AREA with n_out > n_in silently becomes a linear variant, here it
+ * is refused.
+ *
+ * tab: DEVICE, 4-byte aligned, wire_resize_tab_bytes bytes -- per axis (rows first) int32 start[n_out], count[n_out],
+ *   lo[n_in], hi[n_in], then fp32 w[n_out][K], K = the axis' largest count (weights behind count[d] are 0).  The host
+ *   evaluates the same run function as the kernel, so it knows K, and the layout, without reading the device.
+ * wire_resize_tables: one launch writes all of tab (fp64 arithmetic, no contraction).  The forward, the adjoint and the
+ *   loss read tab and nothing else about the geometry -- the adjoint uses the forward's own fp32 weights and is its
+ *   exact transpose -- but every call takes the same (H, W, Hl, Wl, mode, sy, sx), which give the layout.
+ * wire_resize_fwd: y [Hl][Wl][C] = R x.  wire_resize_bwd: g_x [H][W][C] = R^T g_y; EVERY element of g_x is written, the
+ *   sources that no output touches with +0.0.  One thread per element of the side written, any C >= 1, the channel
+ *   fastest; fp32 accumulation from +0.0, rows outer, columns inner, both ascending:
+ *     acc = fma(wv[a], r_a, acc),   r_a = (... fma(wh[1], x[a][1], fma(wh[0], x[a][0], +0.0)) ...)
+ *   (the adjoint: the same with the outputs lo .. hi in place of the taps).  An equal-size call copies the bits (-0.0
+ *   becomes +0.0).  x / y and g_y / g_x must not overlap.
+ * wire_resize_mse_grad: the super-resolution loss of wire_avgpool_mse_grad under R.  y [H*W][O], gt_lr [Hl*Wl][O]:
+ *     rec = R y;   loss = sum (rec - gt_lr)^2 / (Hl Wl O);   g_y = R^T ( fl(2 / (Hl Wl O)) (rec - gt_lr) )
+ *   Two launches: the forward stores the scaled residual to ws, rec to rec_lr (optional, NULL = not wanted) and a sum of
+ *   squares per block of 256 threads (wire_block_sum) to partial; the gather adjoint writes EVERY element of g_y, and its
+ *   block 0 adds the blocks' sums in a fixed order (wire_block_sum) and overwrites loss_out[0].  No atomics, no host
+ *   synchronisation: the same call gives the same bits, whatever ws, partial and the outputs held before.
+ *   ws: wire_resize_mse_grad_ws_bytes(Hl, Wl, O) bytes, 4-byte aligned; partial: >= 1024 floats of scratch.
+ * H, W, Hl or Wl < 1, C / O < 1, a mode outside the enum, AREA with n_out > n_in on either axis or with a last cell that
+ * begins outside the source ((n_out - 1) s >= n_in), a scale that is not finite or <= 0, sizes beyond 63 bits, ws_bytes
+ * too small, or a NULL pointer other than rec_lr: WIRE_ERR_ARG before any HIP call (the size queries too).  tab is
+ * trusted to be what wire_resize_tables wrote for the same geometry; the kernels hold every index they read from it
+ * inside the arrays.                                                                                              */
+typedef enum wire_resize_mode {   /* cv2's INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA */
+  WIRE_RESIZE_NEAREST = 0,
+  WIRE_RESIZE_LINEAR = 1,
+  WIRE_RESIZE_CUBIC = 2,
+  WIRE_RESIZE_AREA = 3
+} wire_resize_mode;
+int64_t wire_resize_tab_bytes(int H, int W, int Hl, int Wl, int mode, double sy, double sx);
+int64_t wire_resize_mse_grad_ws_bytes(int Hl, int Wl, int O);
+int wire_resize_tables(void* stream, int H, int W, int Hl, int Wl, int mode, double sy, double sx, void* tab);
+int wire_resize_fwd(void* stream, const void* tab, int H, int W, int Hl, int Wl, int mode, double sy, double sx,
+                    const float* x, int C, float* y);
+int wire_resize_bwd(void* stream, const void* tab, int H, int W, int Hl, int Wl, int mode, double sy, double sx,
+                    const float* g_y, int C, float* g_x);
+int wire_resize_mse_grad(void* stream, const void* tab, int H, int W, int Hl, int Wl, int mode, double sy, double sx,
+                         const float* y, int O, const float* gt_lr, float* g_y, float* rec_lr, float* loss_out,
+                         void* ws, int64_t ws_bytes, float* partial);
+
 /* Video compressive sensing (per-pixel coded exposure, modules/lin_inverse.py:42-95): the loss of a video estimate
  * against a coded video, fused with its backward.  The T frames of pixel p are multiplied by that pixel's mask and
  * summed in groups of nframes (lin_inverse.py:79-84) into C = ceil(T / nframes) coded frames; nframes > T gives one.

@@ -25,6 +25,8 @@ ABI_VERSION = 1
 LOSS_KIND = {"mse": 0, "l1": 1, "huber": 2, "logistic": 3}
 # the motion models of wire_register_gn_step (cv2's MOTION_TRANSLATION / MOTION_EUCLIDEAN / MOTION_AFFINE integers)
 MOTION_MODEL = {"translation": 0, "euclidean": 1, "affine": 2}
+# enum wire_resize_mode: cv2's INTER_NEAREST / INTER_LINEAR / INTER_CUBIC / INTER_AREA integers
+RESIZE_MODE = {"nearest": 0, "linear": 1, "cubic": 2, "area": 3}
 REG_NSUM = 29       # the sums wire_register_gn_step leaves at the start of its workspace, per (frame, candidate)
 
 # every symbol include/wire_hip.h declares (tests check the .so exports them)
@@ -46,6 +48,8 @@ SYMBOLS = [
     "wire_iso_ws_bytes", "wire_iso_count", "wire_iso_emit", "wire_iso_tet_case", "wire_gauss3_blur",
     "wire_radon_vol_fwd", "wire_radon_vol_bwd", "wire_point_loss_grad",
     "wire_remap_bilinear_fwd", "wire_remap_bilinear_bwd_xy", "wire_register_gn_ws_bytes", "wire_register_gn_step",
+    "wire_resize_tab_bytes", "wire_resize_mse_grad_ws_bytes", "wire_resize_tables", "wire_resize_fwd", "wire_resize_bwd",
+    "wire_resize_mse_grad",
 ]
 
 
@@ -159,6 +163,15 @@ def _declare(l: C.CDLL) -> None:
     l.wire_register_gn_ws_bytes.argtypes = [i32, i32, i32, i32]
     l.wire_register_gn_ws_bytes.restype = i64
     l.wire_register_gn_step.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, i64]
+    geom = [i32, i32, i32, i32, i32, C.c_double, C.c_double]          # H, W, Hl, Wl, mode, sy, sx
+    l.wire_resize_tab_bytes.argtypes = geom
+    l.wire_resize_tab_bytes.restype = i64
+    l.wire_resize_mse_grad_ws_bytes.argtypes = [i32, i32, i32]
+    l.wire_resize_mse_grad_ws_bytes.restype = i64
+    l.wire_resize_tables.argtypes = [vp] + geom + [vp]
+    l.wire_resize_fwd.argtypes = [vp, vp] + geom + [vp, i32, vp]
+    l.wire_resize_bwd.argtypes = [vp, vp] + geom + [vp, i32, vp]
+    l.wire_resize_mse_grad.argtypes = [vp, vp] + geom + [vp, i32, vp, vp, vp, vp, vp, i64, vp]
     l.wire_iso_ws_bytes.argtypes = [i32, i32, i32]
     l.wire_iso_ws_bytes.restype = i64
     l.wire_iso_count.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]

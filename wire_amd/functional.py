@@ -963,3 +963,137 @@ def gauss3_blur(volume: torch.Tensor, sigma: float = 1.0) -> torch.Tensor:
     _lib.check(L.wire_gauss3_blur(_stream_ptr(vol.device), vol.data_ptr(), H, W, T, float(sigma), tmp.data_ptr(),
                                   out.data_ptr()), "wire_gauss3_blur")
     return out
+
+
+# ---------------------------------------------------------------------------
+# image-to-image resampling in cv2.resize's modes and its adjoint (wire_resize.hip)
+# ---------------------------------------------------------------------------
+def _resize_mode(interpolation) -> int:
+    if isinstance(interpolation, str) and interpolation in _lib.RESIZE_MODE:
+        return _lib.RESIZE_MODE[interpolation]
+    if not isinstance(interpolation, (bool, str)) and interpolation in (0, 1, 2, 3):
+        return int(interpolation)
+    raise ValueError(f"interpolation must be one of {sorted(_lib.RESIZE_MODE)} or cv2's integer 0..3, "
+                     f"not {interpolation!r}")
+
+
+def resize_geometry(H: int, W: int, dsize=None, fx=None, fy=None, interpolation="linear"):
+    """``(H, W, Hl, Wl, mode, sy, sx)`` as the wire_resize_* entry points take them, by cv2.resize's rules: an explicit
+    ``dsize = (Wl, Hl)`` gives the scale ``n_in / n_out`` per axis; otherwise ``fx`` and ``fy`` give
+    ``n_out = rint(n_in * f)`` (round half to even, cv2's cvRound) and the scale ``1 / f``.  ValueError for an output
+    side < 1, a factor that is not finite or <= 0, an unknown interpolation, and ``area`` with an output larger than the
+    input on either axis (cv2 silently switches to a linear variant there; this library does not imitate it).  Host
+    only."""
+    mode = _resize_mode(interpolation)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"resize: an image of {H} x {W}")
+    if dsize is not None and tuple(dsize) != (0, 0):
+        if len(dsize) != 2:
+            raise ValueError("resize: dsize must be (Wl, Hl)")
+        Wl, Hl = int(dsize[0]), int(dsize[1])
+        if Hl < 1 or Wl < 1:
+            raise ValueError(f"resize: an output of {Hl} x {Wl}")
+        sy, sx = H / Hl, W / Wl
+    else:
+        if fx is None or fy is None:
+            raise ValueError("resize needs dsize = (Wl, Hl) or both fx and fy")
+        fx, fy = float(fx), float(fy)
+        if not (0.0 < fx < float("inf") and 0.0 < fy < float("inf")):
+            raise ValueError(f"resize: fx = {fx}, fy = {fy} must be finite and > 0")
+        Hl, Wl = int(round(H * fy)), int(round(W * fx))       # Python's round is half to even, as cvRound
+        if Hl < 1 or Wl < 1:
+            raise ValueError(f"resize: fx = {fx}, fy = {fy} give an output of {Hl} x {Wl}")
+        sy, sx = 1.0 / fy, 1.0 / fx
+    if mode == _lib.RESIZE_MODE["area"] and (Hl > H or Wl > W):
+        raise ValueError(f"resize: area does not up-scale ({H} x {W} -> {Hl} x {Wl}); cv2 switches to a linear variant "
+                         "there, use interpolation='linear'")
+    return H, W, Hl, Wl, mode, sy, sx
+
+
+def resize_tables(geom, dev: torch.device) -> torch.Tensor:
+    """The device tables of a geometry (wire_resize_tables): a uint8 tensor to pass wherever a wire_resize_* entry point
+    takes ``tab``.  They depend on the geometry alone; keep them across calls."""
+    L = _lib.lib()
+    tab = torch.empty(_lib.check(L.wire_resize_tab_bytes(*geom), "wire_resize_tab_bytes"), dtype=torch.uint8, device=dev)
+    _lib.check(L.wire_resize_tables(_stream_ptr(dev), *geom, tab.data_ptr()), "wire_resize_tables")
+    return tab
+
+
+def _resize_apply(entry: str, tab, geom, src: torch.Tensor, Cc: int, out_shape) -> torch.Tensor:
+    out = torch.empty(out_shape, dtype=torch.float32, device=src.device)
+    _lib.check(getattr(_lib.lib(), entry)(_stream_ptr(src.device), tab.data_ptr(), *geom, src.data_ptr(), Cc,
+                                          out.data_ptr()), entry)
+    return out
+
+
+class _ResizeFunction(torch.autograd.Function):
+    """y = R x (wire_resize_fwd) and g_x = R^T g_y (wire_resize_bwd), or the two swapped for the adjoint; both read the
+    same tables."""
+
+    @staticmethod
+    def forward(ctx, img, geom, adjoint):
+        x = img.detach()
+        H, W, Hl, Wl = geom[:4]
+        Cc = x.numel() // ((Hl * Wl) if adjoint else (H * W))
+        tab = resize_tables(geom, x.device)
+        shape = ((H, W) if adjoint else (Hl, Wl)) + tuple(x.shape[2:])
+        ctx.save_for_backward(tab)
+        ctx.geom, ctx.adjoint, ctx.Cc, ctx.in_shape = geom, adjoint, Cc, tuple(x.shape)
+        return _resize_apply("wire_resize_bwd" if adjoint else "wire_resize_fwd", tab, geom, x, Cc, shape)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        tab, = ctx.saved_tensors
+        _no_second_order("resize")
+        g = g_out.detach().to(torch.float32).contiguous()
+        return _resize_apply("wire_resize_fwd" if ctx.adjoint else "wire_resize_bwd", tab, ctx.geom, g, ctx.Cc,
+                             ctx.in_shape), None, None
+
+
+def _resize_image(img, what: str) -> None:
+    if not isinstance(img, torch.Tensor) or img.dim() not in (2, 3) or img.numel() == 0:
+        raise ValueError(f"{what} expects a non-empty [H, W] or [H, W, C] tensor")
+
+
+def _resize_device(img: torch.Tensor, what: str) -> None:
+    _require_cuda(img, what)
+    if img.dtype != torch.float32 or not img.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 tensor")
+
+
+def resize(img: torch.Tensor, dsize=None, fx=None, fy=None, interpolation="linear") -> torch.Tensor:
+    """``cv2.resize(img, dsize, fx=fx, fy=fy, interpolation=...)`` on the device: ``img`` is a contiguous CUDA float32
+    [H, W] or [H, W, C] tensor (channel last, any C), the result a new [Hl, Wl] or [Hl, Wl, C] one.
+
+    ``dsize = (Wl, Hl)`` is in cv2's order; ``None`` or ``(0, 0)`` takes the size from ``fx`` / ``fy`` instead,
+    ``n_out = rint(n_in * f)``.  ``interpolation``: ``"nearest"``, ``"linear"``, ``"cubic"``, ``"area"`` or cv2's integer
+    for them (0, 1, 2, 3).  The operator is the separable table include/wire_hip.h defines -- pixel centres at
+    ``(d + 0.5) * scale - 0.5``, border replicated, the Keys cubic at A = -0.75, area as the exact overlap average --
+    with fp32 weights and fp32 accumulation in a fixed order.  It agrees with cv2 BY CONSTRUCTION from cv2's documented
+    formulas (and with ``F.interpolate(align_corners=False)`` / ``avg_pool2d``, which the tests measure); it has NOT been
+    measured against cv2.  Two differences on purpose: cv2's non-integer INTER_AREA drops partial overlaps below 1e-3
+    without renormalising, this operator keeps them; cv2's INTER_AREA up-scaling (silently a linear variant) is not
+    provided -- ``area`` with an output side larger than the input raises ValueError.
+
+    Differentiable with respect to ``img`` through the adjoint kernel (wire_resize_bwd: a gather, no atomics, the same
+    bits every time), first order only.  CPU tensors raise WireHipError; other ranks, dtypes or sizes ValueError."""
+    _resize_image(img, "resize")
+    geom = resize_geometry(img.shape[0], img.shape[1], dsize, fx, fy, interpolation)
+    _resize_device(img, "img")
+    return _ResizeFunction.apply(img, geom, False)
+
+
+def resize_adjoint(g: torch.Tensor, shape, dsize=None, fx=None, fy=None, interpolation="linear") -> torch.Tensor:
+    """``R^T g`` for the ``R`` of ``resize`` on an image of ``shape = (H, W)``: ``g`` is [Hl, Wl] or [Hl, Wl, C] (the
+    size ``resize`` would return for the same ``dsize`` / ``fx`` / ``fy``), the result [H, W] or [H, W, C].  The exact
+    transpose: the same fp32 weights, gathered (wire_resize_bwd); a source that no output touches receives +0.0.
+    Differentiable with respect to ``g`` (through the forward kernel), first order only."""
+    _resize_image(g, "resize_adjoint")
+    if len(shape) != 2:
+        raise ValueError("resize_adjoint: shape must be (H, W)")
+    geom = resize_geometry(shape[0], shape[1], dsize, fx, fy, interpolation)
+    if (int(g.shape[0]), int(g.shape[1])) != (geom[2], geom[3]):
+        raise ValueError(f"resize_adjoint: g is {tuple(g.shape[:2])}, the resized image is {(geom[2], geom[3])}")
+    _resize_device(g, "g")
+    return _ResizeFunction.apply(g, geom, True)

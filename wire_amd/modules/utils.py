@@ -2,7 +2,8 @@
 
 Only the functions the training/eval loop of wire_image_denoise.py and
 wire_occupancy.py touch are provided: coordinate grids, PSNR, parameter count,
-normalisation, the noise model, the total-variation regulariser and logging.  Plotting / montage / table helpers
+normalisation, the noise model, the total-variation regulariser, ``resize`` (the per-channel INTER_AREA of
+modules/utils.py:179-200, on the device) and logging.  Plotting / montage / table helpers
 are out of scope -- except ``get_layer_outputs`` + ``build_montage``, the per-layer
 visualisation query SURVEY section 8 (f)3 names.
 """
@@ -46,6 +47,26 @@ def add_salt_and_pepper_noise(image, salt_prob, pepper_prob):
     noisy[np.random.random(image.shape[:2]) < salt_prob] = 255
     noisy[np.random.random(image.shape[:2]) < pepper_prob] = 0
     return noisy
+
+
+def resize(cube, scale):
+    """A multi-channel image stack (H, W, nchan) scaled by ``fx = fy = scale`` per channel with ``INTER_AREA``
+    (modules/utils.py:179-200), on the device: ``functional.resize(cube, None, fx=scale, fy=scale, "area")``, so the
+    output is ``rint(H * scale) x rint(W * scale)`` (round half to even).  A numpy array comes back as a numpy array of
+    the same dtype (it is computed in float32 on the current CUDA device); a CUDA float32 tensor comes back as a tensor.
+    ``scale > 1`` is a ValueError: cv2's INTER_AREA silently becomes a linear variant when it up-scales and this
+    library does not imitate it.  The operator is built from cv2's documented formulas and has not been measured
+    against cv2; a non-integer factor keeps the partial overlaps below 1e-3 that cv2 drops without renormalising."""
+    from .. import functional
+    if getattr(cube, "ndim", 0) != 3:
+        raise ValueError("resize expects an (H, W, nchan) image stack")
+    functional.resize_geometry(cube.shape[0], cube.shape[1], None, scale, scale, "area")   # its ValueErrors, before a device
+    if isinstance(cube, torch.Tensor):
+        return functional.resize(cube, None, fx=scale, fy=scale, interpolation="area")
+    cube = np.asarray(cube)
+    dev = torch.from_numpy(np.ascontiguousarray(cube, dtype=np.float32)).to("cuda")
+    out = functional.resize(dev, None, fx=scale, fy=scale, interpolation="area")
+    return out.cpu().numpy().astype(cube.dtype, copy=False)
 
 
 def get_inpainting_mask(imsize, mask_type='random2d', mask_frac=0.5):

@@ -618,6 +618,52 @@ class FusedTrainer:
                                                     self.partial.data_ptr()), "avgpool_mse_grad")
         return self._raster_step(loss, prior=(H, W, 1, lam, 0.0))
 
+    def step_resized(self, gt_lr: torch.Tensor, size, interpolation="area", rec_lr: Optional[torch.Tensor] = None,
+                     lambda_tv: float = 0.0) -> torch.Tensor:
+        """``step_downsampled`` under any of ``cv2.resize``'s degradations: the model is evaluated on the WHOLE
+        high-resolution grid in raster order, ``functional.resize`` with ``interpolation`` ("nearest", "linear",
+        "cubic", "area" or cv2's integer) brings the reconstruction to ``size = (Hl, Wl)``, the resolution of ``gt_lr``
+        ([Hl*Wl, O], device float32), at the scale ``n_in / n_out`` per axis -- a non-integer factor and sides that the
+        factor does not divide are fine -- and loss = mean squared error there; backward through the operator's exact
+        adjoint (wire_resize_mse_grad: a gather, no atomics) and the network, Adam.  ``area`` needs
+        ``Hl <= H and Wl <= W`` (ValueError otherwise: cv2's INTER_AREA up-scaling is not provided).  The operator
+        follows cv2's documented formulas and has not been measured against cv2; its non-integer ``area`` keeps the
+        partial overlaps below 1e-3 that cv2 drops without renormalising.
+        The high-resolution reconstruction of this step stays in ``self.y`` ([H*W, O]); ``rec_lr`` (optional) receives
+        the resized one.  ``lambda_tv`` as in ``step_downsampled``: != 0 adds ``lambda_tv *
+        utils.total_variation_loss`` of the high-resolution reconstruction, the returned loss is the total and
+        ``self.tv_parts`` holds [loss, mse, tv, 0]; with 0.0 that kernel is not launched.  The tables and the workspace
+        are made once per (size, interpolation) and reused.
+        2-D grids, single process (an output's taps must not straddle two shards)."""
+        self._need_grid("step_resized")
+        lam = self._tv_weight("lambda_tv", lambda_tv)
+        H, W = int(self.grid[0]), int(self.grid[1])
+        if len(size) != 2:
+            raise ValueError("size must be (Hl, Wl)")
+        Hl, Wl = int(size[0]), int(size[1])
+        geom = functional.resize_geometry(H, W, (Wl, Hl), None, None, interpolation)
+        gt = self._f32_elems("gt_lr", gt_lr, Hl * Wl, self.O)
+        self._f32_like("rec_lr", rec_lr, gt, "gt_lr")
+        name = f"_resize_tab_{Hl}x{Wl}_{geom[4]}"                         # one table per (size, interpolation), kept
+        if getattr(self, name, None) is None:
+            nb = _lib.check(self.L.wire_resize_tab_bytes(*geom), "wire_resize_tab_bytes")
+            try:
+                _lib.check(self.L.wire_resize_tables(self._stream(), *geom,
+                                                     self._buf(name, nb, torch.uint8).data_ptr()), "resize_tables")
+            except Exception:
+                self.__dict__.pop(name, None)                                # never keep a table that was not written
+                raise
+        tab = getattr(self, name)
+        wsb = _lib.check(self.L.wire_resize_mse_grad_ws_bytes(Hl, Wl, self.O), "wire_resize_mse_grad_ws_bytes")
+        ws = self._buf("_resize_ws", wsb, torch.uint8)
+
+        def loss(stream, g):
+            _lib.check(self.L.wire_resize_mse_grad(stream, tab.data_ptr(), *geom, self.y.data_ptr(), self.O,
+                                                   gt.data_ptr(), self.gy.data_ptr(), self._opt_ptr(rec_lr),
+                                                   self._loss_slot(g)[0], ws.data_ptr(), ws.numel(),
+                                                   self.partial.data_ptr()), "resize_mse_grad")
+        return self._raster_step(loss, prior=(H, W, 1, lam, 0.0))
+
     # ------------------------------------------------------------------ total-variation regularised step
     def step_tv(self, lambda_tv: float, indices: Optional[torch.Tensor] = None, first: int = 0,
                 count: Optional[int] = None) -> torch.Tensor:
