@@ -552,6 +552,51 @@ int wire_resize_mse_grad(void* stream, const void* tab, int H, int W, int Hl, in
                          const float* y, int O, const float* gt_lr, float* g_y, float* rec_lr, float* loss_out,
                          void* ws, int64_t ws_bytes, float* partial);
 
+/* Volume rendering of a 3-D net along camera rays (wire_render.hip): the sampler that turns rays
+ * into the net's input rows, the emission-absorption compositing of the net's rows into one colour per ray, its
+ * adjoint, and the loss kernel of a training step.  All pointers DEVICE fp32.  R rays, S >= 1 samples each; the net's
+ * row of sample s of ray r is y[r S + s] = (c_raw[0..C), s_raw) with C = O - 1 colour channels, O in 2..8.
+ * wire_ray_samples: rays [R][6] = (origin, direction); the ray's bounds are (near, far) = bounds[r] when bounds
+ *   [R][2] != NULL, else the two scalars (finite).  jitter [R][S] holds u in [0, 1); NULL means midpoints, u = 0.5.  In
+ *   fp64 from the fp32 inputs, left to right, no contraction, each output rounded to fp32 once:
+ *     t_s = near + ((s + u_s) (far - near)) / S,   t_{s+1} likewise, and far for the last sample,
+ *     coords[r S + s] = o + t_s d,   ts[r][s] = t_s,   deltas[r][s] = (t_{s+1} - t_s) sqrt(dx dx + dy dy + dz dz).
+ *   A ray with far <= near (or a NaN bound) gets t_s = near and deltas = 0 for every sample: it composites to the
+ *   background and receives zero gradient.  coords [R S][3], ts and deltas [R][S]; one thread per sample.
+ * wire_composite_fwd: density = 0: sigma = softplus(s_raw); 1: sigma = max(s_raw, 0).  c = sigmoid(c_raw),
+ *   a_s = sigma_s deltas_s,  tau_s = sum_{j<s} a_j,  T_s = exp(-tau_s),  w_s = T_s (1 - exp(-a_s)),  T_S = exp(-tau_S):
+ *     rgb[r] = sum_s w_s c_s + T_S bg,   acc[r] = 1 - T_S,   depth[r] = sum_s w_s ts_s
+ *   bg [C], NULL = 0; acc and depth [R] are optional outputs; rgb [R][C].
+ * wire_composite_bwd: g_rgb [R][C], optional g_acc and g_depth [R] (NULL = 0); EVERY element of g_y [R S][O] is
+ *   written.  With q_s = <c_s, g_rgb> + ts_s g_depth and q_bg = <bg, g_rgb> - g_acc (acc = 1 - T_S enters through T_S
+ *   alone; g_acc appears nowhere else),
+ *     d/dsigma_s = deltas_s ( T_{s+1} q_s - sum_{j>s} w_j q_j - T_S q_bg ),  times softplus' = sigmoid(s_raw) or the
+ *     mask s_raw > 0;   d/dc_raw_s = w_s g_rgb (.) c (1 - c).
+ * wire_composite_mse_grad: one launch runs the forward sweep,
+ *     loss_out[0] = shard * sum (rgb - target)^2 / (R C),   g_rgb = 2 shard / (R C) * (rgb - target)
+ *   (the factor a single fp32 number, the residual of the fp32-rounded rgb) and the reverse sweep with g_acc = g_depth
+ *   = 0; it writes loss_out[0], every element of g_y and, if rgb != NULL, rgb.  target [R][C].  shard is
+ *   wire_mse_grad's `weight`.  partial: >= 2048 floats of scratch.  g_y and rgb carry the bits of wire_composite_fwd,
+ *   that residual formed in fp32, and wire_composite_bwd.
+ * A wave owns a ray and its lanes consecutive samples, 64 at a time; a_s, tau, T, w, the sums over samples and the
+ * suffix sum (a reverse sweep, not total minus prefix) are fp64, softplus and sigmoid fp32, every output rounded to fp32
+ * once.  No exponential of a positive argument, no inf - inf: finite for every finite input.  No atomics; which lane
+ * adds what, in which order, depends on (R, S, O) alone: the same call gives the same bits, whatever partial held.
+ * y and g_y are 16-byte aligned, everything else 4-byte.  R or S < 1, O outside 2..8, density outside {0, 1}, R S O
+ * beyond 63 bits, more workgroups than a grid holds (2^31 - 1; a workgroup takes 4 rays, the sampler's 256 samples),
+ * scalar bounds or shard not finite, a misaligned pointer, or a NULL pointer other than bounds / jitter / bg / acc /
+ * depth / g_acc / g_depth / rgb of the loss kernel: WIRE_ERR_ARG before any HIP call.  No workspace beyond partial.  */
+int wire_ray_samples(void* stream, const float* rays, const float* bounds, float near_, float far_, const float* jitter,
+                     int64_t R, int S, float* coords, float* ts, float* deltas);
+int wire_composite_fwd(void* stream, const float* y, const float* ts, const float* deltas, const float* bg, int64_t R,
+                       int S, int O, int density, float* rgb, float* acc, float* depth);
+int wire_composite_bwd(void* stream, const float* y, const float* ts, const float* deltas, const float* bg,
+                       const float* g_rgb, const float* g_acc, const float* g_depth, int64_t R, int S, int O,
+                       int density, float* g_y);
+int wire_composite_mse_grad(void* stream, const float* y, const float* ts, const float* deltas, const float* bg,
+                            const float* target, int64_t R, int S, int O, int density, float shard, float* g_y,
+                            float* loss_out, float* rgb, float* partial);
+
 /* Video compressive sensing (per-pixel coded exposure, modules/lin_inverse.py:42-95): the loss of a video estimate
  * against a coded video, fused with its backward.  The T frames of pixel p are multiplied by that pixel's mask and
  * summed in groups of nframes (lin_inverse.py:79-84) into C = ceil(T / nframes) coded frames; nframes > T gives one.

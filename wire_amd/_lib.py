@@ -27,7 +27,9 @@ LOSS_KIND = {"mse": 0, "l1": 1, "huber": 2, "logistic": 3}
 MOTION_MODEL = {"translation": 0, "euclidean": 1, "affine": 2}
 # enum wire_resize_mode: cv2's INTER_NEAREST / INTER_LINEAR / INTER_CUBIC / INTER_AREA integers
 RESIZE_MODE = {"nearest": 0, "linear": 1, "cubic": 2, "area": 3}
-REG_NSUM = 29       # the sums wire_register_gn_step leaves at the start of its workspace, per (frame, candidate)
+# the density modes of wire_composite_fwd / _bwd / _mse_grad
+DENSITY_MODE = {"softplus": 0, "relu": 1}
+REG_NSUM = 29      # the sums wire_register_gn_step leaves at the start of its workspace, per (frame, candidate)
 
 # every symbol include/wire_hip.h declares (tests check the .so exports them)
 SYMBOLS = [
@@ -50,6 +52,7 @@ SYMBOLS = [
     "wire_remap_bilinear_fwd", "wire_remap_bilinear_bwd_xy", "wire_register_gn_ws_bytes", "wire_register_gn_step",
     "wire_resize_tab_bytes", "wire_resize_mse_grad_ws_bytes", "wire_resize_tables", "wire_resize_fwd", "wire_resize_bwd",
     "wire_resize_mse_grad",
+    "wire_ray_samples", "wire_composite_fwd", "wire_composite_bwd", "wire_composite_mse_grad",
 ]
 
 
@@ -172,6 +175,10 @@ def _declare(l: C.CDLL) -> None:
     l.wire_resize_fwd.argtypes = [vp, vp] + geom + [vp, i32, vp]
     l.wire_resize_bwd.argtypes = [vp, vp] + geom + [vp, i32, vp]
     l.wire_resize_mse_grad.argtypes = [vp, vp] + geom + [vp, i32, vp, vp, vp, vp, vp, i64, vp]
+    l.wire_ray_samples.argtypes = [vp, vp, vp, f32, f32, vp, i64, i32, vp, vp, vp]
+    l.wire_composite_fwd.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]
+    l.wire_composite_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]
+    l.wire_composite_mse_grad.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, vp, vp, vp, vp]
     l.wire_iso_ws_bytes.argtypes = [i32, i32, i32]
     l.wire_iso_ws_bytes.restype = i64
     l.wire_iso_count.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]

@@ -715,6 +715,158 @@ def point_loss(y: torch.Tensor, target: torch.Tensor, kind: str = "mse", weight=
 
 
 # ---------------------------------------------------------------------------
+# volume rendering: ray sampling and emission-absorption compositing (wire_render.hip)
+# ---------------------------------------------------------------------------
+def _density_mode(density) -> int:
+    if not isinstance(density, str) or density not in _lib.DENSITY_MODE:
+        raise ValueError(f"density {density!r}: one of {', '.join(repr(k) for k in _lib.DENSITY_MODE)}")
+    return _lib.DENSITY_MODE[density]
+
+
+def _ray_args(rays, near, far, n_samples, jitter):
+    """The argument checks of the ray entry points -> (rays, bounds [R, 2] or None, near, far, R, S, jitter), detached
+    and contiguous.  ``near`` / ``far`` are two finite numbers or two [R] tensors."""
+    if not isinstance(rays, torch.Tensor) or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[0] < 1 \
+            or rays.shape[1] != 6 or not rays.is_contiguous():
+        raise ValueError("rays must be a contiguous float32 tensor [R, 6] with R >= 1")
+    R, S = int(rays.shape[0]), int(n_samples)
+    if S < 1:
+        raise ValueError("n_samples must be >= 1")
+    tn, tf = isinstance(near, torch.Tensor), isinstance(far, torch.Tensor)
+    if tn != tf:
+        raise ValueError("near and far must both be numbers or both be [R] tensors")
+    if tn:
+        for name, t in (("near", near), ("far", far)):
+            if t.dtype != torch.float32 or tuple(t.shape) != (R,) or t.device != rays.device:
+                raise ValueError(f"{name} must be a float32 tensor [{R}] on the device of rays")
+    else:
+        near, far = float(near), float(far)
+        if near != near or far != far or abs(near) == float("inf") or abs(far) == float("inf"):
+            raise ValueError("near and far must be finite")
+    if jitter is not None and (not isinstance(jitter, torch.Tensor) or jitter.dtype != torch.float32
+                               or tuple(jitter.shape) != (R, S) or not jitter.is_contiguous()
+                               or jitter.device != rays.device):
+        raise ValueError(f"jitter must be a contiguous float32 tensor [{R}, {S}] on the device of rays")
+    _require_cuda(rays, "rays")
+    bounds = torch.stack([near.detach(), far.detach()], dim=1).contiguous() if tn else None
+    return rays.detach(), bounds, (0.0 if tn else near), (0.0 if tn else far), R, S, \
+        (jitter.detach() if jitter is not None else None)
+
+
+def _background_arg(background, Cc: int, dev: torch.device):
+    """``background`` None, a number, or [C] values -> a float32 [C] tensor on ``dev`` or None."""
+    if background is None:
+        return None
+    bg = torch.as_tensor(background, dtype=torch.float32).detach()
+    if bg.dim() == 0:
+        bg = bg.expand(Cc)
+    if tuple(bg.shape) != (Cc,):
+        raise ValueError(f"background must be None, a number or {Cc} values")
+    return bg.to(dev).contiguous()
+
+
+def _ray_samples_into(stream, rays, bounds, near, far, jitter, R, S, coords, ts, deltas) -> None:
+    _lib.check(_lib.lib().wire_ray_samples(stream, rays.data_ptr(), bounds.data_ptr() if bounds is not None else None,
+                                           near, far, jitter.data_ptr() if jitter is not None else None, R, S,
+                                           coords.data_ptr(), ts.data_ptr(), deltas.data_ptr()), "wire_ray_samples")
+
+
+@torch.no_grad()
+def ray_samples(rays: torch.Tensor, near, far, n_samples: int, jitter=None):
+    """The sample points of R rays: ``rays`` [R, 6] = (origin, direction) (``utils.get_rays``), ``near`` / ``far`` two
+    numbers or two [R] tensors (``utils.ray_box``), S = ``n_samples`` stratified samples per ray,
+
+        t_s = near + (s + u_s) (far - near) / S,    u = ``jitter`` [R, S] in [0, 1) (``torch.rand``) or 0.5 (None)
+
+    Returns ``(coords [R*S, 3], ts [R, S], deltas [R, S])``: the net's input rows ``o + t_s d``, the parameters, and
+    the world-space lengths ``(t_{s+1} - t_s) |d|`` with ``far`` behind the last sample.  A ray with ``far <= near``
+    gets zero lengths: it composites to the background and receives no gradient.  fp64 arithmetic rounded to fp32
+    once (wire_ray_samples).  No gradient.  Contiguous CUDA float32 tensors; CPU tensors raise WireHipError, other
+    shapes or dtypes ValueError."""
+    r, bounds, nr, fr, R, S, u = _ray_args(rays, near, far, n_samples, jitter)
+    dev = r.device
+    coords = torch.empty(R * S, 3, dtype=torch.float32, device=dev)
+    ts = torch.empty(R, S, dtype=torch.float32, device=dev)
+    deltas = torch.empty(R, S, dtype=torch.float32, device=dev)
+    _ray_samples_into(_stream_ptr(dev), r, bounds, nr, fr, u, R, S, coords, ts, deltas)
+    return coords, ts, deltas
+
+
+class _CompositeFunction(torch.autograd.Function):
+    """wire_composite_fwd and its adjoint wire_composite_bwd."""
+
+    @staticmethod
+    def forward(ctx, y, ts, deltas, bg, mode):
+        L = _lib.lib()
+        yd = y.detach()
+        if yd.data_ptr() % 16:                     # the kernels move a row as 16- or 8-byte words
+            yd = yd.clone()
+        dev = yd.device
+        R, S, O = int(ts.shape[0]), int(ts.shape[1]), int(yd.shape[-1])
+        rgb = torch.empty(R, O - 1, dtype=torch.float32, device=dev)
+        acc = torch.empty(R, dtype=torch.float32, device=dev)
+        depth = torch.empty(R, dtype=torch.float32, device=dev)
+        _lib.check(L.wire_composite_fwd(_stream_ptr(dev), yd.data_ptr(), ts.data_ptr(), deltas.data_ptr(),
+                                        bg.data_ptr() if bg is not None else None, R, S, O, mode, rgb.data_ptr(),
+                                        acc.data_ptr(), depth.data_ptr()), "wire_composite_fwd")
+        ctx.save_for_backward(yd, ts, deltas)
+        ctx.bg, ctx.mode, ctx.shape = bg, mode, tuple(y.shape)
+        return rgb, acc, depth
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_acc, g_depth):
+        L = _lib.lib()
+        yd, ts, deltas = ctx.saved_tensors
+        _no_second_order("composite")
+        dev = yd.device
+        R, S, O = int(ts.shape[0]), int(ts.shape[1]), int(yd.shape[-1])
+        as_f32 = lambda g: None if g is None else g.detach().to(torch.float32).contiguous()
+        g_rgb, g_acc, g_depth = as_f32(g_rgb), as_f32(g_acc), as_f32(g_depth)
+        if g_rgb is None:
+            g_rgb = torch.zeros(R, O - 1, dtype=torch.float32, device=dev)
+        g_y = torch.empty(R * S, O, dtype=torch.float32, device=dev)
+        opt = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(L.wire_composite_bwd(_stream_ptr(dev), yd.data_ptr(), ts.data_ptr(), deltas.data_ptr(), opt(ctx.bg),
+                                        g_rgb.data_ptr(), opt(g_acc), opt(g_depth), R, S, O, ctx.mode, g_y.data_ptr()),
+                   "wire_composite_bwd")
+        return g_y.view(ctx.shape), None, None, None, None
+
+
+def composite(y: torch.Tensor, ts: torch.Tensor, deltas: torch.Tensor, background=None, density: str = "softplus"):
+    """Emission-absorption compositing of the net's rows along R rays of S samples: ``y`` [R*S, O] (or [R, S, O]) holds
+    ``(c_raw[0..C), s_raw)`` per sample, C = O - 1, O in 2..8; ``ts`` and ``deltas`` [R, S] come from ``ray_samples``.
+
+        sigma = softplus(s_raw) ("softplus") or max(s_raw, 0) ("relu"),    c = sigmoid(c_raw)
+        T_s = exp(-sum_{j<s} sigma_j delta_j),    w_s = T_s (1 - exp(-sigma_s delta_s))
+        rgb = sum_s w_s c_s + T_S background,    acc = 1 - T_S,    depth = sum_s w_s t_s
+
+    Returns ``(rgb [R, C], acc [R], depth [R])``.  ``background`` is None (black), a number or [C] values.  Forward
+    is wire_composite_fwd and backward wire_composite_bwd: a wave per ray, optical depth and transmittance in fp64, no
+    [R, S] temporaries and no atomics (the same call gives the same bits).  The gradient reaches ``y`` only: ``ts`` or
+    ``deltas`` that require grad, and second-order use, raise NotImplementedError.  Contiguous CUDA float32 tensors;
+    CPU tensors raise WireHipError, other shapes or dtypes ValueError."""
+    mode = _density_mode(density)
+    if not all(isinstance(t, torch.Tensor) for t in (y, ts, deltas)):
+        raise ValueError("composite expects three tensors")
+    if ts.dtype != torch.float32 or ts.dim() != 2 or ts.shape[0] < 1 or ts.shape[1] < 1 or not ts.is_contiguous():
+        raise ValueError("ts must be a contiguous float32 tensor [R, S] with R, S >= 1")
+    R, S = int(ts.shape[0]), int(ts.shape[1])
+    if deltas.dtype != torch.float32 or deltas.shape != ts.shape or not deltas.is_contiguous() \
+            or deltas.device != ts.device:
+        raise ValueError(f"deltas must be a contiguous float32 tensor [{R}, {S}] on the device of ts")
+    if y.dtype != torch.float32 or y.dim() not in (2, 3) or not y.is_contiguous() or y.device != ts.device \
+            or tuple(y.shape[:-1]) not in ((R * S,), (R, S)) or not 2 <= y.shape[-1] <= 8:
+        raise ValueError(f"y must be a contiguous float32 tensor [{R * S}, O] or [{R}, {S}, O], O in 2..8, on the device "
+                         "of ts")
+    bg = _background_arg(background, int(y.shape[-1]) - 1, y.device)
+    if torch.is_grad_enabled() and (ts.requires_grad or deltas.requires_grad):
+        raise NotImplementedError("composite: the gradient reaches y only; ts and deltas that require grad are not "
+                                  "supported (detach them)")
+    _require_cuda(y, "y")
+    return _CompositeFunction.apply(y, ts.detach(), deltas.detach(), bg, mode)
+
+
+# ---------------------------------------------------------------------------
 # a learnable registration of frames (wire_warp_coords_fwd / wire_warp_coords_bwd)
 # ---------------------------------------------------------------------------
 class _WarpCoordsFunction(torch.autograd.Function):

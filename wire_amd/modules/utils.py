@@ -140,6 +140,48 @@ def axis_tables(H, W, T=None, style="numpy"):
     return ax(W), ax(H), (ax(T) if T is not None else None)
 
 
+def get_rays(H, W, focal, c2w):
+    """Pinhole camera rays as [H*W, 6] = (origin, direction), float32, row i*W + j: in the camera's frame pixel (i, j)
+    looks along ((j - W/2) / focal, -(i - H/2) / focal, -1) -- x right, y up, the camera looking down -z, the convention
+    of the NeRF loaders -- and ``c2w`` ([3, 4] or [4, 4], array or tensor) rotates it into the world and gives the
+    origin.  Directions are not normalised (``functional.ray_samples`` folds their length into ``deltas``).  The rays
+    live on the device of ``c2w`` when that is a tensor.  Plain torch ops: this is not on a step's path."""
+    c2w = torch.as_tensor(c2w).to(torch.float32)
+    if c2w.dim() != 2 or c2w.shape[0] not in (3, 4) or c2w.shape[1] != 4:
+        raise ValueError("c2w must be [3, 4] or [4, 4]")
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or not float(focal) > 0:
+        raise ValueError("get_rays needs H, W >= 1 and focal > 0")
+    i, j = torch.meshgrid(torch.arange(H, dtype=torch.float32, device=c2w.device),
+                          torch.arange(W, dtype=torch.float32, device=c2w.device), indexing="ij")
+    dirs = torch.stack([(j - 0.5 * W) / float(focal), -(i - 0.5 * H) / float(focal), -torch.ones_like(i)], dim=-1)
+    d = (dirs[..., None, :] * c2w[:3, :3]).sum(dim=-1).reshape(H * W, 3)
+    o = c2w[:3, 3].expand(H * W, 3)
+    return torch.cat([o, d], dim=1).contiguous()
+
+
+def ray_box(rays, lo=-1.0, hi=1.0):
+    """(near, far) [R] of ``rays`` [R, 6] against the cube [lo, hi]^3 by the slab method, near clamped at 0 (the ray
+    starts at its origin).  A ray that misses the cube gets far <= near, which ``functional.ray_samples`` turns into
+    zero-length samples.  An axis the ray runs parallel to bounds nothing when the origin lies inside its slab, and
+    rules the ray out otherwise."""
+    if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 6:
+        raise ValueError("rays must be a tensor [R, 6]")
+    o, d = rays[:, :3].to(torch.float32), rays[:, 3:].to(torch.float32)
+    inf = torch.full_like(o, float("inf"))
+    par = d == 0
+    safe = torch.where(par, torch.ones_like(d), d)
+    t0, t1 = (float(lo) - o) / safe, (float(hi) - o) / safe
+    inside = (o >= float(lo)) & (o <= float(hi))
+    tmin = torch.where(par, torch.where(inside, -inf, inf), torch.minimum(t0, t1))
+    tmax = torch.where(par, torch.where(inside, inf, -inf), torch.maximum(t0, t1))
+    near = tmin.max(dim=1).values.clamp_min(0.0)
+    far = tmax.min(dim=1).values
+    miss = ~(far > near)                                   # finite bounds for a miss: its samples sit at the origin
+    zero = torch.zeros_like(near)
+    return torch.where(miss, zero, near).contiguous(), torch.where(miss, zero, far).contiguous()
+
+
 def build_montage(images):
     """Tile ``images`` [n, H, W] (each min-max normalised, ``normalize(.., True)``) row by row into a
     ceil(sqrt(n))-row grid; unused cells stay 0 (modules/utils.py:131-156)."""

@@ -820,6 +820,94 @@ class FusedTrainer:
         self._reserve(n)
         return self._point_step(xy.data_ptr(), n, self._point_loss(code, delta, tab, w, wpe, None, 0, n, None))
 
+    # ------------------------------------------------------------------ volume rendering: a net seen through camera rays
+    def _rays_args(self, what: str, rays, near, far, n_samples, jitter, background, density):
+        """The argument checks of the ray entry points -> (functional._ray_args' tuple, background, density mode)."""
+        if self.world != 1:
+            raise NotImplementedError(f"{what} is single-process")
+        if int(self.desc.in_features) != 3 or not 2 <= self.O <= 8:
+            raise ValueError(f"{what} needs in_features == 3 and out_features == C + 1 in 2..8 (C colours and a density)")
+        mode = functional._density_mode(density)
+        args = functional._ray_args(rays, near, far, n_samples, jitter)
+        if args[0].device != self.dev:
+            raise ValueError("rays must be on the trainer's device")
+        return args, functional._background_arg(background, self.O - 1, self.dev), mode
+
+    def _reserve_rays(self, n: int) -> None:
+        """ts and deltas of n samples, beside the buffers of ``_reserve``."""
+        self._reserve(n)
+        if n > getattr(self, "_ray_cap", 0):
+            self.ray_ts = torch.empty(n, dtype=torch.float32, device=self.dev)
+            self.ray_deltas = torch.empty(n, dtype=torch.float32, device=self.dev)
+            self._ray_cap = n
+
+    def step_rays(self, rays: torch.Tensor, target: torch.Tensor, near, far, n_samples: int, jitter=None,
+                  background=None, density: str = "softplus") -> torch.Tensor:
+        """One optimizer step of a radiance field: the net maps a point of space to ``(c_raw[0..C), s_raw)`` and is seen
+        only through the colours of R camera rays.  ``rays`` [R, 6] (``utils.get_rays``), ``near`` / ``far`` two numbers
+        or two [R] tensors (``utils.ray_box``), ``n_samples`` = S stratified samples per ray with ``jitter`` [R, S]
+        (``torch.rand``) or midpoints, as ``functional.ray_samples``; ``target`` [R, C] the rays' colours;
+        ``background`` and ``density`` as ``functional.composite``.
+
+            loss = mean((composite(net(o + t_s d)) - target)^2)
+
+        Launches: pack, wire_ray_samples into ``self.coords``, the forward of R*S rows, wire_composite_mse_grad (forward
+        sweep, loss and adjoint in one kernel, dL/dy into ``self.gy``), the backward, Adam.  Returns the device loss (no
+        host sync); the rendered colours of the step stay in ``self.ray_rgb`` [R, C], the net's rows in ``self.y``.
+        R and S may change from call to call.  The trainer's grid and target are not used (``target=None`` serves).
+        Needs ``in_features == 3`` and ``out_features == C + 1``; single process; no TV prior; no gradient to the rays."""
+        (r, bounds, nr, fr, R, S, u), bg, mode = self._rays_args("step_rays", rays, near, far, n_samples, jitter,
+                                                                 background, density)
+        tgt = self._f32_elems("target", target, R, self.O - 1)
+        n = R * S
+        self._reserve_rays(n)
+        self.ray_rgb = torch.empty(R, self.O - 1, dtype=torch.float32, device=self.dev)
+        functional._ray_samples_into(self._stream(), r, bounds, nr, fr, u, R, S, self.coords, self.ray_ts,
+                                     self.ray_deltas)
+
+        def loss(stream, g):
+            _lib.check(self.L.wire_composite_mse_grad(stream, self.y.data_ptr(), self.ray_ts.data_ptr(),
+                                                      self.ray_deltas.data_ptr(), self._opt_ptr(bg), tgt.data_ptr(), R,
+                                                      S, self.O, mode, 1.0, self.gy.data_ptr(), self._loss_slot(g)[0],
+                                                      self.ray_rgb.data_ptr(), self.partial.data_ptr()),
+                       "composite_mse_grad")
+        return self._point_step(self.coords.data_ptr(), n, loss)
+
+    @torch.no_grad()
+    def render_rays(self, rays: torch.Tensor, near, far, n_samples: int, tile_rays: int = 4096, background=None,
+                    density: str = "softplus"):
+        """Forward-only rendering of ``rays`` [R, 6] at midpoint samples, ``tile_rays`` rays at a time with no saved
+        activations (as ``render``): ``(rgb [R, C], acc [R], depth [R])``.  The compositing of a ray does not depend on
+        the tiling, so the result has the same bits for every ``tile_rays`` that keeps the net's forward on one GEMM
+        family (the library picks it by the rows of a call, ``tile_rays * n_samples``, with the switch at 4096 rows).
+        Arguments as ``step_rays``."""
+        (r, bounds, nr, fr, R, S, _), bg, mode = self._rays_args("render_rays", rays, near, far, n_samples, None,
+                                                                 background, density)
+        tile = max(1, min(int(tile_rays), R))
+        L, d = self.L, C.byref(self.desc)
+        stream = self._stream()
+        Cc = self.O - 1
+        rgb = torch.empty(R, Cc, dtype=torch.float32, device=self.dev)
+        acc = torch.empty(R, dtype=torch.float32, device=self.dev)
+        depth = torch.empty(R, dtype=torch.float32, device=self.dev)
+        self._pack(stream)
+        ab = _lib.check(L.wire_act_bytes(d, tile * S, 0))
+        act = torch.empty(ab, dtype=torch.uint8, device=self.dev)
+        coords = torch.empty(tile * S, 3, dtype=torch.float32, device=self.dev)
+        ts, deltas = torch.empty(tile * S, dtype=torch.float32, device=self.dev), \
+            torch.empty(tile * S, dtype=torch.float32, device=self.dev)
+        y = torch.empty(tile * S, self.O, dtype=torch.float32, device=self.dev)
+        for r0 in range(0, R, tile):
+            nr_ = min(tile, R - r0)
+            functional._ray_samples_into(stream, r[r0:r0 + nr_], None if bounds is None else bounds[r0:r0 + nr_], nr,
+                                         fr, None, nr_, S, coords, ts, deltas)
+            _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), coords.data_ptr(), nr_ * S, y.data_ptr(),
+                                      act.data_ptr(), ab, 0), "fwd")
+            _lib.check(L.wire_composite_fwd(stream, y.data_ptr(), ts.data_ptr(), deltas.data_ptr(), self._opt_ptr(bg),
+                                            nr_, S, self.O, mode, rgb.data_ptr() + 4 * r0 * Cc,
+                                            acc.data_ptr() + 4 * r0, depth.data_ptr() + 4 * r0), "composite_fwd")
+        return rgb, acc, depth
+
     # ------------------------------------------------------------------ multi-image super-resolution step
     def affine_coords(self, mats) -> torch.Tensor:
         """The coordinates of B frames of the trainer's grid, each moved by its 2 x 3 matrix -- ``motion.get_imstack``'s
