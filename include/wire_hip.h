@@ -597,6 +597,38 @@ int wire_composite_mse_grad(void* stream, const float* y, const float* ts, const
                             const float* target, int64_t R, int S, int O, int density, float shard, float* g_y,
                             float* loss_out, float* rgb, float* partial);
 
+/* Hierarchical sampling along the rays (wire_render.hip): the weights of a coarse pass and the
+ * second set of samples they call for.  All pointers DEVICE fp32, 4-byte aligned except y (16).
+ * wire_composite_weights: w[r][s] = (float)(T_s (1 - exp(-a_s))), the summand of wire_composite_fwd's rgb and acc with
+ *   its lane map, fp64 scan and carry, so the same bits; it reads column O - 1 of y [R S][O] and deltas [R][S] only and
+ *   writes EVERY element of w [R][S].  density as wire_composite_fwd.
+ * wire_ray_resample: rays, bounds / near_ / far_ as wire_ray_samples.  ts_c [R][S]: the coarse samples, nondecreasing
+ *   inside [near, far] as wire_ray_samples makes them (NOT checked: unsorted values give finite, meaningless output);
+ *   w [R][S] their weights; jitter [R][Nf] holds v in [0, 1), NULL means v = 0.5; eps > 0 (NeRF's sample_pdf: 1e-5).
+ *   Per ray, in fp64 from the fp32 inputs, no contraction, each output rounded to fp32 once:
+ *     edges   e_0 = near,  e_s = (ts_c[s-1] + ts_c[s]) / 2,  e_S = far        (bin s contains sample s)
+ *     mass    p_s = min(max(w_s, 0), FLT_MAX) + eps  (NaN counts as 0);  c_0 = 0,  c_{s+1} = c_s + p_s,  tot = c_S
+ *     draws   u_k = ((k + v_k) / Nf) tot,  k = 0 .. Nf-1
+ *     inverse s = the largest index in [0, S-1] with c_s <= u_k,  f = clamp((u_k - c_s) / (c_{s+1} - c_s), 0, 1)
+ *             (f = 0 where eps vanished beside a huge weight and the bin is empty),
+ *             tf_k = min(e_s + f (e_{s+1} - e_s), e_{s+1})
+ *     merge   the S coarse and Nf fine values by rank, coarse first on a tie, compared in fp64:
+ *             pos(coarse i) = i + #{fine < ts_c[i]},  pos(fine k) = k + #{coarse <= tf_k}
+ *   and on the merged t_0 <= ... <= t_{S+Nf-1} the sampler's recipe from the unrounded t, far behind the last one:
+ *     coords[r (S+Nf) + k] = o + t_k d,   ts[r][k] = t_k,   deltas[r][k] = (t_{k+1} - t_k) sqrt(dx dx + dy dy + dz dz).
+ *   A ray with far <= near (or a NaN bound) gets t = near and deltas = 0 everywhere.  coords [R (S+Nf)][3], ts and
+ *   deltas [R][S+Nf]; EVERY element is written.  The CDF is an inclusive scan of 64 samples plus a carry, so its
+ *   association differs from a running sum's.  A wave owns a ray; CDF, fine samples and merged list live in LDS, which
+ *   limits S and Nf to 1024 each.  No atomics: the same call gives the same bits.
+ * R, S or Nf < 1, S or Nf > 1024, O outside 2..8, density outside {0, 1}, R (S+Nf) beyond 63 bits, more workgroups than
+ * a grid holds, scalar bounds not finite, eps not finite or <= 0, a misaligned pointer, or a NULL pointer other than
+ * bounds / jitter: WIRE_ERR_ARG before any HIP call.                                                                 */
+int wire_composite_weights(void* stream, const float* y, const float* deltas, int64_t R, int S, int O, int density,
+                           float* w);
+int wire_ray_resample(void* stream, const float* rays, const float* bounds, float near_, float far_, const float* ts_c,
+                      const float* w, const float* jitter, float eps, int64_t R, int S, int Nf, float* coords,
+                      float* ts, float* deltas);
+
 /* Video compressive sensing (per-pixel coded exposure, modules/lin_inverse.py:42-95): the loss of a video estimate
  * against a coded video, fused with its backward.  The T frames of pixel p are multiplied by that pixel's mask and
  * summed in groups of nframes (lin_inverse.py:79-84) into C = ceil(T / nframes) coded frames; nframes > T gives one.

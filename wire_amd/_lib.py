@@ -27,7 +27,7 @@ LOSS_KIND = {"mse": 0, "l1": 1, "huber": 2, "logistic": 3}
 MOTION_MODEL = {"translation": 0, "euclidean": 1, "affine": 2}
 # enum wire_resize_mode: cv2's INTER_NEAREST / INTER_LINEAR / INTER_CUBIC / INTER_AREA integers
 RESIZE_MODE = {"nearest": 0, "linear": 1, "cubic": 2, "area": 3}
-# the density modes of wire_composite_fwd / _bwd / _mse_grad
+# the density modes of wire_composite_fwd / _bwd / _mse_grad / _weights
 DENSITY_MODE = {"softplus": 0, "relu": 1}
 REG_NSUM = 29      # the sums wire_register_gn_step leaves at the start of its workspace, per (frame, candidate)
 
@@ -53,6 +53,7 @@ SYMBOLS = [
     "wire_resize_tab_bytes", "wire_resize_mse_grad_ws_bytes", "wire_resize_tables", "wire_resize_fwd", "wire_resize_bwd",
     "wire_resize_mse_grad",
     "wire_ray_samples", "wire_composite_fwd", "wire_composite_bwd", "wire_composite_mse_grad",
+    "wire_composite_weights", "wire_ray_resample",
 ]
 
 
@@ -179,6 +180,8 @@ def _declare(l: C.CDLL) -> None:
     l.wire_composite_fwd.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]
     l.wire_composite_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]
     l.wire_composite_mse_grad.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, vp, vp, vp, vp]
+    l.wire_composite_weights.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp]
+    l.wire_ray_resample.argtypes = [vp, vp, vp, f32, f32, vp, vp, vp, f32, i64, i32, i32, vp, vp, vp]
     l.wire_iso_ws_bytes.argtypes = [i32, i32, i32]
     l.wire_iso_ws_bytes.restype = i64
     l.wire_iso_count.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]

@@ -30,7 +30,14 @@
 // wire_composite_mse_grad is built from the functions of the forward / backward pair (ray_forward, ray_backward), so
 // both routes give the same bits.
 //
-// The four entry points of the C ABI (include/wire_hip.h) are at the end of this file.
+//
+// HIERARCHICAL SAMPLING: wire_composite_weights writes the w_s of the forward sweep, and
+// wire_ray_resample turns them into a second set of samples: a per-ray unnormalised CDF over the bins whose edges are the
+// midpoints of the coarse samples, Nf inverse-CDF draws, and a merge by rank with the coarse samples.  A wave owns a
+// ray there too; the CDF, the fine samples and the merged list live in LDS (layout and occupancy at the kernel).
+//
+// The six entry points of the C ABI (include/wire_hip.h) are at the end of this file.
+#include <cfloat>
 #include <cmath>
 
 #include "wire_dev.h"
@@ -40,6 +47,8 @@
 #define RENDER_LOSS_BLOCKS 2048         // the grid of the loss kernel is capped here: partial holds one float per block
 #define RENDER_MAX_BLOCKS 2147483647ll
 #define RENDER_TAU_CAP 800.0            // exp(-800) == 0 in fp64
+#define RESAMPLE_MAX 1024               // the resampler's limit on S and on Nf: its CDF and lists live in LDS
+#define RESAMPLE_SMALL 256              // up to here four rays share a workgroup, beyond it two
 
 // ---------------------------------------------------------------------------
 // the sampler
@@ -316,6 +325,156 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const float* __restr
   }
 }
 
+// w_s alone, for the resampler: the scan, carry and expressions of ray_forward on column O - 1 of y, so w carries the
+// bits of the forward sweep's summand.  O is a run-time number here: no row is moved, only its last float.
+__global__ __launch_bounds__(256) void composite_weights_kernel(const float* __restrict__ y,
+                                                                const float* __restrict__ deltas, long long R, int S,
+                                                                int O, int mode, float* __restrict__ w) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * RENDER_RAYS_PER_WG + (threadIdx.x >> 6);
+  if (r >= R) return;                                      // (a whole wave leaves: no barrier below)
+  const long long row0 = r * S;
+  double carry = 0.0;
+  for (int base = 0; base < S; base += 64) {
+    const int s = base + lane;
+    double a = 0.0;
+    if (s < S) {
+      float sigma, ds;
+      render_density(y[(row0 + s) * O + (O - 1)], mode, sigma, ds);
+      a = (double)sigma * (double)deltas[row0 + s];
+    }
+    const double incl = wave_prefix_incl(a, lane);
+    const double T = exp(-fmin(carry + (incl - a), RENDER_TAU_CAP));
+    if (s < S) w[row0 + s] = (float)(T * -expm1(-a));
+    carry += __shfl(incl, 63);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// the resampler: inverse-CDF draws from the coarse weights, merged with the coarse samples
+// ---------------------------------------------------------------------------
+// A wave owns a ray.  LDS per ray, for S, Nf <= CAP:
+//   tc [CAP]       float    the coarse samples (the merge's searches; the bin edges are their midpoints)
+//   tf [CAP]       double   the fine samples, unrounded
+//   cm [2 CAP + 2] double   first the CDF c_0 .. c_S, then -- the CDF is dead once the draws are inverted -- the merged
+//                           list t_0 .. t_{S+Nf-1} with far behind it, so a lane reads its right neighbour
+// = 28 CAP + 16 bytes.  Two editions: CAP = 256 with four rays per workgroup (28.1 KB: five workgroups = 20 waves per
+// CU of 160 KB LDS) and CAP = 1024 with two rays (56.0 KB: two workgroups = 4 waves per CU).  A ray's arithmetic does
+// not depend on the edition.  Every wave of a workgroup runs every phase (a wave past R works on ray R - 1 and stores
+// nothing), so the barriers between the phases are uniform; S and Nf are the same for every ray.
+// The searches return indices inside their arrays whatever the values are (NaN included), and the merged list is
+// filled with near before the scatter: unsorted coarse samples give meaningless output, never an unwritten element.
+template <int CAP, int RAYS>
+__global__ __launch_bounds__(64 * RAYS) void ray_resample_kernel(const float* __restrict__ rays,
+                                                                 const float* __restrict__ bounds, float near_,
+                                                                 float far_, const float* __restrict__ ts_c,
+                                                                 const float* __restrict__ w,
+                                                                 const float* __restrict__ jitter, float eps,
+                                                                 long long R, int S, int Nf,
+                                                                 float* __restrict__ coords, float* __restrict__ ts,
+                                                                 float* __restrict__ deltas) {
+#pragma clang fp contract(off)
+  __shared__ float s_tc[RAYS][CAP];
+  __shared__ double s_tf[RAYS][CAP];
+  __shared__ double s_cm[RAYS][2 * CAP + 2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long long r = (long long)blockIdx.x * RAYS + wave;
+  const bool active = r < R;
+  if (!active) r = R - 1;
+  float* tc = s_tc[wave];
+  double* tf = s_tf[wave];
+  double* cm = s_cm[wave];
+  const int M = S + Nf;
+  const float* ray = rays + r * 6;
+  const double ox = (double)ray[0], oy = (double)ray[1], oz = (double)ray[2];
+  const double dx = (double)ray[3], dy = (double)ray[4], dz = (double)ray[5];
+  const double nr = (double)(bounds ? bounds[2 * r] : near_), fr = (double)(bounds ? bounds[2 * r + 1] : far_);
+  const bool hit = fr > nr;
+
+  // the coarse samples and the unnormalised CDF: c_0 = 0, c_{s+1} = c_s + p_s
+  const long long row0 = r * S;
+  double carry = 0.0;
+  if (lane == 0) cm[0] = 0.0;
+  for (int base = 0; base < S; base += 64) {
+    const int s = base + lane;
+    double p = 0.0;
+    if (s < S) {
+      tc[s] = ts_c[row0 + s];
+      double wv = (double)w[row0 + s];
+      if (!(wv > 0.0)) wv = 0.0;                            // NaN and negative values count as 0
+      if (wv > (double)FLT_MAX) wv = (double)FLT_MAX;       // +inf as FLT_MAX
+      p = wv + (double)eps;
+    }
+    const double incl = wave_prefix_incl(p, lane);
+    if (s < S) cm[s + 1] = carry + incl;
+    carry += __shfl(incl, 63);
+  }
+  __syncthreads();
+
+  // the draws: u_k = ((k + v_k) / Nf) tot, its bin s = the largest index with c_s <= u_k, the position inside the bin
+  const double tot = cm[S];
+  for (int base = 0; base < Nf; base += 64) {
+    const int k = base + lane;
+    if (k < Nf) {
+      const double v = jitter ? (double)jitter[r * Nf + k] : 0.5;
+      const double u = (((double)k + v) / (double)Nf) * tot;
+      int lo = 0, hi = S;                                   // c_lo <= u (or lo = 0), c_hi > u (or hi = S)
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (cm[mid] <= u) lo = mid; else hi = mid;
+      }
+      const double c0 = cm[lo], den = cm[lo + 1] - c0;
+      double f = den > 0.0 ? (u - c0) / den : 0.0;          // (eps can vanish beside a weight of 1e30: an empty bin)
+      if (!(f > 0.0)) f = 0.0;
+      if (f > 1.0) f = 1.0;
+      const double e0 = lo > 0 ? ((double)tc[lo - 1] + (double)tc[lo]) / 2.0 : nr;
+      const double e1 = lo + 1 < S ? ((double)tc[lo] + (double)tc[lo + 1]) / 2.0 : fr;
+      double t = e0 + f * (e1 - e0);
+      if (t > e1) t = e1;                                   // f = 1 may round past the edge: keep the draws sorted
+      tf[k] = hit ? t : nr;
+    }
+  }
+  __syncthreads();                                          // the CDF is dead: cm becomes the merged list
+  for (int j = lane; j <= M; j += 64) cm[j] = j < M ? nr : (hit ? fr : nr);
+  __syncthreads();
+
+  // merge by rank, coarse first on a tie: pos(coarse i) = i + #{fine < tc_i}, pos(fine k) = k + #{coarse <= tf_k}
+  for (int i = lane; i < S; i += 64) {
+    const double cv = hit ? (double)tc[i] : nr;
+    int lo = 0, hi = Nf;                                    // the first fine sample that is not < cv
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (tf[mid] < cv) lo = mid + 1; else hi = mid;
+    }
+    cm[i + lo] = cv;
+  }
+  for (int k = lane; k < Nf; k += 64) {
+    const double tv = tf[k];
+    int lo = 0, hi = S;                                     // the first coarse sample that is not <= tv
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if ((hit ? (double)tc[mid] : nr) <= tv) lo = mid + 1; else hi = mid;
+    }
+    cm[k + lo] = tv;
+  }
+  __syncthreads();
+
+  // the sampler's recipe on the merged list
+  if (!active) return;
+  const double norm = sqrt(dx * dx + dy * dy + dz * dz);
+  for (int j = lane; j < M; j += 64) {
+    const double t = cm[j];
+    const double dl = hit ? (cm[j + 1] - t) * norm : 0.0;
+    const long long e = r * M + j;
+    coords[3 * e + 0] = (float)(ox + t * dx);
+    coords[3 * e + 1] = (float)(oy + t * dy);
+    coords[3 * e + 2] = (float)(oz + t * dz);
+    ts[e] = (float)t;
+    deltas[e] = (float)dl;
+  }
+}
+
 template <int O>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restrict__ y, const float* __restrict__ ts,
                                                             const float* __restrict__ deltas,
@@ -474,5 +633,43 @@ extern "C" int wire_composite_mse_grad(void* stream, const float* y, const float
   RENDER_DISPATCH(O, LAUNCH)
 #undef LAUNCH
   HIPCHK(launch_mse_final((hipStream_t)stream, partial, (int)nb, scale, loss_out));
+  return WIRE_OK;
+}
+
+extern "C" int wire_composite_weights(void* stream, const float* y, const float* deltas, int64_t R, int S, int O,
+                                      int density, float* w) {
+  RenderGeom g;
+  if (!render_geom(R, S, O, g) || (density != 0 && density != 1) || !y || !deltas || !w || !render_al16(y) ||
+      !render_al4(deltas) || !render_al4(w))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_composite_weights");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  hipLaunchKernelGGL(composite_weights_kernel, dim3((unsigned)g.blocks), dim3(256), 0, (hipStream_t)stream, y, deltas,
+                     (long long)R, S, O, density, w);
+  HIPCHK(hipGetLastError());
+  return WIRE_OK;
+}
+
+extern "C" int wire_ray_resample(void* stream, const float* rays, const float* bounds, float near_, float far_,
+                                 const float* ts_c, const float* w, const float* jitter, float eps, int64_t R, int S,
+                                 int Nf, float* coords, float* ts, float* deltas) {
+  RenderGeom g;
+  if (S < 1 || Nf < 1 || S > RESAMPLE_MAX || Nf > RESAMPLE_MAX || !render_geom(R, S + Nf, 4, g) || !rays || !ts_c ||
+      !w || !coords || !ts || !deltas || !render_al4(rays) || !render_al4(bounds) || !render_al4(ts_c) ||
+      !render_al4(w) || !render_al4(jitter) || !render_al4(coords) || !render_al4(ts) || !render_al4(deltas) ||
+      (!bounds && !(std::isfinite(near_) && std::isfinite(far_))) || !(std::isfinite(eps) && eps > 0.f))
+    return fail(WIRE_ERR_ARG, "bad argument to wire_ray_resample");
+  const bool small = S <= RESAMPLE_SMALL && Nf <= RESAMPLE_SMALL;
+  const long long blocks = (R - 1) / (small ? 4 : 2) + 1;
+  if (blocks > RENDER_MAX_BLOCKS) return fail(WIRE_ERR_ARG, "bad argument to wire_ray_resample");
+  ProfScope ps((hipStream_t)stream, 3, 0);
+  if (small)
+    hipLaunchKernelGGL((ray_resample_kernel<RESAMPLE_SMALL, 4>), dim3((unsigned)blocks), dim3(256), 0,
+                       (hipStream_t)stream, rays, bounds, near_, far_, ts_c, w, jitter, eps, (long long)R, S, Nf, coords,
+                       ts, deltas);
+  else
+    hipLaunchKernelGGL((ray_resample_kernel<RESAMPLE_MAX, 2>), dim3((unsigned)blocks), dim3(128), 0,
+                       (hipStream_t)stream, rays, bounds, near_, far_, ts_c, w, jitter, eps, (long long)R, S, Nf, coords,
+                       ts, deltas);
+  HIPCHK(hipGetLastError());
   return WIRE_OK;
 }

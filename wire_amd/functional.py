@@ -866,6 +866,93 @@ def composite(y: torch.Tensor, ts: torch.Tensor, deltas: torch.Tensor, backgroun
     return _CompositeFunction.apply(y, ts.detach(), deltas.detach(), bg, mode)
 
 
+RESAMPLE_MAX = 1024            # wire_ray_resample keeps a ray's CDF and lists in LDS: S and Nf up to here
+
+
+def _composite_weights_into(stream, y, deltas, R, S, O, mode, w) -> None:
+    _lib.check(_lib.lib().wire_composite_weights(stream, y.data_ptr(), deltas.data_ptr(), R, S, O, mode, w.data_ptr()),
+               "wire_composite_weights")
+
+
+def _ray_resample_into(stream, rays, bounds, near, far, ts_c, w, jitter, eps, R, S, Nf, coords, ts, deltas) -> None:
+    _lib.check(_lib.lib().wire_ray_resample(stream, rays.data_ptr(), bounds.data_ptr() if bounds is not None else None,
+                                            near, far, ts_c.data_ptr(), w.data_ptr(),
+                                            jitter.data_ptr() if jitter is not None else None, eps, R, S, Nf,
+                                            coords.data_ptr(), ts.data_ptr(), deltas.data_ptr()), "wire_ray_resample")
+
+
+def _resample_args(n_samples: int, n_importance: int, eps) -> float:
+    """The limits of wire_ray_resample on S, Nf and eps -> eps as a float."""
+    if not 1 <= int(n_samples) <= RESAMPLE_MAX or not 1 <= int(n_importance) <= RESAMPLE_MAX:
+        raise ValueError(f"resampling takes 1..{RESAMPLE_MAX} coarse samples and 1..{RESAMPLE_MAX} fine samples per ray")
+    eps = float(eps)
+    if not 0.0 < eps < float("inf"):
+        raise ValueError("eps must be a finite number > 0")
+    return eps
+
+
+@torch.no_grad()
+def composite_weights(y: torch.Tensor, deltas: torch.Tensor, density: str = "softplus") -> torch.Tensor:
+    """The compositing weights ``w_s = T_s (1 - exp(-sigma_s delta_s))`` of ``composite``, [R, S]: the summand of its
+    ``rgb`` and ``acc``, from ``y`` [R*S, O] (or [R, S, O]; only the density column is read) and ``deltas`` [R, S], with
+    the forward sweep's fp64 scan (wire_composite_weights).  They say where along a ray the colour came from, which is
+    what ``ray_resample`` draws its second set of samples from.  No gradient: a ``y`` that requires grad is detached.
+    Contiguous CUDA float32 tensors; CPU tensors raise WireHipError, other shapes or dtypes ValueError."""
+    mode = _density_mode(density)
+    if not isinstance(y, torch.Tensor) or not isinstance(deltas, torch.Tensor):
+        raise ValueError("composite_weights expects two tensors")
+    if deltas.dtype != torch.float32 or deltas.dim() != 2 or deltas.shape[0] < 1 or deltas.shape[1] < 1 \
+            or not deltas.is_contiguous():
+        raise ValueError("deltas must be a contiguous float32 tensor [R, S] with R, S >= 1")
+    R, S = int(deltas.shape[0]), int(deltas.shape[1])
+    if y.dtype != torch.float32 or y.dim() not in (2, 3) or not y.is_contiguous() or y.device != deltas.device \
+            or tuple(y.shape[:-1]) not in ((R * S,), (R, S)) or not 2 <= y.shape[-1] <= 8:
+        raise ValueError(f"y must be a contiguous float32 tensor [{R * S}, O] or [{R}, {S}, O], O in 2..8, on the device "
+                         "of deltas")
+    _require_cuda(y, "y")
+    yd = y.detach()
+    if yd.data_ptr() % 16:
+        yd = yd.clone()
+    w = torch.empty(R, S, dtype=torch.float32, device=yd.device)
+    _composite_weights_into(_stream_ptr(yd.device), yd, deltas.detach(), R, S, int(yd.shape[-1]), mode, w)
+    return w
+
+
+@torch.no_grad()
+def ray_resample(rays: torch.Tensor, near, far, ts: torch.Tensor, weights: torch.Tensor, n_importance: int,
+                 jitter=None, eps: float = 1e-5):
+    """Hierarchical sampling: ``n_importance`` = Nf further samples per ray, drawn where the coarse pass found something,
+    merged with the coarse samples.  ``rays``, ``near`` / ``far`` as ``ray_samples``; ``ts`` [R, S] its coarse samples
+    (nondecreasing inside [near, far]; not checked) and ``weights`` [R, S] their ``composite_weights``.  The bins are
+    bounded by ``near``, the midpoints of consecutive coarse samples and ``far``, so that bin s surrounds sample s; the
+    mass of a bin is ``max(w_s, 0) + eps`` (``eps``: NeRF's ``sample_pdf`` constant), and draw k inverts the piecewise
+    linear CDF at ``(k + v_k) / Nf`` of the total, ``v`` = ``jitter`` [R, Nf] in [0, 1) (``torch.rand``) or 0.5 (None).
+
+    Returns ``(coords [R*(S+Nf), 3], ts [R, S+Nf], deltas [R, S+Nf])`` of the sorted union, in ``ray_samples``'
+    conventions (``far`` behind the last sample; a ray with ``far <= near`` gets zero lengths).  fp64 arithmetic rounded
+    to fp32 once, no atomics: the same call gives the same bits (wire_ray_resample).  S and Nf up to 1024.  No gradient.
+    Contiguous CUDA float32 tensors; CPU tensors raise WireHipError, other shapes or dtypes ValueError."""
+    if not isinstance(rays, torch.Tensor) or rays.dim() != 2:               # (_ray_args checks the rest of rays)
+        raise ValueError("rays must be a contiguous float32 tensor [R, 6] with R >= 1")
+    R = int(rays.shape[0])
+    if not isinstance(ts, torch.Tensor) or ts.dtype != torch.float32 or ts.dim() != 2 or ts.shape[0] != R \
+            or ts.shape[1] < 1 or not ts.is_contiguous() or ts.device != rays.device:
+        raise ValueError(f"ts must be a contiguous float32 tensor [{R}, S] with S >= 1 on the device of rays")
+    S = int(ts.shape[1])
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.shape != ts.shape \
+            or not weights.is_contiguous() or weights.device != rays.device:
+        raise ValueError(f"weights must be a contiguous float32 tensor [{R}, {S}] on the device of rays")
+    eps = _resample_args(S, n_importance, eps)
+    r, bounds, nr, fr, R, Nf, v = _ray_args(rays, near, far, n_importance, jitter)
+    dev = r.device
+    coords = torch.empty(R * (S + Nf), 3, dtype=torch.float32, device=dev)
+    ts_out = torch.empty(R, S + Nf, dtype=torch.float32, device=dev)
+    deltas = torch.empty(R, S + Nf, dtype=torch.float32, device=dev)
+    _ray_resample_into(_stream_ptr(dev), r, bounds, nr, fr, ts.detach(), weights.detach(), v, eps, R, S, Nf, coords,
+                       ts_out, deltas)
+    return coords, ts_out, deltas
+
+
 # ---------------------------------------------------------------------------
 # a learnable registration of frames (wire_warp_coords_fwd / wire_warp_coords_bwd)
 # ---------------------------------------------------------------------------

@@ -842,7 +842,8 @@ class FusedTrainer:
             self._ray_cap = n
 
     def step_rays(self, rays: torch.Tensor, target: torch.Tensor, near, far, n_samples: int, jitter=None,
-                  background=None, density: str = "softplus") -> torch.Tensor:
+                  background=None, density: str = "softplus", n_importance: int = 0,
+                  jitter_fine=None) -> torch.Tensor:
         """One optimizer step of a radiance field: the net maps a point of space to ``(c_raw[0..C), s_raw)`` and is seen
         only through the colours of R camera rays.  ``rays`` [R, 6] (``utils.get_rays``), ``near`` / ``far`` two numbers
         or two [R] tensors (``utils.ray_box``), ``n_samples`` = S stratified samples per ray with ``jitter`` [R, S]
@@ -855,56 +856,129 @@ class FusedTrainer:
         sweep, loss and adjoint in one kernel, dL/dy into ``self.gy``), the backward, Adam.  Returns the device loss (no
         host sync); the rendered colours of the step stay in ``self.ray_rgb`` [R, C], the net's rows in ``self.y``.
         R and S may change from call to call.  The trainer's grid and target are not used (``target=None`` serves).
-        Needs ``in_features == 3`` and ``out_features == C + 1``; single process; no TV prior; no gradient to the rays."""
+        Needs ``in_features == 3`` and ``out_features == C + 1``; single process; no TV prior; no gradient to the rays.
+
+        ``n_importance`` = Nf > 0 makes the step hierarchical: a coarse pass tells a second pass
+        where to look.  Launches: pack, wire_ray_samples into coarse buffers of their own, a forward-only pass of the R*S
+        coarse rows with no saved activations, wire_composite_weights into ``self.ray_w`` [R, S], wire_ray_resample
+        (``functional.ray_resample``; ``jitter_fine`` [R, Nf] or midpoints of the strata) into ``self.coords`` /
+        ``self.ray_ts`` / ``self.ray_deltas`` with S + Nf sorted samples per ray, then the step above on those
+        R*(S+Nf) rows.  ONE net serves both passes.  The loss is on the second pass only, whose samples include the
+        coarse ones; the coarse pass carries no gradient, and no gradient flows through the sample positions.  S and Nf
+        up to 1024 each; R, S and Nf may change from call to call; still no host sync.  ``n_importance=0`` is the step
+        without the argument, launch for launch."""
         (r, bounds, nr, fr, R, S, u), bg, mode = self._rays_args("step_rays", rays, near, far, n_samples, jitter,
                                                                  background, density)
         tgt = self._f32_elems("target", target, R, self.O - 1)
+        Nf = int(n_importance)
+        if Nf < 0:
+            raise ValueError("n_importance must be >= 0")
+        if Nf > 0:
+            return self._step_rays_hier(r, bounds, nr, fr, R, S, u, Nf, jitter_fine, tgt, bg, mode)
+        if jitter_fine is not None:
+            raise ValueError("jitter_fine needs n_importance > 0")
         n = R * S
         self._reserve_rays(n)
         self.ray_rgb = torch.empty(R, self.O - 1, dtype=torch.float32, device=self.dev)
         functional._ray_samples_into(self._stream(), r, bounds, nr, fr, u, R, S, self.coords, self.ray_ts,
                                      self.ray_deltas)
+        return self._point_step(self.coords.data_ptr(), n, self._composite_loss(tgt, bg, R, S, mode))
 
+    def _composite_loss(self, tgt, bg, R: int, S: int, mode: int):
+        """The loss callable of the ray steps: wire_composite_mse_grad on ``self.y`` with S samples per ray."""
         def loss(stream, g):
             _lib.check(self.L.wire_composite_mse_grad(stream, self.y.data_ptr(), self.ray_ts.data_ptr(),
                                                       self.ray_deltas.data_ptr(), self._opt_ptr(bg), tgt.data_ptr(), R,
                                                       S, self.O, mode, 1.0, self.gy.data_ptr(), self._loss_slot(g)[0],
                                                       self.ray_rgb.data_ptr(), self.partial.data_ptr()),
                        "composite_mse_grad")
-        return self._point_step(self.coords.data_ptr(), n, loss)
+        return loss
+
+    def _coarse_pass(self, stream, rays, bounds, nr, fr, jitter, R: int, S: int, mode: int, buf: dict) -> None:
+        """wire_ray_samples, a forward-only pass of the R*S rows on the packed parameters and wire_composite_weights,
+        all into the buffers of ``buf`` (coords, ts, deltas, y, act, w)."""
+        functional._ray_samples_into(stream, rays, bounds, nr, fr, jitter, R, S, buf["coords"], buf["ts"], buf["deltas"])
+        _lib.check(self.L.wire_mlp_fwd(stream, C.byref(self.desc), self.packed.data_ptr(), buf["coords"].data_ptr(),
+                                       R * S, buf["y"].data_ptr(), buf["act"].data_ptr(), buf["act_bytes"], 0), "fwd")
+        functional._composite_weights_into(stream, buf["y"], buf["deltas"], R, S, self.O, mode, buf["w"])
+
+    def _step_rays_hier(self, r, bounds, nr, fr, R: int, S: int, u, Nf: int, jitter_fine, tgt, bg, mode: int):
+        """``step_rays`` with ``n_importance`` = Nf > 0; the arguments are checked and detached."""
+        eps = functional._resample_args(S, Nf, 1e-5)
+        if jitter_fine is not None:
+            if not isinstance(jitter_fine, torch.Tensor) or jitter_fine.dtype != torch.float32 \
+                    or tuple(jitter_fine.shape) != (R, Nf) or not jitter_fine.is_contiguous() \
+                    or jitter_fine.device != self.dev:
+                raise ValueError(f"jitter_fine must be a contiguous float32 tensor [{R}, {Nf}] on the trainer's device")
+            jitter_fine = jitter_fine.detach()
+        nc, M = R * S, S + Nf
+        n = R * M
+        self._reserve_rays(n)
+        self.ray_rgb = torch.empty(R, self.O - 1, dtype=torch.float32, device=self.dev)
+        ab = _lib.check(self.L.wire_act_bytes(C.byref(self.desc), nc, 0))
+        buf = dict(coords=self._buf("ray_coords_c", nc * 3), ts=self._buf("ray_ts_c", nc),
+                   deltas=self._buf("ray_deltas_c", nc), y=self._buf("ray_y_c", nc * self.O),
+                   act=self._buf("ray_act_c", max(ab, 16), dtype=torch.uint8), act_bytes=ab,
+                   w=self._buf("_ray_w", nc))
+        self.ray_w = buf["w"][:nc].view(R, S)
+        stream = self._stream()
+        g = self.gbuf[0]
+        self._pack(stream)
+        self._coarse_pass(stream, r, bounds, nr, fr, u, R, S, mode, buf)
+        functional._ray_resample_into(stream, r, bounds, nr, fr, buf["ts"], buf["w"], jitter_fine, eps, R, S, Nf,
+                                      self.coords, self.ray_ts, self.ray_deltas)
+        src = self._fwd_loss_bwd(stream, self.coords.data_ptr(), n, self._composite_loss(tgt, bg, R, M, mode), g,
+                                 self.grad_ptrs[0])
+        return self._finish(stream, g, src)
 
     @torch.no_grad()
     def render_rays(self, rays: torch.Tensor, near, far, n_samples: int, tile_rays: int = 4096, background=None,
-                    density: str = "softplus"):
+                    density: str = "softplus", n_importance: int = 0):
         """Forward-only rendering of ``rays`` [R, 6] at midpoint samples, ``tile_rays`` rays at a time with no saved
         activations (as ``render``): ``(rgb [R, C], acc [R], depth [R])``.  The compositing of a ray does not depend on
         the tiling, so the result has the same bits for every ``tile_rays`` that keeps the net's forward on one GEMM
         family (the library picks it by the rows of a call, ``tile_rays * n_samples``, with the switch at 4096 rows).
-        Arguments as ``step_rays``."""
+        ``n_importance`` = Nf > 0 renders hierarchically, as ``step_rays`` trains: per tile a coarse pass at the S
+        midpoints, its weights, Nf draws at the midpoints of the strata, and the colours of the S + Nf merged samples
+        (two forward calls per tile, of ``tile_rays * S`` and ``tile_rays * (S + Nf)`` rows).  Arguments as
+        ``step_rays``."""
         (r, bounds, nr, fr, R, S, _), bg, mode = self._rays_args("render_rays", rays, near, far, n_samples, None,
                                                                  background, density)
+        Nf = int(n_importance)
+        if Nf < 0:
+            raise ValueError("n_importance must be >= 0")
+        eps = functional._resample_args(S, Nf, 1e-5) if Nf else 0.0
         tile = max(1, min(int(tile_rays), R))
         L, d = self.L, C.byref(self.desc)
         stream = self._stream()
-        Cc = self.O - 1
-        rgb = torch.empty(R, Cc, dtype=torch.float32, device=self.dev)
-        acc = torch.empty(R, dtype=torch.float32, device=self.dev)
-        depth = torch.empty(R, dtype=torch.float32, device=self.dev)
+        Cc, M = self.O - 1, S + Nf
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        rgb, acc, depth = torch.empty(R, Cc, **f32), torch.empty(R, **f32), torch.empty(R, **f32)
         self._pack(stream)
-        ab = _lib.check(L.wire_act_bytes(d, tile * S, 0))
+        ab = _lib.check(L.wire_act_bytes(d, tile * M, 0))
         act = torch.empty(ab, dtype=torch.uint8, device=self.dev)
-        coords = torch.empty(tile * S, 3, dtype=torch.float32, device=self.dev)
-        ts, deltas = torch.empty(tile * S, dtype=torch.float32, device=self.dev), \
-            torch.empty(tile * S, dtype=torch.float32, device=self.dev)
-        y = torch.empty(tile * S, self.O, dtype=torch.float32, device=self.dev)
+        coords = torch.empty(tile * M, 3, **f32)
+        ts, deltas = torch.empty(tile * M, **f32), torch.empty(tile * M, **f32)
+        y = torch.empty(tile * M, self.O, **f32)
+        if Nf:
+            abc = _lib.check(L.wire_act_bytes(d, tile * S, 0))
+            cb = dict(coords=torch.empty(tile * S, 3, **f32), ts=torch.empty(tile * S, **f32),
+                      deltas=torch.empty(tile * S, **f32), y=torch.empty(tile * S, self.O, **f32),
+                      act=torch.empty(max(abc, 16), dtype=torch.uint8, device=self.dev), act_bytes=abc,
+                      w=torch.empty(tile * S, **f32))
         for r0 in range(0, R, tile):
             nr_ = min(tile, R - r0)
-            functional._ray_samples_into(stream, r[r0:r0 + nr_], None if bounds is None else bounds[r0:r0 + nr_], nr,
-                                         fr, None, nr_, S, coords, ts, deltas)
-            _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), coords.data_ptr(), nr_ * S, y.data_ptr(),
+            rt, bt = r[r0:r0 + nr_], None if bounds is None else bounds[r0:r0 + nr_]
+            if Nf:
+                self._coarse_pass(stream, rt, bt, nr, fr, None, nr_, S, mode, cb)
+                functional._ray_resample_into(stream, rt, bt, nr, fr, cb["ts"], cb["w"], None, eps, nr_, S, Nf, coords,
+                                              ts, deltas)
+            else:
+                functional._ray_samples_into(stream, rt, bt, nr, fr, None, nr_, S, coords, ts, deltas)
+            _lib.check(L.wire_mlp_fwd(stream, d, self.packed.data_ptr(), coords.data_ptr(), nr_ * M, y.data_ptr(),
                                       act.data_ptr(), ab, 0), "fwd")
             _lib.check(L.wire_composite_fwd(stream, y.data_ptr(), ts.data_ptr(), deltas.data_ptr(), self._opt_ptr(bg),
-                                            nr_, S, self.O, mode, rgb.data_ptr() + 4 * r0 * Cc,
+                                            nr_, M, self.O, mode, rgb.data_ptr() + 4 * r0 * Cc,
                                             acc.data_ptr() + 4 * r0, depth.data_ptr() + 4 * r0), "composite_fwd")
         return rgb, acc, depth
 
